@@ -13,7 +13,7 @@ calls are undelivered and each call's text is delivered, in order, while the nex
 inside the timed region (hd_flush before the closing barrier).  --sync delivers every step's text before the next step
 starts, like Decoder::operator().  Metric: input complex samples consumed per second over all GPUs (IQ Msamples/s).
 
-TWO timed regions per run, in one process: `cold` -- K steps right behind the W warm-up steps, the protocol of rounds 1-3 --
+With --full, TWO timed regions per run, in one process: `cold` -- K steps right behind the W warm-up steps, the protocol of rounds 1-3 --
 and the sustained one -- the same K steps behind --prewarm untimed steps of the same loop (default: whole passes over the ring, at least 120 steps)
 and W more warm-up steps.  The loop's first ~150 launches run about 10 % below the rate it then holds (the power controller settling at the
 1400 W cap), whatever kept the GPU busy before, and the driver's timed region is 20 steps long.  `value` is the sustained region; `cold` carries the
@@ -29,7 +29,11 @@ AFC every call ("cfg4" in SURVEY.md's 1-based numbering) -- the batched 2.048 MS
 1/2/4/8 GPUs, sharded 1024 streams per GPU (weak scaling).  Each stream carries its own CRC-valid telemetry
 sentence in a seamless ring of HBM-resident chunks; the line reports how many sentences were decoded.
 
-Output: ONE JSON line on rank 0 (contract in the round prompt) with `roofline` for the dominant kernel -- in batch mode
+A plain run does only what `value` needs: it builds the engine and the ring, runs the warm-up, the cold region's steps untimed and the pre-warm pass, times
+the K steps of the sustained region, writes the last timed step's outputs if --dump-outputs DIR is given (dump_outputs) and prints the line (`value`,
+`ms_per_step`, `pipeline`).  Everything below -- `cold`, `roofline`, `box`, `cpu_baseline` with the self-check, `fast`, `also` -- is --full.
+
+Output: ONE JSON line on rank 0; with --full it carries `roofline` for the dominant kernel -- in batch mode
 the step kernel (this call's first decimation stage, the only code that touches full-rate IQ, with the previous call's
 stream tails riding in the same launch); its duration is measured with HIP events on the engine's own stream -- and
 `cpu_baseline` (the CPU oracle timed on ALL of this box's host cores on a bounded sample of the same streams, whose
@@ -453,6 +457,50 @@ def gpu_sensor_reader(torch, dev):
     return read
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(eng, out_dir, S, seed=0):
+    """--dump-outputs: what a caller of the timed path receives after its last step, per stream -- the last call's discriminator output
+    (getDemodulated), the spectrum and its power, the AFC state, the last call's symbols and the symbol count -- as DIR/<name>.npy in float32 /
+    float64, rows in the order of streams.npy.  Every stream where that fits in 64 MB, else a fixed seeded sample of them.  Rows shorter than the
+    longest are padded with NaN (symbols: -1).  Getters only: nothing is taken from the text logs."""
+    def row(s):
+        a = eng.afc(s)
+        return {"demodulated": np.asarray(eng.demodulated(s), np.float32),
+                "spectrum": np.asarray(eng.spectrum(s), np.complex64).view(np.float32).reshape(-1, 2),
+                "power": np.asarray(eng.power(s), np.float32),
+                "afc": np.array([a["correction"], a["shift_hz"], a["noise_floor"], a["noise_var"], a["peak_l"], a["peak_r"], a["spectra"]], np.float64),
+                "symbols": eng.bits(s).astype(np.float32),
+                "symbols_total": np.array([eng.bits_total(s)], np.float64)}
+
+    def stack(rows, fill):
+        n = max(len(r) for r in rows)
+        out = np.full((len(rows), n) + rows[0].shape[1:], fill, rows[0].dtype)
+        for i, r in enumerate(rows):
+            out[i, :len(r)] = r
+        return out
+
+    order = np.random.default_rng(seed).permutation(S)
+    per_stream = max(1, sum(v.nbytes for v in row(0).values()))
+    n = S
+    while True:
+        n = min(n, max(1, int(DUMP_BUDGET_BYTES * 0.95) // per_stream))
+        streams = np.arange(S) if n == S else np.sort(order[:n])
+        rows = [row(int(s)) for s in streams]
+        arrays = {k: stack([r[k] for r in rows], -1.0 if k == "symbols" else np.nan) for k in rows[0]}
+        arrays["streams"] = streams.astype(np.float64)
+        total = sum(a.nbytes for a in arrays.values())
+        if total <= DUMP_BUDGET_BYTES or n == 1:
+            break
+        per_stream = -(-total // n) + 1           # (rows longer than stream 0's: try again with fewer)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", a)
+    return {"dir": str(d), "streams": int(n), "bytes": int(total)}
+
+
 def run_workload(*args, **kwargs):
     """_run_workload with the garbage collector off from before the engines and rings are built until the last timed step is sampled (timeit does the same).  A
     full collection over the heap an earlier leg's all-stream self-check left behind takes tens of milliseconds: inside a region that is the region; between the
@@ -467,11 +515,14 @@ def run_workload(*args, **kwargs):
         gc.enable()
 
 
-def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync, cpu_leg, threads=0, prewarm=None, arith=0, min_kernel_samples=32):
+def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync, cpu_leg, threads=0, prewarm=None, arith=0, min_kernel_samples=32,
+                  full=True, dump=None):
     """Time K steps of one workload (after W warm-up steps) and describe the result; rank 0 gets the full dictionary.
     cpu_leg: "full" = the CPU baseline (oracle timed on the host cores) + the self-check on every stream; "check" = the self-check alone on a few
-    streams; "check_all" = the self-check alone on every stream of the shard (every line carries one of them); threads = N > 0: one process, a Shard +
-    host thread per device; arith: 0 = the engine's exact mode (bit-identical floats), 1 = its fast mode (fused multiply-add, tolerance 1e-5)."""
+    streams; "check_all" = the self-check alone on every stream of the shard; None = neither; threads = N > 0: one process, a Shard +
+    host thread per device; arith: 0 = the engine's exact mode (bit-identical floats), 1 = its fast mode (fused multiply-add, tolerance 1e-5).
+    full=False (a plain bench.py run): only the sustained region -- no `cold` timing (its steps still run, untimed), no kernel sampling pass, sensor
+    readings, roofline, isolated stage-1 pass or box calibration.  dump: a directory that receives rank 0's outputs of the last timed step (dump_outputs)."""
     import threading
     import habdec_amd
     w = dict(WORKLOADS[name])
@@ -501,7 +552,7 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
     # driver's command (--warmup 5, 20 steps = 3 ms) behind nothing else times that ramp: it is reported as `cold`.  The self-check covers every step.
     P = min(ring_chunks * -(-120 // ring_chunks), 512) if prewarm is None else max(0, int(prewarm))     # (whole passes over the ring, at least 120 steps)
     base = sh.base
-    sensors = [gpu_sensor_reader(torch, x.dev) for x in shards]
+    sensors = [gpu_sensor_reader(torch, x.dev) for x in shards] if full else []
 
     def barrier():
         # (device work first, then the ranks meet on the host -- gloo -- and every device is idle on both sides of the region)
@@ -528,10 +579,17 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
         barrier()
         return job_time(dist, d, dev)
 
-    dt_cold = region()                                  # behind --warmup only: what rounds 1-3 timed
-    cold = {"value": round(world * S * C * K / dt_cold / 1e6, 1), "ms_per_step": round(dt_cold / K * 1e3, 4), "timed_region_ms": round(dt_cold * 1e3, 2),
-            "steps": K, "warmup": W, "note": "the same K steps timed right behind the --warmup steps, before the pre-warm pass (the protocol of rounds 1-3)"}
-    cold_kernel_ms = list(sh.front_ms)
+    if full or not P:
+        dt_cold = region()                              # behind --warmup only: what rounds 1-3 timed
+        cold = {"value": round(world * S * C * K / dt_cold / 1e6, 1), "ms_per_step": round(dt_cold / K * 1e3, 4), "timed_region_ms": round(dt_cold * 1e3, 2),
+                "steps": K, "warmup": W, "note": "the same K steps timed right behind the --warmup steps, before the pre-warm pass (the protocol of rounds 1-3)"}
+        cold_kernel_ms = list(sh.front_ms)
+    else:
+        # a plain run reports the sustained region alone: the cold region's W + K steps run untimed, so that the sustained region sits behind the same
+        # steps as in a --full run (and its last step consumes the same slab)
+        for x in shards:
+            x.warm(W + K)
+        cold, cold_kernel_ms = None, []
     if P:
         for x in shards:
             x.warm(P)
@@ -540,12 +598,13 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
         dt = dt_cold
     drain_ms = (sh.t_end - sh.t_loop) * 1e3
     front_ms, total_ms, host_us = list(sh.front_ms), list(sh.total_ms), list(sh.host_us)
+    dumped = dump_outputs(eng, dump, S) if dump and rank == 0 else None     # (before anything else runs on the engine: its last step is the last timed step)
     # The kernel sample of `roofline`: the timed steps that carried HIP events, topped up -- outside the timed region, same loop, same state -- to at
     # least 32 launches (the driver's 20 steps alone carry six or seven).  The device's shader clock and board power are read at the end of that pass,
     # with its last launches still queued (two sysfs reads, ~0.3 ms of driver time: NOT inside a timed region).
     n_region = len(front_ms)
     need = max(0, min_kernel_samples - n_region)
-    if not threads:
+    if full and not threads:
         seen = eng.timing()["timed_calls"]
         for _ in range(max(3 * need + 3, 48 if min_kernel_samples >= 32 else 6)):      # (the suite's all-stream tests ask for a handful: every step taken is a step the oracle decodes)
             sh.step()
@@ -556,12 +615,12 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
         sh.sensors = sensors[0]()
         eng.flush()
         torch.cuda.synchronize(sh.dev)
-    else:
+    elif full:
         for x, rd in zip(shards, sensors):
             x.sensors = rd()
     gc.enable()                                         # (the self-check and the CPU baseline below allocate in earnest)
     rank_sensors = [x.sensors or {"sclk_mhz": None, "power_w": None} for x in shards]
-    if dist is not None:                                # every rank's clock and power, gathered on rank 0 (a 2-float all-gather, outside the timed regions)
+    if dist is not None and full:                       # every rank's clock and power, gathered on rank 0 (a 2-float all-gather, outside the timed regions)
         mine = torch.tensor([rank_sensors[0]["sclk_mhz"] or -1.0, rank_sensors[0]["power_w"] or -1.0], dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -574,6 +633,9 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
         x.eng.close()
         x.ring = None
     chunks = [i % ring_chunks for i in range(steps_taken)]     # what the engine consumed: both regions, the pre-warm pass, the sampling pass (the self-check follows all of it)
+    if rank != 0 and not full:
+        eng.close()
+        return None
     if rank != 0:
         # Every rank checks ITS shard against the oracle -- behind rank 0's CPU-baseline timing, which has the host cores to itself
         # until the barrier -- and rank 0's line carries the verdicts (per_rank[i].gpu_matches_oracle).
@@ -587,6 +649,34 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
     value = world * S * C * K / dt / 1e6
     if not front_ms:                            # fewer steps than the timing period
         front_ms.append(tm["ms_front"]); total_ms.append(tm["ms_total"])
+    res = {
+        "prewarm_steps": P,
+        "value": round(value, 1), "ms_per_step": round(dt / K * 1e3, 4), "steps": K, "S": S, "C": C, "ring_chunks": ring_chunks, "w": w,
+        "timed_region_ms": round(dt * 1e3, 2),
+        "pipeline": {"bytes_per_sample": round(bytes_per_sample(w["D"]), 3),
+                     "hbm_frac_end_to_end": round(value / world * 1e6 * bytes_per_sample(w["D"]) / 1e9 / HBM_PEAK_GBS, 4),
+                     "launch_path": PATHS.get(path, str(path)),
+                     "call_latency_ms": round(float(np.mean(total_ms)), 4),
+                     "sentences_ok_rank0": int(sentences_ok),
+                     "drain_ms": round(drain_ms, 3),
+                     "host_us_enqueue_p50_p90_max": [round(float(np.percentile([h[0] for h in host_us], q)), 1) for q in (50, 90, 100)],
+                     "host_us_per_step": {"enqueue": round(float(np.mean([h[0] for h in host_us])), 1),
+                                          "wait_gpu": round(float(np.mean([h[1] for h in host_us])), 1),
+                                          "text_stage": round(float(np.mean([h[2] for h in host_us])), 1)},
+                     "mode": "sync" if sync else "batch (calls pipelined; up to three undelivered)"},
+        "arith": "fast" if arith else "exact",
+    }
+    if dumped:
+        res["outputs"] = dumped
+    if dt * 1e3 < 50.0:
+        res["pipeline"]["note"] = f"timed region is only {dt * 1e3:.1f} ms ({K} steps): start-up and the final flush weigh in; --steps 0 times one pass over the ring"
+    if not full:
+        eng.close()
+        del ring
+        torch.cuda.empty_cache()
+        return res
+    res["cold"] = cold
+    res["per_rank"] = [dict(rank=i, **x) for i, x in enumerate(rank_sensors)]
     avg_front_ms = float(np.mean(front_ms))
     # The timed kernel and its algorithmic bytes per launch: the step kernel does one call's whole chain --
     # stage 1 of this call and the stream tails of the previous one -- B(D) = 8 + 12/D bytes per input sample;
@@ -620,30 +710,13 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
         rp = {}
     valu = w["D"] == 4                                      # configs[2]: the FIR chain's multiply-adds bind, not HBM
     tflops = value / world * 1e6 * flops_per_sample(w) / 1e12
-    res = {
-        "prewarm_steps": P, "cold": cold,
-        "per_rank": [dict(rank=i, **x) for i, x in enumerate(rank_sensors)],
-        "value": round(value, 1), "ms_per_step": round(dt / K * 1e3, 4), "steps": K, "S": S, "C": C, "ring_chunks": ring_chunks, "w": w,
-        "timed_region_ms": round(dt * 1e3, 2),
-        "roofline": {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(avg_front_ms, 5),
-                     "n_samples": len(front_ms), "min_launch_ms": round(float(np.min(front_ms)), 5), "max_launch_ms": round(float(np.max(front_ms)), 5),
-                     "n_samples_in_timed_region": n_region, "cold_avg_launch_ms": round(float(np.mean(cold_kernel_ms)), 5) if cold_kernel_ms else None,
-                     "sampling": "HIP events on the engine's queue (riding on the dispatch packet) around every 3rd launch of the sustained timed region, topped up to >= 32 launches by a sampling pass of the same loop right behind it",
-                     "frac_of_measured_copy_peak": round(achieved / HBM_COPY_GBS, 4)},
-        "pipeline": {"bytes_per_sample": round(bytes_per_sample(w["D"]), 3),
-                     "hbm_frac_end_to_end": round(value / world * 1e6 * bytes_per_sample(w["D"]) / 1e9 / HBM_PEAK_GBS, 4),
-                     "launch_path": PATHS.get(path, str(path)),
-                     "call_latency_ms": round(float(np.mean(total_ms)), 4),
-                     "sentences_ok_rank0": int(sentences_ok),
-                     "drain_ms": round(drain_ms, 3),
-                     "host_us_enqueue_p50_p90_max": [round(float(np.percentile([h[0] for h in host_us], q)), 1) for q in (50, 90, 100)],
-                     "host_us_per_step": {"enqueue": round(float(np.mean([h[0] for h in host_us])), 1),
-                                          "wait_gpu": round(float(np.mean([h[1] for h in host_us])), 1),
-                                          "text_stage": round(float(np.mean([h[2] for h in host_us])), 1)},
-                     "mode": "sync" if sync else "batch (calls pipelined; up to three undelivered)"},
-    }
+    res["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                       "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(avg_front_ms, 5),
+                       "n_samples": len(front_ms), "min_launch_ms": round(float(np.min(front_ms)), 5), "max_launch_ms": round(float(np.max(front_ms)), 5),
+                       "n_samples_in_timed_region": n_region, "cold_avg_launch_ms": round(float(np.mean(cold_kernel_ms)), 5) if cold_kernel_ms else None,
+                       "sampling": "HIP events on the engine's queue (riding on the dispatch packet) around every 3rd launch of the sustained timed region, topped up to >= 32 launches by a sampling pass of the same loop right behind it",
+                       "frac_of_measured_copy_peak": round(achieved / HBM_COPY_GBS, 4)}
     res["roofline"].update(rp)
     if valu:
         vpeak = VALU_FMA_TFLOPS if arith else VALU_NONFMA_TFLOPS
@@ -653,8 +726,6 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
                            "stage1_hbm": {"achieved": round(achieved, 1), "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "avg_launch_ms": round(avg_front_ms, 5)}}
     if traffic_note:
         res["roofline"]["traffic_note"] = traffic_note
-    if dt * 1e3 < 50.0:
-        res["pipeline"]["note"] = f"timed region is only {dt * 1e3:.1f} ms ({K} steps): start-up and the final flush weigh in; --steps 0 times one pass over the ring"
     if not sync and path in (0, 1, 2, 3):
         # In batch mode the timed kernel shares the GPU (or its own launch) with the previous call's back half.  A short synchronous
         # pass (outside the timed region, own engine) gives the stage-1 kernel's isolated duration next to the contract figure above.
@@ -709,7 +780,6 @@ def _run_workload(torch, dist, dev, rank, local_rank, world, name, K, W, S, sync
             if i < len(res["per_rank"]) and c is not None:
                 res["per_rank"][i].update({"gpu_matches_oracle": c["gpu_matches_oracle_on_sample"], "self_check": {k: c[k] for k in c if k != "gpu_matches_oracle_on_sample"}})
         res["all_ranks_match_oracle"] = all(c is not None and c["gpu_matches_oracle_on_sample"] is True for c in allc)
-    res["arith"] = "fast" if arith else "exact"
     if arith:
         res["float_parity"] = float_parity_probe(w, ring, ring_chunks, S, C, local_rank)
     eng.close()
@@ -733,6 +803,11 @@ def main():
     ap.add_argument("--arith", default="both", choices=["exact", "fast", "both"],
                     help="arithmetic of the FIR sums: exact (bit-identical floats; what `value` always is), fast (fused multiply-add, tolerance 1e-5), both (default: `value` exact and a `fast` block beside it)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: only the launch plumbing (ranks, gloo barrier, MAX over ranks, rank 0's line) -- CPU tests")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the cold region, the kernel sampling pass and the roofline, the isolated stage-1 pass, the box "
+                         "calibration, the CPU baseline and the self-check against the oracle, the fast-mode leg (--arith both) and the configs[2] line (`also`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step (rank 0's shard) to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
 
     # --gpus N > 1 started as a plain command: this process becomes the launcher -- BEFORE torch is imported or HIP touched -- of N ranks of itself
@@ -803,17 +878,18 @@ def main():
     world_arg = world
     only_fast = args.arith == "fast"
     r = run_workload(torch, dist, dev, rank, local_rank, world_arg, args.workload, args.steps, args.warmup, args.streams, args.sync,
-                     cpu_leg="check" if args.no_cpu_baseline else "full", threads=threads, prewarm=args.prewarm, arith=1 if only_fast else 0)
+                     cpu_leg=("check" if args.no_cpu_baseline else "full") if args.full else None, threads=threads, prewarm=args.prewarm,
+                     arith=1 if only_fast else 0, full=args.full, dump=args.dump_outputs)
     # The engine's fast mode (fused multiply-add in every FIR; floats within 1e-5, decisions compared with the oracle's as they are) beside the exact-mode
     # `value`: the same workload, the same regions, its own engine and ring; every stream of the shard through the self-check.
     fast = None
-    if args.arith == "both" and not threads:
+    if args.full and args.arith == "both" and not threads:
         fast = run_workload(torch, dist, dev, rank, local_rank, world_arg, args.workload, args.steps, args.warmup, args.streams, args.sync,
                             cpu_leg="check" if args.no_cpu_baseline else "check_all", prewarm=args.prewarm, arith=1)
     if threads:
         world = threads
     also = also_fast = None
-    if args.workload == "cfg4" and not args.no_also and world == 1:
+    if args.full and args.workload == "cfg4" and not args.no_also and world == 1:
         # BASELINE configs[2] ("1024 batched IQ streams @ 2.048 MS/s, dec=2, on 1 MI355X"): the harder, VALU-bound single-GPU
         # configuration, measured beside the headline (its own ring, a short timed region).
         also = run_workload(torch, dist, dev, rank, local_rank, world, "cfg3", 24, 4, 0, args.sync, cpu_leg="check", arith=1 if only_fast else 0)
@@ -833,13 +909,16 @@ def main():
         "config": {"workload": f"{args.workload}: {w['desc']}", "streams_per_gpu": r["S"], "chunk_samples": r["C"], "ring_chunks": r["ring_chunks"],
                    "sharding": f"{r['S']} independent streams per GPU, no data-path collective"},
         "timed_region_ms": r["timed_region_ms"],
-        "cold": r["cold"],
         "prewarm_steps": r["prewarm_steps"],
         "timed_region_note": "per rank: from the opening barrier (device synchronize + gloo barrier) to the device synchronize behind the flush that delivers the K-th step's text; MAX over ranks; the closing barrier follows and is not timed",
-        "prewarm_note": "`value` / `ms_per_step` are the K steps timed behind the pre-warm pass (untimed steps of the same loop: whole passes over the ring, at least 120) and --warmup more steps: the sustained regime, at the board's 1400 W cap; `cold` is the same K steps timed right behind --warmup alone, before that pass (the protocol of rounds 1-3: the loop's first ~150 launches, DESIGN.md section 6)",
-        "per_rank": r["per_rank"],
-        "roofline": r["roofline"], "pipeline": r["pipeline"], "box": r.get("box"),
+        "prewarm_note": "`value` / `ms_per_step` are the K steps timed behind the pre-warm pass (untimed steps of the same loop: whole passes over the ring, at least 120) and --warmup more steps: the sustained regime, at the board's 1400 W cap; `cold` (--full) is the same K steps timed right behind --warmup alone, before that pass (the protocol of rounds 1-3: the loop's first ~150 launches, DESIGN.md section 6; a plain run takes those steps untimed)",
+        "pipeline": r["pipeline"],
+        "full": bool(args.full),
     }
+    if args.full:
+        line.update({"cold": r["cold"], "per_rank": r["per_rank"], "roofline": r["roofline"], "box": r.get("box")})
+    if "outputs" in r:
+        line["outputs"] = r["outputs"]
     if threads:
         line["config"]["launcher"] = f"one process, {threads} engine(s) each with its own host thread and device (bench.py --threads)"
     if "cpu_baseline" in r:
@@ -854,7 +933,8 @@ def main():
     line["arith"] = r["arith"]
     if same_device:
         line["same_device"] = "HD_BENCH_SAME_DEVICE: every rank ran its shard on device 0 -- a plumbing test, not a scaling measurement"
-    line["all_ranks_match_oracle"] = r.get("all_ranks_match_oracle")
+    if args.full:
+        line["all_ranks_match_oracle"] = r.get("all_ranks_match_oracle")
 
     def fast_block(f):
         cb = f["cpu_baseline"]

@@ -449,6 +449,23 @@ def have_ref() -> bool:
     return (HERE / "_ref" / "libhabdec_ref.so").exists()
 
 
+def reference_dir() -> Path:
+    """The reference checkout `make ref` compiles from: $REFERENCE, else the Makefile's default."""
+    d = os.environ.get("REFERENCE")
+    if not d:
+        d = next(ln.split("?=", 1)[1].strip() for ln in (HERE / "Makefile").read_text().splitlines() if ln.startswith("REFERENCE"))
+    return Path(d)
+
+
+def reference_available() -> bool:
+    """Whether the reference's decoder sources can be read here (absent, or present but unreadable to this user: False, never an exception)."""
+    try:
+        dec = reference_dir() / "code" / "Decoder"
+        return dec.is_dir() and os.access(dec, os.R_OK | os.X_OK)
+    except OSError:
+        return False
+
+
 class _BenchCfg(C.Structure):
     _fields_ = [("sampling_rate", _dbl), ("baud", _dbl), ("factor", _sz), ("bits", _sz), ("stops", C.c_float),
                 ("lowpass_bw", C.c_float), ("lowpass_trans", C.c_float), ("mathh_context", _int), ("ungated", _int), ("with_fft", _int)]

@@ -28,14 +28,14 @@ def _built_oracle():
     from oracle import pyoracle
     if not (ROOT / "oracle" / "liboracle.so").exists():
         pyoracle.build()
-    if Path("/root/reference/code/Decoder").exists() and not pyoracle.have_ref():
+    if pyoracle.reference_available() and not pyoracle.have_ref():
         pyoracle.build(ref=True)
     yield
 
 
 def pytest_collection_modifyitems(config, items):
     from oracle import pyoracle
-    have = pyoracle.have_ref() or Path("/root/reference/code/Decoder").exists()
+    have = pyoracle.have_ref() or pyoracle.reference_available()
     skip = pytest.mark.skip(reason="oracle/_ref not built (no /root/reference here)")
     for it in items:
         if "needs_ref" in it.keywords and not have:

@@ -176,7 +176,7 @@ def test_bench_two_ranks_over_gloo_on_one_device():
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     env = dict(os.environ, HD_BENCH_SAME_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(root / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--prewarm", "0", "--streams", "128", "--no-cpu-baseline", "--no-also"]
+           str(root / "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--prewarm", "0", "--streams", "128", "--no-cpu-baseline", "--no-also", "--full"]
     p = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)          # (a child process: this one's GPU context stays as it is)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

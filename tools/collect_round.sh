@@ -8,9 +8,9 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -12 > $o/pytest.txt
 # then is THIS session's steady-state average); tools/final_lines.sh makes the other lines (its own driver / default lines land in lines/ as a second sample)
 bash tools/profile_then_lines.sh ${2:-r06} > $o/headline.log 2>&1
 cp gpurun_out/headline/* $o/ 2>/dev/null
-bash tools/final_lines.sh > $o/final_lines.log 2>&1
-mkdir -p $o/lines_second_sample; cp gpurun_out/lines/driver_bench_line.json gpurun_out/lines/default_bench_line.json $o/lines_second_sample/ 2>/dev/null
-cp gpurun_out/lines/sync_bench_line.json gpurun_out/lines/other_workloads.jsonl $o/ 2>/dev/null
+bash tools/final_lines.sh $o/lines > $o/final_lines.log 2>&1
+mkdir -p $o/lines_second_sample; cp $o/lines/driver_bench_line.json $o/lines/default_bench_line.json $o/lines_second_sample/ 2>/dev/null
+cp $o/lines/sync_bench_line.json $o/lines/other_workloads.jsonl $o/ 2>/dev/null
 timeout 300 python3 tools/single_stream.py > $o/single_stream.jsonl 2>$o/single.err
 bash tools/gpu_profile.sh sync --sync > $o/profile_sync.log 2>&1
 for w in cfg2 cfg3 cfg5; do bash tools/gpu_kstats.sh ${w}_fast --workload $w --arith fast --steps 40 --warmup 5 --no-also > $o/kstats_${w}_fast.txt 2>&1; done

@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}
 out=$root/gpurun_out/ks_$tag
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ks -- python3 $root/bench.py --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o ks -- python3 $root/bench.py --full --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
 rm -f $out/*kernel_trace.csv
 python3 - <<P
 import csv,glob,re

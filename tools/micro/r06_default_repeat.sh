@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 o=gpurun_out/default_repeat; mkdir -p $o
 for i in $(seq 1 ${1:-3}); do
-  timeout 900 python3 bench.py > $o/line_$i.json 2> $o/err_$i.txt
+  timeout 900 python3 bench.py --full > $o/line_$i.json 2> $o/err_$i.txt
   python3 - $o/line_$i.json <<'P'
 import json, sys
 d = json.load(open(sys.argv[1])); f = d["fast"]
