@@ -32,6 +32,11 @@ class hd_timing(C.Structure):
                 ("path", C.c_uint32), ("step_variant", C.c_uint32), ("host_calls_in_place", C.c_uint64), ("lowpass_fft_calls", C.c_uint64)]
 
 
+class hd_tune_info(C.Structure):
+    _fields_ = [("offset_hz", C.c_double), ("step", C.c_uint32), ("phase", C.c_uint32), ("retunes", C.c_uint64), ("from_call", C.c_uint64),
+                ("auto_afc", C.c_int32)]
+
+
 SENTENCE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p)
 MATCH_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int)
 CHARS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_char), C.c_size_t)
@@ -58,6 +63,9 @@ ENGINE_API = {
     "hd_stream_set_lowpass_trans": (_int, [_vp, _u32, _f]),
     "hd_stream_set_dc_remove": (_int, [_vp, _u32, _int]),
     "hd_stream_reset_frequency_correction": (_int, [_vp, _u32, _dbl]),
+    "hd_stream_set_tune": (_int, [_vp, _u32, _dbl]),
+    "hd_stream_set_auto_afc": (_int, [_vp, _u32, _int, _dbl, _dbl]),
+    "hd_stream_tune": (_int, [_vp, _u32, C.POINTER(hd_tune_info)]),
     "hd_set_sentence_callback": (None, [_vp, SENTENCE_CB, _vp]),
     "hd_set_match_callback": (None, [_vp, MATCH_CB, _vp]),
     "hd_set_chars_callback": (None, [_vp, CHARS_CB, _vp]),
@@ -132,6 +140,9 @@ HOST_API = {
     "hd_host_iqfiles_count": (C.c_uint64, [_vp, C.c_uint32]),
     "hd_host_iqfiles_rewinds": (C.c_uint64, [_vp, C.c_uint32]),
     "hd_host_iqfiles_next": (C.c_uint32, [_vp, _f32p, _sz, C.POINTER(C.c_uint32)]),
+    "hd_host_tune_step": (_int, [_dbl, _dbl, C.POINTER(C.c_uint32)]),
+    "hd_host_tune_tables": (None, [_f32p, _f32p]),
+    "hd_host_tune_rotate": (None, [_f32p, _sz, C.c_uint32, C.c_uint32, _f32p]),
 }
 
 

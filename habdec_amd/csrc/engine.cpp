@@ -30,6 +30,7 @@
 #include "host/fir_design.hpp"
 #include "host/iq_file_batch.hpp"
 #include "host/text_stage.hpp"
+#include "host/tune_host.hpp"
 #include "kernels/launch.h"
 
 // A launcher (or layout helper) of the kernels that exist once per arithmetic mode (kernels/arith.h): hd::exact::fn or hd::fast::fn by the engine's mode.
@@ -110,6 +111,13 @@ struct StreamHost {
     uint64_t demod_ck_call = 0;                               // ... and that call's index (0 = the engine's first hd_process_* call)
     uint64_t demod_ck_hash = 0xCBF29CE484222325ull;           // every delivered call's (n, ck[0], ck[1]) folded into one word (hd_stream_demod_checksum_total)
     uint64_t demod_ck_calls = 0, demod_ck_unknown = 0;        // calls folded in / calls whose slot carried no checksum (the fused back end)
+    // digital tuning of the decimated chunk (hd_stream_set_tune, kernels/tune.h) and the closed loop over it (hd_stream_set_auto_afc)
+    double tune_hz = 0;
+    uint32_t tune_step = 0, tune_phase = 0;   // step and phase of the next call to be submitted
+    uint64_t tune_from = 0, retunes = 0;      // first call of the current offset; automatic retunes so far
+    bool auto_afc = false;
+    double afc_hold_s = 6.0, afc_min_hz = 100.0;
+    uint64_t afc_elapsed = 0;                 // input samples delivered since the loop was set or last retuned
 };
 
 }  // namespace
@@ -199,6 +207,7 @@ struct hd_engine {
     DevBuf<hd::DemodCarry> carry[2];
     DevBuf<float2> fir_head;          // [S][head_cap]: FirHistory heads moved aside -- the first samples of a stream's last low-pass run's input, copied here by the first call in
                                       // which the stream did not run (dev_types.h: the head, lazily); a stream that ran in the previous call finds them in that call's buffer
+    DevBuf<float> tune_tab;           // the phasor tables [C | F] of the per-stream tuning (kernels/tune.h), 2 x 256 (cos, sin)
     DevBuf<uint32_t> demod_ck_acc;    // [S][2]: the discriminator checksum of the call in the back half of the separate-kernels path (k_fir_demod adds, k_symbols collects and clears)
     uint32_t head_cap = 0;
     DevBuf<hd::SymbolParams> d_sym;
@@ -211,6 +220,7 @@ struct hd_engine {
         PinBuf<hd::StreamCall> h_call;
         PinBuf<uint32_t> h_slots;                 // written by the symbol scan kernel over PCIe (zero-copy), read after ev_done
         PinBuf<hd::SpectrumStatsDev> h_stats;    // written by the spectrum kernel
+        PinBuf<uint2> h_tune;                     // (step, phase) of every stream for this call, read by the kernels in place; passed only when some stream is tuned
         bool timed = false, timed_step = false;   // this call carries the timing events (a step call: only the two around its one launch)
         hipEvent_t ev_front = nullptr, ev_done = nullptr, ev_params = nullptr, ev_spec = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
         bool busy = false;
@@ -463,6 +473,13 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HD_HIP(sl.d_call.alloc(S));
         HD_HIP(sl.h_call.alloc(S));
         HD_HIP(sl.h_slots.alloc((size_t)S * e->slot_words));
+        HD_HIP(sl.h_tune.alloc(S));
+    }
+    {
+        std::vector<float> tab(4 * hd::kTuneTable);
+        hd::tune_tables(tab.data(), tab.data() + 2 * hd::kTuneTable);
+        HD_HIP(e->tune_tab.alloc(tab.size()));
+        HD_HIP(hipMemcpy(e->tune_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     if (cfg->enable_spectrum) {
         HD_HIP(e->fft_in.alloc((size_t)S * hd::kFftBins));
@@ -530,7 +547,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         if (e->stages.size() == 2)
             HDK(launch_decimate, q, e->stages[1].ratio, T2, S, 1, e->dec1.p, e->n1_cap, e->hist2[0].p, e->hist2[1].p, e->stage_taps[1].p, e->fbuf[0].p,
                                 e->fbuf_stride, sl.d_call.p, 1, 1, e->fir_hist_cap, nullptr);
-        HDK(launch_dc_remove, q, S, e->fbuf[0].p, e->fbuf_stride, sl.d_call.p, e->fir_hist_cap);
+        HDK(launch_chunk_post, q, S, e->fbuf[0].p, e->fbuf_stride, sl.d_call.p, e->fir_hist_cap, nullptr, e->tune_tab.p);
         if (cfg->enable_spectrum) {
             HDK(launch_fft_feed, q, S, e->fbuf[0].p, e->fbuf_stride, e->fft_in.p, sl.d_call.p, e->fir_hist_cap);
             void* in[1] = {e->fft_in.p};
@@ -663,6 +680,37 @@ int hd_stream_reset_frequency_correction(hd_engine* e, uint32_t s, double c)
     e->st[s].afc.reset(c, hd::kFftBins, e->fsd);
     return HD_OK;
 }
+// Tuning: the offset takes effect from the next call submitted; the phase carries on (f = 0 clears it: the stream is untouched again)
+int hd_stream_set_tune(hd_engine* e, uint32_t s, double offset_hz)
+{
+    if (int r = check_stream(e, s)) return r;
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    uint32_t d = 0;
+    if (!hd::tune_step(offset_hz, e->fsd, &d)) return fail(HD_ERR_INVALID, "tuning offset outside (-fs_dec/2, fs_dec/2)");
+    StreamHost& st = e->st[s];
+    st.tune_hz = offset_hz; st.tune_step = d; st.tune_from = e->calls;
+    if (offset_hz == 0) st.tune_phase = 0;
+    return HD_OK;
+}
+int hd_stream_set_auto_afc(hd_engine* e, uint32_t s, int on, double hold_s, double min_hz)
+{
+    if (int r = check_stream(e, s)) return r;
+    if (!(hold_s >= 0) || !(min_hz >= 0)) return fail(HD_ERR_INVALID, "hold_s and min_hz must be >= 0");
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    StreamHost& st = e->st[s];
+    st.auto_afc = on != 0; st.afc_hold_s = hold_s; st.afc_min_hz = min_hz; st.afc_elapsed = 0;
+    return HD_OK;
+}
+int hd_stream_tune(hd_engine* e, uint32_t s, hd_tune_info* out)
+{
+    if (int r = check_stream(e, s)) return r;
+    if (!out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    const StreamHost& st = e->st[s];
+    out->offset_hz = st.tune_hz; out->step = st.tune_step; out->phase = st.tune_phase;
+    out->retunes = st.retunes; out->from_call = st.tune_from; out->auto_afc = st.auto_afc ? 1 : 0;
+    return HD_OK;
+}
 
 /* ---------------------------------------------------------------- data path ------------------------------------ */
 
@@ -777,6 +825,20 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
         }
         const bool past_batch_gate = c.fir_m || c.clear_pending;
         if (past_batch_gate && e->cfg.enable_spectrum) st.afc.step(st.have_spectrum, st.stats, hd::kFftBins, e->fsd);
+        // closed loop (hd_stream_set_auto_afc): the server's AFC block (websocketServer/main.cpp:247-263) in sample time, retuning the stream instead of a radio.
+        // The new step rides with the parameters of the next call submitted -- no drain.
+        st.afc_elapsed += c.n_in;
+        if (st.auto_afc && (double)st.afc_elapsed >= st.afc_hold_s * e->fs && std::abs(st.afc.correction) > st.afc_min_hz) {
+            const double corr = st.afc.correction;
+            uint32_t d = 0;
+            if (hd::tune_step(st.tune_hz + corr, e->fsd, &d)) {
+                st.tune_hz += corr; st.tune_step = d; st.tune_from = e->calls;
+                if (!d) st.tune_phase = 0;
+                st.afc.reset(corr, hd::kFftBins, e->fsd);
+                st.afc_elapsed = 0;
+                ++st.retunes;
+            }
+        }
         const uint32_t* slot = sl.h_slots.p + (size_t)s * e->slot_words;
         const hd::BitsHeader* hdr = reinterpret_cast<const hd::BitsHeader*>(slot);
         st.held = hdr->held_after;
@@ -871,7 +933,7 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
 
     // ---- host mirror of the reference's size bookkeeping -> one StreamCall per stream
     uint32_t max_in = 0, min_in = 0xFFFFFFFFu, max_n1 = 0, max_n2 = 0, max_m = 0, max_taps = 0, max_new = 0, max_pend = 0;
-    bool any_fft = false, any_dc = false, any_zero1 = false;
+    bool any_fft = false, any_dc = false, any_zero1 = false, any_tune = false;
     uint64_t total_in = 0;
     for (uint32_t s = 0; s < S; ++s) {
         StreamHost& st = e->st[s];
@@ -885,6 +947,8 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
             if (nst > 1) { const size_t want = (size_t)c.n1 + T2 + R2; if (st.stage_buf[1] < want) { st.stage_buf[1] = want; c.zero_hist2 = 1; } }
         }
         c.dc_remove = st.dc && c.n2;
+        sl.h_tune.p[s] = make_uint2(st.tune_step, st.tune_phase);     // (read by the kernels only when some stream of the call is tuned)
+        if (st.tune_step) { any_tune = true; st.tune_phase += c.n2 * st.tune_step; }
         c.pend_before = (uint32_t)st.pending;
         st.pending += c.n2;
         // spectrum collection (Decoder.h:467-489)
@@ -957,7 +1021,8 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     const bool tail = nst == 2 && !any_dc && !e->no_tail && max_n2 <= e->tail_max_n2 &&
                       ((tail_lanes == 256 && max_n2 >= 512u && HDK(tail_layout, ta, tail_lanes, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, 64 * 1024, 4)) ||
                        HDK(tail_layout, ta, tail_lanes, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, 64 * 1024));
-    const bool fuse = tail || (nst == 2 && !any_dc && !e->no_fuse && ((R2 == 2 && T2 == 69) || (R2 == 4 && T2 == 139)) &&
+    // (the fused back end declines tuned calls as it declines DC-removing ones: they take the separate kernels, whose post-pass rotates the chunk)
+    const bool fuse = tail || (nst == 2 && !any_dc && !any_tune && !e->no_fuse && ((R2 == 2 && T2 == 69) || (R2 == 4 && T2 == 139)) &&
                       HDK(backend_lds_bytes, (int)T2, max_n1, max_n2, max_taps) <= 64 * 1024);
     // Step mode: batch decoding of equally sized pushes through a single-wave first stage -- ONE launch per call, on one queue: this
     // call's stage 1 with the previous call's stream tails in front (kernels/decimate.hip k_step).
@@ -972,7 +1037,10 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     }
     e->last_fuse = path;
     e->last_timing.path = (uint32_t)path;
-    if (path == 0 && e->own_fft && e->cfg.enable_spectrum && !any_dc && any_fft) {
+    // The separate kernels change the decimated chunk after the last stage (DC blocker, rotation of a tuned stream) in a post-pass; the stream tails rotate
+    // in their stage-2 store and take no DC-removing call.
+    const bool any_post = any_dc || (any_tune && !tail);
+    if (path == 0 && e->own_fft && e->cfg.enable_spectrum && !any_post && any_fft) {
         // A call whose decimated chunk alone fills a stream's (empty) spectrum buffer: the spectrum launch reads the chunk's head in place and nothing is copied
         // into the collection buffer (fft_take = 0 for the stage that would have fed it; fft_run = 2 for the spectrum kernel) -- at 4096 and more decimated
         // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic, and transform + commit are one pass instead of three.
@@ -1036,13 +1104,14 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     float2* d1 = (e->calls % 3 == 0) ? e->dec1.p : (e->calls % 3 == 1) ? e->dec1b.p : e->dec1c.p;   // never a buffer a call in flight still reads
     const int hin = e->hist_cur, hout = e->hist_cur ^ 1;
     // spectrum collection rides in the final stage's epilogue unless the DC blocker must see the samples first
-    float2* feed = (e->cfg.enable_spectrum && !any_dc) ? e->fft_in.p : nullptr;
+    float2* feed = (e->cfg.enable_spectrum && !any_post) ? e->fft_in.p : nullptr;
     const int cin = e->carry_cur, cout = e->carry_cur ^ 1;
     auto fill_tail = [&](hd::TailArgs& t) {      // buffers of THIS call's stream tails (the LDS carve is already in t)
         t.dec1 = d1; t.dec1_stride = e->n1_cap; t.hist2_in = e->hist2[hin].p; t.hist2_out = e->hist2[hout].p; t.taps2 = e->stage_taps[1].p;
         t.fbuf = fcur; t.fbuf_next = fnext; t.fbuf_stride = e->fbuf_stride; t.fir_hist_cap = e->fir_hist_cap;
         t.lp_taps = e->lp_taps.p; t.taps_stride = e->taps_cap; t.demod = e->demod.p; t.demod_stride = e->demod.n / S;
         t.filtered = e->cfg.keep_filtered ? e->filtered.p : nullptr; t.carry_in = e->carry[cin].p; t.carry_out = e->carry[cout].p;
+        t.tune = any_tune ? sl.h_tune.dev : nullptr; t.tune_tab = e->tune_tab.p;
         t.call = dcall; t.fft_in = feed; t.head_buf = e->fir_head.p; t.fbuf_prev = e->fbuf[(e->cur + 2) % 3].p; t.head_cap = e->head_cap;
         t.n_streams = S;
         t.ring = e->tail.p; t.ring_cap = e->tail_cap; t.sym = e->d_symstate.p; t.flipmask = e->flipmask.p; t.wsum = e->weight.p;
@@ -1227,7 +1296,7 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     }
     auto spectrum = [&](hipStream_t q) -> int {
         if (!(e->cfg.enable_spectrum && max_n2)) return HD_OK;
-        if (!fuse && (any_dc || nst == 0)) HDK(launch_fft_feed, q, S, fcur, e->fbuf_stride, e->fft_in.p, dcall, e->fir_hist_cap);
+        if (!fuse && (any_post || nst == 0)) HDK(launch_fft_feed, q, S, fcur, e->fbuf_stride, e->fft_in.p, dcall, e->fir_hist_cap);
         if (any_fft) {   // only when some stream's 4096-sample buffer completed (every call at >= 4096 decimated samples per push)
             if (const int r = transform_and_commit(e, q, sl.h_stats.dev, dcall, sl.seq, fcur)) return r;
         }
@@ -1238,8 +1307,8 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     // the collection buffer a transform on another queue was still reading -- there is no collection buffer on this route).
     bool spectrum_on_qc = false;
     if (!fuse) {
-        if (any_dc) HDK(launch_dc_remove, qa, S, fcur, e->fbuf_stride, dcall, e->fir_hist_cap);
-        if (path == 0 && !e->one_stream && e->own_fft && e->cfg.enable_spectrum && !any_dc && any_fft && nst != 0) {
+        if (any_post) HDK(launch_chunk_post, qa, S, fcur, e->fbuf_stride, dcall, e->fir_hist_cap, any_tune ? sl.h_tune.dev : nullptr, e->tune_tab.p);
+        if (path == 0 && !e->one_stream && e->own_fft && e->cfg.enable_spectrum && !any_post && any_fft && nst != 0) {
             spectrum_on_qc = true;
             for (uint32_t s = 0; s < S && spectrum_on_qc; ++s) spectrum_on_qc = sl.h_call.p[s].fft_run != 1u;
         }
@@ -1373,7 +1442,12 @@ int hd_process_host(hd_engine* e, const float* iq, size_t stride, const uint32_t
     }
     float2* dst = j ? e->staging2.p : e->staging.p;
     if (e->staging_used[j]) HD_HIP(hipStreamWaitEvent(e->qh, e->ev_staging_free[j], 0));    // the call that read this slab two calls ago is past its stage 1
-    if (!n_per_stream) {
+    if (!stride) {
+        // every stream reads the same recording: one copy, and the streams read it with stride 0 as well
+        uint32_t n_max = n_uniform;
+        if (n_per_stream) { n_max = 0; for (uint32_t s = 0; s < e->S; ++s) n_max = std::max(n_max, n_per_stream[s]); }
+        if (n_max) HD_HIP(hipMemcpyAsync(dst, iq, (size_t)n_max * sizeof(float2), hipMemcpyHostToDevice, e->qh));
+    } else if (!n_per_stream) {
         if (n_uniform)
             HD_HIP(hipMemcpy2DAsync(dst, dstride * sizeof(float2), iq, stride * sizeof(float2), (size_t)n_uniform * sizeof(float2),
                                     e->S, hipMemcpyHostToDevice, e->qh));
@@ -1386,7 +1460,7 @@ int hd_process_host(hd_engine* e, const float* iq, size_t stride, const uint32_t
     HD_HIP(hipEventRecord(e->ev_copy[j], e->qh));
     HD_HIP(hipStreamWaitEvent(e->qa, e->ev_copy[j], 0));
     HD_HIP(hipEventSynchronize(e->ev_copy[j]));          // from here on the caller's buffer is his again
-    const int rc = hd_process_device(e, dst, dstride, n_per_stream, n_uniform);
+    const int rc = hd_process_device(e, dst, stride ? dstride : 0, n_per_stream, n_uniform);
     HD_HIP(hipEventRecord(e->ev_staging_free[j], e->qa));
     e->staging_used[j] = true;
     ++e->host_calls;

@@ -12,6 +12,7 @@
 #include "host/sondehub.hpp"
 #include "host/text_stage.hpp"
 #include "host/iq_file_batch.hpp"
+#include "host/tune_host.hpp"
 #include "kernels/exact_math.h"
 
 struct hd_host_rtty { hd::RttyFramer f; };
@@ -241,6 +242,22 @@ uint32_t hd_host_iqfiles_next(hd_host_iqfiles* h, float* slab, size_t stride, ui
 {
     if (!h || !slab || !n_per_stream || stride < h->batch.chunk()) return 0;
     return h->batch.next(slab, stride, n_per_stream);
+}
+
+/* ---- per-stream tuning (kernels/tune.h) ---- */
+int hd_host_tune_step(double offset_hz, double decimated_rate, uint32_t* step)
+{
+    uint32_t d = 0;
+    if (!hd::tune_step(offset_hz, decimated_rate, &d)) return -1;     // HD_ERR_INVALID
+    if (step) *step = d;
+    return 0;
+}
+void hd_host_tune_tables(float coarse[512], float fine[512]) { hd::tune_tables(coarse, fine); }
+void hd_host_tune_rotate(const float* iq, size_t n, uint32_t phase, uint32_t step, float* out)
+{
+    float tab[4 * hd::kTuneTable];
+    hd::tune_tables(tab, tab + 2 * hd::kTuneTable);
+    hd::tune_rotate(tab, iq, n, phase, step, out);
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "launch.h"
+#include "tune.h"
 #include "tail_body.h"
 #include "stage1_ring.h"
 
@@ -658,15 +659,20 @@ __global__ void k_passthrough(const float2* __restrict__ in, size_t in_stride, f
     if (i < c.n_in) out[(size_t)s * out_stride + fir_hist_cap + c.pend_before + i] = in[(size_t)s * in_stride + i];
 }
 
-// Per-chunk DC blocker (reference Decoder.h:450-459): wp = .97*x0; w = x + .97*wp; y = w - wp; wp = w.
-// Strictly sequential per stream; one wave per stream walks the chunk 64 samples at a time, broadcasting
-// each sample with v_readlane so the recurrence runs uniformly in every lane without LDS or barriers.
+// Per-chunk post-pass of the separate-kernels path (k_dc_remove, generalised), one wave per stream, in place on the decimated chunk:
+//  1. the DC blocker (reference Decoder.h:450-459) where the stream asks for it: wp = .97*x0; w = x + .97*wp; y = w - wp; wp = w.  Strictly
+//     sequential per stream; the wave walks the chunk 64 samples at a time, broadcasting each sample with v_readlane so the recurrence runs
+//     uniformly in every lane without LDS or barriers;
+//  2. then the rotation of a tuned stream (tune.h): sample i by theta = phase + i * step.  The blocker goes first because the LO spike of a
+//     recording stays at the recording's 0 Hz.  A stream with step 0 is not touched by it.
 __global__ __launch_bounds__(64) void k_dc_remove(float2* __restrict__ fbuf, size_t stride, const StreamCall* __restrict__ call,
-                                                    uint32_t fir_hist_cap)
+                                                   uint32_t fir_hist_cap, const uint2* __restrict__ tune, const float* __restrict__ tab)
 {
     const uint32_t s = blockIdx.x;
     const StreamCall c = call[s];
-    if (!c.dc_remove || !c.n2) return;
+    const uint2 tn = tune ? tune[s] : make_uint2(0u, 0u);
+    const bool dc = c.dc_remove != 0, rot = tn.x != 0u;
+    if (!c.n2 || !(dc || rot)) return;
     float2* x = fbuf + (size_t)s * stride + fir_hist_cap + c.pend_before;
     const int lane = threadIdx.x;
     const float2 x0 = x[0];
@@ -674,17 +680,21 @@ __global__ __launch_bounds__(64) void k_dc_remove(float2* __restrict__ fbuf, siz
     for (uint32_t base = 0; base < c.n2; base += 64) {
         const uint32_t i = base + lane;
         float2 v = i < c.n2 ? x[i] : make_float2(0.f, 0.f);
-        float yr = 0.f, yi = 0.f;
+        float yr = v.x, yi = v.y;
+        if (dc) {
+            yr = 0.f; yi = 0.f;
 #pragma unroll 8                                 // (fully unrolled the compiler hoisted all 128 broadcasts to the front: 130 spilled SGPRs)
-        for (int k = 0; k < 64; ++k) {
-            const float xr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v.x), k));
-            const float xi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v.y), k));
-            const float sr = 0.97f * wr, si = 0.97f * wi;
-            const float nr = xr + sr, ni = xi + si;
-            if (lane == k) { yr = nr - wr; yi = ni - wi; }
-            // lanes past the end of the chunk must not disturb the carry (their outputs are not stored)
-            if (base + k < c.n2) { wr = nr; wi = ni; }
+            for (int k = 0; k < 64; ++k) {
+                const float xr = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v.x), k));
+                const float xi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v.y), k));
+                const float sr = 0.97f * wr, si = 0.97f * wi;
+                const float nr = xr + sr, ni = xi + si;
+                if (lane == k) { yr = nr - wr; yi = ni - wi; }
+                // lanes past the end of the chunk must not disturb the carry (their outputs are not stored)
+                if (base + k < c.n2) { wr = nr; wi = ni; }
+            }
         }
+        if (rot) tune_rotate1(tab, tn.y + i * tn.x, yr, yi, yr, yi);
         if (i < c.n2) x[i] = make_float2(yr, yi);
     }
 }
@@ -875,9 +885,10 @@ void launch_passthrough(hipStream_t st, uint32_t n_streams, uint32_t max_n, cons
     hipLaunchKernelGGL(k_passthrough, grid, dim3(256), 0, st, in, in_stride, out, out_stride, call, fir_hist_cap);
 }
 
-void launch_dc_remove(hipStream_t st, uint32_t n_streams, float2* fbuf, size_t stride, const StreamCall* call, uint32_t fir_hist_cap)
+void launch_chunk_post(hipStream_t st, uint32_t n_streams, float2* fbuf, size_t stride, const StreamCall* call, uint32_t fir_hist_cap,
+                       const uint2* tune, const float* tune_tab)
 {
-    hipLaunchKernelGGL(k_dc_remove, dim3(n_streams), dim3(64), 0, st, fbuf, stride, call, fir_hist_cap);
+    hipLaunchKernelGGL(k_dc_remove, dim3(n_streams), dim3(64), 0, st, fbuf, stride, call, fir_hist_cap, tune, tune_tab);
 }
 
 }  // namespace HD_ARITH_NS

@@ -49,6 +49,8 @@ struct TailArgs {
     // every stream carves for itself: the flag-mask image of its searchable backlog, a sample cache for the run sums, a window-sum cache for the edge search)
     uint32_t pend_max, f_off, v_off, ws_off, words_off, tp_off, h2_off, flips_off, fl_cap, strips_off, dyn_off, lds_bytes;
     uint32_t op;          // stage-2 outputs per lane and piece the carve was made for (tail_layout; launch_tail picks the kernel by it)
+    // per-stream tuning (tune.h): (step, phase) of each stream for THIS call, or null when no stream of the call is tuned; the phasor tables [C | F]
+    const uint2* tune; const float* tune_tab;
 };
 
 constexpr uint32_t kStepLdsBytes = 20480;   // LDS of a stage-1 workgroup slot (eight per CU): what a tail riding in the stage-1 launch may use

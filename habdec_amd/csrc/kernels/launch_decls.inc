@@ -19,7 +19,10 @@ void launch_fetch_params(hipStream_t st, const void* host_mapped, void* dst, siz
 // factor 1: copy the chunk behind the FIR history.
 void launch_passthrough(hipStream_t st, uint32_t n_streams, uint32_t max_n, const float2* in, size_t in_stride,
                         float2* out, size_t out_stride, const StreamCall* call, uint32_t fir_hist_cap);
-void launch_dc_remove(hipStream_t st, uint32_t n_streams, float2* fbuf, size_t stride, const StreamCall* call, uint32_t fir_hist_cap);
+// The per-chunk post-pass of the separate-kernels path: the DC blocker where StreamCall::dc_remove asks for it, then the rotation of a tuned stream
+// (tune.h; tune[s] = (step, phase), tune = null: no stream of the call is tuned), in place on the decimated chunk behind the FIR history.
+void launch_chunk_post(hipStream_t st, uint32_t n_streams, float2* fbuf, size_t stride, const StreamCall* call, uint32_t fir_hist_cap,
+                       const uint2* tune, const float* tune_tab);
 void launch_fft_feed(hipStream_t st, uint32_t n_streams, const float2* fbuf, size_t stride, float2* fft_in,
                      const StreamCall* call, uint32_t fir_hist_cap);
 void launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32_t max_taps, const float2* fbuf, size_t stride,

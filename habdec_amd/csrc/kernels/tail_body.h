@@ -25,6 +25,7 @@
 #include "launch.h"
 #include "sym_common.h"
 #include "spectrum_wave.h"
+#include "tune.h"
 
 namespace hd {
 namespace HD_ARITH_NS {
@@ -154,6 +155,9 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
 
     TSTAMP_DECL;
     const StreamCall c = a.call[s];
+    // per-stream tuning (tune.h): read at the top, its round trip hides behind the first piece's loads; step 0 = the stream is not touched
+    const uint2 tn = a.tune ? a.tune[s] : make_uint2(0u, 0u);
+    const bool rot = tn.x != 0u;
     const uint32_t n1 = c.n1, n2 = c.n2, m = c.fir_m, T = c.fir_taps, pb = c.pend_before;
     const uint32_t H = T ? T - 1 : 0;
     const uint32_t Tp = sc_taps_prev(c) ? sc_taps_prev(c) : T;
@@ -418,6 +422,17 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
         }
         if (pc == npieces) break;
         const uint32_t o0 = pc * P, po = min((uint32_t)P, n2 - o0);
+        // a tuned stream: the table entries of this piece's outputs (tune.h), loaded now -- the stage-2 sums below hide their round trip
+        float4 tpc[OP];
+        if (rot) {
+            const float2* tab2 = reinterpret_cast<const float2*>(a.tune_tab);
+#pragma unroll
+            for (int q = 0; q < OP; ++q) {
+                const uint32_t th = tn.y + (o0 + OP * tid + q) * tn.x;
+                const float2 cc = tab2[th >> 24], ff = tab2[kTuneTable + ((th >> 16) & 255u)];
+                tpc[q] = make_float4(cc.x, cc.y, ff.x, ff.y);
+            }
+        }
 #pragma unroll
         for (int u = 0; u < XB; ++u) {
             *reinterpret_cast<float4*>(X + xp0 + u * kXStepP) = tx[u];     // (sample T2 - 1 + 2 k; T2 - 1 is even: a pair never straddles a pad)
@@ -480,6 +495,20 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
             if constexpr (T2 % 4 >= 3) tb_s2_tap<2, OP, D2, NWIN>(acc, win, kc.z);
             TSTAMP(18);
             const bool keepF = keepf || npieces == 1;
+            if (rot) {
+                // a tuned stream: the outputs are rotated on their way to the low-pass buffer, the low-pass image and the spectrum feed.  The stage-2
+                // history carry keeps RAW outputs: where it holds outputs (Q4, below) this lane stores them now, and the carry skips them.
+                const uint32_t q4_lo = n1 - (uint32_t)(T2 - 1);
+#pragma unroll
+                for (int q = 0; q < OP; ++q) {
+                    const uint32_t ol = OP * tid + q, oo = o0 + ol;
+                    if (pc + 1 == npieces && n1 && ol < po && oo >= q4_lo && oo < n2)
+                        a.hist2_out[(size_t)s * (T2 - 1) + (oo - q4_lo)] = make_float2(acc[q].x, acc[q].y);
+                    float yr, yi;
+                    tune_apply(tpc[q].x, tpc[q].y, tpc[q].z, tpc[q].w, acc[q].x, acc[q].y, yr, yi);
+                    acc[q] = (f32x2){yr, yi};
+                }
+            }
             bool done4 = false;
             if constexpr (OP == 4) {
                 // four adjacent outputs per lane: 16-byte stores whenever all four exist and the destinations are 16-byte aligned
@@ -524,6 +553,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
             tb_sync<NT>();
             for (uint32_t k = tid; k < (uint32_t)(T2 - 1); k += NT) {
                 const uint32_t idx = n1 - (T2 - 1) + k;                 // host guarantees n1 >= T2-1
+                if (rot && idx < n2) continue;                          // (raw outputs of a tuned stream: stored by their lanes above)
                 a.hist2_out[(size_t)s * (T2 - 1) + k] = idx < n2 ? F[f_old + idx - fbase] : in_s[idx];
             }
         }

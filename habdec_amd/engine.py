@@ -105,6 +105,16 @@ class Engine:
     def set_lowpass_trans(self, s, t): check(self.L.hd_stream_set_lowpass_trans(self.h, s, t))
     def set_dc_remove(self, s, on): check(self.L.hd_stream_set_dc_remove(self.h, s, int(on)))
     def reset_frequency_correction(self, s, c): check(self.L.hd_stream_reset_frequency_correction(self.h, s, c))
+    def set_tune(self, s, offset_hz): check(self.L.hd_stream_set_tune(self.h, s, float(offset_hz)))
+
+    def set_auto_afc(self, s, on=True, hold_s=6.0, min_hz=100.0):
+        """The server's AFC block per stream, in sample time: retune the stream (not a radio) by the AFC's correction (hd_stream_set_auto_afc)."""
+        check(self.L.hd_stream_set_auto_afc(self.h, s, int(on), float(hold_s), float(min_hz)))
+
+    def tune(self, s=0) -> dict:
+        t = capi.hd_tune_info()
+        check(self.L.hd_stream_tune(self.h, s, C.byref(t)))
+        return {"offset_hz": t.offset_hz, "step": t.step, "phase": t.phase, "retunes": t.retunes, "from_call": t.from_call, "auto_afc": bool(t.auto_afc)}
 
     def on_sentence(self, fn):
         cb = capi.SENTENCE_CB(lambda user, s, call, data, crc: fn(s, call.decode("latin-1"), data.decode("latin-1"), crc.decode("latin-1")))

@@ -108,6 +108,38 @@ int hd_stream_set_dc_remove(hd_engine* e, uint32_t stream, int on);
 /* resetFrequencyCorrection (Decoder.h:806-809 -> AFC.h:187-194) */
 int hd_stream_reset_frequency_correction(hd_engine* e, uint32_t stream, double correction);
 
+/* ---- per-stream digital tuning and closed-loop AFC (not in the reference: its server retunes the radio instead, websocketServer/main.cpp:247-263) ----
+ * A recording has no radio to retune, so the engine tunes each stream itself.  Stream s has an offset f (Hz), a phase step D and a phase P, both uint32 in
+ * units of 2^-32 cycle; fs_dec = hd_engine_decimated_rate(e).
+ *  - Where: the chunk the last decimation stage produces, after the DC blocker and before everything that reads the chunk (low-pass queue, spectrum feed,
+ *    hd_stream_decimated).  The rest of the chain sees what a receiver tuned f higher would have delivered, within the decimators' passband: offsets
+ *    near the band edge of the decimators are attenuated before the rotation.  The decimators' own state (history carries) stays unrotated.
+ *  - Step: D = (uint32_t)(int64_t)nearbyint(-(f / fs_dec) * 2^32), rounded half to even; |f| >= fs_dec / 2 is HD_ERR_INVALID.
+ *  - Phase: sample i (0 <= i < n2) of a call's chunk is rotated by theta = P + i D (mod 2^32); after the call P += n2 D.  A new offset takes effect from
+ *    the first call submitted after it was set, the phase carries on without a jump.
+ *  - Phasor: C[theta >> 24] * F[(theta >> 16) & 255], C[a] = (cos, sin)(2 pi a / 256), F[b] = (cos, sin)(2 pi b / 65536), built in double and rounded
+ *    to float once; every complex product (ur vr - ui vi, ur vi + ui vr) with each product and sum rounded separately, in both arithmetic modes.
+ *    Phase resolution 2^-16 cycle (spurs near -96 dBc).  habdec_amd_host.h restates it (hd_host_tune_*).
+ *  - f = 0 sets D = P = 0, and a stream with D = 0 is not touched at all: bit-identical to an untuned stream on the same launch path.
+ * Paths (hd_timing.path): the stream tail (2) and the step kernel (3) rotate in their stage-2 store, the separate kernels (0) in a per-chunk post-pass;
+ * the fused back end (1) declines calls with a tuned stream (they take path 0). */
+int hd_stream_set_tune(hd_engine* e, uint32_t stream, double offset_hz);
+/* The server's AFC block (websocketServer/main.cpp:247-263) counted in sample time, run per stream at each delivery right after the call's AFC step:
+ * elapsed += the call's input samples; if on, elapsed >= hold_s * sampling_rate and |frequency correction| > min_hz, then f += correction (skipped when
+ * |f + correction| >= fs_dec / 2), D is recomputed, the AFC is reset by the correction (hd_stream_reset_frequency_correction), elapsed = 0 and one retune
+ * is counted.  The new offset applies to the first call submitted after that delivery: the next call at pipeline = 0, later in the pipelined modes by
+ * the calls in flight (hd_tune_info.from_call says which).  Reference values: hold_s = 6 (the server's count() > 5 on whole seconds), min_hz = 100.
+ * A retune does not drain the pipeline.  Setting the loop resets elapsed; turning it off keeps the current offset. */
+int hd_stream_set_auto_afc(hd_engine* e, uint32_t stream, int on, double hold_s, double min_hz);
+typedef struct hd_tune_info {
+    double   offset_hz;   /* current offset: manual settings plus automatic retunes */
+    uint32_t step, phase; /* D, and P of the next call to be submitted */
+    uint64_t retunes;     /* automatic retunes so far */
+    uint64_t from_call;   /* index (hd_process_* calls from 0) of the first call that used the current offset */
+    int32_t  auto_afc;
+} hd_tune_info;
+int hd_stream_tune(hd_engine* e, uint32_t stream, hd_tune_info* out);
+
 /* ---- callbacks: Decoder::sentence_callback_ / character_callback_ (Decoder.h:135-138) ---- */
 typedef void (*hd_sentence_cb)(void* user, uint32_t stream, const char* callsign, const char* data, const char* crc);
 typedef void (*hd_chars_cb)(void* user, uint32_t stream, const char* chars, size_t n);
@@ -120,7 +152,8 @@ void hd_set_chars_callback(hd_engine* e, hd_chars_cb cb, void* user);         /*
 
 /* ---- data path: pushSamples() + operator()() (Decoder.h:206-219, 416-638) for all S streams ----
  * Stream s reads `n` cf32 samples (interleaved I,Q float32: the IQSource_File layout, IQSource_File.h:156-157)
- * starting at `iq + 2*s*stream_stride` floats.  `n_per_stream` (S entries) overrides the uniform `n` when not
+ * starting at `iq + 2*s*stream_stride` floats; stream_stride = 0 makes every stream read the same recording (one recording fanned out to streams
+ * tuned to different offsets, hd_stream_set_tune).  `n_per_stream` (S entries) overrides the uniform `n` when not
  * NULL.  Every n must be <= max_chunk and a multiple of the decimation factor (the Decoder facade keeps the
  * remainder queued on the host exactly like Decoder.h:429-435).  Returns after the decoded text of this
  * call has been delivered (callbacks fired, getters updated). */

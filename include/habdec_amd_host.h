@@ -121,6 +121,16 @@ uint64_t hd_host_iqfiles_rewinds(const hd_host_iqfiles*, uint32_t stream);
  * (a multiple of granule).  Returns the number of streams that read anything (0: all files exhausted and not looping). */
 uint32_t hd_host_iqfiles_next(hd_host_iqfiles*, float* slab, size_t stride, uint32_t* n_per_stream);
 
+/* ---- per-stream digital tuning (hd_stream_set_tune, include/habdec_amd.h): the arithmetic the kernels run, for checks without a GPU ----
+ * hd_host_tune_step: step = (uint32_t)(int64_t)nearbyint(-(offset_hz / decimated_rate) * 2^32), rounded half to even; HD_ERR_INVALID (-1) unless
+ * |offset_hz| < decimated_rate / 2.  hd_host_tune_tables: coarse[2a], coarse[2a+1] = (cos, sin)(2 pi a / 256), fine[2b], fine[2b+1] =
+ * (cos, sin)(2 pi b / 65536), a, b < 256, computed in double and rounded to float once.  hd_host_tune_rotate: out[i] = iq[i] * C[theta >> 24] *
+ * F[(theta >> 16) & 255] with theta = phase + i * step (mod 2^32), interleaved (I, Q) floats, every product and sum rounded separately (no FMA);
+ * out may equal iq. */
+int  hd_host_tune_step(double offset_hz, double decimated_rate, uint32_t* step);
+void hd_host_tune_tables(float coarse[512], float fine[512]);
+void hd_host_tune_rotate(const float* iq, size_t n, uint32_t phase, uint32_t step, float* out);
+
 #ifdef __cplusplus
 }
 #endif
