@@ -76,44 +76,51 @@ struct PinBuf {
     ~PinBuf() { if (p) (void)hipHostFree(p); }
 };
 
-struct StreamHost {
-    // control plane
-    double baud = 300;
-    float lp_bw = 1500, lp_trans = 0.025f;
-    bool dc = false;
-    // size bookkeeping mirrored from the reference
+// The size bookkeeping mirrored from the reference that one call advances.  plan_call computes every stream's next state into
+// hd_engine::mirror_next; commit_call makes it the current one (hd_engine::mirror) once the call is enqueued -- a refused call leaves it as it was.
+struct SizeState {
     size_t stage_buf[2] = {0, 0};   // Decimator::p_buff_.size()
     size_t pending = 0;             // iq_samples_decimated_.size()
     size_t fft_fill = 0;            // freq_in_.size()
-    bool have_spectrum = false;     // freq_out_.size() == 4096
-    uint64_t spectra = 0;
     size_t fir_buf = 0;             // FirFilter::buff_.size()
     uint32_t fir_T_run = 0;         // tap count of the last low-pass run (FirHistory, dev_types.h)
     uint32_t head_n = 0;            // FirHistory head, lazily: how many samples of the last run's input a later run may ask for ...
     uint64_t head_call = ~0ull;     // ... the call that run was in (its input sits in THAT call's low-pass buffer until the buffer's turn comes again) ...
     bool head_aside = false;        // ... or: the head has been copied to the side buffer (the stream did not run in the call behind its last run)
+    uint32_t tune_phase = 0;        // tuning phase of the next call to be submitted
+    uint32_t win_ub = 0, inflight_m = 0;   // upper bound of backlog samples without final window results; low-pass outputs of undelivered calls (collect() learns them back)
+    uint32_t last_n2 = 0, last_pend_before = 0, last_m = 0;   // last call (for the getters)
+    int last_buf = 0;
+};
+
+struct StreamHost {
+    // control plane
+    double baud = 300;
+    float lp_bw = 1500, lp_trans = 0.025f;
+    bool dc = false;
     hd::LowpassDesigner lp;
     bool taps_dirty = false;
+    uint32_t tune_step = 0;         // tuning step of the next call to be submitted (hd_stream_set_tune; its phase: SizeState::tune_phase)
     // data-dependent state learned back from the device
-    uint32_t held = 0, win_ub = 0, inflight_m = 0;   // win_ub: upper bound of backlog samples without final window results
+    uint32_t held = 0;
     bool sym_reset = true;          // symbol parameters changed since the window cache was built
     // host stages
     hd::TextStage text;
     hd::AfcTracker afc;
     hd::SpectrumStats stats{};
-    // last call (for the getters)
-    uint32_t last_n2 = 0, last_pend_before = 0, last_m = 0, last_nbits = 0, last_nflips = 0;
+    bool have_spectrum = false;     // freq_out_.size() == 4096
+    uint64_t spectra = 0;
+    // last call delivered (for the getters)
+    uint32_t last_nbits = 0, last_nflips = 0;
     uint64_t flip_list_full = 0;   // calls in which the device's flip list filled up (kMaxFlipsPerCall) and the search went on a call later
     uint64_t bits_total = 0;
-    int last_buf = 0;
     std::vector<uint32_t> last_words;
     uint32_t demod_ck[2] = {0, 0}, demod_ck_n = 0xFFFFFFFFu;   // discriminator checksum of the call delivered last (BitsHeader::demod_ck)
     uint64_t demod_ck_call = 0;                               // ... and that call's index (0 = the engine's first hd_process_* call)
     uint64_t demod_ck_hash = 0xCBF29CE484222325ull;           // every delivered call's (n, ck[0], ck[1]) folded into one word (hd_stream_demod_checksum_total)
-    uint64_t demod_ck_calls = 0, demod_ck_unknown = 0;        // calls folded in / calls whose slot carried no checksum (the fused back end)
+    uint64_t demod_ck_calls = 0, demod_ck_unknown = 0;        // calls folded in / calls whose slot carried no checksum (0: every route fills it)
     // digital tuning of the decimated chunk (hd_stream_set_tune, kernels/tune.h) and the closed loop over it (hd_stream_set_auto_afc)
     double tune_hz = 0;
-    uint32_t tune_step = 0, tune_phase = 0;   // step and phase of the next call to be submitted
     uint64_t tune_from = 0, retunes = 0;      // first call of the current offset; automatic retunes so far
     bool auto_afc = false;
     double afc_hold_s = 6.0, afc_min_hz = 100.0;
@@ -135,10 +142,9 @@ struct hd_engine {
     bool decode_enabled = true;
     bool fast = false;         // hd_engine_config.arith == HD_ARITH_FAST: the hd::fast kernels (fused multiply-add in every FIR; tolerance 1e-5, not bit-identical floats)
     bool one_stream = false;
-    bool no_fuse = false;      // HD_NO_FUSE: never use the fused back end (kernels/backend.hip); A/B measurements
     bool no_tail = false;      // HD_NO_TAIL: never use the one-wave stream tail (kernels/tail_body.h); A/B measurements
     uint32_t tail_max_n2 = 2048;   // HD_TAIL_MAX_N2: most decimated samples per call for which the stream tail is used
-    int last_fuse = -1;
+    int last_route = -1;       // route of the previous call (Route; the routes use the stage-2 buffers on different queues)
     // Step mode (batch decoding, kernels/decimate.hip k_step): the stream tails of call k ride in the stage-1 launch of call k+1.
     struct PendingTail { bool valid = false; hd::TailArgs ta{}; int slot = 0; bool any_fft = false; int r2 = 0, t2 = 0; } pend;
     bool own_fft = false;      // the spectrum, where it is a launch of its own, as single-wave workgroups (kernels/spectrum_wave.hip) instead of rocFFT + commit: the default; HD_ROCFFT=1 without HD_OWN_FFT=1 switches it off
@@ -172,7 +178,7 @@ struct hd_engine {
 #else
     static constexpr int cu_exp = 0;
 #endif
-    uint32_t n_cus = 0, dec_wgs_per_cu = 0;   // stage-1 linear split: workgroups per CU (0 = classic grid), see kernels/decimate.hip        // path of the previous call (the two paths use the stage-2 buffers on different queues)
+    uint32_t n_cus = 0, dec_wgs_per_cu = 0;   // stage-1 linear split: workgroups per CU (0 = classic grid), see kernels/decimate.hip
     hipStream_t qa = nullptr, qb = nullptr, qc = nullptr;   // front (decimation, spectrum) and back (FIR, symbols, results) HIP streams
     // hd_process_host: copies run on their own stream into two alternating slabs; a call returns once ITS copy has landed, so the
     // caller may reuse (or free) the buffer at once, like Decoder::pushSamples' copy -- whatever the engine still has queued.
@@ -237,6 +243,7 @@ struct hd_engine {
     bool sym_dirty = true;
 
     std::vector<StreamHost> st;
+    std::vector<SizeState> mirror, mirror_next;   // [S]: the streams' size bookkeeping; the call being planned (swapped in by commit_call)
     std::recursive_mutex mtx;   // recursive: a sentence / character callback (fired under it, on the calling thread) may call the text getters
     bool in_callback = false;   // ... but not the data getters that would have to flush the pipeline from inside a delivery
     hd_sentence_cb sentence_cb = nullptr; void* sentence_user = nullptr;
@@ -349,7 +356,6 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
     // Synchronous delivery (pipeline = 0) has nothing to overlap between calls: one queue, no cross-queue event between the front and the back half
     // (0.283 -> 0.268 ms per step at 1024 streams, 12 us of it the hop from one queue to the other).
     e->one_stream = cfg->pipeline == 0;
-    e->no_fuse = getenv("HD_NO_FUSE") != nullptr;
     e->no_tail = getenv("HD_NO_TAIL") != nullptr;
     e->no_claim = getenv("HD_NO_CLAIM") != nullptr;
     if (const char* v = getenv("HD_STEP_RUN")) e->step_run = (uint32_t)atoi(v);
@@ -386,9 +392,8 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         // collect() does not rely on it: every result slot carries the call's tag, stored last behind a wait for the writing wave's other stores
         // (BitsHeader::seq), and a slot counts as delivered when the host reads that tag.
         static const unsigned ev_flags = (unsigned)hipEventDisableSystemFence;
-        static const unsigned done_flags = ev_flags;
         HD_HIP(hipEventCreateWithFlags(&sl.ev_front, hipEventDisableTiming | ev_flags));
-        HD_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming | done_flags));
+        HD_HIP(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming | ev_flags));
         HD_HIP(hipEventCreateWithFlags(&sl.ev_params, hipEventDisableTiming | ev_flags));
         HD_HIP(hipEventCreateWithFlags(&sl.ev_spec, hipEventDisableTiming | ev_flags));
         for (hipEvent_t* ev : {&sl.t0, &sl.t1, &sl.t2, &sl.t3}) HD_HIP(hipEventCreateWithFlags(ev, ev_flags));
@@ -409,6 +414,8 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
     while (e->tail_cap < hd::kVentLimit + 1 + m_cap + 1024) e->tail_cap <<= 1;
 
     e->st.resize(S);
+    e->mirror.resize(S);
+    e->mirror_next.resize(S);
     for (auto& s : e->st) {
         s.baud = cfg->baud; s.lp_bw = cfg->lowpass_bw_hz; s.lp_trans = cfg->lowpass_trans; s.dc = cfg->dc_remove != 0;
         s.text.framer.nbits = cfg->rtty_bits; s.text.framer.nstops = cfg->rtty_stops;
@@ -689,7 +696,7 @@ int hd_stream_set_tune(hd_engine* e, uint32_t s, double offset_hz)
     if (!hd::tune_step(offset_hz, e->fsd, &d)) return fail(HD_ERR_INVALID, "tuning offset outside (-fs_dec/2, fs_dec/2)");
     StreamHost& st = e->st[s];
     st.tune_hz = offset_hz; st.tune_step = d; st.tune_from = e->calls;
-    if (offset_hz == 0) st.tune_phase = 0;
+    if (offset_hz == 0) e->mirror[s].tune_phase = 0;
     return HD_OK;
 }
 int hd_stream_set_auto_afc(hd_engine* e, uint32_t s, int on, double hold_s, double min_hz)
@@ -707,10 +714,12 @@ int hd_stream_tune(hd_engine* e, uint32_t s, hd_tune_info* out)
     if (!out) return fail(HD_ERR_INVALID, "null argument");
     std::lock_guard<std::recursive_mutex> l(e->mtx);
     const StreamHost& st = e->st[s];
-    out->offset_hz = st.tune_hz; out->step = st.tune_step; out->phase = st.tune_phase;
+    out->offset_hz = st.tune_hz; out->step = st.tune_step; out->phase = e->mirror[s].tune_phase;
     out->retunes = st.retunes; out->from_call = st.tune_from; out->auto_afc = st.auto_afc ? 1 : 0;
     return HD_OK;
 }
+
+}  // extern "C"
 
 /* ---------------------------------------------------------------- data path ------------------------------------ */
 
@@ -753,7 +762,7 @@ int run_pending_tail(hd_engine* e)
     }
     const bool own_spectrum = !ta.fft_tw && e->cfg.enable_spectrum && e->pend.any_fft;       // a transform launch follows the tails: the event goes behind that one
     if (!HDK(launch_tail, e->qa, lanes, e->pend.r2, e->pend.t2, e->S, lay, own_spectrum ? nullptr : ps.ev_done)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
-    if (own_spectrum) { if (!ta.fft_tw) { if (const int r = run_spectrum(e, e->qa, ps, e->pend.any_fft)) return r; } HD_HIP(hipEventRecord(ps.ev_done, e->qa)); }
+    if (own_spectrum) { if (const int r = run_spectrum(e, e->qa, ps, e->pend.any_fft)) return r; HD_HIP(hipEventRecord(ps.ev_done, e->qa)); }
     HD_HIP(hipGetLastError());
     return HD_OK;
 }
@@ -833,7 +842,7 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
             uint32_t d = 0;
             if (hd::tune_step(st.tune_hz + corr, e->fsd, &d)) {
                 st.tune_hz += corr; st.tune_step = d; st.tune_from = e->calls;
-                if (!d) st.tune_phase = 0;
+                if (!d) e->mirror[s].tune_phase = 0;
                 st.afc.reset(corr, hd::kFftBins, e->fsd);
                 st.afc_elapsed = 0;
                 ++st.retunes;
@@ -841,9 +850,10 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
         }
         const uint32_t* slot = sl.h_slots.p + (size_t)s * e->slot_words;
         const hd::BitsHeader* hdr = reinterpret_cast<const hd::BitsHeader*>(slot);
+        SizeState& sz = e->mirror[s];
         st.held = hdr->held_after;
-        st.inflight_m -= c.fir_m;
-        st.win_ub = hdr->uncached + st.inflight_m;
+        sz.inflight_m -= c.fir_m;
+        sz.win_ub = hdr->uncached + sz.inflight_m;
         st.last_nbits = hdr->nbits; st.last_nflips = hdr->nflips;
         st.bits_total += hdr->nbits;
         st.demod_ck[0] = hdr->demod_ck[0]; st.demod_ck[1] = hdr->demod_ck[1]; st.demod_ck_n = hdr->demod_n; st.demod_ck_call = e->delivered;
@@ -870,20 +880,559 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
     return rc;
 }
 
-int flush_locked(hd_engine* e)
+// Deliver the oldest calls until at most `depth` are undelivered.  Every call is counted as delivered; the last error is returned.
+int deliver(hd_engine* e, uint64_t depth)
 {
     int rc = HD_OK;
-    // step mode: the newest call's tails have not been launched yet -- start them before the host spends time on the older call's text
-    if (e->delivered < e->calls) { if (const int r = run_pending_tail(e)) return r; }
-    while (e->delivered < e->calls) {           // oldest first
-        const int r = collect(e, e->slot[e->delivered % hd_engine::kSlots]);
-        if (r) rc = r;
+    while (e->calls - e->delivered > depth) {           // oldest first
+        if (const int r = collect(e, e->slot[e->delivered % hd_engine::kSlots])) rc = r;
         ++e->delivered;
     }
     return rc;
 }
 
+int flush_locked(hd_engine* e)
+{
+    // step mode: the newest call's tails have not been launched yet -- start them before the host spends time on the older call's text
+    if (e->delivered < e->calls) { if (const int r = run_pending_tail(e)) return r; }
+    return deliver(e, 0);
+}
+
+/* One hd_process_device call, in stages:
+ *   plan_call    sizes and the reference's bookkeeping: the slot's StreamCall / tuning entries, a summary (CallPlan), the mirror after the call;
+ *   route_call   how the call is launched (CallRoute);
+ *   enqueue_*    the uploads, then the step launch or the front and back halves;
+ *   commit_call  the planned mirror becomes the streams', the slot goes in flight, the buffers turn;
+ *   deliver      older calls' results.
+ * No collect() runs between plan_call and commit_call: collect() writes the mirror too (inflight_m, win_ub; tune_phase on an automatic retune). */
+
+enum class Route : uint32_t {   // hd_timing.path
+    separate = 0,   // stage kernels, k_fir_demod, k_symbols, spectrum launches
+    tail = 2,       // stage 1, then the one-wave stream tails (kernels/tail_body.h) as a launch of their own
+    step = 3,       // batch mode: this call's stage 1 with the previous call's stream tails in front, one launch (kernels/decimate.hip k_step)
+};
+
+struct CallPlan {
+    size_t nst = 0;
+    uint32_t R1 = 1, R2 = 1, T1 = 0, T2 = 0;
+    uint32_t max_in = 0, min_in = 0xFFFFFFFFu, max_n1 = 0, max_n2 = 0, max_m = 0, max_taps = 0, max_new = 0, max_pend = 0;
+    uint64_t total_in = 0;
+    bool any_fft = false, any_dc = false, any_zero1 = false, any_tune = false, any_lp_restart = false;
+};
+
+struct CallRoute {
+    Route route = Route::separate;
+    int tail_lanes = 64;
+    hd::TailArgs ta{}, ta_step{};            // LDS carves of the stream tails: as a launch of their own / riding in the next call's step launch
+    bool lean = false, free_front = false, host_params = false, any_post = false, spectrum_on_qc = false;
+    const hd::StreamCall* dcall = nullptr;   // the call's parameters as the kernels read them
+    float2* feed = nullptr;                  // the spectrum collection buffer the final stage fills, or null
+};
+
+struct CallBufs {   // this call's turn of the rotating buffers
+    float2 *fcur, *fnext, *fprev, *d1;   // low-pass buffers of this call, the next one and the previous one; stage-1 output
+    int hin, hout, cin, cout;            // stage histories and discriminator carries: read / written
+};
+
+CallBufs call_bufs(const hd_engine* e)
+{
+    CallBufs b;
+    b.fcur = e->fbuf[e->cur].p; b.fnext = e->fbuf[(e->cur + 1) % 3].p; b.fprev = e->fbuf[(e->cur + 2) % 3].p;
+    b.d1 = (e->calls % 3 == 0) ? e->dec1.p : (e->calls % 3 == 1) ? e->dec1b.p : e->dec1c.p;   // never a buffer a call in flight still reads
+    b.hin = e->hist_cur; b.hout = e->hist_cur ^ 1;
+    b.cin = e->carry_cur; b.cout = e->carry_cur ^ 1;
+    return b;
+}
+
+// The host mirror of the reference's size bookkeeping -> one StreamCall per stream.  Writes the slot's host blocks and e->mirror_next, not the streams'
+// mirror.  Its one lasting side effect is the control plane's: a low-pass redesign (`redesigned`: the caller drains the pipeline and plans again).
+int plan_call(hd_engine* e, hd_engine::CallSlot& sl, const uint32_t* n_per_stream, uint32_t n_uniform, CallPlan& p, bool& redesigned)
+{
+    p = CallPlan{};
+    p.nst = e->stages.size();
+    if (p.nst > 0) { p.R1 = e->stages[0].ratio; p.T1 = (uint32_t)e->stages[0].taps.size(); }
+    if (p.nst > 1) { p.R2 = e->stages[1].ratio; p.T2 = (uint32_t)e->stages[1].taps.size(); }
+    redesigned = false;
+    for (uint32_t s = 0; s < e->S; ++s) {
+        StreamHost& st = e->st[s];
+        SizeState& nx = e->mirror_next[s];
+        nx = e->mirror[s];
+        hd::StreamCall c{};
+        const uint32_t n = n_per_stream ? n_per_stream[s] : n_uniform;
+        c.n_in = n;
+        c.n1 = n / p.R1;
+        c.n2 = c.n1 / p.R2;
+        if (n) {   // Decimator::setInput growth rule (Decimator.h:74-79, Q5)
+            if (p.nst > 0) { const size_t want = (size_t)n + p.T1 + p.R1; if (nx.stage_buf[0] < want) { nx.stage_buf[0] = want; c.zero_hist1 = 1; } }
+            if (p.nst > 1) { const size_t want = (size_t)c.n1 + p.T2 + p.R2; if (nx.stage_buf[1] < want) { nx.stage_buf[1] = want; c.zero_hist2 = 1; } }
+        }
+        c.dc_remove = st.dc && c.n2;
+        sl.h_tune.p[s] = make_uint2(st.tune_step, nx.tune_phase);     // (read by the kernels only when some stream of the call is tuned)
+        if (st.tune_step) { p.any_tune = true; nx.tune_phase += c.n2 * st.tune_step; }
+        c.pend_before = (uint32_t)nx.pending;
+        nx.pending += c.n2;
+        // spectrum collection (Decoder.h:467-489)
+        c.fft_fill = (uint32_t)nx.fft_fill;
+        if (e->cfg.enable_spectrum && n && nx.fft_fill < (size_t)hd::kFftBins && c.n2) {
+            c.fft_take = (uint32_t)std::min<size_t>(hd::kFftBins - nx.fft_fill, c.n2);
+            nx.fft_fill += c.fft_take;
+        }
+        if (e->cfg.enable_spectrum && n && nx.fft_fill >= (size_t)hd::kFftBins) { c.fft_run = 1; nx.fft_fill = 0; p.any_fft = true; }
+        // batch gate, rate gate, low-pass batch (Decoder.h:492-542)
+        const bool past_batch_gate = n && nx.pending >= hd::kFirBatch;
+        nx.last_m = 0;
+        if (past_batch_gate && !e->decode_enabled) { c.clear_pending = 1; nx.pending = 0; }
+        else if (past_batch_gate) {
+            const uint32_t m = (uint32_t)(nx.pending - nx.pending % hd::kFirBatch);
+            st.lp.batch = m;                                                       // FirFilter::setInput
+            if (st.lp.design(cutoff_rel(e, st), st.lp_trans)) {                    // LP_BlackmanHarris, Decoder.h:538 (only when a stream's batch size changes)
+                st.taps_dirty = true;
+                redesigned = true;
+            }
+            const uint32_t T = (uint32_t)st.lp.taps.size();
+            if (!T) return fail(HD_ERR_UNSUPPORTED, "low-pass transition width leaves no taps (reference filters nothing then)");
+            if (T > e->taps_cap) return fail(HD_ERR_CAPACITY, "low-pass tap count exceeds engine capacity");
+            if (nx.fir_buf < (size_t)m + T) { nx.fir_buf = (size_t)m + T; c.fir_zero_hist = 1; }   // FirFilter.h:141-147
+            c.fir_m = m; c.fir_taps = T;
+            // (tap count of the previous run, and where the first samples of that run's input are: in the previous call's buffer if that is where it ran, else aside)
+            c.fir_taps_prev = hd::sc_pack_taps_prev(nx.fir_T_run ? nx.fir_T_run : T, nx.head_n, !nx.head_aside && nx.head_call + 1 == e->calls, false);
+            nx.fir_T_run = T;
+            nx.head_n = std::min<uint32_t>(m, std::min<uint32_t>(e->head_cap, 0x3FFFu)); nx.head_call = e->calls; nx.head_aside = false;
+            nx.pending -= m;
+            nx.last_m = m;
+            p.max_m = std::max(p.max_m, m);
+            p.max_taps = std::max(p.max_taps, T);
+            p.any_lp_restart |= c.fir_zero_hist != 0;
+            // positions whose windows can become computable this call (device: k_sym_avg range), as an upper bound
+            const uint32_t pending_windows = st.sym_reset ? std::max(st.held, nx.win_ub) : nx.win_ub;
+            p.max_new = std::max(p.max_new, pending_windows + m + 64u);
+            nx.inflight_m += m;
+            nx.win_ub += m;
+        }
+        if (!c.fir_m && nx.head_n && !nx.head_aside) {
+            // no run in this call: a head that still sits in the previous call's buffer moves aside now (that buffer is rewritten two calls on)
+            if (nx.head_call + 1 == e->calls) c.fir_taps_prev = hd::sc_pack_taps_prev(0, nx.head_n, false, true);
+            else nx.head_n = 0;          // (cannot happen: the call behind a run either runs or saves)
+            nx.head_aside = true;
+        }
+        c.pend_after = (uint32_t)nx.pending;
+        p.max_pend = std::max(p.max_pend, std::max(c.pend_before, c.pend_after));
+        nx.last_n2 = c.n2; nx.last_pend_before = c.pend_before; nx.last_buf = e->cur;
+        sl.h_call.p[s] = c;
+        p.max_in = std::max(p.max_in, n); p.min_in = std::min(p.min_in, n); p.max_n1 = std::max(p.max_n1, c.n1); p.max_n2 = std::max(p.max_n2, c.n2);
+        p.any_dc |= c.dc_remove != 0;
+        p.any_zero1 |= c.zero_hist1 != 0;
+        p.total_in += n;
+    }
+    sl.total_in = p.total_in;
+    sl.r1 = p.R1;
+    sl.seq = (uint32_t)(e->calls + 1u);           // (never the tag this slot carried four calls ago)
+    if (!sl.seq) sl.seq = 1u;                     // (0 is what a slot holds before its first call: skipped when the counter wraps after 2^32 calls)
+    return HD_OK;
+}
+
+// How the call is launched.  Host-side only: it rewrites the slot's StreamCall blocks where a spectrum is read in place, and enqueues nothing.
+void route_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRoute& r)
+{
+    const uint32_t S = e->S;
+    const int R2 = (int)p.R2, T2 = (int)p.T2;
+    r = CallRoute{};
+    r.tail_lanes = S >= 2 * e->n_cus ? 64 : 256;
+    // The stream tail: stage 2 through the symbol extractor as one wave per stream that walks the call in pieces, so neither the call size nor the tap
+    // count has to fit an LDS image.  It is the right shape while a call is short: its time grows with the decimated samples per call, and beyond ~2048
+    // of them (e.g. /16 with 65536-sample pushes: 4096) the many-workgroup kernels finish a batch sooner (measured: 156 vs 173 GS/s).  It takes no
+    // DC-removing call.  (A handful of streams, long calls: the 256-lane tail in pieces of 1024 outputs where its windows fit -- one piece for a 65536-sample
+    // push at /64 --, of 256 otherwise.)
+    const bool tail = p.nst == 2 && !p.any_dc && !e->no_tail && p.max_n2 <= e->tail_max_n2 &&
+                      ((r.tail_lanes == 256 && p.max_n2 >= 512u && HDK(tail_layout, r.ta, r.tail_lanes, R2, T2, p.max_taps, e->max_R, e->min_R, e->tail_cap, p.max_pend, 64 * 1024, 4)) ||
+                       HDK(tail_layout, r.ta, r.tail_lanes, R2, T2, p.max_taps, e->max_R, e->min_R, e->tail_cap, p.max_pend, 64 * 1024));
+    // Step mode: batch decoding of equally sized pushes through a single-wave first stage -- ONE launch per call, on one queue: this call's stage 1 with
+    // the previous call's stream tails in front.  Its tails are laid out for k_step's static slot here; enqueue_step may re-lay them for k_step_cu.
+    const uint32_t step_lds = (p.R1 == 32 || p.R1 == 64) ? HDK(step_lds_bytes, (int)p.R1, (int)p.T1) : 0u;
+    const bool step = tail && e->cfg.pipeline && !e->one_stream && p.min_in == p.max_in && p.max_in && step_lds &&
+                      HDK(tail_layout, r.ta_step, 64, R2, T2, p.max_taps, e->max_R, e->min_R, e->tail_cap, p.max_pend, step_lds);
+    r.route = step ? Route::step : tail ? Route::tail : Route::separate;
+    // The separate kernels change the decimated chunk after the last stage (DC blocker, rotation of a tuned stream) in a post-pass; the stream tails
+    // rotate in their stage-2 store.
+    r.any_post = p.any_dc || (p.any_tune && !tail);
+    // Cross-queue event waits cost ~18 us each on this platform (kernel trace: stage 1 of call k+1 started 37 us after stage 1 of call k ended, two barrier
+    // packets later).  Behind a stream tail the stage-1 queue therefore waits for NOTHING: it reads the call's parameters straight from the mapped host
+    // block (32 bytes per workgroup), its output rotates over three buffers (call_bufs), and the parameter fetch for the back half rides in front of the
+    // tails on qb.
+    r.lean = tail && !e->one_stream;
+    // Round 5: the separate kernels of two-stage plans (calls too large for a one-wave tail: /16 and /256 at 4096 decimated samples per call) do not
+    // wait either: the parameter copy rides on qa behind stage 1, which reads the mapped host block.  (Kernel trace before: 15-22 us of barrier packets in
+    // front of every stage 1, on the queue a step waits for.)  What the wait protected was the low-pass buffer this call's second stage writes: three take
+    // turns, and the back half that read it last is call k-3's, which the host has collected.  The known exception is the FirHistory head the back
+    // half of call k-2 reads from that buffer (not covered by the rotation).
+    r.free_front = !tail && p.nst == 2 && !e->one_stream;
+    // One queue and the stream tails behind stage 1 (synchronous delivery): both kernels read the call's parameters from the mapped host block -- one
+    // round trip over PCIe at the start of a workgroup instead of a copy kernel in front of stage 1.  (Not where a spectrum launch reads the device copy.)
+    r.host_params = tail && !step && e->one_stream && (!e->cfg.enable_spectrum || (e->tail_fft && !p.any_dc));
+    r.dcall = r.host_params ? sl.h_call.dev : sl.d_call.p;
+    // Spectrum collection rides in the final stage's epilogue unless the post-pass must change the samples first.
+    r.feed = (e->cfg.enable_spectrum && !r.any_post) ? e->fft_in.p : nullptr;
+    if (r.route != Route::separate || !e->own_fft || !e->cfg.enable_spectrum || r.any_post || !p.any_fft) return;
+    // A call whose decimated chunk alone fills a stream's (empty) spectrum buffer: the spectrum launch reads the chunk's head in place and nothing is copied
+    // into the collection buffer (fft_take = 0 for the stage that would have fed it; fft_run = 2 for the spectrum kernel) -- at 4096 and more decimated
+    // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic, and transform + commit are one pass instead of three.
+    for (uint32_t s = 0; s < S; ++s) {
+        hd::StreamCall& c = sl.h_call.p[s];
+        if (c.fft_run == 1 && c.fft_fill == 0 && c.fft_take == (uint32_t)hd::kFftBins) { c.fft_take = 0; c.fft_run = 2; }
+    }
+    // Where every spectrum of the call is read in place (fft_run == 2 for all of them), the spectrum launch hangs on nothing but this call's chunk: it goes
+    // to the third queue behind the front half's event, off the queue a step waits for (round 5 could not: the next call's second stage refilled the
+    // collection buffer a transform on another queue was still reading -- there is no collection buffer on this route).
+    r.spectrum_on_qc = !e->one_stream && p.nst != 0;
+    for (uint32_t s = 0; s < S && r.spectrum_on_qc; ++s) r.spectrum_on_qc = sl.h_call.p[s].fft_run != 1u;
+}
+
+// Buffers of THIS call's stream tails (the LDS carve is already in t)
+void fill_tail(const hd_engine* e, const hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r, const CallBufs& b, hd::TailArgs& t)
+{
+    t.dec1 = b.d1; t.dec1_stride = e->n1_cap; t.hist2_in = e->hist2[b.hin].p; t.hist2_out = e->hist2[b.hout].p; t.taps2 = e->stage_taps[1].p;
+    t.fbuf = b.fcur; t.fbuf_next = b.fnext; t.fbuf_stride = e->fbuf_stride; t.fir_hist_cap = e->fir_hist_cap;
+    t.lp_taps = e->lp_taps.p; t.taps_stride = e->taps_cap; t.demod = e->demod.p; t.demod_stride = e->demod.n / e->S;
+    t.filtered = e->cfg.keep_filtered ? e->filtered.p : nullptr; t.carry_in = e->carry[b.cin].p; t.carry_out = e->carry[b.cout].p;
+    t.tune = p.any_tune ? sl.h_tune.dev : nullptr; t.tune_tab = e->tune_tab.p;
+    t.call = r.dcall; t.fft_in = r.feed; t.head_buf = e->fir_head.p; t.fbuf_prev = b.fprev; t.head_cap = e->head_cap;
+    t.n_streams = e->S;
+    t.ring = e->tail.p; t.ring_cap = e->tail_cap; t.sym = e->d_symstate.p; t.flipmask = e->flipmask.p; t.wsum = e->weight.p;
+    t.sp = e->d_sym.p; t.slots = sl.h_slots.dev; t.slot_words = e->slot_words; t.seq = sl.seq;
+    t.flips_dbg = e->flips_cap ? e->flips_dbg.p : nullptr; t.flips_cap = e->flips_cap;
+    const bool in_tail = e->tail_fft && e->cfg.enable_spectrum && r.feed;  // the tail transforms a completed buffer itself
+    t.fft_tw = in_tail ? e->fft_tw.p : nullptr; t.spec = e->spec.p; t.power = e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
+}
+
+// Equally sized pushes through a single-wave first stage of a two-stage plan: the stage-1 workgroups (eight resident per CU) draw runs of tiles from
+// per-XCD counters (kernels/decimate.hip) -- no cold start per run, no fixed shares that end ragged.  An empty claim where the shape does not allow it.
+// The caller advances e->step_launches once a launch that draws is enqueued (the two counter sets alternate per such launch).
+hd::StepClaim make_claim(const hd_engine* e, const CallPlan& p, uint32_t lin_wgs /* stage 1 as a launch of its own: the workgroup count of its linear split (which needs four tiles per workgroup); 0 = step launch */,
+                         uint32_t run_len_cu /* != 0: runs for a per-CU ring kernel's loaders */)
+{
+    hd::StepClaim claim{};
+    const int R1 = (int)p.R1, T1 = (int)p.T1;
+    const uint64_t S = e->S;
+    // (tiles: 64 outputs of a single-wave /32 or /64 first stage; for the per-CU ring kernels hd::ring_tiles -- 64 rows of 32 samples advancing by 57 or 58 at /32, 2048 input samples at the smaller ratios)
+    const uint32_t ntiles = run_len_cu ? HDK(ring_tiles, R1, T1, p.max_in) : (p.max_n1 + 63) / 64, n_xcd = e->n_cus / 32u, run_len = run_len_cu ? run_len_cu : e->step_run >= 2 ? e->step_run : 4u;   // (a run must hold the tile in front of which the next draw is issued: at least two; four re-read fewer halos than two)
+    const uint64_t runs = S * ntiles / run_len;
+    const bool shape_ok = run_len_cu ? (HDK(stage1_cu_supported, R1, T1) && p.max_in % 2048u == 0) : ((R1 == 32 || R1 == 64) && p.max_n1 % 64 == 0);
+    if (!e->no_claim && (p.nst == 2 || (run_len_cu && p.nst == 1)) && shape_ok && p.min_in == p.max_in && p.max_in && !p.any_zero1 && n_xcd && e->n_cus % 32u == 0 && n_xcd <= 16 &&
+        ntiles && (ntiles % run_len == 0 || (run_len_cu && R1 >= 32 && (S * ntiles) % run_len == 0)) && runs % n_xcd == 0 && S * ntiles < (1ull << 32) && (uint64_t)ntiles * S >= 4ull * lin_wgs) {
+        claim.ctr = e->step_ctr.p + (size_t)(e->step_launches & 1u) * 16 * 32;
+        claim.ctr_next = e->step_ctr.p + (size_t)((e->step_launches & 1u) ^ 1u) * 16 * 32;
+        claim.n_xcd = n_xcd; claim.runs_per_xcd = (uint32_t)(runs / n_xcd); claim.run_len = run_len;
+        if (run_len_cu && R1 >= 32 && e->ring_short_pct) {
+            // the worker waves' guided hand-out (stage1_ring.h): the last ring_short_pct per cent of an XCD's tiles go out as single tiles
+            const uint32_t tpx = claim.runs_per_xcd * run_len, whole = (uint32_t)((uint64_t)tpx * (100u - e->ring_short_pct) / 100u) / run_len;
+            claim.tiles_per_xcd = tpx; claim.short_from = whole; claim.runs_per_xcd = whole + (tpx - whole * run_len);
+        }
+    }
+    return claim;
+}
+
+// Tiles per drawn run of the per-CU ring kernels: consecutive tiles of one stream (the rows neighbouring tiles share are re-read from the XCD's L2), so it
+// must divide the stream's tile count, and the launch's runs must divide among the XCDs.  The /32 stages' worker waves draw their own runs and the
+// last runs of a launch are its ragged end: four measured best among 3 / 4 / 6 / 9 / 12 (0.1360-0.1368 ms per step against 0.1386 with nine, one box,
+// alternating); the loader / consumer kernels of the smaller ratios keep eight (round 4).  The nearest usable length, the longer one first.
+uint32_t pick_ring_run(const hd_engine* e, uint32_t R1, uint32_t ntiles)
+{
+    const uint64_t S = e->S;
+    const uint32_t n_xcd = e->n_cus / 32u ? e->n_cus / 32u : 1u, want = R1 >= 32 ? 4u : 8u;
+    // (the worker waves of the /32 and /64 stages walk a run on into the next stream: it need not divide a stream's tiles, only the slab's)
+    auto ok = [&](uint32_t r) { return r >= 2u && r <= ntiles && (R1 >= 32 ? (S * ntiles) % r == 0 : ntiles % r == 0) && (S * ntiles / r) % n_xcd == 0; };
+    if (e->ring_run >= 2 && ok(e->ring_run)) return e->ring_run;
+    for (uint32_t d = 0; d <= 8u; ++d) {
+        if (ok(want + d)) return want + d;
+        if (d && d < want && ok(want - d)) return want - d;
+    }
+    return 2u;                                     // (k_step treats shorter runs as "not drawn" while the counter sets have already alternated; make_claim refuses what does not divide)
+}
+
+// Everything of the call in front of its first launch: a drain where the route changes, the wait on call k-2, the parameter fetch, the changed tables.
+int enqueue_uploads(hd_engine* e, hd_engine::CallSlot& sl, const CallRoute& r)
+{
+    const uint32_t S = e->S;
+    hipStream_t qa = e->qa;
+    if (e->last_route >= 0 && e->last_route != (int)r.route) {   // route switch: drain (a pending tail first)
+        if (const int rc = run_pending_tail(e)) return rc;
+        HD_HIP(hipStreamSynchronize(qa)); HD_HIP(hipStreamSynchronize(e->qb));
+    }
+    e->last_route = (int)r.route;
+    e->last_timing.path = (uint32_t)r.route;
+    // (pipelined single-stage plans: the front half writes the low-pass buffer the back half of call k-2 may still be reading)
+    if (!r.lean && !r.free_front && e->calls >= 2 && !e->one_stream) HD_HIP(hipStreamWaitEvent(qa, e->slot[(e->calls - 2) % hd_engine::kSlots].ev_done, 0));
+    const bool step = r.route == Route::step;
+    sl.timed = e->timing_every && (e->calls % e->timing_every) == 0;
+    sl.timed_step = sl.timed && step;                       // a step call is ONE launch: two event records (each a barrier packet), not four
+    if (sl.timed && !step) HD_HIP(hipEventRecord(sl.t0, qa));
+    if (!r.lean && !r.free_front && !r.host_params) {
+        // the parameter block is pulled on its own queue, so it does not wait for the previous call's stage 1 to drain
+        HDK(launch_fetch_params, e->qc, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
+        if (!e->one_stream) { HD_HIP(hipEventRecord(sl.ev_params, e->qc)); HD_HIP(hipStreamWaitEvent(qa, sl.ev_params, 0)); }
+    }
+    // (nothing in flight reads the tables uploaded here: a changed table drained the pipeline before the call was planned)
+    for (uint32_t s = 0; s < S; ++s) {
+        StreamHost& st = e->st[s];
+        if (!st.taps_dirty) continue;
+        HD_HIP(hipMemcpyAsync(e->lp_taps.p + (size_t)s * e->taps_cap, st.lp.taps.data(), st.lp.taps.size() * 4, hipMemcpyHostToDevice, qa));
+        st.taps_dirty = false;
+        e->lpf_k_stale = true;
+    }
+    if (e->sym_dirty) {
+        uint32_t mr = 4;
+        for (uint32_t s = 0; s < S; ++s) {
+            e->h_sym.p[s] = symbol_params(e, e->st[s]);
+            e->h_sym.p[s].reset = e->st[s].sym_reset ? 1u : 0u;
+            mr = std::max(mr, e->h_sym.p[s].R);
+        }
+        e->max_R = mr;
+        { uint32_t lo = mr; for (uint32_t s2 = 0; s2 < S; ++s2) lo = std::min(lo, std::max<uint32_t>(e->h_sym.p[s2].R, 4)); e->min_R = lo; }
+        HD_HIP(hipMemcpyAsync(e->d_sym.p, e->h_sym.p, S * sizeof(hd::SymbolParams), hipMemcpyHostToDevice, qa));
+        e->sym_dirty = false;
+        for (uint32_t s = 0; s < S; ++s)       // a reset flag is consumed by exactly one call: upload again without it next time
+            if (e->st[s].sym_reset) { e->st[s].sym_reset = false; e->sym_dirty = true; }
+    }
+    return HD_OK;
+}
+
+// Step route: ONE launch, [tails of the previous call | this call's stage 1].  Stage 1 reads its parameters from the mapped host block and leaves the
+// device copy the tails (next launch) and the spectrum commit read.  This call's tails are left in r.ta_step for commit_call.
+int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRoute& r, const float2* iq, size_t stride)
+{
+    const uint32_t S = e->S;
+    const int R1 = (int)p.R1, T1 = (int)p.T1, R2 = (int)p.R2, T2 = (int)p.T2;
+    hipStream_t qa = e->qa;
+    const CallBufs b = call_bufs(e);
+    // Where the per-CU step kernel can serve the plan and the sizes, this call's tails are laid out for ITS slice of LDS -- a quarter of what four
+    // worker slots leave of the CU's 160 KB (23 KB: larger caches for the search phase than the 20 KB slot of the single-wave fallback) -- now, behind
+    // the symbol-table upload; the launch that runs them decides.
+    // (... and only where the per-CU kernel's runs can be drawn at all for this stream count -- an odd count never divides among the XCDs --: such
+    // batches keep the 20 KB layout and ride in k_step as before.  What is left for the fallback further down are the transitions: a launch that cannot
+    // be the per-CU kernel although the previous call expected it.)
+    const uint32_t ring_nt = HDK(ring_tiles, R1, T1, p.max_in), ring_run = pick_ring_run(e, p.R1, ring_nt), n_xcd = e->n_cus / 32u;
+    const bool runs_ok = ring_nt && n_xcd && ring_run >= 2u && ((uint64_t)S * ring_nt) % ring_run == 0 && ((uint64_t)S * ring_nt / ring_run) % n_xcd == 0;
+    const bool cu_shape = !e->no_cu_step && !e->no_claim && !p.any_zero1 && p.max_in % 2048u == 0 && runs_ok && HDK(step_cu_supported, R1, T1, R2, T2);
+    const uint32_t cu_tail = cu_shape ? HDK(step_cu_tail_lds, R1, T1) : 0u;
+    if (cu_tail) {
+        hd::TailArgs tacu{};
+        if (HDK(tail_layout, tacu, 64, R2, T2, p.max_taps, e->max_R, e->min_R, e->tail_cap, p.max_pend, cu_tail)) r.ta_step = tacu;
+    }
+    fill_tail(e, sl, p, r, b, r.ta_step);
+    hd_engine::PendingTail prev = e->pend;
+    hd_engine::CallSlot* ps = prev.valid ? &e->slot[prev.slot] : nullptr;
+    // Events of a k_step_cu launch ride on its dispatch packet (launch_step_cu): an event recorded behind it is a barrier packet of its own and
+    // costs the queue ~5 us before the next launch starts.  (Not where the spectra are a launch of their own: ev_done follows that one.)
+    bool ev_on_dispatch = false;
+    const int cu_exp = e->cu_exp;             // timing experiments only (results wrong): 1 = no tails, 2 = no stage 1
+    // One workgroup per CU (four stage-1 worker waves, the tails in the other four) where the plan and the sizes allow it
+    const bool want_cu = cu_tail && ((cu_exp & 1) || (r.ta_step.lds_bytes <= cu_tail && (!prev.valid || prev.ta.lds_bytes <= cu_tail)));
+    const hd::StepClaim claim = make_claim(e, p, 0, want_cu ? ring_run : 0u);
+    bool launched = false;
+    e->last_timing.step_variant = 0;
+    if (want_cu && claim.ctr) {
+        const uint32_t tb = std::max(r.ta_step.lds_bytes, prev.valid ? prev.ta.lds_bytes : 0u);
+        hd::StepClaim cl = claim;
+        if (cu_exp & 2) { cl.runs_per_xcd = 0; cl.tiles_per_xcd = 0; cl.short_from = 0xFFFFFFFFu; }
+        ev_on_dispatch = !ps || prev.ta.fft_tw || !prev.any_fft;
+        if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t1, qa));
+        launched = HDK(launch_step_cu, qa, R1, T1, prev.valid ? prev.r2 : R2, prev.valid ? prev.t2 : T2, S, e->n_cus, iq, stride,
+                                      e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, b.d1, e->n1_cap, sl.h_call.dev, sl.d_call.p, prev.ta,
+                                      (prev.valid && !(cu_exp & 1)) ? S : 0u, p.max_in, cl, tb,
+                                      ev_on_dispatch && sl.timed ? sl.t1 : nullptr, !ev_on_dispatch ? nullptr : sl.timed ? sl.t2 : ps ? ps->ev_done : nullptr);
+        if (!launched && ev_on_dispatch) { ev_on_dispatch = false; if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa)); }
+        e->last_timing.step_variant = launched ? 1u : 0u;
+    }
+    else if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
+    if (launched) ++e->step_launches;
+    else {
+        // (runs cut for the ring kernel's tiles are not k_step's: fixed shares, and the counter set is not drawn from; drawn runs are short, fixed
+        // shares are not: the dispatcher evens out the tail of the launch)
+        const hd::StepClaim fb = (want_cu && claim.ctr) ? hd::StepClaim{} : claim;
+        const uint32_t wgs = (fb.ctr ? 8u : 32u) * e->n_cus;
+        // The previous call's tails were laid out when THAT call was enqueued -- for k_step_cu's 23 KB slice where its shape held -- and the launch that runs
+        // them is this one.  If this launch is the single-wave fallback (the pushes grew, a stream count whose runs do not divide among the XCDs, a size
+        // that is not a multiple of 2048), a tail carved for more than k_step's static slot would read and write LDS past the workgroup's allocation
+        // (reads return 0, writes are dropped: wrong window sums and flips, no error -- ADVICE r05).  Such tails run as a launch of their own, in front,
+        // with the LDS they were laid out for; this launch then carries stage 1 only.
+        if (prev.valid && prev.ta.lds_bytes > HDK(step_lds_bytes, R1, T1)) {
+            if (const int rc = run_pending_tail(e)) return rc;     // (e->pend is still the previous call's; launches the tails, their spectra, records its ev_done)
+            prev.valid = false; ps = nullptr;
+        }
+        if (!HDK(launch_step, qa, R1, T1, prev.valid ? prev.r2 : R2, prev.valid ? prev.t2 : T2, S, p.max_n1, iq, stride, e->hist1[b.hin].p,
+                             e->hist1[b.hout].p, e->stage_taps[0].p, b.d1, e->n1_cap, sl.h_call.dev, sl.d_call.p, wgs, prev.ta, prev.valid ? S : 0u,
+                             p.any_zero1 ? 0u : p.max_in, fb))
+            return fail(HD_ERR_INVALID, "no step kernel for this decimation plan");
+        if (fb.ctr) ++e->step_launches;
+    }
+    if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t2, qa));
+    if (ps) {
+        if (!prev.ta.fft_tw) { if (const int rc = run_spectrum(e, qa, *ps, prev.any_fft)) return rc; }
+        if (!ev_on_dispatch || sl.timed) HD_HIP(hipEventRecord(ps->ev_done, qa));    // (a timed launch's own signal is its t2)
+    }
+    HD_HIP(hipGetLastError());
+    return HD_OK;
+}
+
+// The spectrum of the streams whose 4096-sample buffer completed in this call, where it is a launch of its own
+int call_spectrum(hd_engine* e, hipStream_t q, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r)
+{
+    if (!(e->cfg.enable_spectrum && p.max_n2)) return HD_OK;
+    const float2* fcur = e->fbuf[e->cur].p;
+    if (r.route == Route::separate && (r.any_post || p.nst == 0)) HDK(launch_fft_feed, q, e->S, fcur, e->fbuf_stride, e->fft_in.p, r.dcall, e->fir_hist_cap);
+    if (!p.any_fft) return HD_OK;   // (every call at >= 4096 decimated samples per push)
+    return transform_and_commit(e, q, sl.h_stats.dev, r.dcall, sl.seq, fcur);
+}
+
+// Front half on qa (routes 0 and 2): decimation, [post-pass, spectrum]
+int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r, const float2* iq, size_t stride)
+{
+    const uint32_t S = e->S, R1 = p.R1, T1 = p.T1;
+    const bool tail = r.route == Route::tail;
+    hipStream_t qa = e->qa;
+    const CallBufs b = call_bufs(e);
+    if (p.nst == 0) {
+        if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
+        HDK(launch_passthrough, qa, S, p.max_in, iq, stride, b.fcur, e->fbuf_stride, r.dcall, e->fir_hist_cap);
+        if (sl.timed) HD_HIP(hipEventRecord(sl.t2, qa));
+    } else {
+        const bool single = p.nst == 1;
+        float2* out1 = single ? b.fcur : b.d1;
+        const size_t out1_stride = single ? e->fbuf_stride : e->n1_cap;
+        // (a /64 workgroup holds 36.7 KB of LDS and ~400 VGPRs: four fit a CU, and six per CU would be a launch of one round and a half --
+        // measured at 10 MS/s, /256: 1.73 against 1.84 ms per step)
+        const uint32_t wgs_cu = (R1 == 64 && !e->dec_wgs_forced && e->dec_wgs_per_cu > 4u) ? 4u : e->dec_wgs_per_cu;
+        const uint32_t lin1 = (p.min_in == p.max_in && p.max_in) ? wgs_cu * e->n_cus : 0u;
+        // A /32 first stage over equally sized pushes: one workgroup per CU, LDS-DMA loader waves + computing waves (k_stage1_cu, stage1_ring.h)
+        bool s1_cu = false;
+        if ((single ? R1 == 4 : R1 != 4) && p.min_in == p.max_in && p.max_in && !e->no_cu_step && !p.any_zero1 && p.max_in % 2048u == 0 && HDK(stage1_cu_supported, (int)R1, (int)T1)) {
+            const hd::StepClaim cl = make_claim(e, p, 0, pick_ring_run(e, R1, HDK(ring_tiles, (int)R1, (int)T1, p.max_in)));
+            if (cl.ctr) {
+                if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
+                s1_cu = HDK(launch_stage1_cu, qa, (int)R1, (int)T1, e->n_cus, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
+                                             p.max_in, cl, e->ring_gave_up.dev, hd_engine::kS1Loaders, 16u, (e->cfg.pipeline && !tail && !single) ? hd_engine::kS1Slots : 8u,   // (/4 as the only stage is bound by the vector pipes: eight slots, 0.838 against 0.904 ms per step with four)
+                                             single ? r.dcall : nullptr, e->fir_hist_cap, single ? r.feed : nullptr);
+                if (s1_cu) ++e->step_launches;
+            }
+        }
+        e->last_timing.step_variant = s1_cu ? 1u : 0u;
+        if (!s1_cu) {
+            // (stage 1 alone is HBM-bound: drawing runs there cost 3 % -- more halo re-reads -- where the step launch gains 4 %: fixed shares)
+            if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
+            if (!HDK(launch_decimate, qa, R1, T1, S, p.max_n1, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
+                                     (r.lean || r.free_front) ? sl.h_call.dev : r.dcall, 0, single ? 1 : 0, e->fir_hist_cap, single ? r.feed : nullptr, lin1))
+                return fail(HD_ERR_INVALID, "no kernel for this decimation stage");
+        }
+        if (sl.timed) HD_HIP(hipEventRecord(sl.t2, qa));
+        if (r.free_front) HDK(launch_fetch_params, qa, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
+        if (!single && !tail) {
+            // (Round 4 measured the second stage as a ring kernel too -- /2 with sixteen outputs per lane, /4 with eight: bit-identical, and SLOWER in the
+            // pipelined step (/16: 0.338-0.342 against 0.326-0.338 ms): a ring kernel takes a CU's whole LDS, and the back half of the previous call
+            // can no longer share the CU with it.  The classic grid stays.  NOTES.md.)
+            if (!HDK(launch_decimate, qa, p.R2, p.T2, S, p.max_n2, b.d1, e->n1_cap, e->hist2[b.hin].p, e->hist2[b.hout].p, e->stage_taps[1].p, b.fcur,
+                                     e->fbuf_stride, r.dcall, 1, 1, e->fir_hist_cap, r.feed))
+                return fail(HD_ERR_INVALID, "no kernel for this decimation stage");
+        }
+    }
+    if (!tail) {
+        if (r.any_post) HDK(launch_chunk_post, qa, S, b.fcur, e->fbuf_stride, r.dcall, e->fir_hist_cap, p.any_tune ? sl.h_tune.dev : nullptr, e->tune_tab.p);
+        if (!r.spectrum_on_qc) { if (const int rc = call_spectrum(e, qa, sl, p, r)) return rc; }
+    }
+    if (!e->one_stream) HD_HIP(hipEventRecord(sl.ev_front, qa));
+    if (r.spectrum_on_qc) {
+        HD_HIP(hipStreamWaitEvent(e->qc, sl.ev_front, 0));
+        if (const int rc = call_spectrum(e, e->qc, sl, p, r)) return rc;
+        HD_HIP(hipEventRecord(sl.ev_spec, e->qc));
+    }
+    return HD_OK;
+}
+
+// Fast mode, a long low-pass (configs[4]: 4097 taps): filter through transforms -- [history | inputs | zeros] of N per stream, X conj(K), back -- so that
+// k_fir_demod is handed the filtered samples (it still does the discriminator, the ring append, the carries, the slide).  Returns the transform length in
+// *lpN, 0 where the direct sums run.
+int lowpass_transforms(hd_engine* e, const CallPlan& p, const CallRoute& r, const CallBufs& b, uint32_t* lpN)
+{
+    *lpN = 0;
+    // (Not the run that starts a stream's filter from zeros: a transform's rounding is ~1e-6 of the input's PEAK everywhere, and the start-up transient -- outputs
+    // that are exactly zero or tiny in the direct sum -- would come out as noise at that floor, which the discriminator turns into arbitrary phases.)
+    if (!e->fast || !e->lpf_N[1] || p.max_taps < hd_engine::kLpFftMinTaps || !p.max_m || p.any_lp_restart) return HD_OK;
+    const uint32_t S = e->S, Lmax = p.max_m + p.max_taps - 1;
+    const int w = Lmax <= e->lpf_N[0] ? 0 : Lmax <= e->lpf_N[1] ? 1 : -1;
+    if (w < 0) return HD_OK;
+    const uint32_t N = e->lpf_N[w];
+    hipStream_t qb = e->qb;
+    rocfft_execution_info_set_stream(e->lpf_info, qb);
+    if (e->lpf_k_stale || e->lpf_k_N != N) {           // the taps' spectra, once per design and transform length (a design change has drained the pipeline)
+        for (uint32_t s = 0; s < S; ++s) e->lpf_ntaps.p[s] = (uint32_t)e->st[s].lp.taps.size();
+        HDK(launch_lp_taps_gather, qb, S, e->lp_taps.p, e->taps_cap, e->lpf_ntaps.dev, e->lpf_k.p, N);
+        void* kb[1] = {e->lpf_k.p};
+        if (rocfft_execute(e->lpf_fwd[w], kb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass taps) failed");
+        e->lpf_k_N = N; e->lpf_k_stale = false;
+    }
+    HDK(launch_lp_gather, qb, S, b.fcur, e->fbuf_stride, e->lpf_x.p, N, r.dcall, e->fir_hist_cap, e->fir_head.p, e->head_cap, b.fprev);
+    void* xb[1] = {e->lpf_x.p};
+    if (rocfft_execute(e->lpf_fwd[w], xb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass forward) failed");
+    HDK(launch_lp_mul, qb, S, e->lpf_x.p, e->lpf_k.p, N, r.dcall);
+    if (rocfft_execute(e->lpf_inv[w], xb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass inverse) failed");
+    ++e->lpf_calls;
+    *lpN = N;
+    return HD_OK;
+}
+
+// Back half on qb (routes 0 and 2): [stage 2 +] low-pass + discriminator + buffer slide, [spectrum,] symbol extractor, results.  It may still be running
+// when the NEXT call's front half starts on qa: the two halves touch disjoint buffers (DESIGN.md "two-stream pipeline").
+int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRoute& r)
+{
+    const uint32_t S = e->S;
+    hipStream_t qb = e->qb;
+    const CallBufs b = call_bufs(e);
+    if (!e->one_stream) HD_HIP(hipStreamWaitEvent(qb, sl.ev_front, 0));
+    bool done_on_dispatch = false;
+    const bool ev_ride = !sl.timed && e->one_stream;   // (two queues: the event is not on the step's critical path, and /16 measured no better with it on the dispatch)
+    if (r.route == Route::tail) {
+        if (r.lean) HDK(launch_fetch_params, qb, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
+        fill_tail(e, sl, p, r, b, r.ta);
+        // (the call's completion event rides on the tails' dispatch where nothing is launched behind them)
+        done_on_dispatch = ev_ride && (r.ta.fft_tw || !(e->cfg.enable_spectrum && p.max_n2));
+        if (!HDK(launch_tail, qb, r.tail_lanes, (int)p.R2, (int)p.T2, S, r.ta, done_on_dispatch ? sl.ev_done : nullptr)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
+        if (!r.ta.fft_tw) { if (const int rc = call_spectrum(e, qb, sl, p, r)) return rc; }
+    } else {
+        uint32_t lpN = 0;
+        if (const int rc = lowpass_transforms(e, p, r, b, &lpN)) return rc;
+        HDK(launch_fir_demod, qb, S, p.max_m, lpN ? 0u : p.max_taps, b.fcur, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S,
+                             e->cfg.keep_filtered ? e->filtered.p : nullptr, e->carry[b.cin].p, e->carry[b.cout].p, r.dcall, e->fir_hist_cap,
+                             e->tail.p, e->tail_cap, e->d_symstate.p, b.fnext, e->fir_head.p, e->head_cap, b.fprev, e->demod_ck_acc.p,
+                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f);
+        HDK(launch_symbols, qb, S, p.max_m, p.max_new, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p,
+                           r.dcall, sl.h_slots.dev, e->slot_words, e->flips_cap ? e->flips_dbg.p : nullptr, e->flips_cap, e->min_R, sl.seq, ev_ride ? sl.ev_done : nullptr,
+                           e->demod_ck_acc.p);
+        done_on_dispatch = ev_ride;
+    }
+    if (sl.timed) HD_HIP(hipEventRecord(sl.t3, qb));
+    if (r.spectrum_on_qc) HD_HIP(hipStreamWaitEvent(qb, sl.ev_spec, 0));      // the call is complete when its spectra are
+    if (!done_on_dispatch) HD_HIP(hipEventRecord(sl.ev_done, qb));
+    HD_HIP(hipGetLastError());
+    return HD_OK;
+}
+
+// The call is enqueued: the planned mirror becomes the streams', the slot goes in flight, the buffers turn.
+void commit_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r)
+{
+    e->mirror.swap(e->mirror_next);
+    sl.busy = true;
+    if (r.route == Route::step) {   // this call's tails ride in the next call's launch
+        e->pend.valid = true; e->pend.ta = r.ta_step; e->pend.slot = (int)(e->calls % hd_engine::kSlots); e->pend.any_fft = p.any_fft;
+        e->pend.r2 = (int)p.R2; e->pend.t2 = (int)p.T2; e->pend_max_taps = p.max_taps;
+    }
+    e->cur = (e->cur + 1) % 3;
+    e->carry_cur ^= 1;
+    if (p.max_in && p.nst) e->hist_cur ^= 1;
+    ++e->calls;
+}
+
 }  // namespace
+
+extern "C" {
 
 int hd_flush(hd_engine* e)
 {
@@ -906,500 +1455,54 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + "): no new calls are accepted -- destroy the engine");
     const auto h0 = std::chrono::steady_clock::now();
     HD_HIP(hipSetDevice(e->cfg.device));
-    const uint32_t S = e->S;
     const size_t nst = e->stages.size();
     const uint32_t T1 = nst > 0 ? (uint32_t)e->stages[0].taps.size() : 0, T2 = nst > 1 ? (uint32_t)e->stages[1].taps.size() : 0;
-    const uint32_t R1 = nst > 0 ? e->stages[0].ratio : 1, R2 = nst > 1 ? e->stages[1].ratio : 1;
+    const uint32_t R1 = nst > 0 ? e->stages[0].ratio : 1;
 
-    // ---- validate first, so a rejected call leaves every stream untouched
-    for (uint32_t s = 0; s < S; ++s) {
+    // ---- validate first: a call refused before anything is enqueued leaves every stream, e->calls and the buffer rotations as they were
+    for (uint32_t s = 0; s < e->S; ++s) {
         const uint32_t n = n_per_stream ? n_per_stream[s] : n_uniform;
         if (n > e->cfg.max_chunk) return fail(HD_ERR_CAPACITY, "more samples than max_chunk");
         if (n % e->D) return fail(HD_ERR_INVALID, "sample count must be a multiple of the decimation factor (queue the remainder)");
         if (n && nst > 0 && n + 1 < T1) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the first stage's history (undefined in the reference)");
         if (n && nst > 1 && n / R1 + 1 < T2) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the second stage's history (undefined in the reference)");
     }
-    // Control-plane changes (new low-pass design, new symbol parameters) rewrite device tables the previous call's
-    // back half may still be reading: drain the pipeline first.  Rare.
+    // ---- every drain ahead of planning (collect() writes the mirror): a free slot -- cannot be wanting with depth <= 3, but never reuse a slot in
+    // flight --, then the tables: control-plane changes (new low-pass design, new symbol parameters) rewrite device tables the previous call's back half
+    // may still be reading.  Rare.
+    if (const int rc = deliver(e, hd_engine::kSlots - 1)) return rc;
     bool tables_dirty = e->sym_dirty;
-    for (uint32_t s = 0; s < S && !tables_dirty; ++s) tables_dirty = e->st[s].taps_dirty;
-    if (tables_dirty) { if (int rc = flush_locked(e)) return rc; }
-
+    for (uint32_t s = 0; s < e->S && !tables_dirty; ++s) tables_dirty = e->st[s].taps_dirty;
+    if (tables_dirty) { if (const int rc = flush_locked(e)) return rc; }
     hd_engine::CallSlot& sl = e->slot[e->calls % hd_engine::kSlots];
-    while (sl.busy) {                            // cannot happen with depth <= 3, but never reuse a slot in flight
-        if (int rc = collect(e, e->slot[e->delivered % hd_engine::kSlots])) return rc;
-        ++e->delivered;
-    }
+    CallPlan p;
+    bool redesigned = false;
+    do {   // a low-pass redesign while planning (a stream's batch size changed): drain, and plan again -- the second pass finds the designs unchanged
+        if (redesigned) { if (const int rc = flush_locked(e)) return rc; }
+        if (const int rc = plan_call(e, sl, n_per_stream, n_uniform, p, redesigned)) return rc;
+    } while (redesigned);
+    CallRoute r;
+    route_call(e, sl, p, r);
 
-    // ---- host mirror of the reference's size bookkeeping -> one StreamCall per stream
-    uint32_t max_in = 0, min_in = 0xFFFFFFFFu, max_n1 = 0, max_n2 = 0, max_m = 0, max_taps = 0, max_new = 0, max_pend = 0;
-    bool any_fft = false, any_dc = false, any_zero1 = false, any_tune = false;
-    uint64_t total_in = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-        StreamHost& st = e->st[s];
-        hd::StreamCall c{};
-        const uint32_t n = n_per_stream ? n_per_stream[s] : n_uniform;
-        c.n_in = n;
-        c.n1 = n / R1;
-        c.n2 = c.n1 / R2;
-        if (n) {   // Decimator::setInput growth rule (Decimator.h:74-79, Q5)
-            if (nst > 0) { const size_t want = (size_t)n + T1 + R1; if (st.stage_buf[0] < want) { st.stage_buf[0] = want; c.zero_hist1 = 1; } }
-            if (nst > 1) { const size_t want = (size_t)c.n1 + T2 + R2; if (st.stage_buf[1] < want) { st.stage_buf[1] = want; c.zero_hist2 = 1; } }
-        }
-        c.dc_remove = st.dc && c.n2;
-        sl.h_tune.p[s] = make_uint2(st.tune_step, st.tune_phase);     // (read by the kernels only when some stream of the call is tuned)
-        if (st.tune_step) { any_tune = true; st.tune_phase += c.n2 * st.tune_step; }
-        c.pend_before = (uint32_t)st.pending;
-        st.pending += c.n2;
-        // spectrum collection (Decoder.h:467-489)
-        c.fft_fill = (uint32_t)st.fft_fill;
-        if (e->cfg.enable_spectrum && n && st.fft_fill < (size_t)hd::kFftBins && c.n2) {
-            c.fft_take = (uint32_t)std::min<size_t>(hd::kFftBins - st.fft_fill, c.n2);
-            st.fft_fill += c.fft_take;
-        }
-        if (e->cfg.enable_spectrum && n && st.fft_fill >= (size_t)hd::kFftBins) { c.fft_run = 1; st.fft_fill = 0; any_fft = true; }
-        // batch gate, rate gate, low-pass batch (Decoder.h:492-542)
-        const bool past_batch_gate = n && st.pending >= hd::kFirBatch;
-        st.last_m = 0;
-        if (past_batch_gate && !e->decode_enabled) { c.clear_pending = 1; st.pending = 0; }
-        else if (past_batch_gate) {
-            const uint32_t m = (uint32_t)(st.pending - st.pending % hd::kFirBatch);
-            st.lp.batch = m;                                                       // FirFilter::setInput
-            if (st.lp.design(cutoff_rel(e, st), st.lp_trans)) {                    // LP_BlackmanHarris, Decoder.h:538
-                st.taps_dirty = true;
-                if (int rc = flush_locked(e)) return rc;                           // (only when a stream's batch size changes)
-            }
-            const uint32_t T = (uint32_t)st.lp.taps.size();
-            if (!T) return fail(HD_ERR_UNSUPPORTED, "low-pass transition width leaves no taps (reference filters nothing then)");
-            if (T > e->taps_cap) return fail(HD_ERR_CAPACITY, "low-pass tap count exceeds engine capacity");
-            if (st.fir_buf < (size_t)m + T) { st.fir_buf = (size_t)m + T; c.fir_zero_hist = 1; }   // FirFilter.h:141-147
-            c.fir_m = m; c.fir_taps = T;
-            // (tap count of the previous run, and where the first samples of that run's input are: in the previous call's buffer if that is where it ran, else aside)
-            c.fir_taps_prev = hd::sc_pack_taps_prev(st.fir_T_run ? st.fir_T_run : T, st.head_n, !st.head_aside && st.head_call + 1 == e->calls, false);
-            st.fir_T_run = T;
-            st.head_n = std::min<uint32_t>(m, std::min<uint32_t>(e->head_cap, 0x3FFFu)); st.head_call = e->calls; st.head_aside = false;
-            st.pending -= m;
-            st.last_m = m;
-            max_m = std::max(max_m, m);
-            max_taps = std::max(max_taps, T);
-            // positions whose windows can become computable this call (device: k_sym_avg range), as an upper bound
-            const uint32_t pending_windows = st.sym_reset ? std::max(st.held, st.win_ub) : st.win_ub;
-            max_new = std::max(max_new, pending_windows + m + 64u);
-            st.inflight_m += m;
-            st.win_ub += m;
-        }
-        if (!c.fir_m && st.head_n && !st.head_aside) {
-            // no run in this call: a head that still sits in the previous call's buffer moves aside now (that buffer is rewritten two calls on)
-            if (st.head_call + 1 == e->calls) c.fir_taps_prev = hd::sc_pack_taps_prev(0, st.head_n, false, true);
-            else st.head_n = 0;          // (cannot happen: the call behind a run either runs or saves)
-            st.head_aside = true;
-        }
-        c.pend_after = (uint32_t)st.pending;
-        max_pend = std::max(max_pend, std::max(c.pend_before, c.pend_after));
-        st.last_n2 = c.n2; st.last_pend_before = c.pend_before; st.last_buf = e->cur;
-        sl.h_call.p[s] = c;
-        max_in = std::max(max_in, n); min_in = std::min(min_in, n); max_n1 = std::max(max_n1, c.n1); max_n2 = std::max(max_n2, c.n2);
-        any_dc |= c.dc_remove != 0;
-        any_zero1 |= c.zero_hist1 != 0;
-        total_in += n;
-    }
-    sl.total_in = total_in;
-    sl.r1 = R1;
-    sl.seq = (uint32_t)(e->calls + 1u);           // (never the tag this slot carried four calls ago)
-    if (!sl.seq) sl.seq = 1u;                     // (0 is what a slot holds before its first call: skipped when the counter wraps after 2^32 calls)
-    // ---- uploads: per-call parameters, changed low-pass designs, changed symbol parameters
-    hipStream_t qa = e->qa, qb = e->qb;
-    // Two-stage plans at batch-decoding sizes: stage 2, low-pass, discriminator and slide run as ONE kernel per call on qb
-    // (kernels/backend.hip) when a stream's call fits in LDS and no DC blocker sits in between.
-    // The stream tail (kernels/tail_body.h) goes further: stage 2 through the symbol extractor as one wave per stream that walks the
-    // call in pieces, so neither the call size nor the tap count has to fit an LDS image.
-    hd::TailArgs ta{};
-    const int tail_lanes = (S >= 2 * e->n_cus ? 64 : 256);
-    // One wave per stream is the right shape while a call is short: its time grows with the decimated samples per call, and beyond
-    // ~2048 of them (e.g. /16 with 65536-sample pushes: 4096) the many-workgroup kernels finish a batch sooner (measured: 156 vs 173 GS/s).
-    // (a handful of streams, long calls: the 256-lane tail in pieces of 1024 outputs where its windows fit -- one piece for a 65536-sample push at /64 --, of 256 otherwise)
-    const bool tail = nst == 2 && !any_dc && !e->no_tail && max_n2 <= e->tail_max_n2 &&
-                      ((tail_lanes == 256 && max_n2 >= 512u && HDK(tail_layout, ta, tail_lanes, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, 64 * 1024, 4)) ||
-                       HDK(tail_layout, ta, tail_lanes, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, 64 * 1024));
-    // (the fused back end declines tuned calls as it declines DC-removing ones: they take the separate kernels, whose post-pass rotates the chunk)
-    const bool fuse = tail || (nst == 2 && !any_dc && !any_tune && !e->no_fuse && ((R2 == 2 && T2 == 69) || (R2 == 4 && T2 == 139)) &&
-                      HDK(backend_lds_bytes, (int)T2, max_n1, max_n2, max_taps) <= 64 * 1024);
-    // Step mode: batch decoding of equally sized pushes through a single-wave first stage -- ONE launch per call, on one queue: this
-    // call's stage 1 with the previous call's stream tails in front (kernels/decimate.hip k_step).
-    hd::TailArgs ta_step{};
-    const bool step = tail && e->cfg.pipeline && !e->one_stream && min_in == max_in && max_in && (R1 == 32 || R1 == 64) &&
-                      HDK(step_lds_bytes, (int)R1, (int)T1) &&
-                      HDK(tail_layout, ta_step, 64, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, HDK(step_lds_bytes, (int)R1, (int)T1));
-    const int path = step ? 3 : tail ? 2 : fuse ? 1 : 0;
-    if (e->last_fuse >= 0 && e->last_fuse != path) {   // path switch: drain (a pending tail first)
-        if (const int r = run_pending_tail(e)) return r;
-        HD_HIP(hipStreamSynchronize(qa)); HD_HIP(hipStreamSynchronize(qb));
-    }
-    e->last_fuse = path;
-    e->last_timing.path = (uint32_t)path;
-    // The separate kernels change the decimated chunk after the last stage (DC blocker, rotation of a tuned stream) in a post-pass; the stream tails rotate
-    // in their stage-2 store and take no DC-removing call.
-    const bool any_post = any_dc || (any_tune && !tail);
-    if (path == 0 && e->own_fft && e->cfg.enable_spectrum && !any_post && any_fft) {
-        // A call whose decimated chunk alone fills a stream's (empty) spectrum buffer: the spectrum launch reads the chunk's head in place and nothing is copied
-        // into the collection buffer (fft_take = 0 for the stage that would have fed it; fft_run = 2 for the spectrum kernel) -- at 4096 and more decimated
-        // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic, and transform + commit are one pass instead of three.
-        for (uint32_t s = 0; s < S; ++s) {
-            hd::StreamCall& c = sl.h_call.p[s];
-            if (c.fft_run == 1 && c.fft_fill == 0 && c.fft_take == (uint32_t)hd::kFftBins) { c.fft_take = 0; c.fft_run = 2; }
-        }
-    }
-    // Cross-queue event waits cost ~18 us each on this platform (kernel trace: stage 1 of call k+1 started 37 us after stage 1
-    // of call k ended, two barrier packets later).  On the fused path the stage-1 queue therefore waits for NOTHING: it reads the
-    // call's parameters straight from the mapped host block (32 bytes per workgroup), its output rotates over three buffers --
-    // the one it writes was last read by call k-2, which the host has already collected -- and the parameter fetch for the back
-    // half rides in front of the back end on qb.  The unfused path keeps the fetch queue and the ordering behind call k-2 (its
-    // front half writes the low-pass buffer the back half of call k-2 may still be reading).
-    const bool lean = fuse && !e->one_stream;
-    // Round 5: the unfused TWO-stage plans (calls too large for an LDS image or a one-wave tail: /16 and /256 at 4096 decimated samples per call) do not wait
-    // either.  What the wait protected was the low-pass buffer -- with three of them taking turns, the one this call's second stage writes was last read by
-    // the back half of call k-3, which the host has collected before it submits call k -- and the parameter copy rides on qa behind stage 1, which reads the
-    // mapped host block.  (Kernel trace before: 15-22 us of barrier packets in front of every stage 1, on the queue a step waits for.)
-    const bool free_front = !fuse && nst == 2 && !e->one_stream;
-    if (!lean && !free_front && e->calls >= 2 && !e->one_stream) HD_HIP(hipStreamWaitEvent(qa, e->slot[(e->calls - 2) % hd_engine::kSlots].ev_done, 0));
-    sl.timed = e->timing_every && (e->calls % e->timing_every) == 0;
-    sl.timed_step = sl.timed && step;                       // a step call is ONE launch: two event records (each a barrier packet), not four
-    if (sl.timed && !step) HD_HIP(hipEventRecord(sl.t0, qa));
-    // One queue and the stream tails behind stage 1 (synchronous delivery): both kernels read the call's parameters from the mapped host block -- one
-    // round trip over PCIe at the start of a workgroup instead of a copy kernel in front of stage 1.  (Not where a spectrum launch reads the device copy.)
-    const bool host_params = tail && !step && e->one_stream && (!e->cfg.enable_spectrum || (e->tail_fft && !any_dc));
-    if (lean || free_front) {
-        if (e->sym_dirty && e->calls > e->delivered) { if (int rc = flush_locked(e)) return rc; }   // symbol parameters are uploaded below: nothing may still read them
-    } else if (!host_params) {
-        // the parameter block is pulled on its own queue, so it does not wait for the previous call's stage 1 to drain
-        HDK(launch_fetch_params, e->qc, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
-        if (!e->one_stream) { HD_HIP(hipEventRecord(sl.ev_params, e->qc)); HD_HIP(hipStreamWaitEvent(qa, sl.ev_params, 0)); }
-    }
-    for (uint32_t s = 0; s < S; ++s) {
-        StreamHost& st = e->st[s];
-        if (!st.taps_dirty) continue;
-        HD_HIP(hipMemcpyAsync(e->lp_taps.p + (size_t)s * e->taps_cap, st.lp.taps.data(), st.lp.taps.size() * 4, hipMemcpyHostToDevice, qa));
-        st.taps_dirty = false;
-        e->lpf_k_stale = true;
-    }
-    if (e->sym_dirty) {
-        uint32_t mr = 4;
-        for (uint32_t s = 0; s < S; ++s) {
-            e->h_sym.p[s] = symbol_params(e, e->st[s]);
-            e->h_sym.p[s].reset = e->st[s].sym_reset ? 1u : 0u;
-            mr = std::max(mr, e->h_sym.p[s].R);
-        }
-        e->max_R = mr;
-        { uint32_t lo = mr; for (uint32_t s2 = 0; s2 < S; ++s2) lo = std::min(lo, std::max<uint32_t>(e->h_sym.p[s2].R, 4)); e->min_R = lo; }
-        HD_HIP(hipMemcpyAsync(e->d_sym.p, e->h_sym.p, S * sizeof(hd::SymbolParams), hipMemcpyHostToDevice, qa));
-        e->sym_dirty = false;
-        for (uint32_t s = 0; s < S; ++s)       // a reset flag is consumed by exactly one call: upload again without it next time
-            if (e->st[s].sym_reset) { e->st[s].sym_reset = false; e->sym_dirty = true; }
-    }
-    // ---- front half on qa: decimation, DC blocker, spectrum
+    // ---- enqueue.  From the first upload on, a failure leaves device-side histories part-advanced against the mirror: the engine goes into its failed state.
     const float2* iq = static_cast<const float2*>(d_iq);
-    float2* fcur = e->fbuf[e->cur].p;
-    float2* fnext = e->fbuf[(e->cur + 1) % 3].p;
-    const hd::StreamCall* dcall = host_params ? sl.h_call.dev : sl.d_call.p;
-    float2* d1 = (e->calls % 3 == 0) ? e->dec1.p : (e->calls % 3 == 1) ? e->dec1b.p : e->dec1c.p;   // never a buffer a call in flight still reads
-    const int hin = e->hist_cur, hout = e->hist_cur ^ 1;
-    // spectrum collection rides in the final stage's epilogue unless the DC blocker must see the samples first
-    float2* feed = (e->cfg.enable_spectrum && !any_post) ? e->fft_in.p : nullptr;
-    const int cin = e->carry_cur, cout = e->carry_cur ^ 1;
-    auto fill_tail = [&](hd::TailArgs& t) {      // buffers of THIS call's stream tails (the LDS carve is already in t)
-        t.dec1 = d1; t.dec1_stride = e->n1_cap; t.hist2_in = e->hist2[hin].p; t.hist2_out = e->hist2[hout].p; t.taps2 = e->stage_taps[1].p;
-        t.fbuf = fcur; t.fbuf_next = fnext; t.fbuf_stride = e->fbuf_stride; t.fir_hist_cap = e->fir_hist_cap;
-        t.lp_taps = e->lp_taps.p; t.taps_stride = e->taps_cap; t.demod = e->demod.p; t.demod_stride = e->demod.n / S;
-        t.filtered = e->cfg.keep_filtered ? e->filtered.p : nullptr; t.carry_in = e->carry[cin].p; t.carry_out = e->carry[cout].p;
-        t.tune = any_tune ? sl.h_tune.dev : nullptr; t.tune_tab = e->tune_tab.p;
-        t.call = dcall; t.fft_in = feed; t.head_buf = e->fir_head.p; t.fbuf_prev = e->fbuf[(e->cur + 2) % 3].p; t.head_cap = e->head_cap;
-        t.n_streams = S;
-        t.ring = e->tail.p; t.ring_cap = e->tail_cap; t.sym = e->d_symstate.p; t.flipmask = e->flipmask.p; t.wsum = e->weight.p;
-        t.sp = e->d_sym.p; t.slots = sl.h_slots.dev; t.slot_words = e->slot_words; t.seq = sl.seq;
-        t.flips_dbg = e->flips_cap ? e->flips_dbg.p : nullptr; t.flips_cap = e->flips_cap;
-        const bool in_tail = e->tail_fft && e->cfg.enable_spectrum && feed;  // the tail transforms a completed buffer itself
-        t.fft_tw = in_tail ? e->fft_tw.p : nullptr; t.spec = e->spec.p; t.power = e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
-    };
-    // Equally sized pushes through a single-wave first stage of a two-stage plan: the stage-1 workgroups (eight resident per CU) draw
-    // runs of tiles from per-XCD counters (kernels/decimate.hip) -- no cold start per run, no fixed shares that end ragged.
-    auto make_claim = [&](uint32_t lin_wgs /* stage 1 as a launch of its own: the workgroup count of its linear split (which needs four tiles per workgroup); 0 = step launch */,
-                          uint32_t run_len_cu = 0 /* != 0: runs for a per-CU ring kernel's loaders */) {
-        hd::StepClaim claim{};
-        // (tiles: 64 outputs of a single-wave /32 or /64 first stage; for the per-CU ring kernels hd::ring_tiles -- 64 rows of 32 samples advancing by 57 or 58 at /32, 2048 input samples at the smaller ratios)
-        const uint32_t ntiles = run_len_cu ? HDK(ring_tiles, (int)R1, (int)T1, max_in) : (max_n1 + 63) / 64, n_xcd = e->n_cus / 32u, run_len = run_len_cu ? run_len_cu : e->step_run >= 2 ? e->step_run : 4u;   // (a run must hold the tile in front of which the next draw is issued: at least two; four re-read fewer halos than two)
-        const uint64_t runs = (uint64_t)S * ntiles / run_len;
-        const bool shape_ok = run_len_cu ? (HDK(stage1_cu_supported, (int)R1, (int)T1) && max_in % 2048u == 0) : ((R1 == 32 || R1 == 64) && max_n1 % 64 == 0);
-        if (!e->no_claim && (nst == 2 || (run_len_cu && nst == 1)) && shape_ok && min_in == max_in && max_in && !any_zero1 && n_xcd && e->n_cus % 32u == 0 && n_xcd <= 16 &&
-            ntiles && (ntiles % run_len == 0 || (run_len_cu && R1 >= 32 && ((uint64_t)S * ntiles) % run_len == 0)) && runs % n_xcd == 0 && (uint64_t)S * ntiles < (1ull << 32) && (uint64_t)ntiles * S >= 4ull * lin_wgs) {   // (the two counter sets alternate: a launch that takes one must really run that way)
-            claim.ctr = e->step_ctr.p + (size_t)(e->step_launches & 1u) * 16 * 32;
-            claim.ctr_next = e->step_ctr.p + (size_t)((e->step_launches & 1u) ^ 1u) * 16 * 32;
-            claim.n_xcd = n_xcd; claim.runs_per_xcd = (uint32_t)(runs / n_xcd); claim.run_len = run_len;
-            if (run_len_cu && R1 >= 32 && e->ring_short_pct) {
-                // the worker waves' guided hand-out (stage1_ring.h): the last ring_short_pct per cent of an XCD's tiles go out as single tiles
-                const uint32_t tpx = claim.runs_per_xcd * run_len, whole = (uint32_t)((uint64_t)tpx * (100u - e->ring_short_pct) / 100u) / run_len;
-                claim.tiles_per_xcd = tpx; claim.short_from = whole; claim.runs_per_xcd = whole + (tpx - whole * run_len);
-            }
-            ++e->step_launches;
-        }
-        return claim;
-    };
-    // Tiles per drawn run of the per-CU ring kernels: consecutive tiles of one stream (the rows neighbouring tiles share are re-read from the XCD's L2), so it
-    // must divide the stream's tile count, and the launch's runs must divide among the XCDs.  The /32 stages' worker waves draw their own runs and the
-    // last runs of a launch are its ragged end: four measured best among 3 / 4 / 6 / 9 / 12 (0.1360-0.1368 ms per step against 0.1386 with nine, one box,
-    // alternating); the loader / consumer kernels of the smaller ratios keep eight (round 4).  The nearest usable length, the longer one first.
-    auto pick_ring_run = [&](const uint32_t ntiles) -> uint32_t {
-        const uint32_t n_xcd = e->n_cus / 32u ? e->n_cus / 32u : 1u, want = R1 >= 32 ? 4u : 8u;
-        // (the worker waves of the /32 and /64 stages walk a run on into the next stream: it need not divide a stream's tiles, only the slab's)
-        auto ok = [&](uint32_t r) { return r >= 2u && r <= ntiles && (R1 >= 32 ? ((uint64_t)S * ntiles) % r == 0 : ntiles % r == 0) && ((uint64_t)S * ntiles / r) % n_xcd == 0; };
-        if (e->ring_run >= 2 && ok(e->ring_run)) return e->ring_run;
-        for (uint32_t d = 0; d <= 8u; ++d) {
-            if (ok(want + d)) return want + d;
-            if (d && d < want && ok(want - d)) return want - d;
-        }
-        return 2u;                                     // (k_step treats shorter runs as "not drawn" while the counter sets have already alternated; make_claim refuses what does not divide)
-    };
-    if (step) {
-        // One launch: [tails of the previous call | this call's stage 1].  Stage 1 reads its parameters from the mapped host block and
-        // leaves the device copy the tails (next launch) and the spectrum commit read.
-        // Where the per-CU step kernel can serve the plan and the sizes, this call's tails are laid out for ITS slice of LDS -- a quarter of what four
-        // worker slots leave of the CU's 160 KB (23 KB: larger caches for the search phase than the 20 KB slot of the single-wave fallback) -- now; the
-        // launch that runs them decides.
-        // (... and only where the per-CU kernel's runs can be drawn at all for this stream count -- an odd count never divides among the XCDs --: such
-        // batches keep the 20 KB layout and ride in k_step as before.  What is left for the fallback further down are the transitions: a launch that cannot
-        // be the per-CU kernel although the previous call expected it.)
-        const uint32_t ring_nt = HDK(ring_tiles, (int)R1, (int)T1, max_in), ring_run0 = pick_ring_run(ring_nt), n_xcd0 = e->n_cus / 32u;
-        const bool runs_ok = ring_nt && n_xcd0 && ring_run0 >= 2u && ((uint64_t)S * ring_nt) % ring_run0 == 0 && ((uint64_t)S * ring_nt / ring_run0) % n_xcd0 == 0;
-        const bool cu_shape = !e->no_cu_step && !e->no_claim && !any_zero1 && max_in % 2048u == 0 && runs_ok && HDK(step_cu_supported, (int)R1, (int)T1, (int)R2, (int)T2);
-        const uint32_t cu_tail = cu_shape ? HDK(step_cu_tail_lds, (int)R1, (int)T1) : 0u;
-        if (cu_tail) {
-            hd::TailArgs tacu{};
-            if (HDK(tail_layout, tacu, 64, (int)R2, (int)T2, max_taps, e->max_R, e->min_R, e->tail_cap, max_pend, cu_tail)) ta_step = tacu;
-        }
-        fill_tail(ta_step);
-        hd_engine::PendingTail prev = e->pend;
-        hd_engine::CallSlot* ps = prev.valid ? &e->slot[prev.slot] : nullptr;
-        // Events of a k_step_cu launch ride on its dispatch packet (launch_step_cu): an event recorded behind it is a barrier packet of its own and
-        // costs the queue ~5 us before the next launch starts.  (Not where the spectra are a launch of their own: ev_done follows that one.)
-        const bool ext_events = true;
-        bool ev_on_dispatch = false;
-        uint32_t wgs = 32u * e->n_cus;                          // short runs of tiles: the dispatcher evens out the tail of the launch
-        // One workgroup per CU (four stage-1 worker waves, the tails in the other four) where the plan and the sizes allow it
-        const uint32_t ring_run = ring_run0;
-        const int cu_exp0 = e->cu_exp;             // timing experiments only (results wrong): 1 = no tails, 2 = no stage 1
-        const bool want_cu = cu_tail && ((cu_exp0 & 1) || (ta_step.lds_bytes <= cu_tail && (!prev.valid || prev.ta.lds_bytes <= cu_tail)));
-        const hd::StepClaim claim = make_claim(0, want_cu ? ring_run : 0u);
-        if (claim.ctr) wgs = 8u * e->n_cus;
-        bool launched = false;
-        e->last_timing.step_variant = 0;
-        if (want_cu && claim.ctr) {
-            const uint32_t tb = std::max(ta_step.lds_bytes, prev.valid ? prev.ta.lds_bytes : 0u);
-            hd::StepClaim cl = claim;
-            if (cu_exp0 & 2) { cl.runs_per_xcd = 0; cl.tiles_per_xcd = 0; cl.short_from = 0xFFFFFFFFu; }
-            ev_on_dispatch = ext_events && (!ps || prev.ta.fft_tw || !prev.any_fft);
-            if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t1, qa));
-            launched = HDK(launch_step_cu, qa, (int)R1, (int)T1, prev.valid ? prev.r2 : (int)R2, prev.valid ? prev.t2 : (int)T2, S, e->n_cus, iq, stride,
-                                          e->hist1[hin].p, e->hist1[hout].p, e->stage_taps[0].p, d1, e->n1_cap, sl.h_call.dev, sl.d_call.p, prev.ta,
-                                          (prev.valid && !(cu_exp0 & 1)) ? S : 0u, max_in, cl, tb,
-                                          ev_on_dispatch && sl.timed ? sl.t1 : nullptr, !ev_on_dispatch ? nullptr : sl.timed ? sl.t2 : ps ? ps->ev_done : nullptr);
-            if (!launched && ev_on_dispatch) { ev_on_dispatch = false; if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa)); }
-            e->last_timing.step_variant = launched ? 1u : 0u;
-        }
-        else if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
-        if (!launched) {
-            hd::StepClaim fb = claim;
-            if (want_cu && claim.ctr) {                        // (runs cut for the ring kernel's tiles are not k_step's: fixed shares, and the counter set was not drawn from)
-                --e->step_launches; fb = hd::StepClaim{};
-                wgs = 32u * e->n_cus;
-            }
-            // The previous call's tails were laid out when THAT call was enqueued -- for k_step_cu's 23 KB slice where its shape held -- and the launch that runs
-            // them is this one.  If this launch is the single-wave fallback (the pushes grew, a stream count whose runs do not divide among the XCDs, a size
-            // that is not a multiple of 2048), a tail carved for more than k_step's static slot would read and write LDS past the workgroup's allocation
-            // (reads return 0, writes are dropped: wrong window sums and flips, no error -- ADVICE r05).  Such tails run as a launch of their own, in front,
-            // with the LDS they were laid out for; this launch then carries stage 1 only.
-            if (prev.valid && prev.ta.lds_bytes > HDK(step_lds_bytes, (int)R1, (int)T1)) {
-                if (const int r = run_pending_tail(e)) return r;     // (e->pend is still the previous call's; launches the tails, their spectra, records its ev_done)
-                prev.valid = false; ps = nullptr;
-            }
-            if (!HDK(launch_step, qa, (int)R1, (int)T1, prev.valid ? prev.r2 : (int)R2, prev.valid ? prev.t2 : (int)T2, S, max_n1, iq, stride, e->hist1[hin].p,
-                                 e->hist1[hout].p, e->stage_taps[0].p, d1, e->n1_cap, sl.h_call.dev, sl.d_call.p, wgs, prev.ta, prev.valid ? S : 0u,
-                                 any_zero1 ? 0u : max_in, fb))
-                return fail(HD_ERR_INVALID, "no step kernel for this decimation plan");
-        }
-        if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t2, qa));
-        if (ps) {
-            if (!prev.ta.fft_tw) { if (const int r = run_spectrum(e, qa, *ps, prev.any_fft)) return r; }
-            if (!ev_on_dispatch || sl.timed) HD_HIP(hipEventRecord(ps->ev_done, qa));    // (a timed launch's own signal is its t2)
-        }
-        e->pend.valid = true; e->pend.ta = ta_step; e->pend.slot = (int)(e->calls % hd_engine::kSlots); e->pend.any_fft = any_fft;
-        e->pend.r2 = (int)R2; e->pend.t2 = (int)T2; e->pend_max_taps = max_taps;
-        HD_HIP(hipGetLastError());
-        sl.busy = true;
-        e->cur = (e->cur + 1) % 3;
-        e->carry_cur ^= 1;
-        e->hist_cur ^= 1;
-        ++e->calls;
-        e->last_timing.host_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
-        // Step launches run strictly in order on one queue, so how far the host lags behind with the results is only a matter of the
-        // host-visible slots: pipeline = 2 keeps three calls undelivered instead of two -- results one call later still, and a host that
-        // is held up for a whole launch (a descheduled thread, a burst of sentences) no longer leaves the queue empty.
-        const uint64_t depth = e->cfg.pipeline >= 2 ? 3u : 2u;
-        int rc = HD_OK;
-        while (e->calls - e->delivered > depth) {
-            const int r = collect(e, e->slot[e->delivered % hd_engine::kSlots]);
-            if (r) rc = r;
-            ++e->delivered;
-        }
+    int rc = enqueue_uploads(e, sl, r);
+    if (!rc) rc = r.route == Route::step ? enqueue_step(e, sl, p, r, iq, stride) : enqueue_front(e, sl, p, r, iq, stride);
+    if (!rc && r.route != Route::step) rc = enqueue_back(e, sl, p, r);
+    if (rc) {
+        e->device_failed = true;
+        e->fail_cause = "call " + std::to_string(e->calls) + " was enqueued in part (" + g_err + ")";
         return rc;
     }
-    if (nst == 0) {
-        if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
-        HDK(launch_passthrough, qa, S, max_in, iq, stride, fcur, e->fbuf_stride, dcall, e->fir_hist_cap);
-        if (sl.timed) HD_HIP(hipEventRecord(sl.t2, qa));
-    } else {
-        const bool single = nst == 1;
-        float2* out1 = single ? fcur : d1;
-        const size_t out1_stride = single ? e->fbuf_stride : e->n1_cap;
-        // (a /64 workgroup holds 36.7 KB of LDS and ~400 VGPRs: four fit a CU, and six per CU would be a launch of one round and a half --
-        // measured at 10 MS/s, /256: 1.73 against 1.84 ms per step)
-        const uint32_t wgs_cu = (R1 == 64 && !e->dec_wgs_forced && e->dec_wgs_per_cu > 4u) ? 4u : e->dec_wgs_per_cu;
-        const uint32_t lin1 = (min_in == max_in && max_in) ? wgs_cu * e->n_cus : 0u;
-        // A /32 first stage over equally sized pushes: one workgroup per CU, LDS-DMA loader waves + computing waves (k_stage1_cu, stage1_ring.h)
-        bool s1_cu = false;
-        if ((single ? R1 == 4 : R1 != 4) && min_in == max_in && max_in && !e->no_cu_step && !any_zero1 && max_in % 2048u == 0 && HDK(stage1_cu_supported, (int)R1, (int)T1)) {
-            const hd::StepClaim cl = make_claim(0, pick_ring_run(HDK(ring_tiles, (int)R1, (int)T1, max_in)));
-            if (cl.ctr) {
-                if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
-                s1_cu = HDK(launch_stage1_cu, qa, (int)R1, (int)T1, e->n_cus, iq, stride, e->hist1[hin].p, e->hist1[hout].p, e->stage_taps[0].p, out1, out1_stride,
-                                             max_in, cl, e->ring_gave_up.dev, hd_engine::kS1Loaders, 16u, (e->cfg.pipeline && !fuse && !single) ? hd_engine::kS1Slots : 8u,   // (/4 as the only stage is bound by the vector pipes: eight slots, 0.838 against 0.904 ms per step with four)
-                                             single ? (lean ? sl.h_call.dev : dcall) : nullptr, e->fir_hist_cap, single ? feed : nullptr);
-                if (!s1_cu) --e->step_launches;                // (the counter sets alternate per launch that really draws: this one did not)
-            }
-        }
-        e->last_timing.step_variant = s1_cu ? 1u : 0u;
-        const hd::StepClaim claim1{};                      // (stage 1 alone is HBM-bound: drawing runs there cost 3 % -- more halo re-reads -- where the step launch gains 4 %: fixed shares)
-        if (sl.timed && !s1_cu) HD_HIP(hipEventRecord(sl.t1, qa));
-        if (!s1_cu)
-        if (!HDK(launch_decimate, qa, R1, T1, S, max_n1, iq, stride, e->hist1[hin].p, e->hist1[hout].p, e->stage_taps[0].p, out1, out1_stride,
-                                 (lean || free_front) ? sl.h_call.dev : dcall, 0, single ? 1 : 0, e->fir_hist_cap, single ? feed : nullptr, lin1,
-                                 nullptr, claim1.ctr ? max_in : 0u, claim1))
-            return fail(HD_ERR_INVALID, "no kernel for this decimation stage");
-        if (sl.timed) HD_HIP(hipEventRecord(sl.t2, qa));
-        if (free_front) HDK(launch_fetch_params, qa, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
-        if (!single && !fuse) {
-            // (Round 4 measured the second stage as a ring kernel too -- /2 with sixteen outputs per lane, /4 with eight: bit-identical, and SLOWER in the
-            // pipelined step (/16: 0.338-0.342 against 0.326-0.338 ms): a ring kernel takes a CU's whole LDS, and the back half of the previous call
-            // can no longer share the CU with it.  The classic grid stays.  NOTES.md.)
-            if (!HDK(launch_decimate, qa, R2, T2, S, max_n2, d1, e->n1_cap, e->hist2[hin].p, e->hist2[hout].p, e->stage_taps[1].p, fcur,
-                                     e->fbuf_stride, dcall, 1, 1, e->fir_hist_cap, feed))
-                return fail(HD_ERR_INVALID, "no kernel for this decimation stage");
-        }
-    }
-    auto spectrum = [&](hipStream_t q) -> int {
-        if (!(e->cfg.enable_spectrum && max_n2)) return HD_OK;
-        if (!fuse && (any_post || nst == 0)) HDK(launch_fft_feed, q, S, fcur, e->fbuf_stride, e->fft_in.p, dcall, e->fir_hist_cap);
-        if (any_fft) {   // only when some stream's 4096-sample buffer completed (every call at >= 4096 decimated samples per push)
-            if (const int r = transform_and_commit(e, q, sl.h_stats.dev, dcall, sl.seq, fcur)) return r;
-        }
-        return HD_OK;
-    };
-    // Where every spectrum of the call is read in place out of this call's chunk (fft_run == 2 for all of them), the spectrum launch hangs on nothing but that
-    // chunk: it goes to the third queue behind the front half's event, off the queue a step waits for (round 5 could not: the next call's second stage refilled
-    // the collection buffer a transform on another queue was still reading -- there is no collection buffer on this route).
-    bool spectrum_on_qc = false;
-    if (!fuse) {
-        if (any_post) HDK(launch_chunk_post, qa, S, fcur, e->fbuf_stride, dcall, e->fir_hist_cap, any_tune ? sl.h_tune.dev : nullptr, e->tune_tab.p);
-        if (path == 0 && !e->one_stream && e->own_fft && e->cfg.enable_spectrum && !any_post && any_fft && nst != 0) {
-            spectrum_on_qc = true;
-            for (uint32_t s = 0; s < S && spectrum_on_qc; ++s) spectrum_on_qc = sl.h_call.p[s].fft_run != 1u;
-        }
-        if (!spectrum_on_qc) { if (const int r = spectrum(qa)) return r; }
-    }
-    if (!e->one_stream) HD_HIP(hipEventRecord(sl.ev_front, qa));
-    if (spectrum_on_qc) {
-        HD_HIP(hipStreamWaitEvent(e->qc, sl.ev_front, 0));
-        if (const int r = spectrum(e->qc)) return r;
-        HD_HIP(hipEventRecord(sl.ev_spec, e->qc));
-    }
-    // ---- back half on qb: [stage 2 +] low-pass + discriminator + buffer slide, [spectrum,] symbol extractor, results.  It may
-    // still be running when the NEXT call's front half starts on qa: the two halves touch disjoint buffers (DESIGN.md
-    // "two-stream pipeline").
-    if (!e->one_stream) HD_HIP(hipStreamWaitEvent(qb, sl.ev_front, 0));
-    bool done_on_dispatch = false;
-    const bool ev_ride = !sl.timed && e->one_stream;   // (two queues: the event is not on the step's critical path, and /16 measured no better with it on the dispatch)
-    if (tail) {
-        if (lean) HDK(launch_fetch_params, qb, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
-        fill_tail(ta);
-        // (the call's completion event rides on the tails' dispatch where nothing is launched behind them)
-        done_on_dispatch = ev_ride && (ta.fft_tw || !(e->cfg.enable_spectrum && max_n2));
-        if (!HDK(launch_tail, qb, tail_lanes, (int)R2, (int)T2, S, ta, done_on_dispatch ? sl.ev_done : nullptr)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
-        if (!ta.fft_tw) { if (const int r = spectrum(qb)) return r; }
-    } else if (fuse) {
-        if (lean) HDK(launch_fetch_params, qb, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
-        if (!HDK(launch_backend, qb, (int)R2, (int)T2, S, max_n1, max_n2, max_taps, d1, e->n1_cap, e->hist2[hin].p, e->hist2[hout].p,
-                                e->stage_taps[1].p, fcur, fcur, fnext, e->fbuf_stride, e->fir_hist_cap, e->lp_taps.p, e->taps_cap, e->demod.p,
-                                e->demod.n / S, e->cfg.keep_filtered ? e->filtered.p : nullptr, e->carry[cin].p, e->carry[cout].p, dcall, feed,
-                                e->tail.p, e->tail_cap, e->d_symstate.p, e->fir_head.p, e->head_cap, e->fbuf[(e->cur + 2) % 3].p))
-            return fail(HD_ERR_INVALID, "fused back end refused a shape it was selected for");
-        if (const int r = spectrum(qb)) return r;
-    } else {
-        // Fast mode, a long low-pass (configs[4]: 4097 taps): filter through transforms -- [history | inputs | zeros] of N per stream, X conj(K), back -- and hand
-        // k_fir_demod the filtered samples (it still does the discriminator, the ring append, the carries, the slide).
-        uint32_t lpN = 0;
-        // (Not the run that starts a stream's filter from zeros: a transform's rounding is ~1e-6 of the input's PEAK everywhere, and the start-up transient -- outputs
-        // that are exactly zero or tiny in the direct sum -- would come out as noise at that floor, which the discriminator turns into arbitrary phases.)
-        bool any_lp_restart = false;
-        for (uint32_t s = 0; s < S && !any_lp_restart; ++s) any_lp_restart = sl.h_call.p[s].fir_m && sl.h_call.p[s].fir_zero_hist;
-        if (e->fast && e->lpf_N[1] && max_taps >= hd_engine::kLpFftMinTaps && max_m && !any_lp_restart) {
-            const uint32_t Lmax = max_m + max_taps - 1;
-            const int w = Lmax <= e->lpf_N[0] ? 0 : Lmax <= e->lpf_N[1] ? 1 : -1;
-            if (w >= 0) {
-                lpN = e->lpf_N[w];
-                rocfft_execution_info_set_stream(e->lpf_info, qb);
-                if (e->lpf_k_stale || e->lpf_k_N != lpN) {           // the taps' spectra, once per design and transform length (a design change has drained the pipeline)
-                    for (uint32_t s = 0; s < S; ++s) e->lpf_ntaps.p[s] = (uint32_t)e->st[s].lp.taps.size();
-                    HDK(launch_lp_taps_gather, qb, S, e->lp_taps.p, e->taps_cap, e->lpf_ntaps.dev, e->lpf_k.p, lpN);
-                    void* kb[1] = {e->lpf_k.p};
-                    if (rocfft_execute(e->lpf_fwd[w], kb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass taps) failed");
-                    e->lpf_k_N = lpN; e->lpf_k_stale = false;
-                }
-                HDK(launch_lp_gather, qb, S, fcur, e->fbuf_stride, e->lpf_x.p, lpN, dcall, e->fir_hist_cap, e->fir_head.p, e->head_cap, e->fbuf[(e->cur + 2) % 3].p);
-                void* xb[1] = {e->lpf_x.p};
-                if (rocfft_execute(e->lpf_fwd[w], xb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass forward) failed");
-                HDK(launch_lp_mul, qb, S, e->lpf_x.p, e->lpf_k.p, lpN, dcall);
-                if (rocfft_execute(e->lpf_inv[w], xb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass inverse) failed");
-                ++e->lpf_calls;
-            }
-        }
-        HDK(launch_fir_demod, qb, S, max_m, lpN ? 0u : max_taps, fcur, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S,
-                             e->cfg.keep_filtered ? e->filtered.p : nullptr, e->carry[cin].p, e->carry[cout].p, dcall, e->fir_hist_cap,
-                             e->tail.p, e->tail_cap, e->d_symstate.p, fnext, e->fir_head.p, e->head_cap, e->fbuf[(e->cur + 2) % 3].p, e->demod_ck_acc.p,
-                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f);
-    }
-    if (!tail)
-    HDK(launch_symbols, qb, S, max_m, max_new, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p,
-                       dcall, sl.h_slots.dev, e->slot_words, e->flips_cap ? e->flips_dbg.p : nullptr, e->flips_cap, e->min_R, sl.seq, ev_ride ? sl.ev_done : nullptr,
-                       fuse ? nullptr : e->demod_ck_acc.p);      // (the fused back end, k_backend, leaves no checksum: its slots say demod_n = 0xFFFFFFFF)
-    if (!tail && ev_ride) done_on_dispatch = true;
-    if (sl.timed) HD_HIP(hipEventRecord(sl.t3, qb));
-    if (spectrum_on_qc) HD_HIP(hipStreamWaitEvent(qb, sl.ev_spec, 0));      // the call is complete when its spectra are
-    if (!done_on_dispatch) HD_HIP(hipEventRecord(sl.ev_done, qb));
-    HD_HIP(hipGetLastError());
-    sl.busy = true;
-    e->cur = (e->cur + 1) % 3;
-    e->carry_cur ^= 1;
-    if (max_in && nst) e->hist_cur ^= 1;
-    ++e->calls;
+    commit_call(e, sl, p, r);
     e->last_timing.host_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
-    if (!e->cfg.pipeline) { ++e->delivered; return collect(e, sl); }
-    // pipelined: keep up to two calls in flight; deliver the oldest one's results now (its host stage overlaps the GPU work
-    // of the newer calls, and the GPU always has the next call queued)
-    int rc = HD_OK;
-    while (e->calls - e->delivered > 2) {
-        const int r = collect(e, e->slot[e->delivered % hd_engine::kSlots]);
-        if (r) rc = r;
-        ++e->delivered;
-    }
-    return rc;
+
+    // ---- deliver.  Synchronous: this call.  Pipelined: keep up to two calls in flight and deliver the oldest one's results now (its host stage overlaps the
+    // GPU work of the newer calls, and the GPU always has the next call queued).  Step launches run strictly in order on one queue, so how far the host
+    // lags behind with the results is only a matter of the host-visible slots: pipeline = 2 keeps three calls undelivered instead of two -- results one
+    // call later still, and a host that is held up for a whole launch (a descheduled thread, a burst of sentences) no longer leaves the queue empty.
+    const uint64_t depth = !e->cfg.pipeline ? 0u : (r.route == Route::step && e->cfg.pipeline >= 2) ? 3u : 2u;
+    return deliver(e, depth);
 }
 
 void* hd_pinned_alloc(size_t bytes)
@@ -1429,7 +1532,7 @@ int hd_process_host(hd_engine* e, const float* iq, size_t stride, const uint32_t
         (void)hipGetLastError();                          // (an ordinary pointer: the query's error is not the call's)
     }
     const size_t dstride = e->cfg.max_chunk;
-    // validate the sizes before anything is queued (hd_process_device checks the rest and leaves every stream untouched on error)
+    // validate the sizes before anything is queued (hd_process_device checks the rest and leaves every stream untouched when it refuses a call)
     for (uint32_t s = 0; s < e->S; ++s)
         if ((n_per_stream ? n_per_stream[s] : n_uniform) > e->cfg.max_chunk) return fail(HD_ERR_CAPACITY, "more samples than max_chunk");
     // The copy stream is created on first use, AFTER the engine's compute streams: HIP deals streams to a handful of hardware queues in
@@ -1617,22 +1720,22 @@ size_t hd_stream_demodulated(hd_engine* e, uint32_t s, float* v, size_t cap)
 {
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
-    return fetch(e, e->demod.p + (size_t)s * (e->demod.n / e->S), e->st[s].last_m, sizeof(float), v, cap);
+    return fetch(e, e->demod.p + (size_t)s * (e->demod.n / e->S), e->mirror[s].last_m, sizeof(float), v, cap);
 }
 size_t hd_stream_decimated(hd_engine* e, uint32_t s, float* iq, size_t cap)
 {
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
-    const StreamHost& st = e->st[s];
-    const float2* src = e->fbuf[st.last_buf].p + (size_t)s * e->fbuf_stride + e->fir_hist_cap + st.last_pend_before;
-    return fetch(e, src, st.last_n2, sizeof(float2), iq, cap);
+    const SizeState& sz = e->mirror[s];
+    const float2* src = e->fbuf[sz.last_buf].p + (size_t)s * e->fbuf_stride + e->fir_hist_cap + sz.last_pend_before;
+    return fetch(e, src, sz.last_n2, sizeof(float2), iq, cap);
 }
 size_t hd_stream_filtered(hd_engine* e, uint32_t s, float* iq, size_t cap)
 {
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
     if (!e->cfg.keep_filtered) return 0;
-    return fetch(e, e->filtered.p + (size_t)s * (e->demod.n / e->S), e->st[s].last_m, sizeof(float2), iq, cap);
+    return fetch(e, e->filtered.p + (size_t)s * (e->demod.n / e->S), e->mirror[s].last_m, sizeof(float2), iq, cap);
 }
 size_t hd_stream_bits(hd_engine* e, uint32_t s, uint8_t* bits, size_t cap)
 {

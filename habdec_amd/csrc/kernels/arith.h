@@ -1,5 +1,5 @@
 // The arithmetic mode of the FIR sums (hd_engine_config.arith), chosen per translation unit: every kernel file that carries a FIR of the chain --
-// decimate.hip (+ stage1_ring.h, tail_body.h), fir_demod.hip, backend.hip, tail.hip -- is compiled twice (habdec_amd/build.py), and what it defines lives
+// decimate.hip (+ stage1_ring.h, tail_body.h), fir_demod.hip, tail.hip -- is compiled twice (habdec_amd/build.py), and what it defines lives
 // in the mode's namespace: hd::exact or hd::fast.
 //
 //   exact (default)  out = (...((x[0] k[0]) + x[1] k[1]) + ...): every product and every sum rounded separately, ascending tap order, one accumulator --

@@ -29,7 +29,7 @@ struct StepClaim {
 
 // ---- the fused stream tail (tail_body.h / tail.hip): stage 2 + low-pass + discriminator + symbol extractor, one wave per stream
 struct TailArgs {
-    // stage 2 + low-pass + discriminator (same buffers and conventions as launch_backend)
+    // stage 2 + low-pass + discriminator (same buffers and conventions as launch_decimate + launch_fir_demod)
     const float2* dec1; size_t dec1_stride;
     const float2* hist2_in; float2* hist2_out; const float* taps2;
     float2* fbuf; float2* fbuf_next; size_t fbuf_stride; uint32_t fir_hist_cap;

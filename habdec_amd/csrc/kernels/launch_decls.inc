@@ -1,6 +1,6 @@
 // Launchers of the kernels whose FIR arithmetic depends on the engine's mode (hd_engine_config.arith): declared once per mode namespace by launch.h --
 // hd::exact (separately rounded multiply and add, ascending tap order: bit-identical to the reference's CPU arithmetic) and hd::fast (fused multiply-add,
-// tolerance 1e-5: arith.h).  Defined in decimate.hip, fir_demod.hip, backend.hip and tail.hip, each compiled once per mode (build.py).
+// tolerance 1e-5: arith.h).  Defined in decimate.hip, fir_demod.hip and tail.hip, each compiled once per mode (build.py).
 // One FIR-decimate stage for all streams.  `final_stage`: output lands behind the FIR history in the
 // low-pass input buffer (offset fir_hist_cap + pend_before), else at offset 0 of `out`.
 // Returns false when (ratio, ntaps) is not one of the eight reference designs.  The kernel also carries each
@@ -39,20 +39,8 @@ void launch_lp_gather(hipStream_t st, uint32_t n_streams, const float2* fbuf, si
                       const float2* head_side, uint32_t head_cap, const float2* fbuf_prev);
 void launch_lp_taps_gather(hipStream_t st, uint32_t n_streams, const float* taps, uint32_t taps_stride, const uint32_t* ntaps, float2* kf, uint32_t N);
 void launch_lp_mul(hipStream_t st, uint32_t n_streams, float2* work, const float2* kf, uint32_t N, const StreamCall* call);
-// Fused back end of a two-stage plan (second decimation stage + low-pass + discriminator + slide), one workgroup per stream;
-// returns false when the stage design or the LDS footprint (see backend_lds_bytes) does not allow it -- the caller then
-// runs launch_decimate(stage 2) + launch_fir_demod.  `fbuf` and `fbuf_w` are the same buffer (read: history + pending,
-// written: the new decimated chunk).
-size_t backend_lds_bytes(int ntaps2, uint32_t max_n1, uint32_t max_n2, uint32_t max_taps);
-bool launch_backend(hipStream_t st, int ratio2, int ntaps2, uint32_t n_streams, uint32_t max_n1, uint32_t max_n2, uint32_t max_taps,
-                    const float2* dec1, size_t dec1_stride, const float2* hist2_in, float2* hist2_out, const float* taps2,
-                    const float2* fbuf, float2* fbuf_w, float2* fbuf_next, size_t fbuf_stride, uint32_t fir_hist_cap, const float* lp_taps,
-                    uint32_t taps_stride, float* demod, size_t demod_stride, float2* filtered, const DemodCarry* carry_in,
-                    DemodCarry* carry_out, const StreamCall* call, float2* fft_in, float* sym_ring, uint32_t ring_cap, const SymState* sym,
-                    float2* head_side /* [S][head_cap] */, uint32_t head_cap, const float2* fbuf_prev /* FirHistory, dev_types.h */);
-
 // Fills the LDS carve for `lanes` (64 or 256) lanes per stream; returns false when (ratio2, ntaps2) has no tail instantiation or the
-// windows for max_taps / max_R do not fit into lds_limit bytes -- the caller then runs launch_backend / launch_decimate + launch_fir_demod
+// windows for max_taps / max_R do not fit into lds_limit bytes -- the caller then runs launch_decimate + launch_fir_demod
 // and launch_symbols instead.
 bool tail_layout(TailArgs& a, int lanes, int ratio2, int ntaps2, uint32_t max_taps, uint32_t max_R, uint32_t min_R, uint32_t ring_cap,
                  uint32_t pend_max /* most pending samples any stream has in front of or behind this call's low-pass run */, uint32_t lds_limit,

@@ -3,9 +3,9 @@
 // mask, edge search, run means, bits), plus the bookkeeping the other kernels expect (history carries, buffer slide,
 // spectrum feed, FirHistory head, result slot).
 //
-// Why it exists.  k_backend + k_symbols (backend.hip, symbols.hip) give a stream a 256-lane workgroup each and image the
-// whole call in LDS.  Next to the HBM-bound stage-1 kernel only one such workgroup fits per CU, so in batch mode the back
-// half of call k took about as long as stage 1 of call k+1 and the step was the SUM of the two.  This body needs one
+// Why it exists.  A back half that gives a stream a 256-lane workgroup and images the whole call in LDS (the fused back
+// end this body replaced, retired since) leaves room for only one such workgroup per CU next to the HBM-bound stage-1
+// kernel, so in batch mode the back half of call k took about as long as stage 1 of call k+1 and the step was the SUM of the two.  This body needs one
 // wave, ~17 KB of LDS and no barrier: the call is walked in pieces of P stage-2 outputs whose inputs are prefetched into
 // registers one piece ahead, every stage hands its output to the next through small sliding LDS windows, and the symbol
 // extractor consumes the discriminator output as it appears.  It runs either as its own kernel (k_tail, tail.hip) or as

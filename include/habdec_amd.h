@@ -121,8 +121,7 @@ int hd_stream_reset_frequency_correction(hd_engine* e, uint32_t stream, double c
  *    to float once; every complex product (ur vr - ui vi, ur vi + ui vr) with each product and sum rounded separately, in both arithmetic modes.
  *    Phase resolution 2^-16 cycle (spurs near -96 dBc).  habdec_amd_host.h restates it (hd_host_tune_*).
  *  - f = 0 sets D = P = 0, and a stream with D = 0 is not touched at all: bit-identical to an untuned stream on the same launch path.
- * Paths (hd_timing.path): the stream tail (2) and the step kernel (3) rotate in their stage-2 store, the separate kernels (0) in a per-chunk post-pass;
- * the fused back end (1) declines calls with a tuned stream (they take path 0). */
+ * Paths (hd_timing.path): the stream tail (2) and the step kernel (3) rotate in their stage-2 store, the separate kernels (0) in a per-chunk post-pass. */
 int hd_stream_set_tune(hd_engine* e, uint32_t stream, double offset_hz);
 /* The server's AFC block (websocketServer/main.cpp:247-263) counted in sample time, run per stream at each delivery right after the call's AFC step:
  * elapsed += the call's input samples; if on, elapsed >= hold_s * sampling_rate and |frequency correction| > min_hz, then f += correction (skipped when
@@ -156,7 +155,9 @@ void hd_set_chars_callback(hd_engine* e, hd_chars_cb cb, void* user);         /*
  * tuned to different offsets, hd_stream_set_tune).  `n_per_stream` (S entries) overrides the uniform `n` when not
  * NULL.  Every n must be <= max_chunk and a multiple of the decimation factor (the Decoder facade keeps the
  * remainder queued on the host exactly like Decoder.h:429-435).  Returns after the decoded text of this
- * call has been delivered (callbacks fired, getters updated). */
+ * call has been delivered (callbacks fired, getters updated).  A call the engine refuses (bad sizes, a low-pass design that leaves no taps or exceeds
+ * the tap capacity) leaves every stream as it was; a call that fails after its first upload or launch puts the engine into its failed state
+ * (HD_ERR_DEVICE from then on). */
 int hd_process_host(hd_engine* e, const float* iq, size_t stream_stride, const uint32_t* n_per_stream, uint32_t n);
 /* Page-locked host memory the GPU addresses in place.  An IQ buffer that lives in such memory and is handed to hd_process_host of a SYNCHRONOUS engine
  * (pipeline = 0: the call returns when its kernels are done) is read by the first decimation stage straight over PCIe -- no staging copy inside the call
@@ -210,12 +211,11 @@ size_t hd_stream_fir_taps(hd_engine* e, uint32_t stream, float* taps, size_t cap
 uint32_t hd_stream_symbol_backlog(hd_engine* e, uint32_t stream);                          /* samples held by the symbol extractor */
 /* Checksum of the discriminator output (getDemodulated(), Decoder.h:131) of the call DELIVERED last for this stream, without flushing the
  * pipeline: ck[0] = sum of the samples' bit patterns, ck[1] = sum of (i + 1) * bit pattern, mod 2^32, over n samples; *call_index counts
- * hd_process_* calls from 0.  n = 0xFFFFFFFF when the launch path that served the call does not compute it (the fused back end k_backend; the
- * stream tail and the separate kernels do). */
+ * hd_process_* calls from 0.  Every launch path computes it (n = 0xFFFFFFFF only before the stream's first delivered call). */
 int hd_stream_demod_checksum(hd_engine* e, uint32_t stream, uint64_t* call_index, uint32_t* n, uint32_t ck[2]);
 /* ... and every call delivered so far folded into one word, so that a free-running batch can be compared with a CPU run call by call without reading a
  * sample: hash = fold over the delivered calls, in order, of (n, ck[0], ck[1]) with h = (h ^ x) * 0x100000001B3 starting from 0xCBF29CE484222325 (FNV-1a over
- * 32-bit words); *calls = calls folded in, *calls_without = delivered calls whose launch path left no checksum (not folded in). */
+ * 32-bit words); *calls = calls folded in, *calls_without = delivered calls whose launch path left no checksum (not folded in; 0 since every path fills it). */
 int hd_stream_demod_checksum_total(hd_engine* e, uint32_t stream, uint64_t* calls, uint64_t* calls_without, uint64_t* hash);
 uint64_t hd_stream_bits_total(hd_engine* e, uint32_t stream);                              /* symbols produced since the engine was created (delivered calls) */
 uint64_t hd_stream_flip_list_full(hd_engine* e, uint32_t stream);                          /* delivered calls in which the device's flip list (512 flip points per call) filled up: the symbol search
@@ -233,8 +233,8 @@ typedef struct hd_timing {
     double host_wait_us;    /* blocked on the GPU for the results being delivered */
     double host_text_us;    /* AFC state machines, RTTY framing, sentence scan, callbacks */
     uint64_t timed_calls;   /* how many calls carried the HIP-event timing so far (ms_* are those of the latest one) */
-    uint32_t path;          /* how the most recent call was launched: 0 separate kernels, 1 fused back end (k_backend), 2 stream tail kernel
-                             * (k_tail), 3 step kernel (k_step: stage 1 + the previous call's stream tails in one launch; ms_front is ITS duration) */
+    uint32_t path;          /* how the most recent call was launched: 0 separate kernels, 2 stream tail kernel (k_tail), 3 step kernel (k_step:
+                             * stage 1 + the previous call's stream tails in one launch; ms_front is ITS duration).  1 (a fused back end) is no longer reported */
     uint32_t step_variant;  /* 1 = the kernel that touches full-rate IQ is one workgroup per CU with LDS-DMA loader waves (stage1_ring.h): k_step_cu on path 3,
                              * k_stage1_cu (stage 1 alone) on paths 0-2; 0 = single-wave / classic workgroups (k_step, k_decimate) */
     uint64_t host_calls_in_place;   /* hd_process_host calls so far whose IQ was read in place from page-locked memory (hd_pinned_alloc): no staging copy */

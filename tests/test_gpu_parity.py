@@ -168,7 +168,6 @@ def test_short_symbols_small_averaging_windows(hd, monkeypatch, baud, path):
     from oracle import pyoracle
     if path == "separate":
         monkeypatch.setenv("HD_NO_TAIL", "1")
-        monkeypatch.setenv("HD_NO_FUSE", "1")
     fs = 2.048e6
     iq, sent = make_streams(2, fs, baud, 8, 2, seed0=300 + baud, repeat=3)
     eng, orcs, stats = run_both(hd, pyoracle, iq, fs, factor=64, baud=baud, bits=8, stops=2, lowpass_bw=5000.0, spectrum=False)
@@ -497,6 +496,63 @@ def test_control_plane_changes_mid_stream(hd, dc):
     for s in range(S):
         assert eng.rtty(s) == orcs[s].text("rtty_stream") and eng.take_chars(s) == orcs[s].text("chars_log")
         assert eng.take_sentences(s) == orcs[s].sentences()
+
+
+@pytest.mark.parametrize("pipeline", [0, 1])
+def test_refused_call_leaves_every_stream_untouched(hd, pipeline):
+    """A call refused while it is sized -- stream 1's first low-pass run with a transition width that leaves no taps -- changes no stream: /64 with
+    pushes of 19200 samples (300 decimated, not a multiple of the 256-sample batch), stream 1 idle while the others run, then its refused first push,
+    its transition restored, and every stream call by call against oracles that saw only the accepted pushes."""
+    import habdec_amd
+    from oracle import pyoracle
+    S, fs, n = 3, 2.048e6, 19200
+    iq, _ = make_streams(S, fs, 300, 8, 2, seed0=2100)
+    eng = habdec_amd.Engine(n_streams=S, max_chunk=C, sampling_rate=fs, decimation=64, keep_filtered=True, pipeline=pipeline)
+    orcs = [pyoracle.Decoder("oracle", factor=64) for _ in range(S)]
+    pos = [0] * S
+
+    def push(sizes):
+        sizes = np.array(sizes, np.uint32)
+        buf = np.zeros((S, C), np.complex64)
+        for s in range(S):
+            buf[s, :sizes[s]] = iq[s, pos[s]:pos[s] + sizes[s]]
+        habdec_amd.capi.check(eng.L.hd_process_host(eng.h, buf.ctypes.data, C, sizes.ctypes.data, 0))
+        return sizes
+
+    for k in range(3):
+        sizes = push([n, 0, n])
+        for s in range(S):
+            if sizes[s]:
+                orcs[s](iq[s, pos[s]:pos[s] + n], fs)
+                pos[s] += n
+    eng.set_lowpass_trans(1, 2.0)
+    with pytest.raises(habdec_amd.HabdecError):
+        push([n, n, n])
+    eng.set_lowpass_trans(1, 0.025)
+    k = 0
+    while max(pos) + n <= iq.shape[1]:
+        push([n, n, n])
+        for s in range(S):
+            o = orcs[s]
+            o(iq[s, pos[s]:pos[s] + n], fs)
+            pos[s] += n
+            assert same_bits(eng.decimated(s), o.array("last_decimated")), ("decimated", k, s)
+            assert same_bits(eng.demodulated(s), o.array("last_demod")), ("demod", k, s)
+            assert np.array_equal(eng.bits(s), o.bits()), ("bits", k, s)
+            assert eng.symbol_backlog(s) == o.symex_held(), ("backlog", k, s)
+            gp, op = eng.power(s), o.array("power")
+            if op.size:
+                assert power_close(gp, op), ("power", k, s)
+                assert normwise(eng.spectrum(s), o.array("spectrum")) <= 1e-5, ("spectrum", k, s)
+            ga, oa = eng.afc(s), o.afc()
+            assert (ga["peak_l"], ga["peak_r"]) == (oa["peak_l"], oa["peak_r"]), ("peaks", k, s)
+            assert ga["correction"] == pytest.approx(oa["correction"], rel=1e-9, abs=1e-9), ("correction", k, s)
+        k += 1
+    eng.flush()
+    for s in range(S):
+        assert eng.take_chars(s) == orcs[s].text("chars_log"), s
+        assert eng.take_sentences(s) == orcs[s].sentences(), s
+    assert all(len(o.sentences()) >= 1 for o in orcs)
 
 
 @pytest.mark.parametrize("pipeline", [False, True])
