@@ -146,9 +146,7 @@ struct hd_engine {
     uint32_t tail_max_n2 = 2048;   // HD_TAIL_MAX_N2: most decimated samples per call for which the stream tail is used
     int last_route = -1;       // route of the previous call (Route; the routes use the stage-2 buffers on different queues)
     // Step mode (batch decoding, kernels/decimate.hip k_step): the stream tails of call k ride in the stage-1 launch of call k+1.
-    struct PendingTail { bool valid = false; hd::TailArgs ta{}; int slot = 0; bool any_fft = false; int r2 = 0, t2 = 0; } pend;
-    bool own_fft = false;      // the spectrum, where it is a launch of its own, as single-wave workgroups (kernels/spectrum_wave.hip) instead of rocFFT + commit: the default; HD_ROCFFT=1 without HD_OWN_FFT=1 switches it off
-    bool tail_fft = true;      // a stream tail transforms its stream's completed spectrum buffer itself (kernels/spectrum_wave.h); HD_ROCFFT=1: separate launches
+    struct PendingTail { bool valid = false; hd::TailArgs ta{}; int slot = 0; int r2 = 0, t2 = 0; } pend;
     DevBuf<float2> fft_tw;     // (cos, -sin)(2 pi m / 4096), rounded once from double
     bool no_claim = false;     // HD_NO_CLAIM: step launches with fixed shares of tiles (A/B measurements)
     uint32_t step_run = 0;     // HD_STEP_RUN: tiles per drawn run (default 4, minimum 2)
@@ -189,8 +187,6 @@ struct hd_engine {
     uint64_t host_calls = 0, host_calls_in_place = 0;   // hd_process_host calls through the staging slabs / served in place from page-locked memory
     uint32_t timing_every = 8;   // HIP-event timing on every Nth call (0 = off): each event record is a barrier packet worth ~6 us of queue time
     hd_timing last_timing{};
-    rocfft_plan fft_plan = nullptr;
-    rocfft_execution_info fft_info = nullptr;
     // Fast mode, long low-pass filters (>= kLpFftMinTaps taps: configs[4]'s 4097): the filter as transforms (kernels/fir_demod.hip: k_lp_gather / k_lp_mul around
     // rocFFT, k_fir_demod with the filtered samples handed in).  Two transform lengths, the smaller one where [history | inputs] of every stream fits it.
     static constexpr uint32_t kLpFftMinTaps = 1024;
@@ -203,9 +199,8 @@ struct hd_engine {
     uint32_t lpf_k_N = 0;                  // ... and the transform length (0: none yet)
     bool lpf_k_stale = true;
     uint64_t lpf_calls = 0;
-    DevBuf<char> fft_work;
 
-    DevBuf<float2> staging, dec1, dec1b, dec1c, hist1[2], hist2[2], fbuf[3], fft_in, fft_raw, spec, filtered;   // dec1/b/c: stage-1 output, rotating per call
+    DevBuf<float2> staging, dec1, dec1b, dec1c, hist1[2], hist2[2], fbuf[3], fft_in, spec, filtered;   // dec1/b/c: stage-1 output, rotating per call
     DevBuf<float> stage_taps[2], lp_taps, power, demod, tail, weight;
     DevBuf<unsigned long long> flipmask;
     DevBuf<uint32_t> flips_dbg;
@@ -253,8 +248,6 @@ struct hd_engine {
 
     ~hd_engine()
     {
-        if (fft_plan) rocfft_plan_destroy(fft_plan);
-        if (fft_info) rocfft_execution_info_destroy(fft_info);
         for (rocfft_plan pl : {lpf_fwd[0], lpf_fwd[1], lpf_inv[0], lpf_inv[1]}) if (pl) rocfft_plan_destroy(pl);
         if (lpf_info) rocfft_execution_info_destroy(lpf_info);
         if (qa) (void)hipStreamDestroy(qa);
@@ -490,7 +483,6 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
     }
     if (cfg->enable_spectrum) {
         HD_HIP(e->fft_in.alloc((size_t)S * hd::kFftBins));
-        HD_HIP(e->fft_raw.alloc((size_t)S * hd::kFftBins));
         HD_HIP(e->spec.alloc((size_t)S * hd::kFftBins));
         HD_HIP(e->power.alloc((size_t)S * hd::kFftBins));
         for (auto& sl : e->slot) HD_HIP(sl.h_stats.alloc(S));
@@ -502,25 +494,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
             }
             HD_HIP(e->fft_tw.alloc(hd::kFftBins));
             HD_HIP(hipMemcpy(e->fft_tw.p, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-            e->tail_fft = getenv("HD_ROCFFT") == nullptr;
-            // (round 6: where the spectrum is a launch of its own -- the separate-kernels path -- it is the single-wave kernel by default: it reads a chunk that
-            // fills the buffer by itself in place, and transform + commit are one pass; HD_ROCFFT=1 alone: rocFFT + k_spectrum_commit)
-            e->own_fft = e->tail_fft || getenv("HD_OWN_FFT") != nullptr;
         }
-        std::call_once(g_rocfft_once, [] { rocfft_setup(); });
-        const size_t len = hd::kFftBins;
-        if (rocfft_plan_create(&e->fft_plan, rocfft_placement_notinplace, rocfft_transform_type_complex_forward,
-                               rocfft_precision_single, 1, &len, S, nullptr) != rocfft_status_success)
-            return fail(HD_ERR_DEVICE, "rocfft_plan_create failed");
-        if (rocfft_execution_info_create(&e->fft_info) != rocfft_status_success)
-            return fail(HD_ERR_DEVICE, "rocfft_execution_info_create failed");
-        size_t wsz = 0;
-        rocfft_plan_get_work_buffer_size(e->fft_plan, &wsz);
-        if (wsz) {
-            HD_HIP(e->fft_work.alloc(wsz));
-            rocfft_execution_info_set_work_buffer(e->fft_info, e->fft_work.p, wsz);
-        }
-        rocfft_execution_info_set_stream(e->fft_info, e->qa);
     }
     if (e->fast && e->taps_cap >= hd_engine::kLpFftMinTaps && getenv("HD_NO_LP_FFT") == nullptr) {     // (HD_NO_LP_FFT=1: long filters as direct sums in fast mode too)
         std::call_once(g_rocfft_once, [] { rocfft_setup(); });
@@ -541,7 +515,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HD_HIP(e->lpf_k.alloc((size_t)S * N));
         HD_HIP(e->lpf_ntaps.alloc(S));
     }
-    // Pay first-use costs now (rocFFT's first execute alone stalls ~7 ms): run every kernel once on an all-idle call.
+    // Pay first-use costs now: run every kernel once on an all-idle call.
     {
         hd_engine::CallSlot& sl = e->slot[0];
         hipStream_t q = e->qa;
@@ -557,10 +531,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HDK(launch_chunk_post, q, S, e->fbuf[0].p, e->fbuf_stride, sl.d_call.p, e->fir_hist_cap, nullptr, e->tune_tab.p);
         if (cfg->enable_spectrum) {
             HDK(launch_fft_feed, q, S, e->fbuf[0].p, e->fbuf_stride, e->fft_in.p, sl.d_call.p, e->fir_hist_cap);
-            void* in[1] = {e->fft_in.p};
-            void* outb[1] = {e->fft_raw.p};
-            if (rocfft_execute(e->fft_plan, in, outb, e->fft_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute failed");
-            hd::launch_spectrum_commit(q, S, e->fft_raw.p, e->spec.p, e->power.p, sl.h_stats.dev, sl.d_call.p, e->fsd, e->bins_sep, 0u);
+            hd::launch_spectrum_wave(q, S, e->fft_in.p, e->fft_tw.p, e->spec.p, e->power.p, sl.h_stats.dev, sl.d_call.p, e->fsd, e->bins_sep, 0u);   // (fft_run = 0 everywhere: every wave returns at once)
         }
         HDK(launch_fir_demod, q, S, 0, 0, e->fbuf[0].p, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S, nullptr, e->carry[0].p,
                              e->carry[1].p, sl.d_call.p, e->fir_hist_cap, e->tail.p, e->tail_cap, e->d_symstate.p, e->fbuf[1].p,
@@ -725,27 +696,6 @@ int hd_stream_tune(hd_engine* e, uint32_t s, hd_tune_info* out)
 
 namespace {
 
-// rocFFT + commit for the streams whose 4096-sample buffer completed in the call that owns `sl` (Decoder.h:475-489)
-int transform_and_commit(hd_engine* e, hipStream_t q, hd::SpectrumStatsDev* stats_dev, const hd::StreamCall* dcall, uint32_t seq, const float2* chunk = nullptr)
-{
-    if (e->own_fft) {   // one launch, one wave per stream (kernels/spectrum_wave.hip)
-        hd::launch_spectrum_wave(q, e->S, e->fft_in.p, e->fft_tw.p, e->spec.p, e->power.p, stats_dev, dcall, e->fsd, e->bins_sep, seq, chunk, e->fbuf_stride, e->fir_hist_cap);
-        return HD_OK;
-    }
-    void* in[1] = {e->fft_in.p};
-    void* outb[1] = {e->fft_raw.p};
-    rocfft_execution_info_set_stream(e->fft_info, q);
-    if (rocfft_execute(e->fft_plan, in, outb, e->fft_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute failed");
-    hd::launch_spectrum_commit(q, e->S, e->fft_raw.p, e->spec.p, e->power.p, stats_dev, dcall, e->fsd, e->bins_sep, seq);
-    return HD_OK;
-}
-
-int run_spectrum(hd_engine* e, hipStream_t q, hd_engine::CallSlot& sl, bool any_fft)
-{
-    if (!e->cfg.enable_spectrum || !any_fft) return HD_OK;
-    return transform_and_commit(e, q, sl.h_stats.dev, sl.d_call.p, sl.seq);
-}
-
 // Step mode: the tails of the newest call have not been launched yet (they wait for the next call's launch).  Run them now, as a
 // kernel of their own -- the next call is not coming (flush), or its results are wanted first.
 int run_pending_tail(hd_engine* e)
@@ -760,9 +710,7 @@ int run_pending_tail(hd_engine* e)
         // (same buffers, other LDS offsets)
         if (!HDK(tail_layout, lay, lanes, e->pend.r2, e->pend.t2, e->pend_max_taps, e->max_R, e->min_R, e->tail_cap, e->pend.ta.pend_max, 64 * 1024)) return fail(HD_ERR_INVALID, "stream tail layout");
     }
-    const bool own_spectrum = !ta.fft_tw && e->cfg.enable_spectrum && e->pend.any_fft;       // a transform launch follows the tails: the event goes behind that one
-    if (!HDK(launch_tail, e->qa, lanes, e->pend.r2, e->pend.t2, e->S, lay, own_spectrum ? nullptr : ps.ev_done)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
-    if (own_spectrum) { if (const int r = run_spectrum(e, e->qa, ps, e->pend.any_fft)) return r; HD_HIP(hipEventRecord(ps.ev_done, e->qa)); }
+    if (!HDK(launch_tail, e->qa, lanes, e->pend.r2, e->pend.t2, e->S, lay, ps.ev_done)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
     HD_HIP(hipGetLastError());
     return HD_OK;
 }
@@ -805,7 +753,7 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
         for (uint32_t s = 0; s < e->S && !e->device_failed && !timing_experiment; ++s) {
             await(&reinterpret_cast<const volatile hd::BitsHeader*>(sl.h_slots.p + (size_t)s * e->slot_words)->seq, "result slot", s);
             // ... and the spectrum statistics of a stream whose buffer completed in this call: written by the tail itself (behind the same tag) or by a
-            // commit / spectrum launch of its own, whose stores no event of this engine fences
+            // spectrum launch of its own, whose stores no event of this engine fences
             if (!e->device_failed && e->cfg.enable_spectrum && sl.h_stats.p && sl.h_call.p[s].fft_run)
                 await(reinterpret_cast<const volatile uint32_t*>(&sl.h_stats.p[s].seq), "spectrum statistics", s);
         }
@@ -1067,15 +1015,15 @@ void route_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRo
     // half of call k-2 reads from that buffer (not covered by the rotation).
     r.free_front = !tail && p.nst == 2 && !e->one_stream;
     // One queue and the stream tails behind stage 1 (synchronous delivery): both kernels read the call's parameters from the mapped host block -- one
-    // round trip over PCIe at the start of a workgroup instead of a copy kernel in front of stage 1.  (Not where a spectrum launch reads the device copy.)
-    r.host_params = tail && !step && e->one_stream && (!e->cfg.enable_spectrum || (e->tail_fft && !p.any_dc));
+    // round trip over PCIe at the start of a workgroup instead of a copy kernel in front of stage 1.
+    r.host_params = tail && !step && e->one_stream;
     r.dcall = r.host_params ? sl.h_call.dev : sl.d_call.p;
     // Spectrum collection rides in the final stage's epilogue unless the post-pass must change the samples first.
     r.feed = (e->cfg.enable_spectrum && !r.any_post) ? e->fft_in.p : nullptr;
-    if (r.route != Route::separate || !e->own_fft || !e->cfg.enable_spectrum || r.any_post || !p.any_fft) return;
+    if (r.route != Route::separate || !e->cfg.enable_spectrum || r.any_post || !p.any_fft) return;
     // A call whose decimated chunk alone fills a stream's (empty) spectrum buffer: the spectrum launch reads the chunk's head in place and nothing is copied
     // into the collection buffer (fft_take = 0 for the stage that would have fed it; fft_run = 2 for the spectrum kernel) -- at 4096 and more decimated
-    // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic, and transform + commit are one pass instead of three.
+    // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic.
     for (uint32_t s = 0; s < S; ++s) {
         hd::StreamCall& c = sl.h_call.p[s];
         if (c.fft_run == 1 && c.fft_fill == 0 && c.fft_take == (uint32_t)hd::kFftBins) { c.fft_take = 0; c.fft_run = 2; }
@@ -1100,8 +1048,8 @@ void fill_tail(const hd_engine* e, const hd_engine::CallSlot& sl, const CallPlan
     t.ring = e->tail.p; t.ring_cap = e->tail_cap; t.sym = e->d_symstate.p; t.flipmask = e->flipmask.p; t.wsum = e->weight.p;
     t.sp = e->d_sym.p; t.slots = sl.h_slots.dev; t.slot_words = e->slot_words; t.seq = sl.seq;
     t.flips_dbg = e->flips_cap ? e->flips_dbg.p : nullptr; t.flips_cap = e->flips_cap;
-    const bool in_tail = e->tail_fft && e->cfg.enable_spectrum && r.feed;  // the tail transforms a completed buffer itself
-    t.fft_tw = in_tail ? e->fft_tw.p : nullptr; t.spec = e->spec.p; t.power = e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
+    t.fft_tw = r.feed ? e->fft_tw.p : nullptr;   // the tail transforms a completed buffer itself (a tail route feeds the buffer exactly when the engine has spectra)
+    t.spec = e->spec.p; t.power = e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
 }
 
 // Equally sized pushes through a single-wave first stage of a two-stage plan: the stage-1 workgroups (eight resident per CU) draw runs of tiles from
@@ -1197,7 +1145,7 @@ int enqueue_uploads(hd_engine* e, hd_engine::CallSlot& sl, const CallRoute& r)
 }
 
 // Step route: ONE launch, [tails of the previous call | this call's stage 1].  Stage 1 reads its parameters from the mapped host block and leaves the
-// device copy the tails (next launch) and the spectrum commit read.  This call's tails are left in r.ta_step for commit_call.
+// device copy the tails (next launch) read.  This call's tails are left in r.ta_step for commit_call.
 int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRoute& r, const float2* iq, size_t stride)
 {
     const uint32_t S = e->S;
@@ -1221,31 +1169,27 @@ int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
     fill_tail(e, sl, p, r, b, r.ta_step);
     hd_engine::PendingTail prev = e->pend;
     hd_engine::CallSlot* ps = prev.valid ? &e->slot[prev.slot] : nullptr;
-    // Events of a k_step_cu launch ride on its dispatch packet (launch_step_cu): an event recorded behind it is a barrier packet of its own and
-    // costs the queue ~5 us before the next launch starts.  (Not where the spectra are a launch of their own: ev_done follows that one.)
-    bool ev_on_dispatch = false;
+    // Events of a k_step_cu launch ride on its dispatch packet (launch_step_cu): t1 / t2 when the call is timed, the previous call's ev_done otherwise.  An
+    // event recorded behind a launch is a barrier packet of its own and costs the queue ~5 us before the next launch starts: only a timed launch and the
+    // single-wave fallback record ev_done that way.
     const int cu_exp = e->cu_exp;             // timing experiments only (results wrong): 1 = no tails, 2 = no stage 1
     // One workgroup per CU (four stage-1 worker waves, the tails in the other four) where the plan and the sizes allow it
     const bool want_cu = cu_tail && ((cu_exp & 1) || (r.ta_step.lds_bytes <= cu_tail && (!prev.valid || prev.ta.lds_bytes <= cu_tail)));
     const hd::StepClaim claim = make_claim(e, p, 0, want_cu ? ring_run : 0u);
     bool launched = false;
-    e->last_timing.step_variant = 0;
     if (want_cu && claim.ctr) {
         const uint32_t tb = std::max(r.ta_step.lds_bytes, prev.valid ? prev.ta.lds_bytes : 0u);
         hd::StepClaim cl = claim;
         if (cu_exp & 2) { cl.runs_per_xcd = 0; cl.tiles_per_xcd = 0; cl.short_from = 0xFFFFFFFFu; }
-        ev_on_dispatch = !ps || prev.ta.fft_tw || !prev.any_fft;
-        if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t1, qa));
         launched = HDK(launch_step_cu, qa, R1, T1, prev.valid ? prev.r2 : R2, prev.valid ? prev.t2 : T2, S, e->n_cus, iq, stride,
                                       e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, b.d1, e->n1_cap, sl.h_call.dev, sl.d_call.p, prev.ta,
                                       (prev.valid && !(cu_exp & 1)) ? S : 0u, p.max_in, cl, tb,
-                                      ev_on_dispatch && sl.timed ? sl.t1 : nullptr, !ev_on_dispatch ? nullptr : sl.timed ? sl.t2 : ps ? ps->ev_done : nullptr);
-        if (!launched && ev_on_dispatch) { ev_on_dispatch = false; if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa)); }
-        e->last_timing.step_variant = launched ? 1u : 0u;
+                                      sl.timed ? sl.t1 : nullptr, sl.timed ? sl.t2 : ps ? ps->ev_done : nullptr);
     }
-    else if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
+    e->last_timing.step_variant = launched ? 1u : 0u;
     if (launched) ++e->step_launches;
     else {
+        if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
         // (runs cut for the ring kernel's tiles are not k_step's: fixed shares, and the counter set is not drawn from; drawn runs are short, fixed
         // shares are not: the dispatcher evens out the tail of the launch)
         const hd::StepClaim fb = (want_cu && claim.ctr) ? hd::StepClaim{} : claim;
@@ -1256,7 +1200,7 @@ int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
         // (reads return 0, writes are dropped: wrong window sums and flips, no error -- ADVICE r05).  Such tails run as a launch of their own, in front,
         // with the LDS they were laid out for; this launch then carries stage 1 only.
         if (prev.valid && prev.ta.lds_bytes > HDK(step_lds_bytes, R1, T1)) {
-            if (const int rc = run_pending_tail(e)) return rc;     // (e->pend is still the previous call's; launches the tails, their spectra, records its ev_done)
+            if (const int rc = run_pending_tail(e)) return rc;     // (e->pend is still the previous call's; its ev_done rides on that launch)
             prev.valid = false; ps = nullptr;
         }
         if (!HDK(launch_step, qa, R1, T1, prev.valid ? prev.r2 : R2, prev.valid ? prev.t2 : T2, S, p.max_n1, iq, stride, e->hist1[b.hin].p,
@@ -1265,23 +1209,21 @@ int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
             return fail(HD_ERR_INVALID, "no step kernel for this decimation plan");
         if (fb.ctr) ++e->step_launches;
     }
-    if (sl.timed && !ev_on_dispatch) HD_HIP(hipEventRecord(sl.t2, qa));
-    if (ps) {
-        if (!prev.ta.fft_tw) { if (const int rc = run_spectrum(e, qa, *ps, prev.any_fft)) return rc; }
-        if (!ev_on_dispatch || sl.timed) HD_HIP(hipEventRecord(ps->ev_done, qa));    // (a timed launch's own signal is its t2)
-    }
+    if (sl.timed && !launched) HD_HIP(hipEventRecord(sl.t2, qa));
+    if (ps && (!launched || sl.timed)) HD_HIP(hipEventRecord(ps->ev_done, qa));    // (a timed launch's own signal is its t2)
     HD_HIP(hipGetLastError());
     return HD_OK;
 }
 
-// The spectrum of the streams whose 4096-sample buffer completed in this call, where it is a launch of its own
-int call_spectrum(hd_engine* e, hipStream_t q, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r)
+// The spectrum of the streams whose 4096-sample buffer completed in this call (Decoder.h:475-489) as a launch of its own, one wave per stream
+// (kernels/spectrum_wave.hip): the separate-kernels route only -- a stream tail transforms its stream's buffer itself.
+void call_spectrum(hd_engine* e, hipStream_t q, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r)
 {
-    if (!(e->cfg.enable_spectrum && p.max_n2)) return HD_OK;
+    if (!(e->cfg.enable_spectrum && p.max_n2)) return;
     const float2* fcur = e->fbuf[e->cur].p;
-    if (r.route == Route::separate && (r.any_post || p.nst == 0)) HDK(launch_fft_feed, q, e->S, fcur, e->fbuf_stride, e->fft_in.p, r.dcall, e->fir_hist_cap);
-    if (!p.any_fft) return HD_OK;   // (every call at >= 4096 decimated samples per push)
-    return transform_and_commit(e, q, sl.h_stats.dev, r.dcall, sl.seq, fcur);
+    if (r.any_post || p.nst == 0) HDK(launch_fft_feed, q, e->S, fcur, e->fbuf_stride, e->fft_in.p, r.dcall, e->fir_hist_cap);
+    if (!p.any_fft) return;   // (every call at >= 4096 decimated samples per push)
+    hd::launch_spectrum_wave(q, e->S, e->fft_in.p, e->fft_tw.p, e->spec.p, e->power.p, sl.h_stats.dev, r.dcall, e->fsd, e->bins_sep, sl.seq, fcur, e->fbuf_stride, e->fir_hist_cap);
 }
 
 // Front half on qa (routes 0 and 2): decimation, [post-pass, spectrum]
@@ -1336,12 +1278,12 @@ int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, cons
     }
     if (!tail) {
         if (r.any_post) HDK(launch_chunk_post, qa, S, b.fcur, e->fbuf_stride, r.dcall, e->fir_hist_cap, p.any_tune ? sl.h_tune.dev : nullptr, e->tune_tab.p);
-        if (!r.spectrum_on_qc) { if (const int rc = call_spectrum(e, qa, sl, p, r)) return rc; }
+        if (!r.spectrum_on_qc) call_spectrum(e, qa, sl, p, r);
     }
     if (!e->one_stream) HD_HIP(hipEventRecord(sl.ev_front, qa));
     if (r.spectrum_on_qc) {
         HD_HIP(hipStreamWaitEvent(e->qc, sl.ev_front, 0));
-        if (const int rc = call_spectrum(e, e->qc, sl, p, r)) return rc;
+        call_spectrum(e, e->qc, sl, p, r);
         HD_HIP(hipEventRecord(sl.ev_spec, e->qc));
     }
     return HD_OK;
@@ -1387,15 +1329,12 @@ int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
     hipStream_t qb = e->qb;
     const CallBufs b = call_bufs(e);
     if (!e->one_stream) HD_HIP(hipStreamWaitEvent(qb, sl.ev_front, 0));
-    bool done_on_dispatch = false;
+    // the call's completion event rides on the dispatch of the back half's last launch
     const bool ev_ride = !sl.timed && e->one_stream;   // (two queues: the event is not on the step's critical path, and /16 measured no better with it on the dispatch)
     if (r.route == Route::tail) {
         if (r.lean) HDK(launch_fetch_params, qb, sl.h_call.dev, sl.d_call.p, S * sizeof(hd::StreamCall));
         fill_tail(e, sl, p, r, b, r.ta);
-        // (the call's completion event rides on the tails' dispatch where nothing is launched behind them)
-        done_on_dispatch = ev_ride && (r.ta.fft_tw || !(e->cfg.enable_spectrum && p.max_n2));
-        if (!HDK(launch_tail, qb, r.tail_lanes, (int)p.R2, (int)p.T2, S, r.ta, done_on_dispatch ? sl.ev_done : nullptr)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
-        if (!r.ta.fft_tw) { if (const int rc = call_spectrum(e, qb, sl, p, r)) return rc; }
+        if (!HDK(launch_tail, qb, r.tail_lanes, (int)p.R2, (int)p.T2, S, r.ta, ev_ride ? sl.ev_done : nullptr)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
     } else {
         uint32_t lpN = 0;
         if (const int rc = lowpass_transforms(e, p, r, b, &lpN)) return rc;
@@ -1406,11 +1345,10 @@ int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
         HDK(launch_symbols, qb, S, p.max_m, p.max_new, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p,
                            r.dcall, sl.h_slots.dev, e->slot_words, e->flips_cap ? e->flips_dbg.p : nullptr, e->flips_cap, e->min_R, sl.seq, ev_ride ? sl.ev_done : nullptr,
                            e->demod_ck_acc.p);
-        done_on_dispatch = ev_ride;
     }
     if (sl.timed) HD_HIP(hipEventRecord(sl.t3, qb));
     if (r.spectrum_on_qc) HD_HIP(hipStreamWaitEvent(qb, sl.ev_spec, 0));      // the call is complete when its spectra are
-    if (!done_on_dispatch) HD_HIP(hipEventRecord(sl.ev_done, qb));
+    if (!ev_ride) HD_HIP(hipEventRecord(sl.ev_done, qb));
     HD_HIP(hipGetLastError());
     return HD_OK;
 }
@@ -1421,7 +1359,7 @@ void commit_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, const
     e->mirror.swap(e->mirror_next);
     sl.busy = true;
     if (r.route == Route::step) {   // this call's tails ride in the next call's launch
-        e->pend.valid = true; e->pend.ta = r.ta_step; e->pend.slot = (int)(e->calls % hd_engine::kSlots); e->pend.any_fft = p.any_fft;
+        e->pend.valid = true; e->pend.ta = r.ta_step; e->pend.slot = (int)(e->calls % hd_engine::kSlots);
         e->pend.r2 = (int)p.R2; e->pend.t2 = (int)p.T2; e->pend_max_taps = p.max_taps;
     }
     e->cur = (e->cur + 1) % 3;

@@ -1,6 +1,10 @@
-// The whole spectrum step of a stream as ONE wave: 4096-point forward transform, half swap, dB power, and the reductions the AFC
-// needs (spectrum.hip describes them) -- what rocFFT + k_spectrum_commit do in two launches with a 32 KB round trip through HBM in
-// between (fft_raw), done in registers.  Reference: code/Decoder/FFT.cpp:60-87 (FFTW forward, half swap), AFC.h:235-329.
+// The whole spectrum step of a stream as ONE wave, in registers: 4096-point forward transform, half swap, dB power, and the reductions the
+// AFC needs.  Reference: code/Decoder/FFT.cpp:60-87 (FFTW forward; 77-87: the half swap -> freq_out_), and AFC::FftPower / ComputeVariance /
+// FindPeaks (code/Decoder/AFC.h:235-329), evaluated with wave reductions:
+//   P[i] = 10*log10f( ((|X[i]|^2 / N)^2) / fsd )          float, the /fsd through double   (AFC.h:267-270, Q22)
+//   mean, sigma of P in double                              (AFC.h:103-104, 224-232)
+//   p1 = first arg-max of P; p2 = first arg-max of {P[i] > P[0]} within +-2*sep of p1, |i-p1| > sep/2 (AFC.h:303-319)
+// The scalar state machine on top of these numbers runs on the host (host/afc_tracker.hpp).
 //
 // 4096 = 64 x 64.  With n = 64*n1 + n2 and k = k1 + 64*k2:
 //     X[k1 + 64 k2] = sum_n2 W64^(n2 k2) * [ W4096^(n2 k1) * sum_n1 x[64 n1 + n2] W64^(n1 k1) ]
@@ -11,8 +15,8 @@
 // swapped spectrum and of the power are wave-wide contiguous again.  The 64-point transform is 8 x 8 eight-point transforms on a register
 // array with compile-time indices and twiddles.
 //
-// Parity: like rocFFT's, this transform is compared norm-wise with the exact DFT (FFTW itself is not available to pin against,
-// DESIGN.md section 8): same tolerances, same tests.
+// Parity: this transform is compared norm-wise with the exact DFT (FFTW itself is not available to pin against),
+// and device log10f differs from glibc's by ulps, so P is compared norm-wise too, not bit-wise.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -237,7 +241,7 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
         o.peak1 = pa; o.peak2 = pb; o.power1 = av; o.power2 = bvv; o.seq = 0u;
         o.mean = mean; o.sigma = sigma;
         stats[s] = o;
-        // the call's tag, last (as k_spectrum_commit: the statistics live in mapped host memory and the host waits for the tag, not for an event's fence)
+        // the call's tag, last, behind a wait for the stores above (the statistics live in mapped host memory and the host waits for the tag, not for an event's fence)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(&stats[s].seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }

@@ -1002,7 +1002,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
         }
     }
     // ---- the stream's spectrum, when its 4096-sample buffer completed in this call (Decoder.h:475-489): transform, half swap, power and
-    // AFC statistics by this same wave (spectrum_wave.h) -- no launches of their own, no fft_raw round trip.  The buffer's last samples
+    // AFC statistics by this same wave (spectrum_wave.h) -- no launch of its own, no round trip through HBM.  The buffer's last samples
     // were stored by this workgroup a moment ago.
     if (a.fft_tw && c.fft_run) {
         __threadfence_block();

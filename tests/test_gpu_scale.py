@@ -36,7 +36,7 @@ def headline_ring():
     torch.cuda.empty_cache()
 
 
-@pytest.mark.parametrize("shares", ["drawn", "drawn2", "fixed", "deep", "rocfft", "single_wave", "run9", "run12", "short0", "short60"])
+@pytest.mark.parametrize("shares", ["drawn", "drawn2", "fixed", "deep", "single_wave", "run9", "run12", "short0", "short60"])
 def test_headline_workload_through_the_step_kernel(monkeypatch, headline_ring, shares):
     """shares: which step kernel serves the batch and how its stage-1 tiles are handed out -- k_step_cu (one workgroup per CU: stage-1 worker waves
     that load their own tiles with LDS-DMA and sum them with the systolic tap loop, runs of four 57-output tiles drawn from per-XCD counters: the
@@ -49,8 +49,6 @@ def test_headline_workload_through_the_step_kernel(monkeypatch, headline_ring, s
         monkeypatch.setenv("HD_STEP_RUN", "2")
     if shares == "fixed":
         monkeypatch.setenv("HD_NO_CLAIM", "1")
-    if shares == "rocfft":                                   # the spectra as launches of their own (rocFFT + commit) instead of inside the tails
-        monkeypatch.setenv("HD_ROCFFT", "1")
     if shares == "single_wave":                              # round 2's step kernel (single-wave workgroups) instead of one workgroup per CU
         monkeypatch.setenv("HD_NO_CU_STEP", "1")
     if shares in ("run9", "run12"):                          # k_step_cu with nine- / twelve-tile runs (fewer run changes; 36 tiles per stream and call)
@@ -493,6 +491,52 @@ def test_tails_meet_a_launch_other_than_the_one_they_were_laid_out_for(case):
     eng.close()
     del ring
     torch.cuda.empty_cache()
+
+
+def test_step_launch_events_with_and_without_timing():
+    """Where the completion event of a call rides in step mode: a k_step_cu launch carries t1 / t2 on its dispatch when the call is timed and the previous
+    call's ev_done otherwise; a timed launch, or the single-wave fallback (here: the first call, which restarts the stage-1 histories), records ev_done behind
+    itself.  8 streams (the smallest count whose 36 tiles per stream make runs of four that divide among 8 XCDs), /64, 50 baud 7N2, twelve 65536-sample pushes
+    free running -- 12288 decimated samples, three spectra per stream, each transformed by the tail that completes the buffer -- with the events timed never,
+    on every call, and on every 8th (the default): every call's discriminator output, the text and the AFC must be the oracle's whichever event delivered it."""
+    torch = pytest.importorskip("torch")
+    import habdec_amd
+    from oracle import pyoracle
+    S, fs, ncalls = 8, 2.048e6, 12
+    f0 = [0.0, 120.0, -200.0, 1500.0, 60.0, -90.0, 300.0, -1200.0]
+    iq = np.stack([synth.fsk_iq(synth.rtty_bits("$$A", 7, 2, 1 + (s & 1), 4), fs, 50, sigma=0.08, seed=900 + s, n_samples=ncalls * C, f0=f0[s]) for s in range(S)])
+    orcs = [pyoracle.Decoder("oracle", factor=64, baud=50, bits=7, stops=2) for _ in range(S)]
+    want = []
+    for s, o in enumerate(orcs):
+        h = 0xCBF29CE484222325
+        for k in range(ncalls):
+            o(iq[s, k * C:(k + 1) * C], fs)
+            d = o.array("last_demod").view(np.uint32).astype(np.uint64)
+            for x in (len(d), int(d.sum() & 0xFFFFFFFF), int((d * np.arange(1, len(d) + 1, dtype=np.uint64)).sum() & 0xFFFFFFFF)):
+                h = ((h ^ x) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
+        want.append(((ncalls, 0, h), o.text("chars_log"), o.sentences(), (o.afc()["peak_l"], o.afc()["peak_r"])))
+    slab = torch.from_numpy(np.ascontiguousarray(iq.reshape(S, ncalls, C).transpose(1, 0, 2)).view(np.float32).reshape(ncalls, S, C, 2)).cuda()
+    got = {}
+    for every in (0, 1, None):
+        eng = habdec_amd.Engine(n_streams=S, max_chunk=C, sampling_rate=fs, decimation=64, baud=50, rtty_bits=7, rtty_stops=2, pipeline=1)
+        if every is not None:
+            eng.set_timing(every)
+        for k in range(ncalls):
+            eng.process_device(slab[k].data_ptr(), C, C)
+        t = eng.timing()
+        assert (t["path"], t["step_variant"]) == (3, 1), (every, t)
+        eng.flush()
+        # (calls 0, every, 2 * every, ... carry the timing events)
+        assert eng.timing()["timed_calls"] == (0 if every == 0 else len(range(0, ncalls, 8 if every is None else every))), (every, eng.timing())
+        got[every] = []
+        for s in range(S):
+            a = eng.afc(s)
+            assert a["spectra"] == 3, (every, s, a)
+            got[every].append((eng.demod_checksum_total(s), eng.take_chars(s), eng.take_sentences(s), (a["peak_l"], a["peak_r"])))
+            assert got[every][s] == want[s], (every, s, got[every][s], want[s])
+        eng.close()
+    assert got[0] == got[1] == got[None]
+    assert any(chars for _, chars, _, _ in want)           # (0.38 s of 50 baud: a character or two per stream)
 
 
 @pytest.mark.parametrize("name,steps", [("cfg4", 40), ("cfg2", 12), ("cfg3", 12), ("cfg5", 4)])
