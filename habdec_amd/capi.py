@@ -37,6 +37,10 @@ class hd_tune_info(C.Structure):
                 ("auto_afc", C.c_int32)]
 
 
+class hd_front_tune_info(C.Structure):
+    _fields_ = [("offset_hz", C.c_double), ("step", C.c_uint32), ("phase", C.c_uint32), ("from_call", C.c_uint64)]
+
+
 SENTENCE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p)
 MATCH_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int)
 CHARS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_char), C.c_size_t)
@@ -64,6 +68,8 @@ ENGINE_API = {
     "hd_stream_set_dc_remove": (_int, [_vp, _u32, _int]),
     "hd_stream_reset_frequency_correction": (_int, [_vp, _u32, _dbl]),
     "hd_stream_set_tune": (_int, [_vp, _u32, _dbl]),
+    "hd_stream_set_front_tune": (_int, [_vp, _u32, _dbl]),
+    "hd_stream_front_tune": (_int, [_vp, _u32, C.POINTER(hd_front_tune_info)]),
     "hd_stream_set_auto_afc": (_int, [_vp, _u32, _int, _dbl, _dbl]),
     "hd_stream_tune": (_int, [_vp, _u32, C.POINTER(hd_tune_info)]),
     "hd_set_sentence_callback": (None, [_vp, SENTENCE_CB, _vp]),

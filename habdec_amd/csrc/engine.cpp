@@ -88,6 +88,7 @@ struct SizeState {
     uint64_t head_call = ~0ull;     // ... the call that run was in (its input sits in THAT call's low-pass buffer until the buffer's turn comes again) ...
     bool head_aside = false;        // ... or: the head has been copied to the side buffer (the stream did not run in the call behind its last run)
     uint32_t tune_phase = 0;        // tuning phase of the next call to be submitted
+    uint32_t front_phase = 0;       // ... and the phase of the tuning at the input rate (hd_stream_set_front_tune)
     uint32_t win_ub = 0, inflight_m = 0;   // upper bound of backlog samples without final window results; low-pass outputs of undelivered calls (collect() learns them back)
     uint32_t last_n2 = 0, last_pend_before = 0, last_m = 0;   // last call (for the getters)
     int last_buf = 0;
@@ -125,6 +126,10 @@ struct StreamHost {
     bool auto_afc = false;
     double afc_hold_s = 6.0, afc_min_hz = 100.0;
     uint64_t afc_elapsed = 0;                 // input samples delivered since the loop was set or last retuned
+    // tuning at the input rate, in front of the first decimation stage (hd_stream_set_front_tune; its phase: SizeState::front_phase)
+    double front_hz = 0;
+    uint32_t front_step = 0;
+    uint64_t front_from = 0;                  // first call of the current offset
 };
 
 }  // namespace
@@ -222,6 +227,7 @@ struct hd_engine {
         PinBuf<uint32_t> h_slots;                 // written by the symbol scan kernel over PCIe (zero-copy), read after ev_done
         PinBuf<hd::SpectrumStatsDev> h_stats;    // written by the spectrum kernel
         PinBuf<uint2> h_tune;                     // (step, phase) of every stream for this call, read by the kernels in place; passed only when some stream is tuned
+        PinBuf<uint2> h_front;                    // the same for the tuning at the input rate: read in place by k_decimate_tuned, which runs only when some stream has one
         bool timed = false, timed_step = false;   // this call carries the timing events (a step call: only the two around its one launch)
         hipEvent_t ev_front = nullptr, ev_done = nullptr, ev_params = nullptr, ev_spec = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
         bool busy = false;
@@ -474,6 +480,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HD_HIP(sl.h_call.alloc(S));
         HD_HIP(sl.h_slots.alloc((size_t)S * e->slot_words));
         HD_HIP(sl.h_tune.alloc(S));
+        HD_HIP(sl.h_front.alloc(S));
     }
     {
         std::vector<float> tab(4 * hd::kTuneTable);
@@ -525,6 +532,10 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
             HDK(launch_decimate, q, e->stages[0].ratio, T1, S, 1, e->staging.p, cfg->max_chunk, e->hist1[0].p, e->hist1[1].p, e->stage_taps[0].p,
                                 e->stages.size() == 1 ? e->fbuf[0].p : e->dec1.p, e->stages.size() == 1 ? e->fbuf_stride : e->n1_cap, sl.d_call.p, 0,
                                 e->stages.size() == 1, e->fir_hist_cap, nullptr);
+        if (e->stages.size() >= 1)      // (the first stage of a front-tuned call; the slot's tuning block is all zeros: no stream is rotated)
+            HDK(launch_decimate_tuned, q, e->stages[0].ratio, T1, S, 1, e->staging.p, cfg->max_chunk, e->hist1[0].p, e->hist1[1].p, e->stage_taps[0].p,
+                                      e->stages.size() == 1 ? e->fbuf[0].p : e->dec1.p, e->stages.size() == 1 ? e->fbuf_stride : e->n1_cap, sl.d_call.p,
+                                      e->stages.size() == 1, e->fir_hist_cap, nullptr, 0u, sl.h_front.dev, e->tune_tab.p);
         if (e->stages.size() == 2)
             HDK(launch_decimate, q, e->stages[1].ratio, T2, S, 1, e->dec1.p, e->n1_cap, e->hist2[0].p, e->hist2[1].p, e->stage_taps[1].p, e->fbuf[0].p,
                                 e->fbuf_stride, sl.d_call.p, 1, 1, e->fir_hist_cap, nullptr);
@@ -668,6 +679,28 @@ int hd_stream_set_tune(hd_engine* e, uint32_t s, double offset_hz)
     StreamHost& st = e->st[s];
     st.tune_hz = offset_hz; st.tune_step = d; st.tune_from = e->calls;
     if (offset_hz == 0) e->mirror[s].tune_phase = 0;
+    return HD_OK;
+}
+// Tuning at the input rate: same rules, the step in units of the INPUT rate; the phase advances by the call's input samples (plan_call)
+int hd_stream_set_front_tune(hd_engine* e, uint32_t s, double offset_hz)
+{
+    if (int r = check_stream(e, s)) return r;
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    if (e->stages.empty()) return fail(HD_ERR_UNSUPPORTED, "an engine without a decimation stage has no input-rate tuning: hd_stream_set_tune is the same thing there");
+    uint32_t d = 0;
+    if (!hd::tune_step(offset_hz, e->fs, &d)) return fail(HD_ERR_INVALID, "tuning offset outside (-fs/2, fs/2)");
+    StreamHost& st = e->st[s];
+    st.front_hz = offset_hz; st.front_step = d; st.front_from = e->calls;
+    if (offset_hz == 0) e->mirror[s].front_phase = 0;
+    return HD_OK;
+}
+int hd_stream_front_tune(hd_engine* e, uint32_t s, hd_front_tune_info* out)
+{
+    if (int r = check_stream(e, s)) return r;
+    if (!out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    const StreamHost& st = e->st[s];
+    out->offset_hz = st.front_hz; out->step = st.front_step; out->phase = e->mirror[s].front_phase; out->from_call = st.front_from;
     return HD_OK;
 }
 int hd_stream_set_auto_afc(hd_engine* e, uint32_t s, int on, double hold_s, double min_hz)
@@ -866,6 +899,7 @@ struct CallPlan {
     uint32_t max_in = 0, min_in = 0xFFFFFFFFu, max_n1 = 0, max_n2 = 0, max_m = 0, max_taps = 0, max_new = 0, max_pend = 0;
     uint64_t total_in = 0;
     bool any_fft = false, any_dc = false, any_zero1 = false, any_tune = false, any_lp_restart = false;
+    bool any_front = false;      // some stream of the call is tuned at the input rate: its first stage is k_decimate_tuned, a launch of its own
 };
 
 struct CallRoute {
@@ -917,6 +951,8 @@ int plan_call(hd_engine* e, hd_engine::CallSlot& sl, const uint32_t* n_per_strea
         c.dc_remove = st.dc && c.n2;
         sl.h_tune.p[s] = make_uint2(st.tune_step, nx.tune_phase);     // (read by the kernels only when some stream of the call is tuned)
         if (st.tune_step) { p.any_tune = true; nx.tune_phase += c.n2 * st.tune_step; }
+        sl.h_front.p[s] = make_uint2(st.front_step, nx.front_phase);
+        if (st.front_step | nx.front_phase) { p.any_front = true; nx.front_phase += n * st.front_step; }
         c.pend_before = (uint32_t)nx.pending;
         nx.pending += c.n2;
         // spectrum collection (Decoder.h:467-489)
@@ -997,7 +1033,10 @@ void route_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRo
     // Step mode: batch decoding of equally sized pushes through a single-wave first stage -- ONE launch per call, on one queue: this call's stage 1 with
     // the previous call's stream tails in front.  Its tails are laid out for k_step's static slot here; enqueue_step may re-lay them for k_step_cu.
     const uint32_t step_lds = (p.R1 == 32 || p.R1 == 64) ? HDK(step_lds_bytes, (int)p.R1, (int)p.T1) : 0u;
-    const bool step = tail && e->cfg.pipeline && !e->one_stream && p.min_in == p.max_in && p.max_in && step_lds &&
+    // (Not a front-tuned call: the rotation at the input rate exists in k_decimate_tuned only, a launch of its own -- such a call takes the tail route
+    // or the separate kernels, whatever it would take on a synchronous engine's side of this test, and a step call's pending tails run as for any
+    // other change of route.)
+    const bool step = tail && !p.any_front && e->cfg.pipeline && !e->one_stream && p.min_in == p.max_in && p.max_in && step_lds &&
                       HDK(tail_layout, r.ta_step, 64, R2, T2, p.max_taps, e->max_R, e->min_R, e->tail_cap, p.max_pend, step_lds);
     r.route = step ? Route::step : tail ? Route::tail : Route::separate;
     // The separate kernels change the decimated chunk after the last stage (DC blocker, rotation of a tuned stream) in a post-pass; the stream tails
@@ -1247,7 +1286,7 @@ int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, cons
         const uint32_t lin1 = (p.min_in == p.max_in && p.max_in) ? wgs_cu * e->n_cus : 0u;
         // A /32 first stage over equally sized pushes: one workgroup per CU, LDS-DMA loader waves + computing waves (k_stage1_cu, stage1_ring.h)
         bool s1_cu = false;
-        if ((single ? R1 == 4 : R1 != 4) && p.min_in == p.max_in && p.max_in && !e->no_cu_step && !p.any_zero1 && p.max_in % 2048u == 0 && HDK(stage1_cu_supported, (int)R1, (int)T1)) {
+        if (!p.any_front && (single ? R1 == 4 : R1 != 4) && p.min_in == p.max_in && p.max_in && !e->no_cu_step && !p.any_zero1 && p.max_in % 2048u == 0 && HDK(stage1_cu_supported, (int)R1, (int)T1)) {
             const hd::StepClaim cl = make_claim(e, p, 0, pick_ring_run(e, R1, HDK(ring_tiles, (int)R1, (int)T1, p.max_in)));
             if (cl.ctr) {
                 if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
@@ -1261,8 +1300,11 @@ int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, cons
         if (!s1_cu) {
             // (stage 1 alone is HBM-bound: drawing runs there cost 3 % -- more halo re-reads -- where the step launch gains 4 %: fixed shares)
             if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
-            if (!HDK(launch_decimate, qa, R1, T1, S, p.max_n1, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
-                                     (r.lean || r.free_front) ? sl.h_call.dev : r.dcall, 0, single ? 1 : 0, e->fir_hist_cap, single ? r.feed : nullptr, lin1))
+            const hd::StreamCall* call1 = (r.lean || r.free_front) ? sl.h_call.dev : r.dcall;
+            if (!(p.any_front ? HDK(launch_decimate_tuned, qa, R1, T1, S, p.max_n1, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
+                                                          call1, single ? 1 : 0, e->fir_hist_cap, single ? r.feed : nullptr, lin1, sl.h_front.dev, e->tune_tab.p)
+                              : HDK(launch_decimate, qa, R1, T1, S, p.max_n1, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
+                                                    call1, 0, single ? 1 : 0, e->fir_hist_cap, single ? r.feed : nullptr, lin1)))
                 return fail(HD_ERR_INVALID, "no kernel for this decimation stage");
         }
         if (sl.timed) HD_HIP(hipEventRecord(sl.t2, qa));

@@ -29,6 +29,9 @@
 #include "tail_body.h"
 #include "stage1_ring.h"
 
+#ifndef HD_FRONT_SWEEPS
+#define HD_FRONT_SWEEPS 2   // k_decimate_tuned: sweeps of a tile whose table look-ups are in flight together
+#endif
 #define HD_DEC_MAXW 4     // most waves per SIMD the 256-lane stages are compiled for (their registers and LDS decide what they get: 3-4)
 
 namespace hd {
@@ -71,9 +74,17 @@ constexpr int dec_tile_f4()                        // float4 slots of a workgrou
 extern "C" void HD_DBG_NAME(hd_debug_step_tail_stamps)(unsigned long long* host, size_t n) { (void)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_tail_stamps), n * 8); }
 #endif
 
+// What the tuned first stage (decimate_body<.., true>) keeps per workgroup; the untuned stages keep nothing, and their `staged` is a constant.
+template <bool TUNED> struct FrontTune { static constexpr bool staged = false; };
+template <> struct FrontTune<true> { uint2 tn, tn_next; bool staged; };
+
 // The stage body.  (bx, by, gdx) are the workgroup's coordinates in the stage's own grid -- blockIdx / gridDim when the stage is a
 // launch of its own (k_decimate), shifted when stream tails ride in front of it in the same launch (k_step).
-template <int D, int T, int TO>
+// TUNED (k_decimate_tuned, a first stage only): a stream's samples are rotated at the INPUT rate (hd_stream_set_front_tune) on their way from the
+// load registers into the LDS tile -- sample i of the call by theta = Pf + i Df, ftune[s] = (Df, Pf), with the phasor of tune.h -- and the history
+// carry stores the rotated samples.  History loads and out-of-range zeros are therefore never rotated, and outputs that end up in the history
+// (Q4) are in the rotated domain already.  A stream with Df = Pf = 0 takes a wave-uniform branch around all of it.
+template <int D, int T, int TO, bool TUNED = false>
 __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, size_t in_stride,
                                               const float2* __restrict__ hist_in, float2* __restrict__ hist_out,
                                               const float* __restrict__ taps,
@@ -84,7 +95,9 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
                                               const uint32_t bx, const uint32_t by, const uint32_t gdx, float4* __restrict__ tile4,
                                               const uint32_t uniform_n = 0 /* != 0: every stream brings this many samples and none restarts its history:
                                                                              the per-stream parameter block need not be read (it may sit across PCIe) */,
-                                              const StepClaim claim = StepClaim{} /* runs of tiles handed out by per-XCD counters instead of a fixed share */)
+                                              const StepClaim claim = StepClaim{} /* runs of tiles handed out by per-XCD counters instead of a fixed share */,
+                                              const uint2* __restrict__ ftune = nullptr /* TUNED: (Df, Pf) per stream, read in place (mapped host memory) */,
+                                              const float* ftab = nullptr /* TUNED: the phasor tables [C | F] (tune.h), in LDS or global memory */)
 {
     constexpr int OPL = dec_opl<D>();              // outputs per lane
     constexpr int TOUT = TO * OPL;                 // outputs per tile
@@ -164,6 +177,8 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
     uint32_t pf_s = s;
     bool pf_zero_hist = (stage == 0 ? c.zero_hist1 : c.zero_hist2) != 0;
     CallHead c_next = c;                                    // head of stream s + 1 once the prefetch has crossed the seam
+    FrontTune<TUNED> ft;                                    // TUNED: (Df, Pf) of stream s / of the stream the prefetch has crossed into
+    if constexpr (TUNED) { ft.tn = ftune[s]; ft.tn_next = ft.tn; }
 
     // Edge tiles (the history tile of every stream): branch-free address selection so the loads still issue
     // back to back -- out-of-range samples read a safe address and are zeroed afterwards.
@@ -254,6 +269,36 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
     if (first == 0) leave_copy(s);
     for (uint32_t done = 0; done < count; ++done) {
         DSTAMP_ARRIVED();
+        if constexpr (TUNED) {
+            const uint2 tn = ft.tn;
+            ft.staged = false;
+            if (__builtin_amdgcn_readfirstlane((int)(tn.x | tn.y))) {   // (wave-uniform: an untuned stream's tile goes to LDS as it arrived, below)
+                // Pair k holds the call's samples xi = x0 + 2k and xi + 1; what lies in front of the call (history) or behind it (zeros) stays as it is.
+                // Each sweep is rotated and written in turn, with a fence for the instruction scheduler after every GS sweeps: left alone it requests
+                // the table entries of ALL sweeps up front, four registers per pair on top of the tile in flight (237 spilled registers at /32).
+                ft.staged = true;
+                constexpr int GS = HD_FRONT_SWEEPS;
+                const long x0 = (long)tile_i * TOUT * D - (T - 1) - JS + 2 * (long)threadIdx.x;
+#pragma unroll
+                for (int it = 0; it < ITER; ++it) {
+                    const int k = threadIdx.x + it * TO;
+                    if ((it + 1) * TO <= NP || k < NP) {
+                        const long xi = x0 + 2L * it * TO;
+                        const uint32_t th = tn.y + (uint32_t)xi * tn.x;
+                        float4 v = r[it];
+                        float ar, ai, br, bi;
+                        tune_rotate1(ftab, th, v.x, v.y, ar, ai);
+                        tune_rotate1(ftab, th + tn.x, v.z, v.w, br, bi);
+                        if ((unsigned long)xi < (unsigned long)n) { v.x = ar; v.y = ai; }
+                        if ((unsigned long)(xi + 1) < (unsigned long)n) { v.z = br; v.w = bi; }
+                        const int jj = 2 * k;
+                        *reinterpret_cast<float4*>(tile + jj + 2 * (jj / RD)) = v;
+                    }
+                    if (it % GS == GS - 1) __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        if (!ft.staged) {
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
             const int k = threadIdx.x + it * TO;
@@ -261,6 +306,7 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
                 const int jj = 2 * k;
                 *reinterpret_cast<float4*>(tile + jj + 2 * (jj / RD)) = r[it];
             }
+        }
         }
         __syncthreads();
         DSTAMP(1);
@@ -286,6 +332,7 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
             if (linear && pf_tile == ntiles) {              // ... across the seam into the next stream
                 pf_tile = 0; ++pf_s;
                 if (!uniform_n) c_next = *reinterpret_cast<const CallHead*>(call + pf_s);
+                if constexpr (TUNED) ft.tn_next = ftune[pf_s];
                 pf_zero_hist = (stage == 0 ? c_next.zero_hist1 : c_next.zero_hist2) != 0;
             }
             pf_do = true; pf_which = pf_tile;
@@ -476,18 +523,27 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
                 const float2* in_s = in + (size_t)s * in_stride;
                 for (uint32_t j = threadIdx.x; j < (uint32_t)(T - 1); j += TO) {
                     const uint32_t idx = n - (T - 1) + j;   // host guarantees n >= T-1
+                    if constexpr (TUNED) {                  // the carried inputs are this call's samples: rotated, like the tile's
+                        const uint2 tn = ft.tn;
+                        const float2 x = in_s[idx];
+                        float yr = x.x, yi = x.y;
+                        if (tn.x | tn.y) tune_rotate1(ftab, tn.y + idx * tn.x, x.x, x.y, yr, yi);
+                        hout[j] = idx < nout ? ytile[idx] : make_float2(yr, yi);
+                    } else
                     hout[j] = idx < nout ? ytile[idx] : in_s[idx];
                 }
             }
             if (!jump && done + 1 < count) {                // linear split: walk on into the next stream (its first tile is in flight)
                 __syncthreads();                            // ytile is rewritten by the next tile
                 ++s; tile_i = 0; c = c_next;
+                if constexpr (TUNED) ft.tn = ft.tn_next;
                 leave_copy(s);
             }
         }
         if (jump) {                                         // claimed runs: on to the run drawn a tile ago (its first tile is in flight)
             __syncthreads();
             s = jump_s; tile_i = jump_first; jump = false;
+            if constexpr (TUNED) ft.tn = ftune[s];
             if (!tile_i) leave_copy(s);
         }
     }
@@ -510,6 +566,42 @@ __global__ __launch_bounds__(TO) __attribute__((amdgpu_waves_per_eu(D == 64 ? 1 
     decimate_body<D, T, TO>(in, in_stride, hist_in, hist_out, taps, out, out_stride, call, stage, final_stage, fir_hist_cap, tiles_per_wg, fft_in,
                             n_streams, lin_ntiles, call_copy, blockIdx.x, blockIdx.y, gridDim.x, tile4, TO == 64 ? uniform_n : 0u,
                             TO == 64 ? claim : StepClaim{});
+}
+
+// The first stage of a call in which some stream is tuned at the input rate (hd_stream_set_front_tune): k_decimate with the rotation in the staging
+// loop (decimate_body<.., true>).  A launch of its own only -- fixed shares, every workgroup reads its streams' parameter blocks and leaves no device copy of them.
+// The tables: a lane's two entries per sample are indexed by the top bits of ITS theta.  The 256- and 128-lane shapes keep a 4 KB copy in LDS (their
+// tiles leave room for it at the occupancy their registers give); the single-wave shapes fill a CU's LDS with eight (/32) or four (/64) tiles and
+// read the tables through the vector cache instead, where 4 KB stay resident.
+template <int TO> constexpr bool front_tab_in_lds()
+{
+#ifdef HD_FRONT_TAB_GLOBAL      // A/B builds: every shape reads the tables through the cache
+    return false;
+#else
+    return TO > 64;
+#endif
+}
+
+template <int D, int T, int TO>
+__global__ __launch_bounds__(TO) __attribute__((amdgpu_waves_per_eu(D == 64 ? 1 : 2, TO == 64 ? 2 : HD_DEC_MAXW))) void k_decimate_tuned(const float2* __restrict__ in, size_t in_stride,
+                                                   const float2* __restrict__ hist_in, float2* __restrict__ hist_out,
+                                                   const float* __restrict__ taps,
+                                                   float2* __restrict__ out, size_t out_stride,
+                                                   const StreamCall* __restrict__ call, int final_stage,
+                                                   uint32_t fir_hist_cap, uint32_t tiles_per_wg, float2* __restrict__ fft_in,
+                                                   uint32_t n_streams, uint32_t lin_ntiles,
+                                                   const uint2* __restrict__ ftune, const float* __restrict__ ftab)
+{
+    constexpr bool kLds = front_tab_in_lds<TO>();
+    __shared__ float4 tile4[dec_tile_f4<D, T, TO>()];
+    __shared__ float4 tab4[kLds ? kTuneTable : 1];            // [C | F]: 2 x 256 (cos, sin)
+    if constexpr (kLds) {
+        for (uint32_t i = threadIdx.x; i < kTuneTable; i += TO) tab4[i] = reinterpret_cast<const float4*>(ftab)[i];
+        __syncthreads();
+    }
+    decimate_body<D, T, TO, true>(in, in_stride, hist_in, hist_out, taps, out, out_stride, call, 0, final_stage, fir_hist_cap, tiles_per_wg, fft_in,
+                                  n_streams, lin_ntiles, nullptr, blockIdx.x, blockIdx.y, gridDim.x, tile4, 0u, StepClaim{}, ftune,
+                                  kLds ? reinterpret_cast<const float*>(tab4) : ftab);
 }
 
 // One launch per step in batch mode: workgroups [0, n_tail) are the stream tails of the PREVIOUS call (tail_body.h: stage 2, low-pass,
@@ -699,14 +791,26 @@ __global__ __launch_bounds__(64) void k_dc_remove(float2* __restrict__ fbuf, siz
     }
 }
 
-template <int D, int T, int TO>
+template <int D, int T, int TO, bool TUNED = false>
 static void launch_one(hipStream_t st, uint32_t n_streams, uint32_t max_out, const float2* in, size_t in_stride,
                        const float2* hist_in, float2* hist_out, const float* taps, float2* out, size_t out_stride,
                        const StreamCall* call, int stage, int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs, StreamCall* call_copy,
-                       uint32_t uniform_n, const StepClaim& claim)
+                       uint32_t uniform_n, const StepClaim& claim, const uint2* ftune = nullptr, const float* ftab = nullptr)
 {
     constexpr uint32_t TOUT = TO * dec_opl<D>();
     const uint32_t ntiles = (max_out + TOUT - 1) / TOUT;
+    if constexpr (TUNED) {      // the same two grids; stage 0, no drawn runs, the parameter blocks are read
+        if (TO == 64 && lin_wgs && (uint64_t)ntiles * n_streams >= 4ull * lin_wgs) {
+            hipLaunchKernelGGL((k_decimate_tuned<D, T, TO>), dim3(lin_wgs), dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
+                               final_stage, fir_hist_cap, 0u, fft_in, n_streams, ntiles, ftune, ftab);
+            return;
+        }
+        uint32_t per = 1;
+        while (per < 16 && (uint64_t)((ntiles + 2 * per - 1) / (2 * per)) * n_streams >= 2048) per *= 2;
+        hipLaunchKernelGGL((k_decimate_tuned<D, T, TO>), dim3((ntiles + per - 1) / per, n_streams), dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps,
+                           out, out_stride, call, final_stage, fir_hist_cap, per, fft_in, n_streams, 0u, ftune, ftab);
+        return;
+    }
     // Linear split (single-wave instantiations, every stream the same size -- the caller vouches for that by passing lin_wgs):
     // exactly lin_wgs workgroups share the slab's tiles evenly.  The caller picks lin_wgs = k * CUs to decide how many of a CU's
     // eight 19.5 KB LDS slots this kernel takes -- the rest stays free for the back-half kernels of the previous call.
@@ -733,6 +837,19 @@ bool launch_decimate(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, u
     if (!max_out) return true;
 #define HD_CASE(D, T, TO) \
     if (ratio == D && ntaps == T) { launch_one<D, T, TO>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, stage, final_stage, fir_hist_cap, fft_in, lin_wgs, call_copy, uniform_n, claim); return true; }
+    HD_CASE(2, 69, 256) HD_CASE(4, 139, 256) HD_CASE(8, 280, 256) HD_CASE(8, 54, 256)
+    HD_CASE(16, 107, 128) HD_CASE(32, 212, 64) HD_CASE(32, 174, 64) HD_CASE(64, 348, 64)
+#undef HD_CASE
+    return false;
+}
+
+bool launch_decimate_tuned(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, uint32_t max_out, const float2* in, size_t in_stride,
+                           const float2* hist_in, float2* hist_out, const float* taps, float2* out, size_t out_stride, const StreamCall* call,
+                           int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs, const uint2* ftune, const float* ftab)
+{
+    if (!max_out) return true;
+#define HD_CASE(D, T, TO) \
+    if (ratio == D && ntaps == T) { launch_one<D, T, TO, true>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, 0, final_stage, fir_hist_cap, fft_in, lin_wgs, nullptr, 0u, StepClaim{}, ftune, ftab); return true; }
     HD_CASE(2, 69, 256) HD_CASE(4, 139, 256) HD_CASE(8, 280, 256) HD_CASE(8, 54, 256)
     HD_CASE(16, 107, 128) HD_CASE(32, 212, 64) HD_CASE(32, 174, 64) HD_CASE(64, 348, 64)
 #undef HD_CASE

@@ -14,6 +14,13 @@ bool launch_decimate(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, u
                      StreamCall* call_copy = nullptr /* linear split only: leave a device copy of each stream's parameters here */,
                      uint32_t uniform_n = 0 /* linear split, not the final stage: the streams' common sample count, no stream restarts its history */,
                      const StepClaim& claim = StepClaim{} /* with uniform_n: the lin_wgs workgroups draw their tiles */);
+// The same stage as the FIRST stage of a call in which some stream is tuned at the input rate (hd_stream_set_front_tune): sample i of stream s's input is
+// rotated by theta = Pf + i Df on its way into the tile, ftune[s] = (Df, Pf) read in place (mapped host memory), ftab = the phasor tables [C | F] of
+// tune.h in device memory; the history carry holds rotated samples.  A stream with Df = Pf = 0 is computed exactly as by launch_decimate.
+bool launch_decimate_tuned(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, uint32_t max_out,
+                           const float2* in, size_t in_stride, const float2* hist_in, float2* hist_out, const float* taps,
+                           float2* out, size_t out_stride, const StreamCall* call, int final_stage,
+                           uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs, const uint2* ftune, const float* ftab);
 // copy `bytes` (multiple of 16) from mapped pinned host memory into device memory with a kernel
 void launch_fetch_params(hipStream_t st, const void* host_mapped, void* dst, size_t bytes);
 // factor 1: copy the chunk behind the FIR history.

@@ -107,6 +107,15 @@ class Engine:
     def reset_frequency_correction(self, s, c): check(self.L.hd_stream_reset_frequency_correction(self.h, s, c))
     def set_tune(self, s, offset_hz): check(self.L.hd_stream_set_tune(self.h, s, float(offset_hz)))
 
+    def set_front_tune(self, s, offset_hz):
+        """Tune stream s at the INPUT rate, in front of the first decimation stage (hd_stream_set_front_tune): |offset_hz| < sampling_rate / 2."""
+        check(self.L.hd_stream_set_front_tune(self.h, s, float(offset_hz)))
+
+    def front_tune(self, s=0) -> dict:
+        t = capi.hd_front_tune_info()
+        check(self.L.hd_stream_front_tune(self.h, s, C.byref(t)))
+        return {"offset_hz": t.offset_hz, "step": t.step, "phase": t.phase, "from_call": t.from_call}
+
     def set_auto_afc(self, s, on=True, hold_s=6.0, min_hz=100.0):
         """The server's AFC block per stream, in sample time: retune the stream (not a radio) by the AFC's correction (hd_stream_set_auto_afc)."""
         check(self.L.hd_stream_set_auto_afc(self.h, s, int(on), float(hold_s), float(min_hz)))

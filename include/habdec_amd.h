@@ -121,8 +121,31 @@ int hd_stream_reset_frequency_correction(hd_engine* e, uint32_t stream, double c
  *    to float once; every complex product (ur vr - ui vi, ur vi + ui vr) with each product and sum rounded separately, in both arithmetic modes.
  *    Phase resolution 2^-16 cycle (spurs near -96 dBc).  habdec_amd_host.h restates it (hd_host_tune_*).
  *  - f = 0 sets D = P = 0, and a stream with D = 0 is not touched at all: bit-identical to an untuned stream on the same launch path.
- * Paths (hd_timing.path): the stream tail (2) and the step kernel (3) rotate in their stage-2 store, the separate kernels (0) in a per-chunk post-pass. */
+ * Paths (hd_timing.path): the stream tail (2) and the step kernel (3) rotate in their stage-2 store, the separate kernels (0) in a per-chunk post-pass.
+ * The band limit above -- (-fs_dec/2, fs_dec/2), and less near the decimators' band edge -- is what hd_stream_set_front_tune below lifts. */
 int hd_stream_set_tune(hd_engine* e, uint32_t stream, double offset_hz);
+/* Per-stream tuning at the INPUT rate, applied to a stream's IQ before the first decimation stage: one wideband recording fanned out (stream_stride = 0)
+ * to streams whose payloads lie hundreds of kHz apart.  Df, Pf: uint32, units of 2^-32 cycle; fs = hd_engine_config.sampling_rate.
+ *  - Step: Df = hd_host_tune_step(offset_hz, fs); |offset_hz| >= fs / 2 is HD_ERR_INVALID.  An engine with decimation 1 returns HD_ERR_UNSUPPORTED
+ *    (hd_stream_set_tune is the same thing there).
+ *  - Phase: input sample i (0 <= i < n) of a call is rotated by theta = Pf + i Df (mod 2^32); after the call Pf += n Df (a stream that brings n = 0 does
+ *    not advance).  A new offset applies from the first call submitted after it was set; the phase carries on without a jump; nothing is drained.
+ *  - Phasor: the one of hd_stream_set_tune (the same tables and roundings, in both arithmetic modes; hd_host_tune_rotate restates it).
+ *  - Offset 0 sets Df = Pf = 0, and a stream with Df = Pf = 0 is not touched: bit-identical to an untuned stream on the same launch path.
+ *  - Defining property: a front-tuned stream fed x is, in every float and every decoded character, a stream without front tuning fed
+ *    hd_host_tune_rotate(x, Pf, Df) call by call -- also across a change of offset, on a first call, and on pushes so short that the first stage's
+ *    history carry holds outputs: the first stage's history holds ROTATED samples.  Everything downstream (DC blocker, hd_stream_set_tune, the
+ *    automatic AFC -- which keeps adjusting the decimated-rate offset only --, spectrum) sees the rotated input's decimation.
+ *  - Paths: a call in which some stream has Df or Pf != 0 runs its first stage as a launch of its own with the rotation in its staging loop, then the
+ *    stream tails (hd_timing.path 2) or the separate kernels (0); it never takes the step kernel (3) and reports step_variant 0.  When the last
+ *    front offset goes back to 0 the next call is routed as before. */
+int hd_stream_set_front_tune(hd_engine* e, uint32_t stream, double offset_hz);
+typedef struct hd_front_tune_info {
+    double   offset_hz;   /* current offset */
+    uint32_t step, phase; /* Df, and Pf of the next call to be submitted */
+    uint64_t from_call;   /* index (hd_process_* calls from 0) of the first call that used the current offset */
+} hd_front_tune_info;
+int hd_stream_front_tune(hd_engine* e, uint32_t stream, hd_front_tune_info* out);
 /* The server's AFC block (websocketServer/main.cpp:247-263) counted in sample time, run per stream at each delivery right after the call's AFC step:
  * elapsed += the call's input samples; if on, elapsed >= hold_s * sampling_rate and |frequency correction| > min_hz, then f += correction (skipped when
  * |f + correction| >= fs_dec / 2), D is recomputed, the AFC is reset by the correction (hd_stream_reset_frequency_correction), elapsed = 0 and one retune
