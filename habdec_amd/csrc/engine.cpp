@@ -157,7 +157,9 @@ struct hd_engine {
     uint32_t step_run = 0;     // HD_STEP_RUN: tiles per drawn run (default 4, minimum 2)
     bool no_cu_step = false;   // HD_NO_CU_STEP: step launches as single-wave workgroups (k_step) instead of one workgroup per CU (k_step_cu)
     uint32_t ring_run = 0;     // HD_RING_RUN: tiles per drawn run of the per-CU ring kernels (default: pick_ring_run)
+    uint32_t ring_chain = 1;   // HD_RING_CHAIN: 0 = the /32 worker waves' tiles all stand alone (the plain schedule: 64 - HR outputs per tile); default: chained runs (host/ring_schedule.hpp)
     uint32_t ring_short_pct = 25;   // HD_RING_SHORT_PCT: share of an XCD's tiles the worker waves draw as SINGLE tiles at the end of a launch (guided hand-out; 0 = whole runs to the end)
+    bool ring_short_set = false;    // ... was given.  Not given, chained launches take an eighth of the streams, not a quarter (make_claim)
     static constexpr uint32_t kS1Loaders = 2;   // LDS-DMA loader waves of k_stage1_cu at /8 and /4 (round 4: with the nt policy on the body rows one loader's three
                                                 // tiles in flight bound the launch -- 102.7 us with one loader, 94.7 with two, one box, alternating)
 #ifndef HD_S1_SLOTS_BATCH
@@ -360,7 +362,8 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
     if (const char* v = getenv("HD_STEP_RUN")) e->step_run = (uint32_t)atoi(v);
     e->no_cu_step = getenv("HD_NO_CU_STEP") != nullptr;
     if (const char* v = getenv("HD_RING_RUN")) e->ring_run = (uint32_t)atoi(v);
-    if (const char* v = getenv("HD_RING_SHORT_PCT")) e->ring_short_pct = std::min<uint32_t>((uint32_t)atoi(v), 100u);
+    if (const char* v = getenv("HD_RING_CHAIN")) e->ring_chain = atoi(v) ? 1u : 0u;
+    if (const char* v = getenv("HD_RING_SHORT_PCT")) { e->ring_short_pct = std::min<uint32_t>((uint32_t)atoi(v), 100u); e->ring_short_set = true; }
     if (const char* v = getenv("HD_TAIL_MAX_N2")) e->tail_max_n2 = (uint32_t)strtoul(v, nullptr, 0);
     {
         hipDeviceProp_t prop;
@@ -1113,6 +1116,23 @@ hd::StepClaim make_claim(const hd_engine* e, const CallPlan& p, uint32_t lin_wgs
             // the worker waves' guided hand-out (stage1_ring.h): the last ring_short_pct per cent of an XCD's tiles go out as single tiles
             const uint32_t tpx = claim.runs_per_xcd * run_len, whole = (uint32_t)((uint64_t)tpx * (100u - e->ring_short_pct) / 100u) / run_len;
             claim.tiles_per_xcd = tpx; claim.short_from = whole; claim.runs_per_xcd = whole + (tpx - whole * run_len);
+        }
+        // Chained tiles (host/ring_schedule.hpp; the /32 worker waves): a ticket is a run of ONE stream, so the ticket space is restated per stream -- the
+        // streams must divide among the XCDs, nothing else: runs need not divide anything, a stream's closing run is a ticket like any other.  Of an XCD's
+        // share the last ring_short_pct per cent of the STREAMS keep the plain schedule and go out tile by tile behind the chained runs (the guided hand-out;
+        // 0: every stream chained, 100: none).  Where the streams do not divide, or a push holds a single tile's rows, the plain grid above stays.
+        // (The share: a plain stream costs 36 tiles where a chained one costs 33, so the guided end is bought with tiles; an eighth of the streams measured
+        // best on two boxes -- 0.1323 ms per step against 0.1332 with none and 0.1333 with a quarter, NOTES.md -- and is what a launch takes unless told.)
+        if (run_len_cu && R1 == 32 && e->ring_chain && S % n_xcd == 0) {
+            const uint32_t hr = (uint32_t)((T1 - 1 + 31) / 32), rows = p.max_in / 32u, rl = e->ring_run >= 2u ? e->ring_run : 4u, sx = (uint32_t)(S / n_xcd);
+            const hd::RingSchedule ch = hd::ring_schedule(rows, hr, rl, true), pl = hd::ring_schedule(rows, hr, 1u, false);
+            const uint32_t sp = hd::ring_plain_streams(sx, e->ring_short_set ? e->ring_short_pct : 12u);
+            if (ch.chained && pl.ntiles && (uint64_t)sx * pl.ntiles < (1ull << 31)) {
+                claim.chain_rl = ch.rl; claim.chain_sx = sx; claim.chain_sc = sx - sp;
+                claim.chain_nfull = ch.n_full; claim.chain_kclose = ch.k_close; claim.chain_ntp = pl.ntiles;
+                claim.runs_per_xcd = hd::ring_tickets(ch, pl, sx, sx - sp);
+                claim.run_len = ch.rl; claim.short_from = 0xFFFFFFFFu; claim.tiles_per_xcd = 0;
+            }
         }
     }
     return claim;

@@ -641,11 +641,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D == 64 ? 1 
 // shared slots) nothing is shared between the waves of a CU and the loads in flight grow with the waves that exist.
 template <int T, int D2, int T2>
 __global__ __launch_bounds__(512) void k_step_cu(const RingArgs ra, const StreamCall* __restrict__ call, StreamCall* __restrict__ call_copy,
-                                                 const TailArgs ta, const uint32_t n_tail, const uint32_t n_streams, const uint32_t tail_bytes /* >= kWorkSlotBytes */)
+                                                 const TailArgs ta, const uint32_t n_tail, const uint32_t n_streams, const uint32_t tail_bytes /* >= kWorkSlotBytes + kWorkKeepBytes */)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char cu_lds[];
     RingCtl* ctl = reinterpret_cast<RingCtl*>(cu_lds);
-    unsigned char* slots = cu_lds + kRingCtlBytes;                           // worker slots of roles 0-3 (0-7 in a launch without tails)
+    unsigned char* keeps = cu_lds + 256;                                     // keep areas of workers 0-3 (kStepCtlBytes)
+    unsigned char* dump = keeps + 4 * kWorkKeepBytes;                        // ... and the area the lanes that keep nothing store into
+    unsigned char* slots = cu_lds + kStepCtlBytes;                           // worker slots of roles 0-3 (0-7 in a launch without tails, their keep areas behind them)
     unsigned char* tails = slots + 4 * kWorkSlotBytes;                       // four tail slices of tail_bytes each
     ring_ctl_init(ctl, 0u);
     __syncthreads();
@@ -675,7 +677,7 @@ __global__ __launch_bounds__(512) void k_step_cu(const RingArgs ra, const Stream
         w = (uint32_t)__builtin_amdgcn_readfirstlane((int)pick);
     }
     if (w < 4u) {
-        ring_worker<T>(ra, slots + w * (uint32_t)kWorkSlotBytes, w);
+        ring_worker<T>(ra, slots + w * (uint32_t)kWorkSlotBytes, keeps + w * (uint32_t)kWorkKeepBytes, dump, w);
     } else {
         const uint32_t k = w - 4u, lane = threadIdx.x & 63u;
         const uint32_t s = blockIdx.x * 4u + k;                          // (the grid has at least n_streams / 4 workgroups)
@@ -689,7 +691,8 @@ __global__ __launch_bounds__(512) void k_step_cu(const RingArgs ra, const Stream
             if (call_copy && lane < 4) reinterpret_cast<uint4*>(call_copy + s)[lane] = reinterpret_cast<const uint4*>(call + s)[lane];
         }
         // the tail is done: one more worker -- its slot is the tail's own slice (a launch without tails: the ring region's slots 4-7)
-        ring_worker<T>(ra, n_tail ? tails + k * tail_bytes : slots + w * (uint32_t)kWorkSlotBytes, w);
+        ring_worker<T>(ra, n_tail ? tails + k * tail_bytes : slots + w * (uint32_t)kWorkSlotBytes,
+                       n_tail ? tails + k * tail_bytes + (uint32_t)kWorkSlotBytes : slots + 8u * (uint32_t)kWorkSlotBytes + k * (uint32_t)kWorkKeepBytes, dump, w);
     }
 }
 
@@ -703,7 +706,10 @@ __global__ __launch_bounds__(D == 4 ? 1024 : D == 64 ? 256 : 512) void k_stage1_
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char cu_lds[];
     if constexpr (D == 32 || D == 64) {
-        ring_worker<T, D>(ra, cu_lds + (threadIdx.x >> 6) * (uint32_t)work_slot_bytes<D>(), threadIdx.x >> 6);
+        // (/32: the waves' keep areas behind the eight slots, the dump area behind those)
+        unsigned char* keeps = cu_lds + 8u * (uint32_t)work_slot_bytes<D>();
+        ring_worker<T, D>(ra, cu_lds + (threadIdx.x >> 6) * (uint32_t)work_slot_bytes<D>(), D == 32 ? keeps + (threadIdx.x >> 6) * (uint32_t)kWorkKeepBytes : nullptr,
+                          D == 32 ? keeps + 8 * kWorkKeepBytes : nullptr, threadIdx.x >> 6);
     } else {
     unsigned char* ring = cu_lds;
     RingCtl* ctl = reinterpret_cast<RingCtl*>(cu_lds + n_slots * ring_slot_bytes<T>());
@@ -900,10 +906,23 @@ static bool ring_limits_ok(uint32_t ntiles, const StepClaim& claim, bool workers
     return ntiles && ntiles <= 4096u && claim.run_len && ntiles % claim.run_len == 0 && total < (1ull << 24) && total / ntiles <= (1ull << 20);
 }
 
+// A claim on the chained schedule (StepClaim::chain_rl, host/ring_schedule.hpp): the /32 worker kernels only, and the ticket count must be the one the
+// kernel's own arithmetic walks -- a ticket names a stream of its XCD's share, so the shares must be the launch's streams (n_streams = 0: not known here).
+static bool ring_chain_ok(int ratio, int ntaps, uint32_t n, const StepClaim& claim, uint32_t n_streams)
+{
+    if (ratio != 32 || claim.chain_rl < 2u || !claim.n_xcd || !claim.chain_sx || claim.chain_sc > claim.chain_sx) return false;
+    const uint32_t hr = (uint32_t)((ntaps - 1 + ratio - 1) / ratio), rows = n / (uint32_t)ratio;
+    const RingSchedule ch = ring_schedule(rows, hr, claim.chain_rl, true), pl = ring_schedule(rows, hr, 1u, false);
+    if (!ch.chained || ch.rl != claim.chain_rl || ch.n_full != claim.chain_nfull || ch.k_close != claim.chain_kclose || pl.ntiles != claim.chain_ntp) return false;
+    if (!ch.ntiles || !pl.ntiles || (n_streams && (uint64_t)claim.chain_sx * claim.n_xcd != n_streams)) return false;
+    return (uint64_t)claim.chain_sx * (ch.ntiles > pl.ntiles ? ch.ntiles : pl.ntiles) * claim.n_xcd < (1ull << 32) &&
+           claim.runs_per_xcd == ring_tickets(ch, pl, claim.chain_sx, claim.chain_sc);
+}
+
 uint32_t step_cu_tail_lds(int ratio, int ntaps)
 {
     if (ratio != 32 || (ntaps != 212 && ntaps != 174)) return 0;
-    return ((163840u - (uint32_t)kRingCtlBytes - 4u * (uint32_t)kWorkSlotBytes) / 4u) & ~15u;      // four worker slots + four tail slices fill the CU's 160 KB
+    return ((163840u - (uint32_t)kStepCtlBytes - 4u * (uint32_t)kWorkSlotBytes) / 4u) & ~15u;      // the control block, four worker slots + four tail slices fill the CU's 160 KB
 }
 
 bool launch_step_cu(hipStream_t st, int ratio, int ntaps, int ratio2, int ntaps2, uint32_t n_streams, uint32_t n_cus, const float2* in, size_t in_stride,
@@ -913,13 +932,13 @@ bool launch_step_cu(hipStream_t st, int ratio, int ntaps, int ratio2, int ntaps2
 {
     if (ratio != 32 || !claim.ctr || !uniform_n || uniform_n % 2048u) return false;
     const uint32_t ntiles = ring_tiles(ratio, ntaps, uniform_n);
-    if (!ring_limits_ok(ntiles, claim, true)) return false;
-    if (tail_bytes < (uint32_t)kWorkSlotBytes) tail_bytes = (uint32_t)kWorkSlotBytes;       // (a finished tail's slice is its wave's tile slot)
+    if (claim.chain_rl ? !ring_chain_ok(ratio, ntaps, uniform_n, claim, n_streams) : !ring_limits_ok(ntiles, claim, true)) return false;
+    if (tail_bytes < (uint32_t)(kWorkSlotBytes + kWorkKeepBytes)) tail_bytes = (uint32_t)(kWorkSlotBytes + kWorkKeepBytes);       // (a finished tail's slice is its wave's tile slot and keep area)
     tail_bytes = (tail_bytes + 15u) & ~15u;
     RingArgs ra{in, in_stride, hist_in, hist_out, taps, out, out_stride, uniform_n, ntiles, claim, nullptr, nullptr, 0u, nullptr};
 #define HD_CU_CASE(T, D2, T2)                                                                                                         \
     if (ntaps == T && ratio2 == D2 && ntaps2 == T2) {                                                                                 \
-        const uint32_t lds = (uint32_t)kRingCtlBytes + (n_tail ? 4u * (uint32_t)kWorkSlotBytes + 4u * tail_bytes : 8u * (uint32_t)kWorkSlotBytes); \
+        const uint32_t lds = (uint32_t)kStepCtlBytes + (n_tail ? 4u * (uint32_t)kWorkSlotBytes + 4u * tail_bytes : 8u * (uint32_t)kWorkSlotBytes + 4u * (uint32_t)kWorkKeepBytes); \
         if (lds > 163840u) return false;                                                                                              \
         static bool attr_set[64] = {};                             /* per device: the attribute belongs to the function on the current device */ \
         int dev_ = 0;                                                                                                                 \
@@ -962,14 +981,14 @@ bool launch_stage1_cu(hipStream_t st, int ratio, int ntaps, uint32_t n_cus, cons
     if (n_waves < 8u || n_waves > 16u) n_waves = 8u;
     if (!claim.ctr || !uniform_n || uniform_n % 2048u) return false;
     const uint32_t ntiles = ring_tiles(ratio, ntaps, uniform_n);
-    if (!ring_limits_ok(ntiles, claim, ratio >= 32)) return false;
+    if (claim.chain_rl ? !ring_chain_ok(ratio, ntaps, uniform_n, claim, 0u) : !ring_limits_ok(ntiles, claim, ratio >= 32)) return false;
     if ((ratio <= 4) != (final_call != nullptr)) return false;               // /4 exists as a FINAL stage only (the only stage of a plan), the others as first stages only
     RingArgs ra{in, in_stride, hist_in, hist_out, taps, out, out_stride, uniform_n, ntiles, claim, gave_up, final_call, fir_hist_cap, fft_in};
 #define HD_S1_CASE(D, T)                                                                                                              \
     if (ratio == D && ntaps == T) {                                                                                                   \
         static_assert(D >= 32 || (uint32_t)ring_bytes<T, kRingNSLAlone>() <= 163840u, "eight tile slots must fit a CU's LDS");       \
         const uint32_t workers = D == 32 ? 8u : n_slots <= 4u ? 3u : 4u;            /* (/64: 33 KB slots; three leave room for the other queue's FIR tile) */ \
-        const uint32_t lds = D >= 32 ? workers * (uint32_t)work_slot_bytes<(D >= 32 ? D : 32)>() : n_slots * (uint32_t)ring_slot_bytes<T>() + (uint32_t)kRingCtlBytes; \
+        const uint32_t lds = D >= 32 ? workers * (uint32_t)work_slot_bytes<(D >= 32 ? D : 32)>() + (D == 32 ? (workers + 1u) * (uint32_t)kWorkKeepBytes : 0u) : n_slots * (uint32_t)ring_slot_bytes<T>() + (uint32_t)kRingCtlBytes; \
         static bool attr_set[64] = {};                                                                                                \
         int dev_ = 0;                                                                                                                 \
         if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) return false;                                                \

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../dev_types.h"
+#include "../host/ring_schedule.hpp"
 
 namespace hd {
 
@@ -25,6 +26,12 @@ struct StepClaim {
     // are SINGLE tiles, so that the end of a launch is ragged by one tile's time instead of one run's (runs_per_xcd counts the tickets of both kinds;
     // tiles_per_xcd = short_from * run_len + (runs_per_xcd - short_from)).  short_from = 0xFFFFFFFF: every ticket is a whole run.
     uint32_t short_from = 0xFFFFFFFFu, tiles_per_xcd = 0;
+    // Worker-wave kernels of the /32 stages only -- chained tiles (host/ring_schedule.hpp).  chain_rl >= 2: the launch's streams divide among the XCDs,
+    // chain_sx to each; the first chain_sc streams of a share are tiled with the chained schedule (runs of chain_rl tiles, one ticket per run), the
+    // other chain_sx - chain_sc with the plain one and drawn tile by tile behind them (the guided hand-out).  A ticket is hd::ring_ticket of it,
+    // runs_per_xcd = hd::ring_tickets; run_len, short_from and tiles_per_xcd are not looked at.  chain_rl = 0: the plain grid described above.
+    uint32_t chain_rl = 0, chain_sx = 0, chain_sc = 0;
+    uint32_t chain_nfull = 0, chain_kclose = 0, chain_ntp = 0;   // hd::RingSchedule::n_full and ::k_close of the chained schedule (chain_rl is its ::rl), ::ntiles of the plain one
 };
 
 // ---- the fused stream tail (tail_body.h / tail.hip): stage 2 + low-pass + discriminator + symbol extractor, one wave per stream

@@ -52,6 +52,8 @@ typedef float r_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kRingRowBytes = 272;                  // 32 samples + one 16-byte pad
 constexpr int kRingNSLAlone = 4;                      // tile slots per loader wave of the loader / consumer kernels (k_stage1_cu at /8 and /4: eight slots)
 constexpr int kWorkSlotBytes = 64 * kRingRowBytes;    // a worker wave's tile slot (ring_worker: the /32 stages): 64 padded rows
+constexpr int kWorkKeepBytes = 128;                   // ... and the sums it keeps from one tile of a chained run to the next (ring_worker): HR hand-overs x 8 bytes (16 in fast mode)
+constexpr int kStepCtlBytes = 256 + 5 * kWorkKeepBytes;   // head of k_step_cu's LDS: RingCtl, the keep areas of workers 0-3 (a finished tail keeps its sums in its own slice, behind its tile slot), the dump area
 constexpr int kRingCtlBytes = 384;                 // (256 bytes of RingCtl; every 16 bytes count when a fifth tile slot has to fit beside four tails)
 constexpr uint32_t kRingSpinLimit = 1u << 22;   // polls before a waiting wave gives up (seconds; a correct run waits microseconds)
 template <int T> constexpr int ring_halo_rows() { return (T - 1 + 31) / 32; }
@@ -167,7 +169,9 @@ __device__ __forceinline__ void glds4(const void* base, uint32_t off, uint32_t l
 
 // Seventeen of them back to back -- a tile's 64 rows -- with M0 stepped by 1 KiB in between: one scalar instruction per DMA instruction
 // instead of five (the loader's issue time per tile is what bounds a CU's stream when nothing else does).
-template <bool HEAD_KEPT = false /* the tile's first rows are another tile's last ones and that tile has not come yet (a run's first tile): default policy there too */>
+// POLICY 1: the tile's first rows are another tile's last ones and that tile has not come yet (a run's first tile): default policy there too.
+// POLICY 2: nt on all seventeen -- a chained tile (host/ring_schedule.hpp), whose rows no later tile of its run reads again.
+template <int POLICY = 0>
 __device__ __forceinline__ void glds16_x17(const void* base, const uint32_t (&off)[17], uint32_t lds_dst)
 {
     unsigned keep, scc_keep;                      // (s_add_u32 writes SCC, which compiler code around the statement may hold live: saved and restored)
@@ -186,7 +190,11 @@ __device__ __forceinline__ void glds16_x17(const void* base, const uint32_t (&of
     // (Round 5: the worker waves of an XCD walk neighbouring runs at the same time, so the rows a run's FIRST tile shares with the previous run's last tile are
     // loaded long before that last tile comes -- with nt they were gone by then: 16 MB per step launch fetched twice at runs of four.  Such a tile keeps its
     // first two instructions -- rows 0 .. 7.5 -- on the default policy as well.)
-    if constexpr (HEAD_KEPT)
+    if constexpr (POLICY == 2)
+        asm volatile("s_cselect_b32 %1, 1, 0\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %20\n\ts_nop 0\n\t"
+                     HD_G1(2) HD_G1(3) HD_G1(4) HD_G1(5) HD_G1(6) HD_G1(7) HD_G1(8) HD_G1(9) HD_G1(10) HD_G1(11) HD_G1(12) HD_G1(13) HD_G1(14) HD_G1(15) HD_G1(16) HD_G1(17)
+                     "global_load_lds_dwordx4 %18, %19" HD_GLDS_BODY_POLICY "\n\ts_mov_b32 m0, %0\n\ts_cmp_lg_u32 %1, 0" HD_G17_OPS);
+    else if constexpr (POLICY == 1)
         asm volatile("s_cselect_b32 %1, 1, 0\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %20\n\ts_nop 0\n\t"
                      HD_G1D(2) HD_G1D(3) HD_G1(4) HD_G1(5) HD_G1(6) HD_G1(7) HD_G1(8) HD_G1(9) HD_G1(10) HD_G1(11) HD_G1(12) HD_G1(13) HD_G1(14) HD_G1(15) HD_G1(16) HD_G1D(17)
                      "global_load_lds_dwordx4 %18, %19\n\ts_mov_b32 m0, %0\n\ts_cmp_lg_u32 %1, 0" HD_G17_OPS);
@@ -729,7 +737,8 @@ __device__ __forceinline__ void ring_consumer(const RingArgs& a, const RingGeom&
 // walks its output's whole window reads 6.6 x as much) -- and the ACCUMULATORS move: the sum of output origin + o starts in lane o, takes the taps that
 // fall on that lane's row, and is handed to lane o + 1 (one DPP rotate per component) for the next row.  Every sum still receives its T products in
 // ascending tap order, separately rounded: bit-identical to the lane-owns-the-window loop by construction.  After HR hand-overs lane l >= HR holds
-// output origin + l - HR; the sums that wrapped past lane 63 are the next tile's (ring_adv).
+// output origin + l - HR; the sums that left lane 63 are the next tile's: recomputed there when the tile stands alone (ring_adv), or -- a chained run of
+// the /32 stages, host/ring_schedule.hpp -- kept and handed to the next tile's lane 0, so that its lanes < HR end with outputs too.
 // (Row length D: the stage's ratio -- 32 samples at /32, 64 at /64 -- so that output o's window starts in row o.  A row is D / 2 sixteen-byte chunks plus one pad
 // chunk; 64 rows are D / 2 + 1 DMA instructions.)
 template <int D> constexpr int work_row_bytes() { return D * 8 + 16; }
@@ -760,7 +769,9 @@ __device__ __forceinline__ void glds16_x11(const void* base, const uint32_t* off
 }
 
 template <int T, int D = 32>
-__device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __restrict__ slot, const uint32_t role /* diagnostic builds: the wave's row in the stamp table */)
+__device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __restrict__ slot, unsigned char* keep_lds /* kWorkKeepBytes of LDS of the wave's own (the /32 stages) */,
+                                            unsigned char* dump_lds /* kWorkKeepBytes that nobody reads, shared by the workgroup's waves */,
+                                            const uint32_t role /* diagnostic builds: the wave's row in the stamp table */)
 {
     static_assert(D == 32 || D == 64, "a row is one output's stride");
     constexpr int HR = work_halo_rows<T, D>();
@@ -794,9 +805,10 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
         const int h = (r / HQ - HR) * D + (r % HQ) * 32 + (int)(lane >> 1) + (T - 1);      // index into the T-1 history samples (< 0: in front of them, never read)
         hist_off[r] = (uint32_t)(h < 0 ? 0 : h) * 8u + (lane & 1u) * 4u;
     }
-    auto issue = [&](const uint32_t s, const uint32_t tile, const bool run_start) {
+    // a tile is its stream and its first loaded row (host/ring_schedule.hpp: row0 = -HR for a stream's first tile); `chained`: a further tile of a chained run
+    auto issue = [&](const uint32_t s, const int32_t row0, const bool run_start, const bool chained) {
         const unsigned char* in_s = reinterpret_cast<const unsigned char*>(a.in + (size_t)s * a.in_stride);
-        if (tile == 0) {                            // rows 0 .. HR-1: the stage history; rows HR .. 63: the call's first ADV rows
+        if (row0 < 0) {                             // rows 0 .. HR-1: the stage history; rows HR .. 63: the call's first ADV rows
             const unsigned char* hb = reinterpret_cast<const unsigned char*>(a.hist_in + (size_t)s * (T - 1));
 #pragma unroll
             for (int r = 0; r < HR * HQ; ++r) glds4(hb, hist_off[r], dst + (uint32_t)((r / HQ) * ROWB + (r % HQ) * 256));
@@ -804,9 +816,9 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
             for (int i = 0; i < NB0; ++i)
                 if (64 * (i + 1) <= (int)ADV * CPR || lane < (uint32_t)((int)ADV * CPR - 64 * i)) glds16(in_s, boff[i], dst + (uint32_t)(HR * ROWB) + 1024u * i);
         } else {
-            const uint32_t origin = tile * ADV < rows - ADV ? tile * ADV : rows - ADV;
-            const unsigned char* src = in_s + (size_t)(origin - (uint32_t)HR) * (uint32_t)(D * 8);
-            if constexpr (D == 32) { if (run_start) glds16_x17<true>(src, boff, dst); else glds16_x17<false>(src, boff, dst); }
+            // (wave-uniform by construction; said again because the cursor's quotients come out of the vector pipe and the DMA's base must be a scalar pair)
+            const unsigned char* src = static_cast<const unsigned char*>(uniform_ptr(in_s + (size_t)(uint32_t)row0 * (uint32_t)(D * 8)));
+            if constexpr (D == 32) { if (chained) glds16_x17<2>(src, boff, dst); else if (run_start) glds16_x17<1>(src, boff, dst); else glds16_x17<0>(src, boff, dst); }
             else { glds16_x11<11>(src, boff, dst); glds16_x11<11>(src, boff + 11, dst + 11u * 1024u); glds16_x11<7>(src, boff + 22, dst + 22u * 1024u); }
         }
     };
@@ -823,21 +835,67 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
     const uint32_t runs = a.claim.runs_per_xcd, run_len = a.claim.run_len, short_from = a.claim.short_from < runs ? a.claim.short_from : runs;
     const uint32_t tpx = a.claim.tiles_per_xcd ? a.claim.tiles_per_xcd : runs * run_len;
     auto draw = [&]() -> unsigned int { unsigned int t = 0; if (lane == 0) t = __hip_atomic_fetch_add(my_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return t; };
-    uint32_t s = 0, tile = 0, left = 0, this_run = 0;   // the run's cursor: (s, tile) is the next tile to issue, `left` of the run's this_run tiles are still to be issued
+    // Chained tiles (the /32 stages; host/ring_schedule.hpp, StepClaim::chain_rl): a ticket is a run of ONE stream's chained schedule -- its further tiles
+    // start 64 rows on and take over the sums that wrapped past lane 63 of the tile before, so all 64 lanes end with an output and no halo row is loaded
+    // twice inside a run -- or, behind those, a single tile of a stream that keeps the plain schedule (the guided hand-out).
+    constexpr bool CH = D == 32;
+    const bool chain_mode = CH && a.claim.chain_rl >= 2u;
+    // the run's cursor: the next tile to issue is the one of stream s whose first loaded row is row0 (host/ring_schedule.hpp: -HR for a stream's first tile;
+    // the tile that ends with the push's last row is the stream's last); `left` of the run's this_run tiles are still to be issued
+    uint32_t s = 0, left = 0, this_run = 0;
+    int32_t row0 = 0;
     auto take_run = [&](const unsigned int ticket) -> bool {          // the ticket's run, or false: the XCD's share is used up
         const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);
         if (t == runs && lane == 0) (void)__hip_atomic_exchange(next_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (t >= runs) return false;
+        auto uni = [](const uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };   // (quotients come out of the vector pipe)
+        if (chain_mode) {
+            // the two schedules of the launch, from the figures the host worked out (StepClaim; checked against ring_schedule by the launcher)
+            RingSchedule ch{}, pl{};
+            ch.rows = pl.rows = rows; ch.hr = pl.hr = (uint32_t)HR;
+            ch.chained = true; ch.rl = a.claim.chain_rl; ch.n_full = a.claim.chain_nfull; ch.k_close = a.claim.chain_kclose; ch.run_out = 64u * ch.rl - (uint32_t)HR;
+            ch.close_row0 = (int32_t)rows - (int32_t)(64u * ch.k_close); ch.nruns = ch.n_full + (ch.k_close ? 1u : 0u); ch.ntiles = ch.n_full * ch.rl + ch.k_close;
+            pl.run_out = ADV; pl.ntiles = pl.nruns = a.claim.chain_ntp;
+            const RingTicket k = ring_ticket(ch, pl, a.claim.chain_sc, t);
+            s = uni(xcd * a.claim.chain_sx + k.stream); left = this_run = uni(k.ntiles); row0 = (int32_t)uni((uint32_t)k.row0);
+            return true;
+        }
         const uint32_t g0 = xcd * tpx + (t < short_from ? t * run_len : short_from * run_len + (t - short_from));
-        s = g0 / a.ntiles; tile = g0 - s * a.ntiles; left = this_run = t < short_from ? run_len : 1u;
+        s = uni(g0 / a.ntiles); left = this_run = t < short_from ? run_len : 1u;
+        row0 = (int32_t)uni((uint32_t)ring_plain_row0(rows, (uint32_t)HR, g0 - s * a.ntiles));
         return true;
     };
-    auto advance = [&]() { ++tile; --left; if (tile == a.ntiles) { tile = 0; ++s; } };
+    auto advance = [&]() {
+        --left;
+        if (chain_mode) row0 += 64;                      // (a run stays inside its stream; behind the run's last tile the cursor is not looked at)
+        else if (row0 + 64 == (int32_t)rows) { ++s; row0 = -HR; }                               // the plain grid: a run goes on into the next stream
+        else row0 = row0 + (int32_t)ADV < (int32_t)rows - 64 ? row0 + (int32_t)ADV : (int32_t)rows - 64;
+    };
+    // the tile the cursor stands on, for the tap loop and the store: its stream, bit 31 set for a further tile of a chained run
+    auto tile_here = [&]() -> uint32_t { return s | ((chain_mode && left != this_run) ? 0x80000000u : 0u); };
 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (a former tail wave: every LDS access of the tail has completed before DMA lands in its slice)
     if (!take_run(draw())) { RSTAMP_WRITE(role, 0); return; }
-    uint32_t cs = s, ct = tile;                     // the tile in (or on its way into) my slot
-    issue(cs, ct, true); advance();
+    uint32_t cs = tile_here();                      // the tile in (or on its way into) my slot: stream (| chained), first row
+    int32_t crow0 = row0;
+    issue(s, crow0, true, false); advance();
+    // The sums that left lane 63 at each hand-over of the last tile (fast mode: both chains) wait in LDS, one entry per hand-over.  They cost no vector
+    // instruction: every lane stores its sum in front of the rotate -- lane 63 into the entry, the others into a dump area nobody reads (one address: the
+    // store needs no lane mask) --, every lane reads the entry a unit ahead (a broadcast; only lane 0's copy is used), and the
+    // rotate itself -- wave_shr:1, which leaves lane 0 without a source, so lane 0 keeps the operand the result is tied to -- puts it into lane 0.
+#ifdef HD_FAST_ARITH
+    typedef r_f32x4 kept_t;                         // (acc, acc_b)
+#else
+    typedef r_f32x2 kept_t;
+#endif
+    static_assert(!CH || sizeof(kept_t) * HR <= (size_t)kWorkKeepBytes, "the keep area");
+    // (the area's LDS address stays in a vector register: as a scalar it is copied into one in front of every access)
+    uint32_t kept_at = CH ? lds_addr_of(keep_lds) : 0u;
+    if constexpr (CH) asm volatile("" : "+v"(kept_at));
+    typedef kept_t __attribute__((address_space(3)))* kept_ptr_t;
+    const kept_ptr_t kept = (kept_ptr_t)kept_at;
+    uint32_t kept_to = CH ? (lane == 63u ? lds_addr_of(keep_lds) : lds_addr_of(dump_lds)) : 0u;
+    const kept_ptr_t kept_w = (kept_ptr_t)kept_to;
     unsigned int ticket = 0;                        // the draw in flight (lane 0's register) once the run's last tile has been issued
     if (!left) ticket = draw();
 
@@ -870,15 +928,15 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
         RSTAMP(3);
         bool more = true;
         if (!left) more = take_run(ticket);         // (drawn behind the DMA of the run's last tile: it arrived with that tile)
-        uint32_t ns = 0, nt = 0;
+        uint32_t ns = 0;
+        int32_t nrow0 = 0;
         if (more) {
-            ns = s; nt = tile;
-            issue(ns, nt, left == this_run); advance();
+            ns = tile_here(); nrow0 = row0;
+            issue(s, nrow0, left == this_run, (ns >> 31) != 0u); advance();
             if (!left) ticket = draw();
         }
         RSTAMP(4);
 
-        const uint32_t origin = ct * ADV < rows - ADV ? ct * ADV : rows - ADV;
         r_f32x2 acc = {0.f, 0.f};
 #ifdef HD_FAST_ARITH
         r_f32x2 acc_b = {0.f, 0.f};                     // fast mode: the odd slots' chain (ring_fma16x2); it travels with `acc` and joins it at the end
@@ -909,16 +967,31 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
             }
 #endif
         };
-        auto rot1 = [&](r_f32x2& v) {                   // lane l takes lane l - 1's sum (wave_ror:1)
+        // Lane l takes lane l - 1's sum.  The /32 stages: lane 0 takes what left lane 63 at the SAME hand-over of the tile before (`kin`, read a unit ahead).  In a
+        // chained tile that is the sum its row continues -- the chain of one accumulator goes on across the tile boundary: every sum still receives its T
+        // products in ascending tap order, it only rests in LDS for one tile's time --; in any other tile lane 0 starts a sum that ends in a lane < HR and
+        // is never stored, so it may take the kept value just the same: no branch, no select.  (/64: wave_ror:1, the wrapped sums are thrown away.)
+        kept_t kin{}, kout{};                             // read for the coming hand-over / left lane 63 at the last one (stored at the head of the next unit,
+                                                        // behind that unit's wait for its taps: a store issued in front of that wait would be waited for)
+        auto rot1 = [&](r_f32x2& v, const r_f32x2 k0) {
             // (through scalars: __builtin_bit_cast of an ext-vector ELEMENT reads the vector's first element whichever was named -- clang 20)
-            const float re = v.x, im = v.y;
-            v.x = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, re), 0x13C, 0xF, 0xF, false));
-            v.y = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, im), 0x13C, 0xF, 0xF, false));
+            const float re = v.x, im = v.y, kre = k0.x, kim = k0.y;
+            if constexpr (CH) {
+                v.x = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, kre), __builtin_bit_cast(int, re), 0x138, 0xF, 0xF, false));
+                v.y = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, kim), __builtin_bit_cast(int, im), 0x138, 0xF, 0xF, false));
+            } else {
+                v.x = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, re), 0x13C, 0xF, 0xF, false));
+                v.y = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, im), 0x13C, 0xF, 0xF, false));
+            }
         };
         auto rot = [&]() {
-            rot1(acc);
 #ifdef HD_FAST_ARITH
-            rot1(acc_b);
+            if constexpr (CH) kout = (kept_t){acc.x, acc.y, acc_b.x, acc_b.y};
+            rot1(acc, kin.xy);
+            rot1(acc_b, kin.zw);
+#else
+            if constexpr (CH) kout = acc;
+            rot1(acc, kin);
 #endif
         };
         // A unit's taps (32 slots) are requested a unit ahead through the scalar cache.  Scalar loads return out of order, so waiting for any of them waits for
@@ -935,6 +1008,8 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
                 ldk(kk[(u + 1) & 1][0], std::integral_constant<int, 2 * u + 2>{});
                 ldk(kk[(u + 1) & 1][1], std::integral_constant<int, 2 * u + 3>{});
             }
+            if constexpr (CH && u % UPS == 0 && u > 0) kept_w[u / UPS - 1] = kout;                 // (the hand-over in front of this unit; lane 63's is the entry)
+            if constexpr (CH && (u + 1) % UPS == 0 && u + 1 < NU) kin = kept[(u + 1) / UPS - 1];   // (the hand-over behind this unit)
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (JS < 32 * u + 16 && 32 * u < NS) mac_chunk(kk[u & 1][0], std::integral_constant<int, 2 * u>{});
             if constexpr (32 * u + 16 < NS && JS < 32 * u + 32) mac_chunk(kk[u & 1][1], std::integral_constant<int, 2 * u + 1>{});
@@ -948,11 +1023,13 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
         ++n_done;
 #endif
         RSTAMP(1);
-        if (lane >= (uint32_t)HR) a.out[(size_t)cs * a.out_stride + origin + lane - (uint32_t)HR] = make_float2(acc.x, acc.y);
-        if (ct + 1 == a.ntiles) {                   // the stream's last tile: carry the last T-1 inputs (Decimator.h:140-143)
+        // lane l holds output crow0 + l: all 64 in a chained tile, the lanes behind the HR wrapped sums in any other
+        const uint32_t cstream = cs & 0x7FFFFFFFu;
+        if (lane >= (uint32_t)HR || (cs >> 31)) a.out[(size_t)cstream * a.out_stride + (size_t)(uint32_t)(crow0 + (int32_t)lane)] = make_float2(acc.x, acc.y);
+        if (crow0 + 64 == (int32_t)rows) {                           // the stream's last tile: carry the last T-1 inputs (Decimator.h:140-143)
             // (all loads, then all stores: ONE wait -- which the DMA in flight has to see out anyway)
-            const float2* in_s = a.in + (size_t)cs * a.in_stride + (a.n - (uint32_t)(T - 1));
-            float2* hout = a.hist_out + (size_t)cs * (T - 1);
+            const float2* in_s = a.in + (size_t)cstream * a.in_stride + (a.n - (uint32_t)(T - 1));
+            float2* hout = a.hist_out + (size_t)cstream * (T - 1);
             constexpr int NH = (T - 1 + 63) / 64;
             float2 h[NH];
 #pragma unroll
@@ -961,7 +1038,7 @@ __device__ __forceinline__ void ring_worker(const RingArgs& a, unsigned char* __
             for (int k = 0; k < NH; ++k) if (lane + 64u * k < (uint32_t)(T - 1)) hout[lane + 64u * k] = h[k];
         }
         if (!more) break;
-        cs = ns; ct = nt;
+        cs = ns; crow0 = nrow0;
     }
     RSTAMP(2);
     RSTAMP_WRITE(role, n_done);
