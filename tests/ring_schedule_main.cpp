@@ -5,6 +5,7 @@
 //     the tile before), against plain left-to-right sums: bit for bit.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
 #include <vector>
@@ -136,8 +137,21 @@ static void check_handover(uint32_t rows, int T, uint32_t run_len, uint32_t seed
     }
 }
 
-int main()
+// With arguments (rows hr run_len chained) the program prints that schedule instead -- one line per tile: k row0 out0 out_n chained last first_of_run --
+// for tests that need the tile geometry (tests/fir_probe.py: which outputs are wrapped rows, a run's first tile, the closing tile).
+static int print_schedule(char** a)
 {
+    const hd::RingSchedule s = hd::ring_schedule((uint32_t)std::strtoul(a[1], nullptr, 10), (uint32_t)std::strtoul(a[2], nullptr, 10), (uint32_t)std::strtoul(a[3], nullptr, 10), std::strtoul(a[4], nullptr, 10) != 0);
+    for (uint32_t k = 0; k < s.ntiles; ++k) {
+        const hd::RingTile t = hd::ring_tile(s, k);
+        std::printf("tile %u %d %u %u %d %d %d\n", k, t.row0, t.out0, t.out_n, (int)t.chained, (int)t.last, (int)!t.chained);
+    }
+    return s.ntiles ? 0 : 1;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc == 5) return print_schedule(argv);
     const uint32_t rows_set[] = {64, 128, 192, 2048, 32768}, hr_set[] = {6, 7}, rl_set[] = {2, 3, 4, 9};
     for (uint32_t rows : rows_set) for (uint32_t hr : hr_set) for (uint32_t rl : rl_set) for (int ch = 0; ch < 2; ++ch) check_schedule(rows, hr, rl, ch != 0);
     // the figure the design quotes: /32, 2048 rows, runs of four -> 8 x 4 + 1 = 33 tiles against 36

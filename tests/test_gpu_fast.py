@@ -10,6 +10,9 @@ code/Decoder/Decimator.h:128-138, FirFilter.h:155-161):
   c. at bench size, free running as bench.py drives it: symbols produced, characters and sentences identical on EVERY stream of the headline workload
      (1024 streams x ~60 steps through k_step_cu) and of the other four workloads, plus the floats of sampled streams inside the step kernel.
 
+The norm-wise gate is relative to the output's peak: a wrong edge tap, a lost chain of a wrapped sum or a history row off by one passes it.  Those are
+tests/test_gpu_fast_taps.py's business (sparse probes against a float64 model, componentwise, every tap of every FIR on every launch path).
+
 The exact mode stays the default and is what every other test file runs."""
 import json
 from pathlib import Path
