@@ -41,6 +41,14 @@ class hd_front_tune_info(C.Structure):
     _fields_ = [("offset_hz", C.c_double), ("step", C.c_uint32), ("phase", C.c_uint32), ("from_call", C.c_uint64)]
 
 
+class hd_survey_params(C.Structure):
+    _fields_ = [("threshold_db", C.c_double), ("merge_hz", C.c_double), ("dc_guard_hz", C.c_double), ("max_width_hz", C.c_double)]
+
+
+class hd_survey_candidate(C.Structure):
+    _fields_ = [("offset_hz", C.c_double), ("snr_db", C.c_double), ("width_hz", C.c_double), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32)]
+
+
 SENTENCE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p)
 MATCH_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int)
 CHARS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_char), C.c_size_t)
@@ -49,6 +57,7 @@ _vp, _u32, _sz, _dbl, _int, _f = C.c_void_p, C.c_uint32, C.c_size_t, C.c_double,
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
+_f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 
 # name -> (restype, argtypes): every symbol declared in include/habdec_amd.h
 ENGINE_API = {
@@ -102,6 +111,14 @@ ENGINE_API = {
     "hd_min_chunk": (_u32, [_u32]),
     "hd_engine_timing": (_int, [_vp, C.POINTER(hd_timing)]),
     "hd_engine_set_timing": (None, [_vp, _int]),
+    "hd_survey_create": (_int, [_vp, C.POINTER(_vp)]),
+    "hd_survey_destroy": (None, [_vp]),
+    "hd_survey_reset": (_int, [_vp]),
+    "hd_survey_push_device": (_int, [_vp, _vp, C.c_uint64]),
+    "hd_survey_push_host": (_int, [_vp, _vp, C.c_uint64]),
+    "hd_survey_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
+    "hd_survey_params_default": (None, [C.POINTER(hd_survey_params)]),
+    "hd_survey_detect": (_int, [_vp, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
 }
 # every symbol declared in include/habdec_amd_host.h
 HOST_API = {
@@ -149,6 +166,8 @@ HOST_API = {
     "hd_host_tune_step": (_int, [_dbl, _dbl, C.POINTER(C.c_uint32)]),
     "hd_host_tune_tables": (None, [_f32p, _f32p]),
     "hd_host_tune_rotate": (None, [_f32p, _sz, C.c_uint32, C.c_uint32, _f32p]),
+    "hd_host_survey_window": (None, [_f32p]),
+    "hd_host_survey_detect": (_int, [_f64p, C.c_uint64, _dbl, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
 }
 
 

@@ -29,9 +29,11 @@
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
 #include "host/iq_file_batch.hpp"
+#include "host/survey.hpp"
 #include "host/text_stage.hpp"
 #include "host/tune_host.hpp"
 #include "kernels/launch.h"
+#include "kernels/survey.h"
 
 // A launcher (or layout helper) of the kernels that exist once per arithmetic mode (kernels/arith.h): hd::exact::fn or hd::fast::fn by the engine's mode.
 #define HDK(fn, ...) (e->fast ? hd::fast::fn(__VA_ARGS__) : hd::exact::fn(__VA_ARGS__))
@@ -1798,6 +1800,217 @@ uint32_t hd_stream_symbol_backlog(hd_engine* e, uint32_t s)
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
     return e->st[s].held;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- wideband survey (kernels/survey.hip) -------------------------- */
+
+struct hd_survey {
+    hd_engine* e = nullptr;
+    hipStream_t q = nullptr;               // the survey's own queue: launches, staging copies and the read-back
+    uint32_t runs_per_launch = 1024;       // HD_SURVEY_RUNS, read at creation
+    const float2* tw = nullptr;            // the engine's twiddles, or own_tw where the engine computes no spectra
+    float2* own_tw = nullptr;
+    float* win = nullptr;                  // [4096] the window table
+    float* partial = nullptr;              // [runs_per_launch][4096] float rows of the launch in flight (launches of one queue run in order)
+    double* acc = nullptr;                 // [4096], for the life of the survey
+    float2* slab = nullptr;                // hd_survey_push_host: staging for kSlabSegs segments, allocated by the first host push
+    double* h_acc = nullptr;               // page-locked landing place of the read-back
+    double sum_w2 = 0;                     // sum of w^2, in double over the float table
+    uint64_t segments = 0;
+    static constexpr uint32_t kSlabSegs = 256;   // whole segments one staging copy carries ((256 + 1) hops = 4 MiB + 16 KiB)
+    ~hd_survey()
+    {
+        for (void* p : {(void*)own_tw, (void*)win, (void*)partial, (void*)acc, (void*)slab}) if (p) (void)hipFree(p);
+        if (h_acc) (void)hipHostFree(h_acc);
+        if (q) (void)hipStreamDestroy(q);
+    }
+};
+
+namespace {
+
+// Segments [seg0, seg1) of a push whose run length is r, read from x (x[0] = the push's first sample when base_seg = 0, else sample 2048 base_seg):
+// launches of at most runs_per_launch runs, each followed by its reduction.  seg0 - base_seg is a multiple of r.
+int survey_enqueue(hd_survey* sv, const float2* x, uint64_t base_seg, uint64_t seg0, uint64_t seg1, uint32_t r)
+{
+    for (uint64_t s = seg0; s < seg1;) {
+        const uint64_t runs_left = (seg1 - s + r - 1) / r;
+        const uint32_t runs = (uint32_t)std::min<uint64_t>(runs_left, sv->runs_per_launch);
+        hd::launch_survey(sv->q, runs, x, sv->win, sv->tw, sv->partial, s - base_seg, seg1 - base_seg, r);
+        hd::launch_survey_reduce(sv->q, sv->partial, runs, sv->acc);
+        HD_HIP(hipGetLastError());
+        s += (uint64_t)runs * r;
+    }
+    return HD_OK;
+}
+
+int survey_enter(hd_survey* sv)
+{
+    if (sv->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + sv->e->fail_cause + ") -- destroy the engine");
+    HD_HIP(hipSetDevice(sv->e->cfg.device));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hd_survey_create(hd_engine* e, hd_survey** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_survey> sv(new hd_survey);
+    sv->e = e;
+    if (const int rc = survey_enter(sv.get())) return rc;
+    if (const char* v = getenv("HD_SURVEY_RUNS")) sv->runs_per_launch = (uint32_t)std::min(std::max(atol(v), 1L), 4096L);
+    HD_HIP(hipStreamCreateWithFlags(&sv->q, hipStreamNonBlocking));
+    std::vector<float> w(hd::kSurveyBins);
+    hd::survey_window(w.data());
+    for (float v : w) sv->sum_w2 += (double)v * (double)v;
+    // (plain allocations, filled on the survey's queue: nothing here runs on the null stream or waits for the engine's queues)
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->win), hd::kSurveyBins * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->partial), (size_t)sv->runs_per_launch * hd::kSurveyBins * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->acc), hd::kSurveyBins * sizeof(double)));
+    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&sv->h_acc), hd::kSurveyBins * sizeof(double), hipHostMallocDefault));
+    std::vector<float2> tw;
+    sv->tw = e->fft_tw.p;
+    if (!sv->tw) {   // an engine without spectra holds no twiddles: the same table, the survey's own
+        tw.resize(hd::kFftBins);
+        for (size_t m = 0; m < tw.size(); ++m) {
+            const double a = 2.0 * 3.14159265358979323846264338327950288 * (double)m / (double)hd::kFftBins;
+            tw[m] = make_float2((float)std::cos(a), (float)-std::sin(a));
+        }
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->own_tw), tw.size() * sizeof(float2)));
+        HD_HIP(hipMemcpyAsync(sv->own_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, sv->q));
+        sv->tw = sv->own_tw;
+    }
+    HD_HIP(hipMemcpyAsync(sv->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, sv->q));
+    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->q));
+    HD_HIP(hipStreamSynchronize(sv->q));   // (the tables above are locals)
+    *out = sv.release();
+    return HD_OK;
+}
+
+void hd_survey_destroy(hd_survey* sv)
+{
+    if (!sv) return;
+    hd_engine* e = sv->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    (void)hipSetDevice(e->cfg.device);
+    if (sv->q) (void)hipStreamSynchronize(sv->q);
+    delete sv;
+}
+
+int hd_survey_reset(hd_survey* sv)
+{
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->q));
+    HD_HIP(hipStreamSynchronize(sv->q));   // (what was pushed before is done with its buffers)
+    sv->segments = 0;
+    return HD_OK;
+}
+
+int hd_survey_push_device(hd_survey* sv, const void* d_iq, uint64_t n)
+{
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    if (!d_iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    if (reinterpret_cast<uintptr_t>(d_iq) & 7) return fail(HD_ERR_INVALID, "IQ base must be 8-byte aligned");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    const uint64_t n_seg = hd::survey_segments(n);
+    if (!n_seg) return HD_OK;
+    {   // what the kernel reads must be memory the GPU can address: a host pointer HIP does not know never reaches a launch
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_iq) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
+                                                                 !(at.type == hipMemoryTypeHost && at.devicePointer))) {
+            (void)hipGetLastError();
+            return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_survey_push_host takes host memory)");
+        }
+    }
+    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);
+    if (const int rc = survey_enqueue(sv, static_cast<const float2*>(d_iq), 0, 0, n_seg, r)) return rc;
+    sv->segments += n_seg;
+    return HD_OK;
+}
+
+int hd_survey_push_host(hd_survey* sv, const float* iq, uint64_t n)
+{
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    const uint64_t n_seg = hd::survey_segments(n);
+    if (!n_seg) return HD_OK;
+    if (!sv->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->slab), (size_t)(hd_survey::kSlabSegs + 1) * hd::kSurveyHop * sizeof(float2)));
+    // The run length is the whole push's; a slab carries whole runs of it (at least one: r <= 64 segments), so every wave sums the segments it would
+    // have summed in one device push, and the rows reach the accumulators in the same order.  Copies and launches share the queue: a slab is
+    // overwritten only behind the launch that read it.
+    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);
+    const uint64_t per_slab = (uint64_t)(hd_survey::kSlabSegs / r) * r;
+    for (uint64_t s = 0; s < n_seg; s += per_slab) {
+        const uint64_t s1 = std::min(n_seg, s + per_slab);
+        const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
+        HD_HIP(hipMemcpyAsync(sv->slab, iq + 2 * (size_t)s * hd::kSurveyHop, samples * sizeof(float2), hipMemcpyHostToDevice, sv->q));
+        if (const int rc = survey_enqueue(sv, sv->slab, s, s, s1, r)) return rc;
+    }
+    HD_HIP(hipStreamSynchronize(sv->q));   // from here on the caller's buffer is theirs again
+    sv->segments += n_seg;
+    return HD_OK;
+}
+
+int hd_survey_power(hd_survey* sv, double* p, size_t cap, uint64_t* segments)
+{
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    if (!p) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    if (segments) *segments = sv->segments;
+    if (cap < hd::kSurveyBins) return 0;
+    HD_HIP(hipMemcpyAsync(sv->h_acc, sv->acc, hd::kSurveyBins * sizeof(double), hipMemcpyDeviceToHost, sv->q));
+    HD_HIP(hipStreamSynchronize(sv->q));
+    const double norm = (double)sv->segments * sv->sum_w2;
+    for (uint32_t i = 0; i < hd::kSurveyBins; ++i) p[i] = sv->segments ? sv->h_acc[i] / norm : 0.0;
+    return (int)hd::kSurveyBins;
+}
+
+// Measurement hook (tools/micro/survey_rate.py; not part of the ABI): hd_survey_push_device between two HIP events on the survey's queue.
+int hd_debug_survey_push_timed(hd_survey* sv, const void* d_iq, uint64_t n, float* ms)
+{
+    if (!sv || !ms) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    HD_HIP(hipEventCreate(&t0));
+    HD_HIP(hipEventCreate(&t1));
+    HD_HIP(hipEventRecord(t0, sv->q));
+    const int rc = hd_survey_push_device(sv, d_iq, n);
+    HD_HIP(hipEventRecord(t1, sv->q));
+    HD_HIP(hipEventSynchronize(t1));
+    HD_HIP(hipEventElapsedTime(ms, t0, t1));
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    return rc;
+}
+
+void hd_survey_params_default(hd_survey_params* p) { if (p) hd::survey_params_default(p); }
+
+int hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap, uint32_t* found)
+{
+    if (found) *found = 0;
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    if (!p || !found || (cap && !out)) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    std::vector<double> pw(hd::kSurveyBins);
+    uint64_t segs = 0;
+    const int n = hd_survey_power(sv, pw.data(), pw.size(), &segs);
+    if (n < 0) return n;
+    const int rc = hd::survey_detect(pw.data(), segs, sv->e->fs, p, out, cap, found);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "hd_survey_detect needs at least 16 segments and a floor above zero (" + std::to_string(segs) + " segments so far)");
+    if (rc) return fail(rc, "hd_survey_detect: bad parameters or a NaN / negative power");
+    return HD_OK;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "host/sondehub.hpp"
 #include "host/text_stage.hpp"
 #include "host/iq_file_batch.hpp"
+#include "host/survey.hpp"
 #include "host/tune_host.hpp"
 #include "kernels/exact_math.h"
 
@@ -258,6 +259,14 @@ void hd_host_tune_rotate(const float* iq, size_t n, uint32_t phase, uint32_t ste
     float tab[4 * hd::kTuneTable];
     hd::tune_tables(tab, tab + 2 * hd::kTuneTable);
     hd::tune_rotate(tab, iq, n, phase, step, out);
+}
+
+/* ---- wideband survey (kernels/survey.hip; see host/survey.hpp) ---- */
+void hd_host_survey_window(float w[4096]) { if (w) hd::survey_window(w); }
+int hd_host_survey_detect(const double* power, uint64_t segments, double sampling_rate, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap,
+                          uint32_t* found)
+{
+    return hd::survey_detect(power, segments, sampling_rate, p, out, cap, found);
 }
 
 }  // extern "C"

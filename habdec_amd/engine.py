@@ -51,6 +51,9 @@ class Engine:
         self._cbs = []
 
     def close(self):
+        for sv in getattr(self, "_surveys", []):       # (a survey uses its engine's device, twiddles and mutex: it goes first)
+            sv.close()
+        self._surveys = []
         if getattr(self, "h", None):
             self.L.hd_engine_destroy(self.h)
             self.h = None
@@ -204,6 +207,84 @@ class Engine:
     def set_timing(self, every: int):
         """HIP-event timing on every `every`-th call (0 = off); see hd_engine_set_timing."""
         self.L.hd_engine_set_timing(self.h, every)
+
+    def survey(self) -> "Survey":
+        """A wideband survey on this engine's GPU and sampling rate (hd_survey_*): close it before the engine."""
+        sv = Survey(self)
+        self._surveys = getattr(self, "_surveys", []) + [sv]
+        return sv
+
+
+def _candidates(out, n) -> list:
+    return [{"offset_hz": c.offset_hz, "snr_db": c.snr_db, "width_hz": c.width_hz, "bin_lo": c.bin_lo, "bin_hi": c.bin_hi} for c in out[:n]]
+
+
+def survey_detect(power: np.ndarray, segments: int, sampling_rate: float, cap: int = 64, **params) -> list:
+    """hd_host_survey_detect on a 4096-bin averaged power spectrum (no GPU): candidates as dicts, strongest first; params as hd_survey_params."""
+    L = lib()
+    p = capi.hd_survey_params()
+    L.hd_survey_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, float(v))
+    out, found = (capi.hd_survey_candidate * max(cap, 1))(), C.c_uint32(0)
+    rc = L.hd_host_survey_detect(np.ascontiguousarray(power, np.float64), int(segments), float(sampling_rate), C.byref(p), out, cap, C.byref(found))
+    if rc:
+        raise HabdecError(f"habdec_amd error {rc}: hd_host_survey_detect")
+    if found.value > cap:
+        return survey_detect(power, segments, sampling_rate, found.value, **params)
+    return _candidates(out, found.value)
+
+
+class Survey:
+    """Welch-averaged power spectrum of full-rate IQ and the payload detector on top of it (hd_survey_*, include/habdec_amd.h)."""
+
+    def __init__(self, eng: Engine):
+        self.L, self.eng = eng.L, eng
+        h = C.c_void_p()
+        check(self.L.hd_survey_create(eng.h, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_survey_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_device(self, dev_ptr: int, n: int):
+        """n cf32 samples at a device address; the buffer must stay valid until power() / detect() / reset() has returned."""
+        check(self.L.hd_survey_push_device(self.h, dev_ptr, n))
+
+    def push_host(self, iq: np.ndarray):
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        check(self.L.hd_survey_push_host(self.h, iq.ctypes.data, iq.size))
+
+    def power(self):
+        """(float64[4096], segments): p[i] belongs to (i - 2048) * sampling_rate / 4096."""
+        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
+        n = self.L.hd_survey_power(self.h, p.ctypes.data, p.size, C.byref(seg))
+        if n != 4096:
+            check(n if n < 0 else -1)
+        return p, int(seg.value)
+
+    def detect(self, cap: int = 64, **params) -> list:
+        """Candidates as dicts (offset_hz is what Engine.set_front_tune takes), strongest first; params as hd_survey_params."""
+        p = capi.hd_survey_params()
+        self.L.hd_survey_params_default(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, float(v))
+        out, found = (capi.hd_survey_candidate * max(cap, 1))(), C.c_uint32(0)
+        check(self.L.hd_survey_detect(self.h, C.byref(p), out, cap, C.byref(found)))
+        if found.value > cap:
+            return self.detect(found.value, **params)
+        return _candidates(out, found.value)
+
+    def reset(self):
+        check(self.L.hd_survey_reset(self.h))
 
 
 class IqFiles:

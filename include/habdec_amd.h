@@ -269,6 +269,53 @@ int hd_engine_timing(hd_engine* e, hd_timing* out);
  * hd_engine_timing() reports the most recent timed call. */
 void hd_engine_set_timing(hd_engine* e, int every);
 
+/* ---- wideband survey: where in a capture are the payloads? (not in the reference: its only spectrum is per decoder, at the decimated rate) ----
+ * A Welch-averaged power spectrum of cf32 IQ at the INPUT rate, and a detector on top of it whose candidate offsets are what hd_stream_set_front_tune
+ * takes, sign included: survey (one bin = fs / 4096) -> front tune -> the per-stream AFC / hd_stream_set_auto_afc for the fine part.
+ *  - Segments: a push of n samples contributes n < 4096 ? 0 : 1 + (n - 4096) / 2048 segments; segment s is samples [2048 s, 2048 s + 4096) of THAT push.
+ *    Segments never straddle pushes and the samples behind the last whole hop are not used: push a capture in large pieces.
+ *  - Per segment: periodic Hann window (hd_host_survey_window: a float table, one rounded multiply per part), the engine's 4096-point in-wave transform,
+ *    re^2 + im^2 per bin.  One wave sums a run of r = min(HD_SURVEY_RUN, ceil(segments / runs_per_launch)) consecutive segments in float (runs_per_launch =
+ *    1024; environment HD_SURVEY_RUNS, read by hd_survey_create); the runs' rows are added in run order into double accumulators that live as long as
+ *    the survey.  No floating-point atomics: the same pushes give the same bytes, from device or from host memory.
+ *  - Queue: the survey's launches and copies run on a HIP stream of its own.  It never waits for, drains or reorders the engine's pipeline
+ *    (hd_survey_destroy frees device memory, which waits for the device).  A survey uses its engine's device, sampling rate, twiddles and mutex: destroy
+ *    it before the engine.  Calls are serialised by the engine's mutex, like the getters.
+ *  - Errors: null arguments and a device pointer that is not 8-byte aligned are HD_ERR_INVALID; an engine in its failed state is HD_ERR_DEVICE. */
+#define HD_SURVEY_BINS 4096
+#define HD_SURVEY_HOP 2048
+#define HD_SURVEY_RUN 64
+typedef struct hd_survey hd_survey;
+int  hd_survey_create(hd_engine* e, hd_survey** out);
+void hd_survey_destroy(hd_survey* sv);
+int  hd_survey_reset(hd_survey* sv);                       /* accumulators = 0, segments = 0 */
+/* n cf32 samples in DEVICE memory on the engine's GPU (or page-locked mapped host memory by its device address), 8-byte aligned.  Returns once the
+ * launches are queued: the buffer must stay valid until hd_survey_power / hd_survey_detect / hd_survey_reset has returned.  n < 4096: HD_OK, adds nothing. */
+int  hd_survey_push_device(hd_survey* sv, const void* d_iq, uint64_t n);
+/* The same from host memory, pageable or page-locked, staged through a device slab in pieces of whole runs -- segmentation and run structure are those
+ * of the one push, so the result is byte-identical to hd_survey_push_device of the same samples.  The buffer is the caller's again on return. */
+int  hd_survey_push_host(hd_survey* sv, const float* iq, uint64_t n);
+/* Waits for the survey's own queue only.  p[i] = acc[i] / (segments * sum w^2) (the sum in double over the float table) belongs to
+ * f = (i - 2048) fs / 4096: white noise of complex variance s^2 reads about s^2.  No segments yet: zeros.  Returns the bins written (4096), 0 when
+ * cap < 4096 (nothing written), or a negative HD_ERR_*; *segments (optional) = segments accumulated since creation or the last reset. */
+int  hd_survey_power(hd_survey* sv, double* p, size_t cap, uint64_t* segments);
+typedef struct hd_survey_params {
+    double threshold_db;   /* a bin is marked at P >= floor * max(10^(threshold_db / 10), 1 + 8 / sqrt(segments)); default 6 */
+    double merge_hz;       /* marked bins with at most ceil(merge_hz / (fs / 4096)) unmarked bins between them form one cluster; default 1500 */
+    double dc_guard_hz;    /* > 0: bins with |f| < dc_guard_hz count neither for the floor nor as candidates (a receiver's DC spike); default 0 */
+    double max_width_hz;   /* > 0: clusters wider than this are dropped (broadcast carriers, not RTTY); default 0 */
+} hd_survey_params;
+typedef struct hd_survey_candidate {
+    double offset_hz;      /* power-weighted centroid of the cluster's marked bins: what hd_stream_set_front_tune takes */
+    double snr_db;         /* 10 log10(sum (P_i - floor) / floor) over the marked bins */
+    double width_hz;       /* (bin_hi - bin_lo + 1) fs / 4096 */
+    uint32_t bin_lo, bin_hi;
+} hd_survey_candidate;
+void hd_survey_params_default(hd_survey_params* p);
+/* hd_survey_power followed by hd_host_survey_detect (habdec_amd_host.h has the algorithm).  *found = clusters found, the first min(found, cap) of them
+ * are written, strongest first.  Fewer than 16 segments: HD_ERR_UNSUPPORTED. */
+int  hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap, uint32_t* found);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@
 #define HABDEC_AMD_HOST_H
 #include <stddef.h>
 #include <stdint.h>
+
+#include "habdec_amd.h"   /* hd_survey_params, hd_survey_candidate */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -130,6 +132,22 @@ uint32_t hd_host_iqfiles_next(hd_host_iqfiles*, float* slab, size_t stride, uint
 int  hd_host_tune_step(double offset_hz, double decimated_rate, uint32_t* step);
 void hd_host_tune_tables(float coarse[512], float fine[512]);
 void hd_host_tune_rotate(const float* iq, size_t n, uint32_t phase, uint32_t step, float* out);
+
+/* ---- wideband survey (hd_survey_*, include/habdec_amd.h): the window the kernel multiplies by, and the detector ----
+ * hd_host_survey_window: w[n] = 0.5 - 0.5 cos(2 pi n / 4096) (periodic Hann), computed in double and rounded to float once.
+ * hd_host_survey_detect: a pure function of a 4096-bin averaged power spectrum (power[i] at f_i = (i - 2048) sampling_rate / 4096).  In order:
+ *  1. segments < 16 is HD_ERR_UNSUPPORTED (a threshold means nothing over a handful of periodograms); a NaN or negative power, threshold_db < 0 or a
+ *     negative Hz parameter is HD_ERR_INVALID (so are null arguments, and a guard that leaves no bin); a floor of 0 is HD_ERR_UNSUPPORTED.
+ *  2. Eligible bins: those with |f| >= dc_guard_hz (all when it is 0).  floor = their median (the mean of the two middle values of the sorted list).
+ *  3. An eligible bin is marked when P >= floor * max(10^(threshold_db / 10), 1 + 8 / sqrt(segments)); the second term is where noise alone ends.
+ *  4. Marked bins form one cluster while at most g = ceil(merge_hz / (sampling_rate / 4096)) unmarked bins lie between neighbours (index difference
+ *     <= g + 1); no wrap-around between bin 4095 and bin 0.
+ *  5. Over a cluster's marked bins: offset_hz = sum f_i (P_i - floor) / sum (P_i - floor), snr_db = 10 log10(sum (P_i - floor) / floor),
+ *     width_hz = (bin_hi - bin_lo + 1) sampling_rate / 4096; clusters wider than max_width_hz are dropped when it is > 0.
+ *  6. Sorted by snr_db descending, ties by lower offset_hz; *found = clusters, the first min(found, cap) are written. */
+void hd_host_survey_window(float w[4096]);
+int  hd_host_survey_detect(const double* power, uint64_t segments, double sampling_rate, const hd_survey_params* p, hd_survey_candidate* out,
+                           uint32_t cap, uint32_t* found);
 
 #ifdef __cplusplus
 }
