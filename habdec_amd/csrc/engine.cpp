@@ -162,8 +162,6 @@ struct hd_engine {
     uint32_t ring_chain = 1;   // HD_RING_CHAIN: 0 = the /32 worker waves' tiles all stand alone (the plain schedule: 64 - HR outputs per tile); default: chained runs (host/ring_schedule.hpp)
     uint32_t ring_short_pct = 25;   // HD_RING_SHORT_PCT: share of an XCD's tiles the worker waves draw as SINGLE tiles at the end of a launch (guided hand-out; 0 = whole runs to the end)
     bool ring_short_set = false;    // ... was given.  Not given, chained launches take an eighth of the streams, not a quarter (make_claim)
-    static constexpr uint32_t kS1Loaders = 2;   // LDS-DMA loader waves of k_stage1_cu at /8 and /4 (round 4: with the nt policy on the body rows one loader's three
-                                                // tiles in flight bound the launch -- 102.7 us with one loader, 94.7 with two, one box, alternating)
 #ifndef HD_S1_SLOTS_BATCH
 #define HD_S1_SLOTS_BATCH 4
 #endif
@@ -1099,8 +1097,7 @@ void fill_tail(const hd_engine* e, const hd_engine::CallSlot& sl, const CallPlan
 // Equally sized pushes through a single-wave first stage of a two-stage plan: the stage-1 workgroups (eight resident per CU) draw runs of tiles from
 // per-XCD counters (kernels/decimate.hip) -- no cold start per run, no fixed shares that end ragged.  An empty claim where the shape does not allow it.
 // The caller advances e->step_launches once a launch that draws is enqueued (the two counter sets alternate per such launch).
-hd::StepClaim make_claim(const hd_engine* e, const CallPlan& p, uint32_t lin_wgs /* stage 1 as a launch of its own: the workgroup count of its linear split (which needs four tiles per workgroup); 0 = step launch */,
-                         uint32_t run_len_cu /* != 0: runs for a per-CU ring kernel's loaders */)
+hd::StepClaim make_claim(const hd_engine* e, const CallPlan& p, uint32_t run_len_cu /* != 0: runs for a per-CU ring kernel's loaders */)
 {
     hd::StepClaim claim{};
     const int R1 = (int)p.R1, T1 = (int)p.T1;
@@ -1110,7 +1107,7 @@ hd::StepClaim make_claim(const hd_engine* e, const CallPlan& p, uint32_t lin_wgs
     const uint64_t runs = S * ntiles / run_len;
     const bool shape_ok = run_len_cu ? (HDK(stage1_cu_supported, R1, T1) && p.max_in % 2048u == 0) : ((R1 == 32 || R1 == 64) && p.max_n1 % 64 == 0);
     if (!e->no_claim && (p.nst == 2 || (run_len_cu && p.nst == 1)) && shape_ok && p.min_in == p.max_in && p.max_in && !p.any_zero1 && n_xcd && e->n_cus % 32u == 0 && n_xcd <= 16 &&
-        ntiles && (ntiles % run_len == 0 || (run_len_cu && R1 >= 32 && (S * ntiles) % run_len == 0)) && runs % n_xcd == 0 && S * ntiles < (1ull << 32) && (uint64_t)ntiles * S >= 4ull * lin_wgs) {
+        ntiles && (ntiles % run_len == 0 || (run_len_cu && R1 >= 32 && (S * ntiles) % run_len == 0)) && runs % n_xcd == 0 && S * ntiles < (1ull << 32)) {
         claim.ctr = e->step_ctr.p + (size_t)(e->step_launches & 1u) * 16 * 32;
         claim.ctr_next = e->step_ctr.p + (size_t)((e->step_launches & 1u) ^ 1u) * 16 * 32;
         claim.n_xcd = n_xcd; claim.runs_per_xcd = (uint32_t)(runs / n_xcd); claim.run_len = run_len;
@@ -1236,7 +1233,7 @@ int enqueue_step(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
     const int cu_exp = e->cu_exp;             // timing experiments only (results wrong): 1 = no tails, 2 = no stage 1
     // One workgroup per CU (four stage-1 worker waves, the tails in the other four) where the plan and the sizes allow it
     const bool want_cu = cu_tail && ((cu_exp & 1) || (r.ta_step.lds_bytes <= cu_tail && (!prev.valid || prev.ta.lds_bytes <= cu_tail)));
-    const hd::StepClaim claim = make_claim(e, p, 0, want_cu ? ring_run : 0u);
+    const hd::StepClaim claim = make_claim(e, p, want_cu ? ring_run : 0u);
     bool launched = false;
     if (want_cu && claim.ctr) {
         const uint32_t tb = std::max(r.ta_step.lds_bytes, prev.valid ? prev.ta.lds_bytes : 0u);
@@ -1309,11 +1306,11 @@ int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, cons
         // A /32 first stage over equally sized pushes: one workgroup per CU, LDS-DMA loader waves + computing waves (k_stage1_cu, stage1_ring.h)
         bool s1_cu = false;
         if (!p.any_front && (single ? R1 == 4 : R1 != 4) && p.min_in == p.max_in && p.max_in && !e->no_cu_step && !p.any_zero1 && p.max_in % 2048u == 0 && HDK(stage1_cu_supported, (int)R1, (int)T1)) {
-            const hd::StepClaim cl = make_claim(e, p, 0, pick_ring_run(e, R1, HDK(ring_tiles, (int)R1, (int)T1, p.max_in)));
+            const hd::StepClaim cl = make_claim(e, p, pick_ring_run(e, R1, HDK(ring_tiles, (int)R1, (int)T1, p.max_in)));
             if (cl.ctr) {
                 if (sl.timed) HD_HIP(hipEventRecord(sl.t1, qa));
                 s1_cu = HDK(launch_stage1_cu, qa, (int)R1, (int)T1, e->n_cus, iq, stride, e->hist1[b.hin].p, e->hist1[b.hout].p, e->stage_taps[0].p, out1, out1_stride,
-                                             p.max_in, cl, e->ring_gave_up.dev, hd_engine::kS1Loaders, 16u, (e->cfg.pipeline && !tail && !single) ? hd_engine::kS1Slots : 8u,   // (/4 as the only stage is bound by the vector pipes: eight slots, 0.838 against 0.904 ms per step with four)
+                                             p.max_in, cl, e->ring_gave_up.dev, (e->cfg.pipeline && !tail && !single) ? hd_engine::kS1Slots : 8u,   // (/4 as the only stage is bound by the vector pipes: eight slots, 0.838 against 0.904 ms per step with four)
                                              single ? r.dcall : nullptr, e->fir_hist_cap, single ? r.feed : nullptr);
                 if (s1_cu) ++e->step_launches;
             }

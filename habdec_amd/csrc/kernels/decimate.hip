@@ -559,13 +559,11 @@ __global__ __launch_bounds__(TO) __attribute__((amdgpu_waves_per_eu(D == 64 ? 1 
                                                    float2* __restrict__ out, size_t out_stride,
                                                    const StreamCall* __restrict__ call, int stage, int final_stage,
                                                    uint32_t fir_hist_cap, uint32_t tiles_per_wg, float2* __restrict__ fft_in,
-                                                   uint32_t n_streams, uint32_t lin_ntiles, StreamCall* __restrict__ call_copy,
-                                                   const uint32_t uniform_n, const StepClaim claim)
+                                                   uint32_t n_streams, uint32_t lin_ntiles)
 {
     __shared__ float4 tile4[dec_tile_f4<D, T, TO>()];
     decimate_body<D, T, TO>(in, in_stride, hist_in, hist_out, taps, out, out_stride, call, stage, final_stage, fir_hist_cap, tiles_per_wg, fft_in,
-                            n_streams, lin_ntiles, call_copy, blockIdx.x, blockIdx.y, gridDim.x, tile4, TO == 64 ? uniform_n : 0u,
-                            TO == 64 ? claim : StepClaim{});
+                            n_streams, lin_ntiles, nullptr, blockIdx.x, blockIdx.y, gridDim.x, tile4);
 }
 
 // The first stage of a call in which some stream is tuned at the input rate (hd_stream_set_front_tune): k_decimate with the rotation in the staging
@@ -800,49 +798,39 @@ __global__ __launch_bounds__(64) void k_dc_remove(float2* __restrict__ fbuf, siz
 template <int D, int T, int TO, bool TUNED = false>
 static void launch_one(hipStream_t st, uint32_t n_streams, uint32_t max_out, const float2* in, size_t in_stride,
                        const float2* hist_in, float2* hist_out, const float* taps, float2* out, size_t out_stride,
-                       const StreamCall* call, int stage, int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs, StreamCall* call_copy,
-                       uint32_t uniform_n, const StepClaim& claim, const uint2* ftune = nullptr, const float* ftab = nullptr)
+                       const StreamCall* call, int stage, int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs,
+                       const uint2* ftune = nullptr, const float* ftab = nullptr)
 {
     constexpr uint32_t TOUT = TO * dec_opl<D>();
     const uint32_t ntiles = (max_out + TOUT - 1) / TOUT;
-    if constexpr (TUNED) {      // the same two grids; stage 0, no drawn runs, the parameter blocks are read
-        if (TO == 64 && lin_wgs && (uint64_t)ntiles * n_streams >= 4ull * lin_wgs) {
-            hipLaunchKernelGGL((k_decimate_tuned<D, T, TO>), dim3(lin_wgs), dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
-                               final_stage, fir_hist_cap, 0u, fft_in, n_streams, ntiles, ftune, ftab);
-            return;
-        }
-        uint32_t per = 1;
-        while (per < 16 && (uint64_t)((ntiles + 2 * per - 1) / (2 * per)) * n_streams >= 2048) per *= 2;
-        hipLaunchKernelGGL((k_decimate_tuned<D, T, TO>), dim3((ntiles + per - 1) / per, n_streams), dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps,
-                           out, out_stride, call, final_stage, fir_hist_cap, per, fft_in, n_streams, 0u, ftune, ftab);
-        return;
-    }
     // Linear split (single-wave instantiations, every stream the same size -- the caller vouches for that by passing lin_wgs):
     // exactly lin_wgs workgroups share the slab's tiles evenly.  The caller picks lin_wgs = k * CUs to decide how many of a CU's
     // eight 19.5 KB LDS slots this kernel takes -- the rest stays free for the back-half kernels of the previous call.
-    if (TO == 64 && lin_wgs && (uint64_t)ntiles * n_streams >= 4ull * lin_wgs) {
-        hipLaunchKernelGGL((k_decimate<D, T, TO>), dim3(lin_wgs), dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
-                           stage, final_stage, fir_hist_cap, 0u, fft_in, n_streams, ntiles, call_copy, final_stage ? 0u : uniform_n,
-                           (final_stage || !uniform_n) ? StepClaim{} : claim);
-        return;
+    dim3 grid(lin_wgs);
+    uint32_t per = 0, lin_ntiles = ntiles;
+    if (!(TO == 64 && lin_wgs && (uint64_t)ntiles * n_streams >= 4ull * lin_wgs)) {
+        // Walk several tiles per workgroup (prefetch pipelining) once there are enough workgroups to fill the chip:
+        // 256 CUs x ~4 resident workgroups; keep >= ~2048 workgroups when the batch allows it.
+        per = 1;
+        while (per < 16 && (uint64_t)((ntiles + 2 * per - 1) / (2 * per)) * n_streams >= 2048) per *= 2;
+        grid = dim3((ntiles + per - 1) / per, n_streams);
+        lin_ntiles = 0;
     }
-    // Walk several tiles per workgroup (prefetch pipelining) once there are enough workgroups to fill the chip:
-    // 256 CUs x ~4 resident workgroups; keep >= ~2048 workgroups when the batch allows it.
-    uint32_t per = 1;
-    while (per < 16 && (uint64_t)((ntiles + 2 * per - 1) / (2 * per)) * n_streams >= 2048) per *= 2;
-    dim3 grid((ntiles + per - 1) / per, n_streams);
-    hipLaunchKernelGGL((k_decimate<D, T, TO>), grid, dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
-                       stage, final_stage, fir_hist_cap, per, fft_in, n_streams, 0u, (StreamCall*)nullptr, 0u, StepClaim{});
+    if constexpr (TUNED)        // stage 0, and the streams' rotations
+        hipLaunchKernelGGL((k_decimate_tuned<D, T, TO>), grid, dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
+                           final_stage, fir_hist_cap, per, fft_in, n_streams, lin_ntiles, ftune, ftab);
+    else
+        hipLaunchKernelGGL((k_decimate<D, T, TO>), grid, dim3(TO), 0, st, in, in_stride, hist_in, hist_out, taps, out, out_stride, call,
+                           stage, final_stage, fir_hist_cap, per, fft_in, n_streams, lin_ntiles);
 }
 
 bool launch_decimate(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, uint32_t max_out, const float2* in, size_t in_stride,
                      const float2* hist_in, float2* hist_out, const float* taps, float2* out, size_t out_stride, const StreamCall* call,
-                     int stage, int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs, StreamCall* call_copy,
-                     uint32_t uniform_n, const StepClaim& claim)
+                     int stage, int final_stage, uint32_t fir_hist_cap, float2* fft_in, uint32_t lin_wgs)
 {
     if (!max_out) return true;
 #define HD_CASE(D, T, TO) \
-    if (ratio == D && ntaps == T) { launch_one<D, T, TO>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, stage, final_stage, fir_hist_cap, fft_in, lin_wgs, call_copy, uniform_n, claim); return true; }
+    if (ratio == D && ntaps == T) { launch_one<D, T, TO>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, stage, final_stage, fir_hist_cap, fft_in, lin_wgs); return true; }
     HD_CASE(2, 69, 256) HD_CASE(4, 139, 256) HD_CASE(8, 280, 256) HD_CASE(8, 54, 256)
     HD_CASE(16, 107, 128) HD_CASE(32, 212, 64) HD_CASE(32, 174, 64) HD_CASE(64, 348, 64)
 #undef HD_CASE
@@ -855,7 +843,7 @@ bool launch_decimate_tuned(hipStream_t st, int ratio, int ntaps, uint32_t n_stre
 {
     if (!max_out) return true;
 #define HD_CASE(D, T, TO) \
-    if (ratio == D && ntaps == T) { launch_one<D, T, TO, true>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, 0, final_stage, fir_hist_cap, fft_in, lin_wgs, nullptr, 0u, StepClaim{}, ftune, ftab); return true; }
+    if (ratio == D && ntaps == T) { launch_one<D, T, TO, true>(st, n_streams, max_out, in, in_stride, hist_in, hist_out, taps, out, out_stride, call, 0, final_stage, fir_hist_cap, fft_in, lin_wgs, ftune, ftab); return true; }
     HD_CASE(2, 69, 256) HD_CASE(4, 139, 256) HD_CASE(8, 280, 256) HD_CASE(8, 54, 256)
     HD_CASE(16, 107, 128) HD_CASE(32, 212, 64) HD_CASE(32, 174, 64) HD_CASE(64, 348, 64)
 #undef HD_CASE
@@ -969,16 +957,14 @@ bool stage1_cu_supported(int ratio, int ntaps)
 }
 
 bool launch_stage1_cu(hipStream_t st, int ratio, int ntaps, uint32_t n_cus, const float2* in, size_t in_stride, const float2* hist_in, float2* hist_out,
-                      const float* taps, float2* out, size_t out_stride, uint32_t uniform_n, const StepClaim& claim, unsigned int* gave_up, uint32_t n_loaders, uint32_t n_waves,
+                      const float* taps, float2* out, size_t out_stride, uint32_t uniform_n, const StepClaim& claim, unsigned int* gave_up,
                       uint32_t n_slots, const StreamCall* final_call, uint32_t fir_hist_cap, float2* fft_in)
 {
-    if (n_loaders != 1u) n_loaders = 2u;
-    if (ratio <= 4) {            // 278 flop per input sample (/4): the vector pipes bind, not HBM -- one loader is plenty, and every other wave slot computes
-        n_loaders = 1u;
-        n_waves = 16u;
-    }
+    // LDS-DMA loader waves in front of the computing waves: two at /8 (round 4: with the nt policy on the body rows one loader's three tiles in flight bound the
+    // launch -- 102.7 us with one loader, 94.7 with two, one box, alternating), 8 waves in all.  278 flop per input sample (/4): the vector pipes bind,
+    // not HBM -- one loader is plenty, and every other wave slot computes: 16 waves.  (/32 and /64: worker waves that load for themselves, counted below.)
+    const uint32_t n_loaders = ratio <= 4 ? 1u : 2u;
     if (n_slots < 2u * n_loaders || n_slots > 8u) n_slots = 8u;
-    if (n_waves < 8u || n_waves > 16u) n_waves = 8u;
     if (!claim.ctr || !uniform_n || uniform_n % 2048u) return false;
     const uint32_t ntiles = ring_tiles(ratio, ntaps, uniform_n);
     if (claim.chain_rl ? !ring_chain_ok(ratio, ntaps, uniform_n, claim, 0u) : !ring_limits_ok(ntiles, claim, ratio >= 32)) return false;
@@ -996,7 +982,7 @@ bool launch_stage1_cu(hipStream_t st, int ratio, int ntaps, uint32_t n_cus, cons
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_stage1_cu<T, D>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840) != hipSuccess) return false; \
             attr_set[dev_] = true;                                                                                                    \
         }                                                                                                                             \
-        hipLaunchKernelGGL((k_stage1_cu<T, D>), dim3(n_cus), dim3(64u * (D == 4 ? n_waves : D >= 32 ? workers : 8u)), lds, st, ra, n_loaders, n_slots);   \
+        hipLaunchKernelGGL((k_stage1_cu<T, D>), dim3(n_cus), dim3(64u * (D == 4 ? 16u : D >= 32 ? workers : 8u)), lds, st, ra, n_loaders, n_slots);   \
         return true;                                                                                                                  \
     }
     HD_S1_CASE(32, 212) HD_S1_CASE(32, 174) HD_S1_CASE(64, 348) HD_S1_CASE(8, 54) HD_S1_CASE(4, 139)

@@ -10,10 +10,7 @@ bool launch_decimate(hipStream_t st, int ratio, int ntaps, uint32_t n_streams, u
                      const float2* in, size_t in_stride, const float2* hist_in, float2* hist_out, const float* taps,
                      float2* out, size_t out_stride, const StreamCall* call, int stage, int final_stage,
                      uint32_t fir_hist_cap, float2* fft_in /* final stage: spectrum input buffer [S][4096], or null */,
-                     uint32_t lin_wgs = 0 /* != 0: every stream has the same size; use exactly this many workgroups (single-wave kernels) */,
-                     StreamCall* call_copy = nullptr /* linear split only: leave a device copy of each stream's parameters here */,
-                     uint32_t uniform_n = 0 /* linear split, not the final stage: the streams' common sample count, no stream restarts its history */,
-                     const StepClaim& claim = StepClaim{} /* with uniform_n: the lin_wgs workgroups draw their tiles */);
+                     uint32_t lin_wgs = 0 /* != 0: every stream has the same size; use exactly this many workgroups (single-wave kernels) */);
 // The same stage as the FIRST stage of a call in which some stream is tuned at the input rate (hd_stream_set_front_tune): sample i of stream s's input is
 // rotated by theta = Pf + i Df on its way into the tile, ftune[s] = (Df, Pf) read in place (mapped host memory), ftab = the phasor tables [C | F] of
 // tune.h in device memory; the history carry holds rotated samples.  A stream with Df = Pf = 0 is computed exactly as by launch_decimate.
@@ -69,14 +66,13 @@ bool launch_step_cu(hipStream_t st, int ratio, int ntaps, int ratio2, int ntaps2
                     const float2* hist_in, float2* hist_out, const float* taps, float2* out, size_t out_stride, const StreamCall* call,
                     StreamCall* call_copy, const TailArgs& ta, uint32_t n_tail, uint32_t uniform_n, const StepClaim& claim, uint32_t tail_bytes,
                     hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr /* signalled by the dispatch itself (hipExtLaunchKernel), not by a packet behind it */);
-// Stage 1 alone in the same shape (eight tile slots, one loader wave and seven computing waves by default): a /32 or /8 first stage, equally sized pushes that are a multiple of 2048
-// samples, drawn runs, no history restart; false otherwise (the caller then launches k_decimate).  The call's parameter block is not copied.
 uint32_t ring_tiles(int ratio, int ntaps, uint32_t n);   // tiles per stream and call of the per-CU ring kernels for n input samples (0: none); the drawn runs must divide it
 bool step_cu_supported(int ratio, int ntaps, int ratio2, int ntaps2);   // plans k_step_cu is instantiated for: /64 (/32 212 + /2 69), /128 (/32 174 + /4 139)
 bool stage1_cu_supported(int ratio, int ntaps);   // stages k_stage1_cu exists for: /32 (212, 174 taps), /8 (54 taps) as first stages; /4 (139 taps) as the only stage of a plan
+// Stage 1 alone in the same shape (eight tile slots by default; two loader and six computing waves at /8, one and fifteen at /4, worker waves at /32 and /64): a /32, /64 or /8 first stage or /4 as the only one,
+// equally sized pushes that are a multiple of 2048 samples, drawn runs, no history restart; false otherwise (the caller then launches k_decimate).  The call's parameter block is not copied.
 bool launch_stage1_cu(hipStream_t st, int ratio, int ntaps, uint32_t n_cus, const float2* in, size_t in_stride, const float2* hist_in, float2* hist_out,
                       const float* taps, float2* out, size_t out_stride, uint32_t uniform_n, const StepClaim& claim, unsigned int* gave_up,
-                      uint32_t n_loaders /* 1 or 2 */, uint32_t n_waves /* 8 .. 16 waves per workgroup: loaders + computing waves */,
                       uint32_t n_slots = 8 /* tile slots (2 per loader .. 8): fewer leave LDS for the other queue's kernels */,
                       const StreamCall* final_call = nullptr /* /4 only: the stage is the final one of a single-stage plan -- per-stream pend_before / fft_take / fft_fill */,
                       uint32_t fir_hist_cap = 0, float2* fft_in = nullptr);

@@ -102,6 +102,46 @@ __device__ __forceinline__ void pin64(f32x2 (&a)[64])
     for (int i = 0; i < 64; ++i) asm volatile("" : "+v"(a[i]));
 }
 
+// The second half of the 4096-point transform, n = 64 n1 + n2, k = k1 + 64 k2, in one wave: in, lane l = n2 holds pass 1's output for k1 at a[xpos(k1)];
+// out, lane l = k1 holds X[l + 64 k2] at a[xpos(k2)].  G twiddle factors are gathered at a time; `plane`: 64 x 65 floats of LDS of the wave's own.
+template <int G>
+__device__ __forceinline__ void finish4096(f32x2 (&a)[64], const float2* __restrict__ tw4096, float* __restrict__ plane, const uint32_t l)
+{
+    // ---- twiddle W4096^(n2 k1), then the transpose (lane n2, register k1) -> (lane k1, register n2), one plane at a time
+#pragma unroll
+    for (int g = 0; g < 64; g += G) {
+        __builtin_amdgcn_sched_barrier(0);
+        float2 w[G];
+#pragma unroll
+        for (int u = 0; u < G; ++u) w[u] = tw4096[(l * (uint32_t)xpos(g + u)) & (kFftBins - 1)];   // (cos, -sin); register i holds k1 = xpos(i)
+#pragma unroll
+        for (int u = 0; u < G; ++u) {
+            const f32x2 v = a[g + u];
+            a[g + u] = (f32x2){v.x * w[u].x - v.y * w[u].y, v.x * w[u].y + v.y * w[u].x};
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[xpos(k1)].x;
+    __builtin_amdgcn_s_waitcnt(0xC07F);                             // lgkmcnt(0): the plane is wave-private
+    __builtin_amdgcn_wave_barrier();
+    // (the two components move independently: .x of every register is replaced while .y still sits at its pass-1 index)
+#pragma unroll
+    for (int n2 = 0; n2 < 64; ++n2) a[n2].x = plane[l * 65 + n2];
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[xpos(k1)].y;
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int n2 = 0; n2 < 64; ++n2) a[n2].y = plane[l * 65 + n2];
+    // ---- pass 2: transform over n2; a[xpos(k2)] = X[l + 64 k2]
+    pin64(a);
+    fft64(a);
+    pin64(a);
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -142,40 +182,9 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
         for (int u = 0; u < 8; ++u) { const float2 v = xg[64 * u + l]; a[g + u] = (f32x2){v.x, v.y}; }
     }
     specwave::fft64(a);
-    // ---- twiddle W4096^(n2 k1), then the transpose (lane n2, register k1) -> (lane k1, register n2), one plane at a time
+    // ---- twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
     // (sixteen factors at a time: all 63 gathers hoisted in front of pass 1 would need another 126 registers)
-#pragma unroll
-    for (int g = 0; g < 64; g += 16) {
-        __builtin_amdgcn_sched_barrier(0);
-        float2 w[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) w[u] = tw4096[(l * (uint32_t)specwave::xpos(g + u)) & (kFftBins - 1)];   // (cos, -sin); register i holds k1 = xpos(i)
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const f32x2 v = a[g + u];
-            a[g + u] = (f32x2){v.x * w[u].x - v.y * w[u].y, v.x * w[u].y + v.y * w[u].x};
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[specwave::xpos(k1)].x;
-    __builtin_amdgcn_s_waitcnt(0xC07F);                             // lgkmcnt(0): the plane is wave-private
-    __builtin_amdgcn_wave_barrier();
-    // (the two components move independently: .x of every register is replaced while .y still sits at its pass-1 index)
-#pragma unroll
-    for (int n2 = 0; n2 < 64; ++n2) a[n2].x = plane[l * 65 + n2];
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[specwave::xpos(k1)].y;
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int n2 = 0; n2 < 64; ++n2) a[n2].y = plane[l * 65 + n2];
-    // ---- pass 2: transform over n2; a[xpos(k2)] = X[l + 64 k2]
-    specwave::pin64(a);
-    specwave::fft64(a);
-    specwave::pin64(a);
+    specwave::finish4096<16>(a, tw4096, plane, l);
     // ---- half swap, dB power, statistics.  Bin k = l + 64 k2 lands at i = (k + 2048) & 4095 = l + 64 j, j = (k2 + 32) & 63.
     float2* so = spec + (size_t)s * kFftBins;
     float* po = power + (size_t)s * kFftBins;

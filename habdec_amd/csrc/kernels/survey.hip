@@ -2,8 +2,8 @@
 // decoder at the decimated rate (Decoder.h:467-520), so it sees +-fs_dec/2 around an offset that is already known.
 //
 // k_survey: one wave per run of consecutive 4096-sample segments (hop 2048).  Per segment: window (periodic Hann, a float table), the in-wave
-// 64 x 64 transform of spectrum_wave.h -- the same load layout, twiddles and transpose as spectrum_wave_body, restated here so that the kernels that
-// include that body stay as they are --, then |X|^2 of the lane's 64 bins added into 64 float accumulators that live in registers for the whole run.
+// 64 x 64 transform of spectrum_wave.h -- the same load layout as spectrum_wave_body, and its twiddles, transpose and second pass
+// (specwave::finish4096) --, then |X|^2 of the lane's 64 bins added into 64 float accumulators that live in registers for the whole run.
 // The run's row goes out fftshifted.  k_survey_reduce adds the rows of a launch, in run order, into the survey's double accumulators.
 // No atomics: which sums are formed depends on the push's length alone, so the same pushes give the same bytes.
 //
@@ -49,38 +49,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             for (int u = 0; u < 16; ++u) a[g + u] = (f32x2){a[g + u].x * wv[u], a[g + u].y * wv[u]};
         }
         specwave::fft64(a);
-        // ---- twiddle W4096^(n2 k1), then the transpose (lane n2, register k1) -> (lane k1, register n2), one plane at a time
-#pragma unroll
-        for (int g = 0; g < 64; g += 8) {
-            __builtin_amdgcn_sched_barrier(0);
-            float2 w[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) w[u] = tw4096[(l * (uint32_t)specwave::xpos(g + u)) & (kFftBins - 1)];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const f32x2 v = a[g + u];
-                a[g + u] = (f32x2){v.x * w[u].x - v.y * w[u].y, v.x * w[u].y + v.y * w[u].x};
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[specwave::xpos(k1)].x;
-        __builtin_amdgcn_s_waitcnt(0xC07F);                         // lgkmcnt(0): the plane is wave-private
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int n2 = 0; n2 < 64; ++n2) a[n2].x = plane[l * 65 + n2];
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k1 = 0; k1 < 64; ++k1) plane[k1 * 65 + l] = a[specwave::xpos(k1)].y;
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int n2 = 0; n2 < 64; ++n2) a[n2].y = plane[l * 65 + n2];
-        // ---- pass 2: transform over n2; a[xpos(k2)] = X[l + 64 k2]
-        specwave::pin64(a);
-        specwave::fft64(a);
-        specwave::pin64(a);
+        specwave::finish4096<8>(a, tw4096, plane, l);                // twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
 #pragma unroll
         for (int i = 0; i < 64; ++i) acc[i] = acc[i] + (a[i].x * a[i].x + a[i].y * a[i].y);
     }
