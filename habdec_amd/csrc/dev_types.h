@@ -26,8 +26,9 @@ struct StreamCall {
     uint32_t pend_before;   // decimated samples already pending in front of the FIR
     uint32_t fft_fill;      // samples already collected for the next spectrum
     uint32_t fft_take;      // samples of this chunk's head to append (0..n2)
-    uint32_t fft_run;       // 1 = the spectrum buffer completes in this call; 2 = ... and this call's chunk alone fills it: the spectrum launch reads the chunk's head in place
-                            //     (fft_take = 0: nothing is copied into the collection buffer; separate-kernels path only)
+    uint32_t fft_run;       // bits 0-1 (sc_fft_run): 1 = the spectrum buffer completes in this call; 2 = ... and this call's chunk alone fills it: the spectrum launch reads
+                            //     the chunk's head in place (fft_take = 0: nothing is copied into the collection buffer; separate-kernels path only);
+                            // bit 8 (sc_fft_buf): which of the stream's two collection buffers this call appends to / completes (sc_fft_row)
     uint32_t fir_m;         // samples to filter/demodulate this call (0 = FIR does not run)
     uint32_t fir_taps;      // tap count in use
     uint32_t fir_zero_hist; // Q5 for the low-pass
@@ -37,6 +38,14 @@ struct StreamCall {
     uint32_t fir_taps_prev; // bits 0-15: tap count of the stream's previous low-pass run (== fir_taps unless the design changed; see FirHistory);
                             // bits 16-29: head_n, bit 30: head_prev, bit 31: head_save -- where the FirHistory head is (sc_* below)
 };
+// The spectrum collection, [S][2][kFftBins]: a stream has two buffers and fills them alternately, one per spectrum, where the engine transforms a completed
+// buffer again when a getter asks for the spectrum (batch mode: the tails store only the AFC statistics) -- the buffer completed last then stays as it is
+// until the other one has completed, four calls later on the headline path.  Every other engine uses buffer 0 alone.
+__host__ __device__ inline uint32_t sc_fft_run(const StreamCall& c) { return c.fft_run & 3u; }
+__host__ __device__ inline uint32_t sc_fft_buf(const StreamCall& c) { return (c.fft_run >> 8) & 1u; }
+__host__ __device__ inline size_t sc_fft_row(const StreamCall& c, uint32_t s) { return ((size_t)s * 2u + sc_fft_buf(c)) * (size_t)kFftBins; }   // first sample of the buffer in use
+__host__ __device__ inline uint32_t sc_pack_fft_run(uint32_t run, uint32_t buf) { return (run & 3u) | ((buf & 1u) << 8); }
+
 // FirHistory head, lazily (round 6).  The head -- the first samples of the previous run's input -- is only read by the first run after a tap-count INCREASE, and
 // the previous run's input still sits where that run read it: in the low-pass buffer of the call it ran in, which nothing overwrites for two more calls (three
 // buffers take turns).  So no run writes a head any more (33 MB per step at /16, 67 at /4, 8.4 in the headline launch, for a change that may never come):

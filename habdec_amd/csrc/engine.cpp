@@ -94,6 +94,10 @@ struct SizeState {
     uint32_t win_ub = 0, inflight_m = 0;   // upper bound of backlog samples without final window results; low-pass outputs of undelivered calls (collect() learns them back)
     uint32_t last_n2 = 0, last_pend_before = 0, last_m = 0;   // last call (for the getters)
     int last_buf = 0;
+    uint8_t fft_buf = 0;            // which of the stream's two spectrum collection buffers the next call appends to (dev_types.h sc_fft_buf; always 0 unless hd_engine::lazy_spectra)
+    uint8_t spec_buf = 0;           // ... and the one that completed last
+    bool spec_stale = false;        // the spectrum of that buffer has not been stored into `spec` / `power`: the tail that transformed it kept the statistics only (refresh_spectra)
+    bool demod_in_ring = false;     // the last call's discriminator output was not stored into `demod`: it is the newest last_m samples of the symbol ring (fill_tail)
 };
 
 struct StreamHost {
@@ -149,6 +153,7 @@ struct hd_engine {
     bool decode_enabled = true;
     bool fast = false;         // hd_engine_config.arith == HD_ARITH_FAST: the hd::fast kernels (fused multiply-add in every FIR; tolerance 1e-5, not bit-identical floats)
     bool one_stream = false;
+    bool lazy_spectra = false; // batch mode: the stream tails store a spectrum's AFC statistics only; `spec` / `power` are filled when a getter asks (refresh_spectra).  HD_EAGER_SPECTRA=1: stored by every tail
     bool no_tail = false;      // HD_NO_TAIL: never use the one-wave stream tail (kernels/tail_body.h); A/B measurements
     uint32_t tail_max_n2 = 2048;   // HD_TAIL_MAX_N2: most decimated samples per call for which the stream tail is used
     int last_route = -1;       // route of the previous call (Route; the routes use the stage-2 buffers on different queues)
@@ -220,6 +225,7 @@ struct hd_engine {
     uint32_t head_cap = 0;
     DevBuf<hd::SymbolParams> d_sym;
     PinBuf<hd::SymbolParams> h_sym;
+    PinBuf<hd::StreamCall> h_spec_call;   // [S], lazy_spectra: the parameter block of the spectrum launch a getter triggers (only fft_run is set: which streams, which buffer)
     // Everything a call in flight owns, double-buffered so call k+1 can be enqueued (and its front half can run)
     // while call k's back half is still executing and its results have not been read yet.
     static constexpr int kSlots = 4;   // calls whose host-visible blocks (parameters, result slots, spectrum statistics) may be in use at once: in flight + being delivered
@@ -358,6 +364,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
     // (0.283 -> 0.268 ms per step at 1024 streams, 12 us of it the hop from one queue to the other).
     e->one_stream = cfg->pipeline == 0;
     e->no_tail = getenv("HD_NO_TAIL") != nullptr;
+    { const char* v = getenv("HD_EAGER_SPECTRA"); e->lazy_spectra = cfg->pipeline >= 1 && cfg->enable_spectrum && !(v && atoi(v)); }
     e->no_claim = getenv("HD_NO_CLAIM") != nullptr;
     if (const char* v = getenv("HD_STEP_RUN")) e->step_run = (uint32_t)atoi(v);
     e->no_cu_step = getenv("HD_NO_CU_STEP") != nullptr;
@@ -492,7 +499,8 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HD_HIP(hipMemcpy(e->tune_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     if (cfg->enable_spectrum) {
-        HD_HIP(e->fft_in.alloc((size_t)S * hd::kFftBins));
+        HD_HIP(e->fft_in.alloc((size_t)S * 2 * hd::kFftBins));        // two collection buffers per stream (dev_types.h sc_fft_row)
+        if (e->lazy_spectra) HD_HIP(e->h_spec_call.alloc(S));
         HD_HIP(e->spec.alloc((size_t)S * hd::kFftBins));
         HD_HIP(e->power.alloc((size_t)S * hd::kFftBins));
         for (auto& sl : e->slot) HD_HIP(sl.h_stats.alloc(S));
@@ -790,7 +798,7 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
             await(&reinterpret_cast<const volatile hd::BitsHeader*>(sl.h_slots.p + (size_t)s * e->slot_words)->seq, "result slot", s);
             // ... and the spectrum statistics of a stream whose buffer completed in this call: written by the tail itself (behind the same tag) or by a
             // spectrum launch of its own, whose stores no event of this engine fences
-            if (!e->device_failed && e->cfg.enable_spectrum && sl.h_stats.p && sl.h_call.p[s].fft_run)
+            if (!e->device_failed && e->cfg.enable_spectrum && sl.h_stats.p && hd::sc_fft_run(sl.h_call.p[s]))
                 await(reinterpret_cast<const volatile uint32_t*>(&sl.h_stats.p[s].seq), "spectrum statistics", s);
         }
         std::atomic_thread_fence(std::memory_order_acquire);
@@ -811,7 +819,7 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
     for (uint32_t s = 0; s < e->S; ++s) {
         StreamHost& st = e->st[s];
         const hd::StreamCall& c = sl.h_call.p[s];
-        if (c.fft_run) {
+        if (hd::sc_fft_run(c)) {
             std::memcpy(&st.stats, &sl.h_stats.p[s], sizeof(st.stats));
             st.have_spectrum = true;
             ++st.spectra;
@@ -964,7 +972,12 @@ int plan_call(hd_engine* e, hd_engine::CallSlot& sl, const uint32_t* n_per_strea
             c.fft_take = (uint32_t)std::min<size_t>(hd::kFftBins - nx.fft_fill, c.n2);
             nx.fft_fill += c.fft_take;
         }
-        if (e->cfg.enable_spectrum && n && nx.fft_fill >= (size_t)hd::kFftBins) { c.fft_run = 1; nx.fft_fill = 0; p.any_fft = true; }
+        c.fft_run = hd::sc_pack_fft_run(0, nx.fft_buf);
+        if (e->cfg.enable_spectrum && n && nx.fft_fill >= (size_t)hd::kFftBins) {
+            c.fft_run = hd::sc_pack_fft_run(1, nx.fft_buf); nx.fft_fill = 0; p.any_fft = true;
+            nx.spec_buf = nx.fft_buf;
+            if (e->lazy_spectra) nx.fft_buf ^= 1u;      // the completed buffer stays as it is until the other one has completed
+        }
         // batch gate, rate gate, low-pass batch (Decoder.h:492-542)
         const bool past_batch_gate = n && nx.pending >= hd::kFirBatch;
         nx.last_m = 0;
@@ -1068,21 +1081,26 @@ void route_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallRo
     // samples per call that is every call: 8 + 8 bytes per decimated sample less traffic.
     for (uint32_t s = 0; s < S; ++s) {
         hd::StreamCall& c = sl.h_call.p[s];
-        if (c.fft_run == 1 && c.fft_fill == 0 && c.fft_take == (uint32_t)hd::kFftBins) { c.fft_take = 0; c.fft_run = 2; }
+        if (hd::sc_fft_run(c) == 1 && c.fft_fill == 0 && c.fft_take == (uint32_t)hd::kFftBins) { c.fft_take = 0; c.fft_run = hd::sc_pack_fft_run(2, hd::sc_fft_buf(c)); }
     }
     // Where every spectrum of the call is read in place (fft_run == 2 for all of them), the spectrum launch hangs on nothing but this call's chunk: it goes
     // to the third queue behind the front half's event, off the queue a step waits for (round 5 could not: the next call's second stage refilled the
     // collection buffer a transform on another queue was still reading -- there is no collection buffer on this route).
     r.spectrum_on_qc = !e->one_stream && p.nst != 0;
-    for (uint32_t s = 0; s < S && r.spectrum_on_qc; ++s) r.spectrum_on_qc = sl.h_call.p[s].fft_run != 1u;
+    for (uint32_t s = 0; s < S && r.spectrum_on_qc; ++s) r.spectrum_on_qc = hd::sc_fft_run(sl.h_call.p[s]) != 1u;
 }
+
+// Batch mode: a stream tail does not store the call's discriminator output into `demod` -- the same samples are the newest fir_m of the symbol ring it
+// appends to, and only hd_stream_demodulated asks for them, behind a flush (4 bytes per decimated sample and launch less, half the stores of the tail's
+// discriminator phase).  A synchronous engine keeps the array; so do the separate kernels, where k_symbols reads it.
+bool demod_in_ring(const hd_engine* e, Route route) { return e->cfg.pipeline >= 1 && route != Route::separate; }
 
 // Buffers of THIS call's stream tails (the LDS carve is already in t)
 void fill_tail(const hd_engine* e, const hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r, const CallBufs& b, hd::TailArgs& t)
 {
     t.dec1 = b.d1; t.dec1_stride = e->n1_cap; t.hist2_in = e->hist2[b.hin].p; t.hist2_out = e->hist2[b.hout].p; t.taps2 = e->stage_taps[1].p;
     t.fbuf = b.fcur; t.fbuf_next = b.fnext; t.fbuf_stride = e->fbuf_stride; t.fir_hist_cap = e->fir_hist_cap;
-    t.lp_taps = e->lp_taps.p; t.taps_stride = e->taps_cap; t.demod = e->demod.p; t.demod_stride = e->demod.n / e->S;
+    t.lp_taps = e->lp_taps.p; t.taps_stride = e->taps_cap; t.demod = demod_in_ring(e, r.route) ? nullptr : e->demod.p; t.demod_stride = e->demod.n / e->S;
     t.filtered = e->cfg.keep_filtered ? e->filtered.p : nullptr; t.carry_in = e->carry[b.cin].p; t.carry_out = e->carry[b.cout].p;
     t.tune = p.any_tune ? sl.h_tune.dev : nullptr; t.tune_tab = e->tune_tab.p;
     t.call = r.dcall; t.fft_in = r.feed; t.head_buf = e->fir_head.p; t.fbuf_prev = b.fprev; t.head_cap = e->head_cap;
@@ -1091,7 +1109,7 @@ void fill_tail(const hd_engine* e, const hd_engine::CallSlot& sl, const CallPlan
     t.sp = e->d_sym.p; t.slots = sl.h_slots.dev; t.slot_words = e->slot_words; t.seq = sl.seq;
     t.flips_dbg = e->flips_cap ? e->flips_dbg.p : nullptr; t.flips_cap = e->flips_cap;
     t.fft_tw = r.feed ? e->fft_tw.p : nullptr;   // the tail transforms a completed buffer itself (a tail route feeds the buffer exactly when the engine has spectra)
-    t.spec = e->spec.p; t.power = e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
+    t.spec = e->lazy_spectra ? nullptr : e->spec.p; t.power = e->lazy_spectra ? nullptr : e->power.p; t.stats = sl.h_stats.dev; t.rate = e->fsd; t.bins_sep = e->bins_sep;
 }
 
 // Equally sized pushes through a single-wave first stage of a two-stage plan: the stage-1 workgroups (eight resident per CU) draw runs of tiles from
@@ -1418,6 +1436,13 @@ int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
 void commit_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, const CallRoute& r)
 {
     e->mirror.swap(e->mirror_next);
+    const bool in_ring = demod_in_ring(e, r.route);
+    const bool lazy = e->lazy_spectra && r.route != Route::separate;      // (the spectrum launches of the separate kernels store what they transform)
+    for (uint32_t s = 0; s < e->S; ++s) {
+        SizeState& sz = e->mirror[s];
+        sz.demod_in_ring = in_ring;
+        if (hd::sc_fft_run(sl.h_call.p[s])) sz.spec_stale = lazy;
+    }
     sl.busy = true;
     if (r.route == Route::step) {   // this call's tails ride in the next call's launch
         e->pend.valid = true; e->pend.ta = r.ta_step; e->pend.slot = (int)(e->calls % hd_engine::kSlots);
@@ -1690,15 +1715,51 @@ int hd_stream_afc(hd_engine* e, uint32_t s, hd_afc_info* out)
     return HD_OK;
 }
 
+// Batch mode (hd_engine::lazy_spectra): the spectra the stream tails transformed but did not store -- one spectrum launch over the streams whose stored
+// spectrum is older than their last completed collection buffer, which is still as that tail read it.  Same transform body, same inputs: the bytes a
+// tail would have stored.  The statistics were delivered with the call (null pointer: not written again).  The pipeline is drained when this runs.
+static int refresh_spectra(hd_engine* e)
+{
+    if (!e->lazy_spectra) return HD_OK;
+    bool any = false;
+    for (uint32_t s = 0; s < e->S; ++s) {
+        const SizeState& sz = e->mirror[s];
+        e->h_spec_call.p[s].fft_run = sz.spec_stale ? hd::sc_pack_fft_run(1, sz.spec_buf) : 0u;
+        any |= sz.spec_stale;
+    }
+    if (!any) return HD_OK;
+    HD_HIP(hipSetDevice(e->cfg.device));
+    hd::launch_spectrum_wave(e->qa, e->S, e->fft_in.p, e->fft_tw.p, e->spec.p, e->power.p, nullptr, e->h_spec_call.dev, e->fsd, e->bins_sep, 0u);
+    HD_HIP(hipGetLastError());
+    HD_HIP(hipStreamSynchronize(e->qa));
+    for (SizeState& sz : e->mirror) sz.spec_stale = false;
+    return HD_OK;
+}
+// A data getter in two steps: refuse it inside a callback and drain the pipeline (getter_ready), then copy (copy_to_host).  fetch is both.
+static bool getter_ready(hd_engine* e)
+{
+    if (e->in_callback) { fail(HD_ERR_INVALID, "data getters cannot be called from a sentence / character callback (text getters can)"); return false; }
+    (void)flush_locked(e);                                  // pipelined mode: wait for the call in flight
+    return true;
+}
+static bool copy_to_host(hd_engine* e, void* host, const void* dev, size_t bytes)
+{
+    return !bytes || (hipSetDevice(e->cfg.device) == hipSuccess && hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost) == hipSuccess);
+}
 static size_t fetch(hd_engine* e, const void* dev, size_t count, size_t elem, void* host, size_t cap)
 {
-    if (e->in_callback) { fail(HD_ERR_INVALID, "data getters cannot be called from a sentence / character callback (text getters can)"); return 0; }
-    (void)flush_locked(e);                                  // pipelined mode: wait for the call in flight
+    if (!getter_ready(e)) return 0;
     const size_t n = std::min(count, cap);
     if (!n || !host) return count;
-    if (hipSetDevice(e->cfg.device) != hipSuccess) return 0;
-    if (hipMemcpy(host, dev, n * elem, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return count;
+    return copy_to_host(e, host, dev, n * elem) ? count : 0;
+}
+
+static size_t fetch_spectrum(hd_engine* e, const void* dev, size_t elem, void* host, size_t cap)
+{
+    if (!getter_ready(e) || refresh_spectra(e) != HD_OK) return 0;
+    const size_t n = std::min<size_t>(hd::kFftBins, cap);
+    if (!n || !host) return hd::kFftBins;
+    return copy_to_host(e, host, dev, n * elem) ? (size_t)hd::kFftBins : 0;
 }
 
 size_t hd_stream_spectrum(hd_engine* e, uint32_t s, float* iq, size_t cap)
@@ -1706,20 +1767,32 @@ size_t hd_stream_spectrum(hd_engine* e, uint32_t s, float* iq, size_t cap)
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
     if (!e->cfg.enable_spectrum || !e->st[s].have_spectrum) return 0;
-    return fetch(e, e->spec.p + (size_t)s * hd::kFftBins, hd::kFftBins, sizeof(float2), iq, cap);
+    return fetch_spectrum(e, e->spec.p + (size_t)s * hd::kFftBins, sizeof(float2), iq, cap);
 }
 size_t hd_stream_power(hd_engine* e, uint32_t s, float* p, size_t cap)
 {
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
     if (!e->cfg.enable_spectrum || !e->st[s].have_spectrum) return 0;
-    return fetch(e, e->power.p + (size_t)s * hd::kFftBins, hd::kFftBins, sizeof(float), p, cap);
+    return fetch_spectrum(e, e->power.p + (size_t)s * hd::kFftBins, sizeof(float), p, cap);
 }
 size_t hd_stream_demodulated(hd_engine* e, uint32_t s, float* v, size_t cap)
 {
     if (check_stream(e, s)) return 0;
     std::lock_guard<std::recursive_mutex> l(e->mtx);
-    return fetch(e, e->demod.p + (size_t)s * (e->demod.n / e->S), e->mirror[s].last_m, sizeof(float), v, cap);
+    const SizeState& sz = e->mirror[s];
+    if (!sz.demod_in_ring) return fetch(e, e->demod.p + (size_t)s * (e->demod.n / e->S), sz.last_m, sizeof(float), v, cap);
+    // A stream tail of a batch-mode engine left the call's output in the symbol ring only (fill_tail): the last_m samples in front of the ring's append
+    // position, which is base + held of the stream's SymState once the pipeline is drained (the tail's symbol search moves base and held, never their sum).
+    if (!getter_ready(e)) return 0;
+    const size_t count = sz.last_m, n = std::min(count, cap);
+    if (!n || !v) return count;
+    hd::SymState st;
+    if (!copy_to_host(e, &st, e->d_symstate.p + s, sizeof(st))) return 0;
+    const float* ring = e->tail.p + (size_t)s * e->tail_cap;
+    const uint32_t first = (st.base + st.held - (uint32_t)count) & (e->tail_cap - 1u);       // (count <= m_cap < tail_cap)
+    const size_t n0 = std::min<size_t>(n, e->tail_cap - first);                              // up to the ring's end, then from its start
+    return copy_to_host(e, v, ring + first, n0 * sizeof(float)) && copy_to_host(e, v + n0, ring, (n - n0) * sizeof(float)) ? count : 0;
 }
 size_t hd_stream_decimated(hd_engine* e, uint32_t s, float* iq, size_t cap)
 {

@@ -117,8 +117,8 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
     // tiles of the slab are dealt evenly to gridDim.x workgroups, whatever that number is -- it decides how many of a CU's LDS
     // slots this kernel occupies -- and a workgroup simply walks on into the next stream where its range crosses a seam.
     // Per-stream context (s, the stream's StreamCall head) therefore is a variable; the prefetch runs one tile ahead of it.
-    struct CallHead { uint32_t n_in, n1, n2, zero_hist1, zero_hist2, pend_before, fft_fill, fft_take; };   // first 32 bytes of StreamCall
-    static_assert(sizeof(CallHead) == 32, "CallHead mirrors the head of StreamCall");
+    struct CallHead { uint32_t n_in, n1, n2, zero_hist1, zero_hist2, pend_before, fft_fill, fft_take, fft_run; };   // first 36 bytes of StreamCall
+    static_assert(sizeof(CallHead) == 36, "CallHead mirrors the head of StreamCall");
     const bool linear = lin_ntiles != 0;
     uint32_t s, first, count;                               // current stream, first tile in it, tiles this workgroup walks in total
     // Claimed runs (step launches): the slab's tiles are cut into runs of claim.run_len consecutive tiles of one stream; XCD x owns the
@@ -509,7 +509,7 @@ __device__ __forceinline__ void decimate_body(const float2* __restrict__ in, siz
         nv_prev = o < nout ? min((uint32_t)OPL, nout - o) : 0u;
         dst_prev = out + (size_t)s * out_stride + (final_stage ? (size_t)fir_hist_cap + c.pend_before : 0) + o;
         nf_prev = (fft_in && o < c.fft_take) ? min((uint32_t)OPL, c.fft_take - o) : 0u;
-        fdst_prev = fft_in ? fft_in + (size_t)s * kFftBins + c.fft_fill + o : nullptr;
+        fdst_prev = fft_in ? fft_in + ((size_t)s * 2u + ((c.fft_run >> 8) & 1u)) * kFftBins + c.fft_fill + o : nullptr;   // (the stream's buffer in use: dev_types.h sc_fft_row)
         __syncthreads();                                    // everyone is done with this tile's LDS image
         DSTAMP(3);
         ++tile_i;

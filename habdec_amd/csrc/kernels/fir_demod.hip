@@ -280,7 +280,7 @@ __global__ void k_fft_feed(const float2* __restrict__ fbuf, size_t stride, float
     const StreamCall c = call[s];
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= c.fft_take) return;
-    fft_in[(size_t)s * kFftBins + c.fft_fill + j] = fbuf[(size_t)s * stride + fir_hist_cap + c.pend_before + j];
+    fft_in[sc_fft_row(c, s) + c.fft_fill + j] = fbuf[(size_t)s * stride + fir_hist_cap + c.pend_before + j];
 }
 
 // Per-call parameters come from mapped pinned host memory; one small kernel pulls them into HBM so that the

@@ -41,7 +41,8 @@ struct TailArgs {
     const float2* hist2_in; float2* hist2_out; const float* taps2;
     float2* fbuf; float2* fbuf_next; size_t fbuf_stride; uint32_t fir_hist_cap;
     const float* lp_taps; uint32_t taps_stride;
-    float* demod; size_t demod_stride; float2* filtered;
+    float* demod /* or null: the call's discriminator output is not stored a second time -- it is ring[(base + held - fir_m + i) & (ring_cap - 1)] of the
+                    stream's SymState once the tail has run, which is where hd_stream_demodulated then reads it (batch mode) */; size_t demod_stride; float2* filtered;
     const DemodCarry* carry_in; DemodCarry* carry_out;
     const StreamCall* call; float2* fft_in;
     float2* head_buf /* [S][head_cap]: FirHistory heads moved aside */; const float2* fbuf_prev /* the previous call's low-pass buffers (dev_types.h: FirHistory head, lazily) */; uint32_t head_cap, n_streams;

@@ -165,6 +165,8 @@ constexpr uint32_t kSpecWaveLds = 64 * 65 * 4;                      // the trans
 
 // x: the stream's 4096 input samples (wave-uniform pointer) -- its row of the spectrum input collection, or, where one call's chunk alone fills the
 // buffer, the head of that chunk where the last decimation stage left it (StreamCall::fft_run == 2: no second copy of the samples)
+// spec, power: both given or both null -- null: nothing but the statistics is stored (a batch-mode tail; the engine runs this body again over the kept
+// inputs when a getter asks, k_spectrum_wave).  stats: null where the statistics have been delivered already (that second run).
 __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x, const float2* __restrict__ tw4096, float2* __restrict__ spec,
                                                    float* __restrict__ power, SpectrumStatsDev* __restrict__ stats, const uint32_t s, const double rate,
                                                    const int bins_sep, float* __restrict__ plane, const uint32_t seq)
@@ -186,32 +188,39 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
     // (sixteen factors at a time: all 63 gathers hoisted in front of pass 1 would need another 126 registers)
     specwave::finish4096<16>(a, tw4096, plane, l);
     // ---- half swap, dB power, statistics.  Bin k = l + 64 k2 lands at i = (k + 2048) & 4095 = l + 64 j, j = (k2 + 32) & 63.
-    float2* so = spec + (size_t)s * kFftBins;
-    float* po = power + (size_t)s * kFftBins;
     int mybad = 0;
     double lsum = 0.0;
     // P[l + 64 j] replaces the real part of the bin it was computed from (register xpos((j + 32) & 63)): no second array beside a[]
 #define HD_SW_P(j_) a[specwave::xpos(((j_) + 32) & 63)].x
-    float2* sg = so;
-    float* pg = po;
+    // Eight bins at a time (the logarithms' temporaries add up otherwise): their spectrum stores, their powers, their power stores.  The stores sit behind
+    // a wave-uniform test per group, not per bin, and there is one copy of the arithmetic whether they are made or not.
+    const bool store = spec != nullptr;
 #pragma unroll
-    for (int j = 0; j < 64; ++j) {
-        if ((j & 7) == 0) {                                         // eight bins at a time: the logarithms' temporaries add up otherwise
-            __builtin_amdgcn_sched_barrier(0);
-            sg = so + 64 * j; pg = po + 64 * j;
-            asm volatile("" : "+s"(sg), "+s"(pg));
+    for (int g = 0; g < 64; g += 8) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (store) {
+            float2* sg = spec + (size_t)s * kFftBins + 64 * g;
+            asm volatile("" : "+s"(sg));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const f32x2 v = a[specwave::xpos((g + u + 32) & 63)]; sg[l + 64 * u] = make_float2(v.x, v.y); }
         }
-        const int k2 = (j + 32) & 63;
-        const f32x2 v = a[specwave::xpos(k2)];
-        sg[l + 64 * (j & 7)] = make_float2(v.x, v.y);
-        float q = (v.x * v.x + v.y * v.y) / (float)kFftBins;
-        q = q * q;
-        q = (float)((double)q / rate);
-        q = 10.0f * log10f(q);
-        if (v.x != v.x || v.y != v.y || isinf(v.x) || isinf(v.y) || q != q || isinf(q)) mybad = 1;
-        HD_SW_P(j) = q;
-        pg[l + 64 * (j & 7)] = q;
-        lsum += (double)q;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const f32x2 v = a[specwave::xpos((g + u + 32) & 63)];
+            float q = (v.x * v.x + v.y * v.y) / (float)kFftBins;
+            q = q * q;
+            q = (float)((double)q / rate);
+            q = 10.0f * log10f(q);
+            if (v.x != v.x || v.y != v.y || isinf(v.x) || isinf(v.y) || q != q || isinf(q)) mybad = 1;
+            HD_SW_P(g + u) = q;
+            lsum += (double)q;
+        }
+        if (store) {
+            float* pg = power + (size_t)s * kFftBins + 64 * g;
+            asm volatile("" : "+s"(pg));
+#pragma unroll
+            for (int u = 0; u < 8; ++u) pg[l + 64 * u] = HD_SW_P(g + u);
+        }
     }
     const bool bad = __builtin_amdgcn_ballot_w64(mybad != 0) != 0ull;
     const double mean = specwave::wave_sum(lsum) / (double)kFftBins;
@@ -240,7 +249,7 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
         if (i >= lo && i < hi && pj > floor0 && abs(i - p1) > bins_sep / 2 && pj > cv) { cv = pj; ci = i; }
     }
     specwave::wave_argmax(cv, ci);
-    if (l == 0) {
+    if (l == 0 && stats) {
         int pa = p1, pb = 0;
         float av = p1v, bvv = floor0;
         if (ci < (int)kFftBins) { pb = ci; bvv = cv; }

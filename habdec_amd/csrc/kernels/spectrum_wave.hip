@@ -12,11 +12,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 {
     __shared__ float plane[64 * 65];
     const uint32_t s = blockIdx.x;
-    const uint32_t run = call[s].fft_run;
+    const StreamCall c = call[s];
+    const uint32_t run = sc_fft_run(c);
     if (!run) return;
     // fft_run == 2: this call's decimated chunk alone fills the buffer (Decoder.h:467-473 with an empty freq_in_ and >= 4096 new samples): its head is read where
     // the last decimation stage left it -- behind the low-pass history and the pending samples -- instead of from a second copy in fft_in
-    const float2* x = run == 2u ? chunk + (size_t)s * chunk_stride + fir_hist_cap + call[s].pend_before : fft_in + (size_t)s * kFftBins;
+    const float2* x = run == 2u ? chunk + (size_t)s * chunk_stride + fir_hist_cap + c.pend_before : fft_in + sc_fft_row(c, s);
     spectrum_wave_body(x, tw4096, spec, power, stats, s, rate, bins_sep, plane, seq);
 }
 

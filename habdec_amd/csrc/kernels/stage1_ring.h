@@ -688,7 +688,7 @@ __device__ __forceinline__ void ring_consumer(const RingArgs& a, const RingGeom&
             for (int q = 0; q < OPL; q += 2) *reinterpret_cast<float4*>(dst + q) = make_float4(acc[q].x, acc[q].y, acc[q + 1].x, acc[q + 1].y);
         } else {
             // the final stage of a single-stage plan: behind the pending low-pass input, and the head of the chunk into the spectrum collection
-            const uint32_t pend = a.call[s].pend_before, ftake = a.call[s].fft_take, ffill = a.call[s].fft_fill;
+            const uint32_t pend = a.call[s].pend_before, ftake = a.call[s].fft_take, ffill = a.call[s].fft_fill, fbuf = (a.call[s].fft_run >> 8) & 1u;   // (fbuf: dev_types.h sc_fft_buf)
             float2* dst = a.out + (size_t)s * a.out_stride + a.fir_hist_cap + pend + o0;
             if (((a.fir_hist_cap + pend) & 1u) == 0u) {
 #pragma unroll
@@ -698,7 +698,7 @@ __device__ __forceinline__ void ring_consumer(const RingArgs& a, const RingGeom&
                 for (int q = 0; q < OPL; ++q) dst[q] = make_float2(acc[q].x, acc[q].y);
             }
             if (a.fft_in && o0 < ftake) {
-                float2* fd = a.fft_in + (size_t)s * kFftBins + ffill + o0;
+                float2* fd = a.fft_in + ((size_t)s * 2u + fbuf) * kFftBins + ffill + o0;
                 if (o0 + (uint32_t)OPL <= ftake && (ffill & 1u) == 0u) {
 #pragma unroll
                     for (int q = 0; q < OPL; q += 2) *reinterpret_cast<float4*>(fd + q) = make_float4(acc[q].x, acc[q].y, acc[q + 1].x, acc[q + 1].y);

@@ -178,6 +178,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
     const uint32_t ring_cap = a.ring_cap, rmask = ring_cap - 1;
     float* vring = a.ring + (size_t)s * ring_cap;
     float* gw = a.wsum + (size_t)s * ring_cap;
+    float* const dm_row = a.demod ? a.demod + (size_t)s * a.demod_stride : nullptr;   // the call's discriminator output as an array of its own, where the engine wants one
     unsigned long long* gmask = a.flipmask + (size_t)s * (ring_cap / 64);
     uint32_t* slot = a.slots + (size_t)s * a.slot_words;
     BitsHeader* hdr = reinterpret_cast<BitsHeader*>(slot);
@@ -519,7 +520,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
                     if (keepF) { float4* f4 = reinterpret_cast<float4*>(F + (f_old + oo - fbase)); f4[0] = y01; f4[1] = y23; }
                     { float4* c4 = reinterpret_cast<float4*>(cur + fhc + pb + oo); c4[0] = y01; c4[1] = y23; }   // the decimated chunk stays readable (getters, the unfused path next call)
                     if (a.fft_in && oo < c.fft_take) {                  // Decoder.h:467-473
-                        float2* fi = a.fft_in + (size_t)s * kFftBins + c.fft_fill + oo;
+                        float2* fi = a.fft_in + sc_fft_row(c, s) + c.fft_fill + oo;
                         if (oo + 3 < c.fft_take && !(c.fft_fill & 1u)) { reinterpret_cast<float4*>(fi)[0] = y01; reinterpret_cast<float4*>(fi)[1] = y23; }
                         else {
 #pragma unroll
@@ -538,7 +539,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
                         const float2 y = make_float2(acc[q].x, acc[q].y);
                         if (keepF) F[f_old + oo - fbase] = y;
                         cur[fhc + pb + oo] = y;
-                        if (a.fft_in && oo < c.fft_take) a.fft_in[(size_t)s * kFftBins + c.fft_fill + oo] = y;
+                        if (a.fft_in && oo < c.fft_take) a.fft_in[sc_fft_row(c, s) + c.fft_fill + oo] = y;
                     }
                 }
             }
@@ -637,13 +638,15 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
 #pragma unroll
                             for (int u = 0; u < 4; ++u)
                                 if ((uint32_t)u < nv) { const uint32_t b = __builtin_bit_cast(uint32_t, d[u]); ck0 += b; ck1 += (i + (uint32_t)u + 1u) * b; }
-                            float* dm = a.demod + (size_t)s * a.demod_stride + i;   // i and demod_stride are even
                             const uint32_t pos = end_old + i;           // SymbolExtractor::pushSamples: append to the backlog ring
                             const float4 d4 = make_float4(d[0], d[1], d[2], d[3]);
-                            if (nv == 4 && !(i & 3u)) *reinterpret_cast<float4*>(dm) = d4;
-                            else {
-                                if (nv >= 2) *reinterpret_cast<float2*>(dm) = make_float2(d[0], d[1]); else dm[0] = d[0];
-                                if (nv == 4) *reinterpret_cast<float2*>(dm + 2) = make_float2(d[2], d[3]); else if (nv == 3) dm[2] = d[2];
+                            if (dm_row) {                               // (batch mode: not stored -- the ring below holds the same samples, see TailArgs::demod)
+                                float* dm = dm_row + i;                 // i and demod_stride are even
+                                if (nv == 4 && !(i & 3u)) *reinterpret_cast<float4*>(dm) = d4;
+                                else {
+                                    if (nv >= 2) *reinterpret_cast<float2*>(dm) = make_float2(d[0], d[1]); else dm[0] = d[0];
+                                    if (nv == 4) *reinterpret_cast<float2*>(dm + 2) = make_float2(d[2], d[3]); else if (nv == 3) dm[2] = d[2];
+                                }
                             }
                             if (nv == 4 && !(pos & 3u)) *reinterpret_cast<float4*>(vring + (pos & rmask)) = d4;   // (an aligned quad never straddles the ring's end)
                             else {
@@ -1004,11 +1007,11 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
     // ---- the stream's spectrum, when its 4096-sample buffer completed in this call (Decoder.h:475-489): transform, half swap, power and
     // AFC statistics by this same wave (spectrum_wave.h) -- no launch of its own, no round trip through HBM.  The buffer's last samples
     // were stored by this workgroup a moment ago.
-    if (a.fft_tw && c.fft_run) {
+    if (a.fft_tw && sc_fft_run(c)) {
         __threadfence_block();
         tb_sync<NT>();                                                  // every wave is done with the LDS images
         if (wave == 0)
-            spectrum_wave_body(a.fft_in + (size_t)s * kFftBins, a.fft_tw, a.spec, a.power, a.stats, s, a.rate, a.bins_sep, reinterpret_cast<float*>(lds + kTailHdrBytes), a.seq);
+            spectrum_wave_body(a.fft_in + sc_fft_row(c, s), a.fft_tw, a.spec, a.power, a.stats, s, a.rate, a.bins_sep, reinterpret_cast<float*>(lds + kTailHdrBytes), a.seq);
     }
     // the call's tag, LAST: every store this wave has issued -- header, bits, spectrum statistics, all by wave 0 -- has been acknowledged before it goes out
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
