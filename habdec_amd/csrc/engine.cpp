@@ -33,6 +33,7 @@
 #include "host/text_stage.hpp"
 #include "host/tune_host.hpp"
 #include "kernels/launch.h"
+#include "kernels/spectrum_math.h"
 #include "kernels/survey.h"
 
 // A launcher (or layout helper) of the kernels that exist once per arithmetic mode (kernels/arith.h): hd::exact::fn or hd::fast::fn by the engine's mode.
@@ -159,7 +160,7 @@ struct hd_engine {
     int last_route = -1;       // route of the previous call (Route; the routes use the stage-2 buffers on different queues)
     // Step mode (batch decoding, kernels/decimate.hip k_step): the stream tails of call k ride in the stage-1 launch of call k+1.
     struct PendingTail { bool valid = false; hd::TailArgs ta{}; int slot = 0; int r2 = 0, t2 = 0; } pend;
-    DevBuf<float2> fft_tw;     // (cos, -sin)(2 pi m / 4096), rounded once from double
+    DevBuf<float2> fft_tw;     // [64][64] the transform's twiddles, lane-major (kernels/spectrum_math.h: fft_twiddles), rounded once from double
     bool no_claim = false;     // HD_NO_CLAIM: step launches with fixed shares of tiles (A/B measurements)
     uint32_t step_run = 0;     // HD_STEP_RUN: tiles per drawn run (default 4, minimum 2)
     bool no_cu_step = false;   // HD_NO_CU_STEP: step launches as single-wave workgroups (k_step) instead of one workgroup per CU (k_step_cu)
@@ -506,10 +507,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         for (auto& sl : e->slot) HD_HIP(sl.h_stats.alloc(S));
         {
             std::vector<float2> tw(hd::kFftBins);
-            for (size_t m = 0; m < hd::kFftBins; ++m) {
-                const double a = 2.0 * 3.14159265358979323846264338327950288 * (double)m / (double)hd::kFftBins;
-                tw[m] = make_float2((float)std::cos(a), (float)-std::sin(a));
-            }
+            hd::specwave::fft_twiddles(tw.data());
             HD_HIP(e->fft_tw.alloc(hd::kFftBins));
             HD_HIP(hipMemcpy(e->fft_tw.p, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
         }
@@ -1948,10 +1946,7 @@ int hd_survey_create(hd_engine* e, hd_survey** out)
     sv->tw = e->fft_tw.p;
     if (!sv->tw) {   // an engine without spectra holds no twiddles: the same table, the survey's own
         tw.resize(hd::kFftBins);
-        for (size_t m = 0; m < tw.size(); ++m) {
-            const double a = 2.0 * 3.14159265358979323846264338327950288 * (double)m / (double)hd::kFftBins;
-            tw[m] = make_float2((float)std::cos(a), (float)-std::sin(a));
-        }
+        hd::specwave::fft_twiddles(tw.data());
         HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->own_tw), tw.size() * sizeof(float2)));
         HD_HIP(hipMemcpyAsync(sv->own_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, sv->q));
         sv->tw = sv->own_tw;

@@ -64,8 +64,8 @@ struct TailArgs {
 constexpr uint32_t kStepLdsBytes = 20480;   // LDS of a stage-1 workgroup slot (eight per CU): what a tail riding in the stage-1 launch may use
 
 // ---- the launcher that does not depend on the arithmetic mode (spectrum_wave.hip)
-// The spectrum step in one launch, one wave per stream; tw4096[m] = (cos, -sin)(2 pi m / 4096).
-void launch_spectrum_wave(hipStream_t st, uint32_t n_streams, const float2* fft_in, const float2* tw4096, float2* spec, float* power,
+// The spectrum step in one launch, one wave per stream; tw64: the lane-major twiddle table (spectrum_math.h: fft_twiddles).
+void launch_spectrum_wave(hipStream_t st, uint32_t n_streams, const float2* fft_in, const float2* tw64, float2* spec, float* power,
                           SpectrumStatsDev* stats, const StreamCall* call, double rate, int bins_sep,
                           uint32_t seq /* the call's tag, stored last into every SpectrumStatsDev written (SpectrumStatsDev::seq) */,
                           const float2* chunk = nullptr /* the low-pass input buffers [S][chunk_stride]: streams with StreamCall::fft_run == 2 take their 4096 samples from the head of this call's decimated chunk */,

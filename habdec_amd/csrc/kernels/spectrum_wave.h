@@ -9,7 +9,8 @@
 // 4096 = 64 x 64.  With n = 64*n1 + n2 and k = k1 + 64*k2:
 //     X[k1 + 64 k2] = sum_n2 W64^(n2 k2) * [ W4096^(n2 k1) * sum_n1 x[64 n1 + n2] W64^(n1 k1) ]
 // Pass 1: lane n2 loads its 64 samples x[64 n1 + n2] (a wave-wide load per n1: 512 contiguous bytes) and runs a 64-point transform
-// over n1 in registers; the result is multiplied by W4096^(n2 k1) (table in HBM/L2, computed in double on the host); an LDS transpose
+// over n1 in registers; the result is multiplied by W4096^(n2 k1) (a lane-major table in HBM/L2, computed in double on the host: one
+// wave-wide contiguous 512-byte load per register, spectrum_math.h); an LDS transpose
 // (one float plane at a time, 65-float pitch: conflict-free both ways) hands lane k1 the 64 values of all n2; pass 2 is the same
 // 64-point transform over n2, after which lane k1 holds X[k1 + 64 k2], k2 = 0..63 -- bins that are 64 apart, so the stores of the
 // swapped spectrum and of the power are wave-wide contiguous again.  The 64-point transform is 8 x 8 eight-point transforms on a register
@@ -21,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "spectrum_math.h"
 #include "sym_common.h"
 
 namespace hd {
@@ -30,10 +32,6 @@ namespace specwave {
 __device__ static constexpr float kW64[2][32] = {
 #include "fft64_tw.inc"
 };
-
-// Where bin k of a 64-point transform sits in the register array after fft64 (8 x 8 decomposition, second-level output k2 left in its
-// row): X[k1 + 8 k2] = a[8 k1 + k2].
-constexpr int xpos(int k) { return 8 * (k & 7) + (k >> 3); }
 
 // 8-point transform of v[0..7] in place, natural order in and out: three radix-2 stages (decimation in time) with W8 = (1 - i)/sqrt(2).
 __device__ __forceinline__ void fft8(f32x2 (&v)[8])
@@ -102,22 +100,44 @@ __device__ __forceinline__ void pin64(f32x2 (&a)[64])
     for (int i = 0; i < 64; ++i) asm volatile("" : "+v"(a[i]));
 }
 
-// The second half of the 4096-point transform, n = 64 n1 + n2, k = k1 + 64 k2, in one wave: in, lane l = n2 holds pass 1's output for k1 at a[xpos(k1)];
-// out, lane l = k1 holds X[l + 64 k2] at a[xpos(k2)].  G twiddle factors are gathered at a time; `plane`: 64 x 65 floats of LDS of the wave's own.
-template <int G>
-__device__ __forceinline__ void finish4096(f32x2 (&a)[64], const float2* __restrict__ tw4096, float* __restrict__ plane, const uint32_t l)
+// Rows g .. g + n - 1 of the twiddle table (spectrum_math.h: fft_twiddles), the factors of registers g .. g + n - 1: row i of the wave is 512 contiguous
+// bytes, lane l takes its pair.  Rows in groups of eight behind a scalar base, like the sample loads: one offset register and immediate row offsets.
+// (The table is device memory whoever calls: said so behind the opaque base, or the loads would be flat ones that the LDS waits count too.)
+typedef const __attribute__((address_space(1))) f32x2* gptr_t;
+__device__ __forceinline__ void load_tw(f32x2 (&w)[64], const float2* __restrict__ tw64, const int g, const int n, const uint32_t l)
 {
+#pragma unroll
+    for (int h = g; h < g + n; h += 8) {
+        const float2* tg = tw64 + 64 * h;
+        asm volatile("" : "+s"(tg));
+        const gptr_t tg1 = (gptr_t)tg;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) w[h + u] = tg1[64 * u + l];
+    }
+}
+
+// The second half of the 4096-point transform, n = 64 n1 + n2, k = k1 + 64 k2, in one wave: in, lane l = n2 holds pass 1's output for k1 at a[xpos(k1)];
+// out, lane l = k1 holds X[l + 64 k2] at a[xpos(k2)].  The twiddle rows are loaded ahead of their use, never waited for right behind their issue:
+// rows 0 .. H - 1 by the caller (load_tw) in front of pass 1, which depends on none of them and is some 1200 vector instructions; the later ones here,
+// G rows at a time, so that the products of D groups lie between a group's issue and its use (w[] is 64 names, not 64 pairs of registers: a row lives
+// from its load to its product).  G, H, D are each kernel's own choice under its register budget.  `plane`: 64 x 65 floats of LDS of the wave's own.
+template <int G, int H, int D>
+__device__ __forceinline__ void finish4096(f32x2 (&a)[64], f32x2 (&w)[64], const float2* __restrict__ tw64, float* __restrict__ plane, const uint32_t l)
+{
+    static_assert(G % 8 == 0 && H % G == 0 && H >= G && 64 % G == 0 && D >= 1, "whole groups of eight rows; the first group comes from the caller");
     // ---- twiddle W4096^(n2 k1), then the transpose (lane n2, register k1) -> (lane k1, register n2), one plane at a time
 #pragma unroll
     for (int g = 0; g < 64; g += G) {
         __builtin_amdgcn_sched_barrier(0);
-        float2 w[G];
+        // (group g / G is multiplied in this round: every group up to D behind it is in flight or here)
 #pragma unroll
-        for (int u = 0; u < G; ++u) w[u] = tw4096[(l * (uint32_t)xpos(g + u)) & (kFftBins - 1)];   // (cos, -sin); register i holds k1 = xpos(i)
+        for (int n = g + G; n <= g + G * D && n < 64; n += G)
+            if (n >= H && (g == 0 || n == g + G * D)) load_tw(w, tw64, n, G, l);              // (issued in exactly one round: the first that reaches it)
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int u = 0; u < G; ++u) {
+        for (int u = 0; u < G; ++u) {                              // (cos, -sin); register i holds k1 = xpos(i); register 0's factor is (1, -0), multiplied like the rest
             const f32x2 v = a[g + u];
-            a[g + u] = (f32x2){v.x * w[u].x - v.y * w[u].y, v.x * w[u].y + v.y * w[u].x};
+            a[g + u] = (f32x2){v.x * w[g + u].x - v.y * w[g + u].y, v.x * w[g + u].y + v.y * w[g + u].x};
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -162,12 +182,15 @@ __device__ __forceinline__ void wave_argmax(float& v, int& idx)
 }  // namespace specwave
 
 constexpr uint32_t kSpecWaveLds = 64 * 65 * 4;                      // the transpose plane
+// spectrum_wave_body's twiddle schedule (finish4096): rows per group, rows in front of pass 1, groups of look-ahead.  32 rows wait behind pass 1, the
+// other 32 go out in front of the first products: 96 registers of factors at the most beside the 128 of a[] (k_step_cu<174,4,139>: 249 of 256)
+constexpr int kTwG = 16, kTwH = 32, kTwD = 2;
 
 // x: the stream's 4096 input samples (wave-uniform pointer) -- its row of the spectrum input collection, or, where one call's chunk alone fills the
 // buffer, the head of that chunk where the last decimation stage left it (StreamCall::fft_run == 2: no second copy of the samples)
 // spec, power: both given or both null -- null: nothing but the statistics is stored (a batch-mode tail; the engine runs this body again over the kept
 // inputs when a getter asks, k_spectrum_wave).  stats: null where the statistics have been delivered already (that second run).
-__device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x, const float2* __restrict__ tw4096, float2* __restrict__ spec,
+__device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x, const float2* __restrict__ tw64, float2* __restrict__ spec,
                                                    float* __restrict__ power, SpectrumStatsDev* __restrict__ stats, const uint32_t s, const double rate,
                                                    const int bins_sep, float* __restrict__ plane, const uint32_t seq)
 {
@@ -180,15 +203,18 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
     for (int g = 0; g < 64; g += 8) {
         const float2* xg = x + 64 * g;
         asm volatile("" : "+s"(xg));
+        const specwave::gptr_t xg1 = (specwave::gptr_t)xg;          // (device memory on every route; a flat load would make every later wait a wait for all loads)
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { const float2 v = xg[64 * u + l]; a[g + u] = (f32x2){v.x, v.y}; }
+        for (int u = 0; u < 8; ++u) a[g + u] = xg1[64 * u + l];
     }
+    // (the first twiddle rows go out in front of pass 1; all 64 there would need another 128 registers)
+    f32x2 w[64];
+    specwave::load_tw(w, tw64, 0, kTwH, l);
     specwave::fft64(a);
     // ---- twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
-    // (sixteen factors at a time: all 63 gathers hoisted in front of pass 1 would need another 126 registers)
-    specwave::finish4096<16>(a, tw4096, plane, l);
+    specwave::finish4096<kTwG, kTwH, kTwD>(a, w, tw64, plane, l);
     // ---- half swap, dB power, statistics.  Bin k = l + 64 k2 lands at i = (k + 2048) & 4095 = l + 64 j, j = (k2 + 32) & 63.
-    int mybad = 0;
+    const double rinv = 1.0 / rate;                                 // (wave-uniform: the bins multiply, specwave::spec_div)
     double lsum = 0.0;
     // P[l + 64 j] replaces the real part of the bin it was computed from (register xpos((j + 32) & 63)): no second array beside a[]
 #define HD_SW_P(j_) a[specwave::xpos(((j_) + 32) & 63)].x
@@ -204,14 +230,31 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
 #pragma unroll
             for (int u = 0; u < 8; ++u) { const f32x2 v = a[specwave::xpos((g + u + 32) & 63)]; sg[l + 64 * u] = make_float2(v.x, v.y); }
         }
+        // q / rate through double as a product wherever that is the same float (spec_div); the division itself sits behind a branch the wave skips
+        // when no lane needs it -- about one bin in 2^26, and streams whose power leaves the normal floats
+        float r[8];
+        bool slow = false;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const f32x2 v = a[specwave::xpos((g + u + 32) & 63)];
             float q = (v.x * v.x + v.y * v.y) / (float)kFftBins;
             q = q * q;
-            q = (float)((double)q / rate);
-            q = 10.0f * log10f(q);
-            if (v.x != v.x || v.y != v.y || isinf(v.x) || isinf(v.y) || q != q || isinf(q)) mybad = 1;
+            const double t = (double)q * rinv;
+            slow |= !specwave::spec_div_fast_ok(t);
+            r[u] = (float)t;
+        }
+        if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const f32x2 v = a[specwave::xpos((g + u + 32) & 63)];
+                float q = (v.x * v.x + v.y * v.y) / (float)kFftBins;
+                q = q * q;
+                r[u] = specwave::spec_div(q, rate, rinv);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float q = 10.0f * log10f(r[u]);
             HD_SW_P(g + u) = q;
             lsum += (double)q;
         }
@@ -222,8 +265,11 @@ __device__ __forceinline__ void spectrum_wave_body(const float2* __restrict__ x,
             for (int u = 0; u < 8; ++u) pg[l + 64 * u] = HD_SW_P(g + u);
         }
     }
-    const bool bad = __builtin_amdgcn_ballot_w64(mybad != 0) != 0ull;
-    const double mean = specwave::wave_sum(lsum) / (double)kFftBins;
+    // (valid from the sum: a non-finite sample, a zero bin (-Inf dB) or an overflowing one makes its P non-finite and with it the sum; 4096 finite floats
+    // cannot overflow a double, so the sum is non-finite exactly when a term is)
+    const double total = specwave::wave_sum(lsum);
+    const bool bad = !isfinite(total);
+    const double mean = total / (double)kFftBins;
     double lvar = 0.0;
     float bv = -__builtin_huge_valf();
     int bi = kFftBins;

@@ -20,8 +20,8 @@ inline uint32_t survey_run_len(uint64_t n_seg, uint32_t runs_per_launch)
 }
 
 // One wave per run: run b of the launch sums segments [seg0 + b run_len, min(seg0 + (b + 1) run_len, n_seg)) of the push at x into partial[b][4096]
-// (fftshifted).  win[4096]: the window; tw4096[m] = (cos, -sin)(2 pi m / 4096).  Every block must own at least one segment.
-void launch_survey(hipStream_t st, uint32_t n_runs, const float2* x, const float* win, const float2* tw4096, float* partial, uint64_t seg0, uint64_t n_seg,
+// (fftshifted).  win[4096]: the window; tw64: the lane-major twiddle table (spectrum_math.h: fft_twiddles).  Every block must own at least one segment.
+void launch_survey(hipStream_t st, uint32_t n_runs, const float2* x, const float* win, const float2* tw64, float* partial, uint64_t seg0, uint64_t n_seg,
                    uint32_t run_len);
 // acc[i] += partial[0][i], then partial[1][i], ... partial[n_runs - 1][i], in double, one thread per bin
 void launch_survey_reduce(hipStream_t st, const float* partial, uint32_t n_runs, double* acc);

@@ -18,8 +18,11 @@ namespace hd {
 
 static_assert(kSurveyBins == (uint32_t)kFftBins, "the survey uses the engine's 4096-point transform and twiddles");
 
+// k_survey's own twiddle schedule (finish4096): with one wave per SIMD nothing else hides a load, and the register file has the room
+constexpr int kSvTwG = 16, kSvTwH = 32, kSvTwD = 2;
+
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_survey(const float2* __restrict__ x, const float* __restrict__ win,
-                                                                                          const float2* __restrict__ tw4096, float* __restrict__ partial,
+                                                                                          const float2* __restrict__ tw64, float* __restrict__ partial,
                                                                                           const uint64_t seg0, const uint64_t n_seg, const uint32_t run_len)
 {
     __shared__ float plane[64 * 65];
@@ -48,8 +51,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 #pragma unroll
             for (int u = 0; u < 16; ++u) a[g + u] = (f32x2){a[g + u].x * wv[u], a[g + u].y * wv[u]};
         }
+        f32x2 w[64];
+        specwave::load_tw(w, tw64, 0, kSvTwH, l);                    // (the first twiddle rows, in front of pass 1)
         specwave::fft64(a);
-        specwave::finish4096<8>(a, tw4096, plane, l);                // twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
+        specwave::finish4096<kSvTwG, kSvTwH, kSvTwD>(a, w, tw64, plane, l);                // twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
 #pragma unroll
         for (int i = 0; i < 64; ++i) acc[i] = acc[i] + (a[i].x * a[i].x + a[i].y * a[i].y);
     }
@@ -83,10 +88,10 @@ __global__ __launch_bounds__(256) void k_survey_reduce(const float* __restrict__
     acc[i] = v;
 }
 
-void launch_survey(hipStream_t st, uint32_t n_runs, const float2* x, const float* win, const float2* tw4096, float* partial, uint64_t seg0, uint64_t n_seg,
+void launch_survey(hipStream_t st, uint32_t n_runs, const float2* x, const float* win, const float2* tw64, float* partial, uint64_t seg0, uint64_t n_seg,
                    uint32_t run_len)
 {
-    hipLaunchKernelGGL(k_survey, dim3(n_runs), dim3(64), 0, st, x, win, tw4096, partial, seg0, n_seg, run_len);
+    hipLaunchKernelGGL(k_survey, dim3(n_runs), dim3(64), 0, st, x, win, tw64, partial, seg0, n_seg, run_len);
 }
 
 void launch_survey_reduce(hipStream_t st, const float* partial, uint32_t n_runs, double* acc)
