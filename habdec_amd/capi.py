@@ -49,6 +49,17 @@ class hd_survey_candidate(C.Structure):
     _fields_ = [("offset_hz", C.c_double), ("snr_db", C.c_double), ("width_hz", C.c_double), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32)]
 
 
+# IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
+IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
+IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
+IQ_NAMES = {"cf32": IQ_CF32, "cs16": IQ_CS16, "cs8": IQ_CS8, "cu8": IQ_CU8}
+
+
+def iq_fmt(fmt) -> int:
+    """'cs16' / 'cs8' / 'cu8' / 'cf32' or an HD_IQ_* number -> the number (unknown numbers pass through: the library refuses them)."""
+    return IQ_NAMES[fmt] if isinstance(fmt, str) else int(fmt)
+
+
 SENTENCE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p)
 MATCH_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int)
 CHARS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.POINTER(C.c_char), C.c_size_t)
@@ -86,6 +97,8 @@ ENGINE_API = {
     "hd_set_chars_callback": (None, [_vp, CHARS_CB, _vp]),
     "hd_process_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
     "hd_process_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_process_host_fmt": (_int, [_vp, _int, _vp, _sz, _vp, _u32]),
+    "hd_process_device_fmt": (_int, [_vp, _int, _vp, _sz, _vp, _u32]),
     "hd_flush": (_int, [_vp]),
     "hd_ingest_run": (_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "hd_stream_rtty": (_sz, [_vp, _u32, C.c_char_p, _sz]),
@@ -116,6 +129,8 @@ ENGINE_API = {
     "hd_survey_reset": (_int, [_vp]),
     "hd_survey_push_device": (_int, [_vp, _vp, C.c_uint64]),
     "hd_survey_push_host": (_int, [_vp, _vp, C.c_uint64]),
+    "hd_survey_push_host_fmt": (_int, [_vp, _int, _vp, C.c_uint64]),
+    "hd_survey_push_device_fmt": (_int, [_vp, _int, _vp, C.c_uint64]),
     "hd_survey_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
     "hd_survey_params_default": (None, [C.POINTER(hd_survey_params)]),
     "hd_survey_detect": (_int, [_vp, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
@@ -163,6 +178,10 @@ HOST_API = {
     "hd_host_iqfiles_count": (C.c_uint64, [_vp, C.c_uint32]),
     "hd_host_iqfiles_rewinds": (C.c_uint64, [_vp, C.c_uint32]),
     "hd_host_iqfiles_next": (C.c_uint32, [_vp, _f32p, _sz, C.POINTER(C.c_uint32)]),
+    "hd_host_iqfiles_open_fmt": (_vp, [C.POINTER(C.c_char_p), C.c_uint32, _int, C.c_uint32, C.c_uint32, _dbl, _int]),
+    "hd_host_iqfiles_next_raw": (C.c_uint32, [_vp, _vp, _sz, C.POINTER(C.c_uint32)]),
+    "hd_host_iq_bytes": (_sz, [_int]),
+    "hd_host_iq_convert": (None, [_int, _vp, _sz, _f32p]),
     "hd_host_tune_step": (_int, [_dbl, _dbl, C.POINTER(C.c_uint32)]),
     "hd_host_tune_tables": (None, [_f32p, _f32p]),
     "hd_host_tune_rotate": (None, [_f32p, _sz, C.c_uint32, C.c_uint32, _f32p]),

@@ -28,6 +28,7 @@
 #include "host/afc_tracker.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
+#include "host/iq_convert.hpp"
 #include "host/iq_file_batch.hpp"
 #include "host/survey.hpp"
 #include "host/text_stage.hpp"
@@ -198,6 +199,13 @@ struct hd_engine {
     hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_staging_free[2] = {nullptr, nullptr};
     bool staging_used[2] = {false, false};
     uint64_t host_calls = 0, host_calls_in_place = 0;   // hd_process_host calls through the staging slabs / served in place from page-locked memory
+    // hd_process_*_fmt: a packed call is unpacked into the staging slab of its turn (kernels/iq_unpack.hip) and goes on as a cf32 call on that slab -- on
+    // qh, or on a synchronous engine's own queue where there is nothing to copy.  packed[j]: where the packed bytes of a pageable (or batch-mode) host
+    // buffer land first, [S][max_chunk] samples of the widest format seen so far, allocated on first use; unpack_n: the call's per-stream counts for the
+    // kernel (one array: the unpack that read it is done when its call returns).
+    unsigned char* packed[2] = {nullptr, nullptr};
+    size_t packed_bytes[2] = {0, 0};
+    DevBuf<uint32_t> unpack_n;
     uint32_t timing_every = 8;   // HIP-event timing on every Nth call (0 = off): each event record is a barrier packet worth ~6 us of queue time
     hd_timing last_timing{};
     // Fast mode, long low-pass filters (>= kLpFftMinTaps taps: configs[4]'s 4097): the filter as transforms (kernels/fir_demod.hip: k_lp_gather / k_lp_mul around
@@ -269,6 +277,7 @@ struct hd_engine {
         if (qb && qb != qa) (void)hipStreamDestroy(qb);
         if (qc && qc != qa) (void)hipStreamDestroy(qc);
         if (qh) (void)hipStreamDestroy(qh);
+        for (unsigned char* pk : packed) if (pk) (void)hipFree(pk);
         for (hipEvent_t ev : {ev_copy[0], ev_copy[1], ev_staging_free[0], ev_staging_free[1]}) if (ev) (void)hipEventDestroy(ev);
     }
 };
@@ -1452,6 +1461,22 @@ void commit_call(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, const
     ++e->calls;
 }
 
+// The sizes hd_process_device accepts: checked before anything is enqueued
+int check_sizes(const hd_engine* e, const uint32_t* n_per_stream, uint32_t n_uniform)
+{
+    const size_t nst = e->stages.size();
+    const uint32_t T1 = nst > 0 ? (uint32_t)e->stages[0].taps.size() : 0, T2 = nst > 1 ? (uint32_t)e->stages[1].taps.size() : 0;
+    const uint32_t R1 = nst > 0 ? e->stages[0].ratio : 1;
+    for (uint32_t s = 0; s < e->S; ++s) {
+        const uint32_t n = n_per_stream ? n_per_stream[s] : n_uniform;
+        if (n > e->cfg.max_chunk) return fail(HD_ERR_CAPACITY, "more samples than max_chunk");
+        if (n % e->D) return fail(HD_ERR_INVALID, "sample count must be a multiple of the decimation factor (queue the remainder)");
+        if (n && nst > 0 && n + 1 < T1) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the first stage's history (undefined in the reference)");
+        if (n && nst > 1 && n / R1 + 1 < T2) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the second stage's history (undefined in the reference)");
+    }
+    return HD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1477,18 +1502,9 @@ int hd_process_device(hd_engine* e, const void* d_iq, size_t stride, const uint3
     if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + "): no new calls are accepted -- destroy the engine");
     const auto h0 = std::chrono::steady_clock::now();
     HD_HIP(hipSetDevice(e->cfg.device));
-    const size_t nst = e->stages.size();
-    const uint32_t T1 = nst > 0 ? (uint32_t)e->stages[0].taps.size() : 0, T2 = nst > 1 ? (uint32_t)e->stages[1].taps.size() : 0;
-    const uint32_t R1 = nst > 0 ? e->stages[0].ratio : 1;
 
     // ---- validate first: a call refused before anything is enqueued leaves every stream, e->calls and the buffer rotations as they were
-    for (uint32_t s = 0; s < e->S; ++s) {
-        const uint32_t n = n_per_stream ? n_per_stream[s] : n_uniform;
-        if (n > e->cfg.max_chunk) return fail(HD_ERR_CAPACITY, "more samples than max_chunk");
-        if (n % e->D) return fail(HD_ERR_INVALID, "sample count must be a multiple of the decimation factor (queue the remainder)");
-        if (n && nst > 0 && n + 1 < T1) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the first stage's history (undefined in the reference)");
-        if (n && nst > 1 && n / R1 + 1 < T2) return fail(HD_ERR_UNSUPPORTED, "chunk shorter than the second stage's history (undefined in the reference)");
-    }
+    if (const int rc = check_sizes(e, n_per_stream, n_uniform)) return rc;
     // ---- every drain ahead of planning (collect() writes the mirror): a free slot -- cannot be wanting with depth <= 3, but never reuse a slot in
     // flight --, then the tables: control-plane changes (new low-pass design, new symbol parameters) rewrite device tables the previous call's back half
     // may still be reading.  Rare.
@@ -1592,6 +1608,121 @@ int hd_process_host(hd_engine* e, const float* iq, size_t stride, const uint32_t
     return rc;
 }
 
+}  // extern "C"
+
+namespace {
+
+// hd_process_host_fmt / hd_process_device_fmt of a packed format: the packed rows -- the caller's device buffer, the caller's page-locked mapped buffer
+// (synchronous engine) or the packed slab a host buffer was copied into -- are unpacked on qh into the staging slab of this call's turn, and the
+// call goes on as hd_process_host's does behind its copy: hd_process_device on the slab.
+int process_packed(hd_engine* e, int fmt, const void* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n_uniform, bool device)
+{
+    if (!e) return fail(HD_ERR_INVALID, "null engine");
+    const size_t bps = hd::iq_bytes(fmt);
+    if (!bps || fmt == HD_IQ_CF32) return fail(HD_ERR_INVALID, "unknown IQ format (HD_IQ_CF32, HD_IQ_CS16, HD_IQ_CS8, HD_IQ_CU8)");
+    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(HD_ERR_INVALID, "packed IQ base must be aligned to one sample (4 bytes cs16, 2 bytes cs8 / cu8)");
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);   // (recursive: hd_process_device below takes it again)
+    if (e->in_callback) return fail(HD_ERR_INVALID, "hd_process_* cannot be called from a sentence / character callback");
+    if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + "): no new calls are accepted -- destroy the engine");
+    HD_HIP(hipSetDevice(e->cfg.device));
+    // everything hd_process_device would refuse the sizes for is refused here, before anything is queued
+    if (const int rc = check_sizes(e, n_per_stream, n_uniform)) return rc;
+    const uint32_t S = e->S;
+    const size_t dstride = e->cfg.max_chunk;
+    uint32_t n_max = n_uniform;
+    if (n_per_stream) { n_max = 0; for (uint32_t s = 0; s < S; ++s) n_max = std::max(n_max, n_per_stream[s]); }
+    const int j = (int)(e->host_calls & 1u);
+    if (j == 1 && !e->staging2.p) {
+        HD_HIP(e->staging2.alloc((size_t)S * e->cfg.max_chunk));
+        HD_HIP(hipDeviceSynchronize());      // the allocation's memset runs on the null stream: it must not trail the unpack below
+    }
+    if (!e->unpack_n.p) { HD_HIP(e->unpack_n.alloc(S)); HD_HIP(hipDeviceSynchronize()); }
+    float2* dst = j ? e->staging2.p : e->staging.p;
+    const void* src = iq;
+    size_t sstride = stride;
+    bool in_place = device;
+    if (!device && !e->cfg.pipeline) {       // synchronous engine, page-locked mapped memory: the unpack reads the caller's buffer in place over PCIe
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, iq) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) {
+            src = at.devicePointer;
+            in_place = true;
+            ++e->host_calls_in_place;
+        } else {
+            (void)hipGetLastError();         // (an ordinary pointer: the query's error is not the call's)
+        }
+    }
+    // Synchronous engine with nothing to copy: its one queue is idle between calls and the call is done when it returns, so the unpack goes straight in
+    // front of stage 1 on that queue -- no event between two queues (~18 us) and no host wait for it.  Everything else: the copy queue, as hd_process_host.
+    const bool direct = in_place && !e->cfg.pipeline;
+    if (!direct && !e->qh) HD_HIP(hipStreamCreateWithFlags(&e->qh, hipStreamNonBlocking));   // (created on first use: see hd_process_host)
+    hipStream_t q = direct ? e->qa : e->qh;
+    if (e->staging_used[j] && !direct) HD_HIP(hipStreamWaitEvent(q, e->ev_staging_free[j], 0));    // the call that read this slab two calls ago is past its stage 1
+    if (!in_place) {
+        // the packed bytes into the packed slab of this turn, in the three shapes of hd_process_host's copy
+        const size_t need = (size_t)S * dstride * bps;
+        if (e->packed_bytes[j] < need) {
+            HD_HIP(hipStreamSynchronize(q));          // (a wider format than the slab was made for: nothing may still read the old one)
+            if (e->packed[j]) { (void)hipFree(e->packed[j]); e->packed[j] = nullptr; e->packed_bytes[j] = 0; }
+            HD_HIP(hipMalloc(reinterpret_cast<void**>(&e->packed[j]), need));
+            e->packed_bytes[j] = need;
+        }
+        unsigned char* pk = e->packed[j];
+        const unsigned char* h = static_cast<const unsigned char*>(iq);
+        if (!stride) {
+            if (n_max) HD_HIP(hipMemcpyAsync(pk, h, (size_t)n_max * bps, hipMemcpyHostToDevice, q));
+        } else if (!n_per_stream) {
+            if (n_uniform) HD_HIP(hipMemcpy2DAsync(pk, dstride * bps, h, stride * bps, (size_t)n_uniform * bps, S, hipMemcpyHostToDevice, q));
+        } else {
+            for (uint32_t s = 0; s < S; ++s) {
+                const uint32_t n = n_per_stream[s];
+                if (n) HD_HIP(hipMemcpyAsync(pk + (size_t)s * dstride * bps, h + (size_t)s * stride * bps, (size_t)n * bps, hipMemcpyHostToDevice, q));
+            }
+        }
+        src = pk;
+        sstride = stride ? dstride : 0;
+    }
+    if (!stride) {
+        // one shared row: converted once, and the streams read it with stride 0
+        if (!hd::launch_iq_unpack(q, fmt, 1, n_max, src, 0, nullptr, n_max, dst, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
+    } else {
+        const uint32_t* d_n = nullptr;
+        if (n_per_stream) {
+            HD_HIP(hipMemcpyAsync(e->unpack_n.p, n_per_stream, (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+            d_n = e->unpack_n.p;
+        }
+        if (!hd::launch_iq_unpack(q, fmt, S, n_max, src, sstride, d_n, n_uniform, dst, dstride)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
+    }
+    HD_HIP(hipGetLastError());
+    if (!direct) {
+        HD_HIP(hipEventRecord(e->ev_copy[j], q));
+        HD_HIP(hipStreamWaitEvent(e->qa, e->ev_copy[j], 0));
+        HD_HIP(hipEventSynchronize(e->ev_copy[j]));      // from here on the caller's buffer (and n_per_stream) is theirs again
+    }
+    const int rc = hd_process_device(e, dst, stride ? dstride : 0, n_per_stream, n_uniform);
+    if (direct && rc) (void)hipStreamSynchronize(q);     // (a call refused behind the unpack: the caller's buffer is theirs again only when the unpack has read it)
+    HD_HIP(hipEventRecord(e->ev_staging_free[j], e->qa));
+    e->staging_used[j] = true;
+    ++e->host_calls;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hd_process_host_fmt(hd_engine* e, int fmt, const void* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n_uniform)
+{
+    if (fmt == HD_IQ_CF32) return hd_process_host(e, static_cast<const float*>(iq), stride, n_per_stream, n_uniform);
+    return process_packed(e, fmt, iq, stride, n_per_stream, n_uniform, false);
+}
+
+int hd_process_device_fmt(hd_engine* e, int fmt, const void* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n_uniform)
+{
+    if (fmt == HD_IQ_CF32) return hd_process_device(e, d_iq, stride, n_per_stream, n_uniform);
+    return process_packed(e, fmt, d_iq, stride, n_per_stream, n_uniform, true);
+}
+
 /* ---------------------------------------------------------------- batched file ingest -------------------------- */
 
 int hd_ingest_run(hd_engine* e, hd_host_iqfiles* src, uint64_t max_rounds, uint64_t* samples_done)
@@ -1604,11 +1735,12 @@ int hd_ingest_run(hd_engine* e, hd_host_iqfiles* src, uint64_t max_rounds, uint6
     HD_HIP(hipSetDevice(e->cfg.device));
     constexpr int kSlabs = 4;      // round r's slab is refilled for round r+4: by then call r is delivered even with two calls in flight
     const size_t stride = src->batch.chunk();
-    struct Slab { float* iq = nullptr; std::vector<uint32_t> n; uint32_t alive = 0; };
+    const int fmt = src->batch.fmt();                  // a packed batch keeps its slabs packed: hd_process_host_fmt unpacks them on the GPU
+    struct Slab { void* iq = nullptr; std::vector<uint32_t> n; uint32_t alive = 0; };
     Slab slab[kSlabs];
     auto release = [&] { for (auto& b : slab) if (b.iq) (void)hipHostFree(b.iq); };
     for (auto& b : slab) {
-        if (hipHostMalloc(reinterpret_cast<void**>(&b.iq), (size_t)S * stride * sizeof(float2), hipHostMallocDefault) != hipSuccess) {
+        if (hipHostMalloc(&b.iq, (size_t)S * stride * src->batch.bytes_per_sample(), hipHostMallocDefault) != hipSuccess) {
             release();
             return fail(HD_ERR_DEVICE, "pinned slab allocation failed");
         }
@@ -1628,7 +1760,7 @@ int hd_ingest_run(hd_engine* e, hd_host_iqfiles* src, uint64_t max_rounds, uint6
                 if (stop) return;
             }
             Slab& b = slab[r % kSlabs];
-            b.alive = src->batch.next(b.iq, stride, b.n.data());
+            b.alive = src->batch.next_raw(b.iq, stride, b.n.data());
             {
                 std::lock_guard<std::mutex> l(m);
                 filled = r + 1;
@@ -1654,7 +1786,7 @@ int hd_ingest_run(hd_engine* e, hd_host_iqfiles* src, uint64_t max_rounds, uint6
         }
         bool uniform = true;
         for (uint32_t s = 1; s < S; ++s) uniform = uniform && b.n[s] == b.n[0];
-        rc = hd_process_host(e, b.iq, stride, uniform ? nullptr : b.n.data(), uniform ? b.n[0] : 0);
+        rc = hd_process_host_fmt(e, fmt, b.iq, stride, uniform ? nullptr : b.n.data(), uniform ? b.n[0] : 0);
         if (rc) break;
         for (uint32_t s = 0; s < S; ++s) total += b.n[s];
         {
@@ -1884,13 +2016,14 @@ struct hd_survey {
     float* partial = nullptr;              // [runs_per_launch][4096] float rows of the launch in flight (launches of one queue run in order)
     double* acc = nullptr;                 // [4096], for the life of the survey
     float2* slab = nullptr;                // hd_survey_push_host: staging for kSlabSegs segments, allocated by the first host push
+    unsigned char* pslab = nullptr;        // hd_survey_push_host_fmt: the same segments packed (sized for cs16), in front of the unpack into `slab`
     double* h_acc = nullptr;               // page-locked landing place of the read-back
     double sum_w2 = 0;                     // sum of w^2, in double over the float table
     uint64_t segments = 0;
     static constexpr uint32_t kSlabSegs = 256;   // whole segments one staging copy carries ((256 + 1) hops = 4 MiB + 16 KiB)
     ~hd_survey()
     {
-        for (void* p : {(void*)own_tw, (void*)win, (void*)partial, (void*)acc, (void*)slab}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)own_tw, (void*)win, (void*)partial, (void*)acc, (void*)slab, (void*)pslab}) if (p) (void)hipFree(p);
         if (h_acc) (void)hipHostFree(h_acc);
         if (q) (void)hipStreamDestroy(q);
     }
@@ -2027,6 +2160,68 @@ int hd_survey_push_host(hd_survey* sv, const float* iq, uint64_t n)
     return HD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// A packed push, host or device: the slab loop of hd_survey_push_host with an unpack in front of every slab's launches.
+int survey_push_packed(hd_survey* sv, int fmt, const void* iq, uint64_t n, bool device)
+{
+    if (!sv) return fail(HD_ERR_INVALID, "null survey");
+    const size_t bps = hd::iq_bytes(fmt);
+    if (!bps || fmt == HD_IQ_CF32) return fail(HD_ERR_INVALID, "unknown IQ format (HD_IQ_CF32, HD_IQ_CS16, HD_IQ_CS8, HD_IQ_CU8)");
+    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(HD_ERR_INVALID, "packed IQ base must be aligned to one sample (4 bytes cs16, 2 bytes cs8 / cu8)");
+    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
+    if (const int rc = survey_enter(sv)) return rc;
+    const uint64_t n_seg = hd::survey_segments(n);
+    if (!n_seg) return HD_OK;
+    if (device) {   // what the kernel reads must be memory the GPU can address
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, iq) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
+                                                               !(at.type == hipMemoryTypeHost && at.devicePointer))) {
+            (void)hipGetLastError();
+            return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_survey_push_host_fmt takes host memory)");
+        }
+    }
+    const size_t slab_samples = (size_t)(hd_survey::kSlabSegs + 1) * hd::kSurveyHop;
+    if (!sv->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->slab), slab_samples * sizeof(float2)));
+    if (!device && !sv->pslab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->pslab), slab_samples * 4u));
+    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);     // the whole push's run length; a slab carries whole runs (hd_survey_push_host)
+    const uint64_t per_slab = (uint64_t)(hd_survey::kSlabSegs / r) * r;
+    const unsigned char* p = static_cast<const unsigned char*>(iq);
+    for (uint64_t s = 0; s < n_seg; s += per_slab) {
+        const uint64_t s1 = std::min(n_seg, s + per_slab);
+        const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
+        const unsigned char* from = p + (size_t)s * hd::kSurveyHop * bps;
+        if (!device) {
+            HD_HIP(hipMemcpyAsync(sv->pslab, from, samples * bps, hipMemcpyHostToDevice, sv->q));
+            from = sv->pslab;
+        }
+        if (!hd::launch_iq_unpack(sv->q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, sv->slab, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
+        if (const int rc = survey_enqueue(sv, sv->slab, s, s, s1, r)) return rc;
+    }
+    HD_HIP(hipStreamSynchronize(sv->q));   // from here on the caller's buffer is theirs again
+    sv->segments += n_seg;
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hd_survey_push_host_fmt(hd_survey* sv, int fmt, const void* iq, uint64_t n)
+{
+    if (fmt == HD_IQ_CF32) return hd_survey_push_host(sv, static_cast<const float*>(iq), n);
+    return survey_push_packed(sv, fmt, iq, n, false);
+}
+
+int hd_survey_push_device_fmt(hd_survey* sv, int fmt, const void* d_iq, uint64_t n)
+{
+    if (fmt == HD_IQ_CF32) return hd_survey_push_device(sv, d_iq, n);
+    return survey_push_packed(sv, fmt, d_iq, n, true);
+}
+
 int hd_survey_power(hd_survey* sv, double* p, size_t cap, uint64_t* segments)
 {
     if (!sv) return fail(HD_ERR_INVALID, "null survey");
@@ -2058,6 +2253,31 @@ int hd_debug_survey_push_timed(hd_survey* sv, const void* d_iq, uint64_t n, floa
     HD_HIP(hipEventElapsedTime(ms, t0, t1));
     (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     return rc;
+}
+
+// Measurement and test hook (tools/micro/iq_format_rate.py, tests/test_gpu_iq_formats.py; not part of the ABI): one unpack launch straight into a buffer
+// of the caller's, between two HIP events on the host-copy queue -- row r reads d_n[r] (a device array; null: n_uniform) samples at
+// d_src + r * src_stride * bps and writes them at d_dst + r * dst_stride.  With fmt = HD_IQ_CF32: a device-to-device copy of rows * n_uniform * 8 bytes.
+int hd_debug_iq_unpack_timed(hd_engine* e, int fmt, const void* d_src, size_t src_stride, const uint32_t* d_n, uint32_t n_uniform, uint32_t max_n,
+                             uint32_t rows, void* d_dst, size_t dst_stride, float* ms)
+{
+    if (!e || !d_src || !d_dst || !ms) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    HD_HIP(hipSetDevice(e->cfg.device));
+    if (!e->qh) HD_HIP(hipStreamCreateWithFlags(&e->qh, hipStreamNonBlocking));
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    HD_HIP(hipEventCreate(&t0));
+    HD_HIP(hipEventCreate(&t1));
+    HD_HIP(hipEventRecord(t0, e->qh));
+    bool ok = true;
+    if (fmt == HD_IQ_CF32) HD_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)rows * n_uniform * sizeof(float2), hipMemcpyDeviceToDevice, e->qh));
+    else ok = hd::launch_iq_unpack(e->qh, fmt, rows, max_n, d_src, src_stride, d_n, n_uniform, static_cast<float2*>(d_dst), dst_stride);
+    HD_HIP(hipEventRecord(t1, e->qh));
+    HD_HIP(hipEventSynchronize(t1));
+    HD_HIP(hipEventElapsedTime(ms, t0, t1));
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    HD_HIP(hipGetLastError());
+    return ok ? HD_OK : fail(HD_ERR_INVALID, "unknown IQ format");
 }
 
 void hd_survey_params_default(hd_survey_params* p) { if (p) hd::survey_params_default(p); }

@@ -228,11 +228,15 @@ size_t hd_host_json_number(double v, char* buf, size_t cap)
 /* ---- batched cf32 file ingest (IQSource_File.h:124-172 per file; see host/iq_file_batch.hpp) ---- */
 hd_host_iqfiles* hd_host_iqfiles_open(const char* const* paths, uint32_t n_files, int loop, uint32_t chunk, uint32_t granule, double realtime_rate)
 {
-    if (!paths || !n_files) return nullptr;
+    return hd_host_iqfiles_open_fmt(paths, n_files, loop, chunk, granule, realtime_rate, HD_IQ_CF32);
+}
+hd_host_iqfiles* hd_host_iqfiles_open_fmt(const char* const* paths, uint32_t n_files, int loop, uint32_t chunk, uint32_t granule, double realtime_rate, int fmt)
+{
+    if (!paths || !n_files || !hd::iq_bytes(fmt)) return nullptr;
     std::vector<std::string> v;
     for (uint32_t i = 0; i < n_files; ++i) { if (!paths[i]) return nullptr; v.emplace_back(paths[i]); }
     auto* h = new hd_host_iqfiles;
-    if (!h->batch.open(v, loop != 0, chunk, granule, realtime_rate)) { delete h; return nullptr; }
+    if (!h->batch.open(v, loop != 0, chunk, granule, realtime_rate, fmt)) { delete h; return nullptr; }
     return h;
 }
 void hd_host_iqfiles_close(hd_host_iqfiles* h) { delete h; }
@@ -244,6 +248,13 @@ uint32_t hd_host_iqfiles_next(hd_host_iqfiles* h, float* slab, size_t stride, ui
     if (!h || !slab || !n_per_stream || stride < h->batch.chunk()) return 0;
     return h->batch.next(slab, stride, n_per_stream);
 }
+uint32_t hd_host_iqfiles_next_raw(hd_host_iqfiles* h, void* slab, size_t stride, uint32_t* n_per_stream)
+{
+    if (!h || !slab || !n_per_stream || stride < h->batch.chunk()) return 0;
+    return h->batch.next_raw(slab, stride, n_per_stream);
+}
+size_t hd_host_iq_bytes(int fmt) { return hd::iq_bytes(fmt); }
+void hd_host_iq_convert(int fmt, const void* src, size_t n, float* out) { if (src && out) hd::iq_convert(fmt, src, n, out); }
 
 /* ---- per-stream tuning (kernels/tune.h) ---- */
 int hd_host_tune_step(double offset_hz, double decimated_rate, uint32_t* step)

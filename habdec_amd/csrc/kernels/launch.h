@@ -71,6 +71,12 @@ void launch_spectrum_wave(hipStream_t st, uint32_t n_streams, const float2* fft_
                           const float2* chunk = nullptr /* the low-pass input buffers [S][chunk_stride]: streams with StreamCall::fft_run == 2 take their 4096 samples from the head of this call's decimated chunk */,
                           size_t chunk_stride = 0, uint32_t fir_hist_cap = 0);
 
+// Packed IQ -> cf32 (iq_unpack.hip), grid (tiles, rows): row r reads n_per_row[r] (a DEVICE array; null: n_uniform) samples of `fmt` (HD_IQ_CS16 / CS8 / CU8)
+// at src + r * src_stride * bytes-per-sample and writes them to dst + r * dst_stride; max_n = the largest count of the launch.  A shared row is
+// n_rows = 1 with both strides unused.  A cs16 row may start on any 4-byte boundary, a cs8 / cu8 row on any 2-byte boundary.  false: unknown fmt.
+bool launch_iq_unpack(hipStream_t st, int fmt, uint32_t n_rows, uint32_t max_n, const void* src, size_t src_stride, const uint32_t* n_per_row,
+                      uint32_t n_uniform, float2* dst, size_t dst_stride);
+
 // ---- launchers of the mode-dependent kernels, once per arithmetic mode (arith.h)
 namespace exact {
 #include "launch_decls.inc"

@@ -68,8 +68,23 @@ class Engine:
             pass
 
     # ---- data path
-    def process_host(self, iq: np.ndarray, n: int | None = None):
-        """iq: complex64 [S, stride]; stream s hands over its first n samples."""
+    def process_host(self, iq: np.ndarray, n: int | None = None, fmt=None):
+        """iq: complex64 [S, stride]; stream s hands over its first n samples.
+        Packed IQ (hd_process_host_fmt): an integer array [S, stride, 2] of dtype int16 / int8 / uint8 (cs16 / cs8 / cu8), or `fmt=` naming the format."""
+        iq = np.asarray(iq)
+        if fmt is None and iq.dtype in (np.int16, np.int8, np.uint8):
+            fmt = {np.dtype(np.int16): capi.IQ_CS16, np.dtype(np.int8): capi.IQ_CS8, np.dtype(np.uint8): capi.IQ_CU8}[iq.dtype]
+        if fmt is not None and capi.iq_fmt(fmt) != capi.IQ_CF32:
+            fmt = capi.iq_fmt(fmt)
+            if fmt in capi.IQ_DTYPES and iq.dtype != capi.IQ_DTYPES[fmt]:
+                raise HabdecError(f"IQ format {fmt} wants dtype {capi.IQ_DTYPES[fmt]}, not {iq.dtype}")
+            iq = np.ascontiguousarray(iq)
+            if iq.ndim == 2:
+                iq = iq[None, :, :]
+            assert iq.ndim == 3 and iq.shape[0] == self.S and iq.shape[2] == 2, iq.shape
+            n = iq.shape[1] if n is None else n
+            check(self.L.hd_process_host_fmt(self.h, fmt, iq.ctypes.data, iq.shape[1], None, n))
+            return
         iq = np.ascontiguousarray(iq, dtype=np.complex64)
         if iq.ndim == 1:
             iq = iq[None, :]
@@ -88,11 +103,15 @@ class Engine:
         self._pinned = getattr(self, "_pinned", []) + [p]
         return arr
 
-    def process_device(self, dev_ptr: int, stride: int, n: int):
+    def process_device(self, dev_ptr: int, stride: int, n: int, fmt=None):
+        """fmt: the samples at dev_ptr are packed (hd_process_device_fmt); stride and n count complex samples either way."""
+        if fmt is not None:
+            check(self.L.hd_process_device_fmt(self.h, capi.iq_fmt(fmt), dev_ptr, stride, None, n))
+            return
         check(self.L.hd_process_device(self.h, dev_ptr, stride, None, n))
 
     def ingest(self, files: "IqFiles", max_rounds: int = 1 << 62) -> int:
-        """Pump a batch of cf32 files (one per stream) through the engine (hd_ingest_run); returns the samples consumed."""
+        """Pump a batch of IQ files (one per stream; cf32, or packed when opened with fmt=) through the engine (hd_ingest_run); returns the samples consumed."""
         import ctypes as C
         done = C.c_uint64(0)
         check(self.L.hd_ingest_run(self.h, files.h, max_rounds, C.byref(done)))
@@ -255,11 +274,23 @@ class Survey:
         except Exception:
             pass
 
-    def push_device(self, dev_ptr: int, n: int):
-        """n cf32 samples at a device address; the buffer must stay valid until power() / detect() / reset() has returned."""
+    def push_device(self, dev_ptr: int, n: int, fmt=None):
+        """n cf32 samples at a device address; the buffer must stay valid until power() / detect() / reset() has returned.
+        fmt: n packed samples (hd_survey_push_device_fmt); the buffer is the caller's again on return."""
+        if fmt is not None:
+            check(self.L.hd_survey_push_device_fmt(self.h, capi.iq_fmt(fmt), dev_ptr, n))
+            return
         check(self.L.hd_survey_push_device(self.h, dev_ptr, n))
 
-    def push_host(self, iq: np.ndarray):
+    def push_host(self, iq: np.ndarray, fmt=None):
+        """fmt: iq is packed, an integer array [n, 2] (or flat, I then Q) of the format's dtype (hd_survey_push_host_fmt)."""
+        if fmt is not None and capi.iq_fmt(fmt) != capi.IQ_CF32:
+            fmt = capi.iq_fmt(fmt)
+            iq = np.ascontiguousarray(iq).reshape(-1)
+            if fmt in capi.IQ_DTYPES and iq.dtype != capi.IQ_DTYPES[fmt]:
+                raise HabdecError(f"IQ format {fmt} wants dtype {capi.IQ_DTYPES[fmt]}, not {iq.dtype}")
+            check(self.L.hd_survey_push_host_fmt(self.h, fmt, iq.ctypes.data, iq.size // 2))
+            return
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
         check(self.L.hd_survey_push_host(self.h, iq.ctypes.data, iq.size))
 
@@ -288,15 +319,16 @@ class Survey:
 
 
 class IqFiles:
-    """Batched cf32 file source (hd_host_iqfiles_*): one IQSource_File-like reader per stream, read in lock step."""
+    """Batched IQ file source (hd_host_iqfiles_*): one IQSource_File-like reader per stream, read in lock step; cf32 files, or packed ones with fmt=."""
 
-    def __init__(self, paths, chunk: int, granule: int, loop: bool = False, realtime_rate: float = 0.0):
+    def __init__(self, paths, chunk: int, granule: int, loop: bool = False, realtime_rate: float = 0.0, fmt=None):
         import ctypes as C
         self.L = lib()
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
-        self.h = self.L.hd_host_iqfiles_open(arr, len(paths), int(loop), chunk, granule, realtime_rate)
+        self.fmt = capi.IQ_CF32 if fmt is None else capi.iq_fmt(fmt)
+        self.h = self.L.hd_host_iqfiles_open_fmt(arr, len(paths), int(loop), chunk, granule, realtime_rate, self.fmt)
         if not self.h:
-            raise HabdecError("hd_host_iqfiles_open failed (missing file, chunk < granule, ...)")
+            raise HabdecError("hd_host_iqfiles_open failed (missing file, chunk < granule, unknown format, ...)")
         self.S, self.chunk = len(paths), chunk
 
     def close(self):
@@ -320,4 +352,13 @@ class IqFiles:
         slab = np.zeros((self.S, stride), np.complex64)
         n = np.zeros(self.S, np.uint32)
         alive = self.L.hd_host_iqfiles_next(self.h, slab.view(np.float32), stride, n.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return slab, n, int(alive)
+
+    def next_raw(self, stride: int | None = None):
+        """One round in the files' own bytes: (slab [S, stride, 2] of the format's dtype, n_per_stream, streams that read anything)."""
+        import ctypes as C
+        stride = stride or self.chunk
+        slab = np.zeros((self.S, stride, 2), capi.IQ_DTYPES[self.fmt])
+        n = np.zeros(self.S, np.uint32)
+        alive = self.L.hd_host_iqfiles_next_raw(self.h, slab.ctypes.data, stride, n.ctypes.data_as(C.POINTER(C.c_uint32)))
         return slab, n, int(alive)

@@ -191,6 +191,27 @@ void  hd_pinned_free(void* p);
 /* Same, but `d_iq` is DEVICE memory on the engine's GPU (HBM-resident batches; base 16-byte aligned,
  * stream_stride even). */
 int hd_process_device(hd_engine* e, const void* d_iq, size_t stream_stride, const uint32_t* n_per_stream, uint32_t n);
+/* ---- packed IQ: what receivers write (rtl_sdr: cu8, HackRF: cs8, Airspy / SDRplay / most recorders: cs16), expanded on the GPU ----
+ * Little-endian, I then Q.  The float a packed sample stands for:
+ *     HD_IQ_CS16  4 bytes/sample  (float)v * 2^-15
+ *     HD_IQ_CS8   2 bytes/sample  (float)v * 2^-7
+ *     HD_IQ_CU8   2 bytes/sample  (float)(2*v - 255) * 2^-8      (centre 127.5: 0 -> -255/256, 255 -> +255/256)
+ * Every value is exact in float, so a packed push is, float for float, the cf32 push of hd_host_iq_convert's output (habdec_amd_host.h): a kernel of
+ * its own (kernels/iq_unpack.hip) expands the packed rows into the cf32 staging slabs hd_process_host uses, and every kernel behind it runs as on cf32.
+ * Only the packed bytes cross the host link: a half (cs16) or a quarter (cs8, cu8) of the cf32 bytes.
+ * `stream_stride`, `n_per_stream` and `n` count complex samples as above; a cs16 row may start on any 4-byte boundary and a cs8 / cu8 row on any 2-byte
+ * boundary (odd strides, bases with an offset).  HD_IQ_CF32 through these calls IS hd_process_host / hd_process_device, with their alignment rules.
+ * Where the bytes come from: pageable host memory, and any host buffer in batch mode, is copied packed into a device slab and unpacked from there;
+ * page-locked mapped memory (hd_pinned_alloc) of a synchronous engine is unpacked in place over PCIe (counted in hd_timing.host_calls_in_place); a device
+ * pointer is unpacked straight from the caller's buffer.  The call returns when the caller's buffer is theirs again.
+ * Errors: an unknown fmt, a null pointer or a base off its sample boundary: HD_ERR_INVALID; n > max_chunk: HD_ERR_CAPACITY; the rest as hd_process_device.
+ * A refused call leaves every stream untouched. */
+#define HD_IQ_CF32 0
+#define HD_IQ_CS16 1
+#define HD_IQ_CS8 2
+#define HD_IQ_CU8 3
+int hd_process_host_fmt(hd_engine* e, int fmt, const void* iq, size_t stream_stride, const uint32_t* n_per_stream, uint32_t n);
+int hd_process_device_fmt(hd_engine* e, int fmt, const void* d_iq, size_t stream_stride, const uint32_t* n_per_stream, uint32_t n);
 /* Pipelined mode: wait for the call in flight and deliver its results (no-op otherwise).  Getters that read
  * device buffers flush implicitly. */
 int hd_flush(hd_engine* e);
@@ -200,6 +221,7 @@ int hd_flush(hd_engine* e);
  * or `max_rounds` rounds were pushed.  A reader thread fills pinned push slabs (four, so that a slab is never refilled
  * while a pipelined call may still copy from it) while the calling thread runs hd_process_host on the previous one --
  * file reads, the H2D copy and the GPU work overlap.  Text is delivered as by hd_process_host; ends with hd_flush.
+ * A batch opened with a packed format (hd_host_iqfiles_open_fmt) keeps its slabs packed and goes through hd_process_host_fmt.
  * `samples_done` (optional) receives the IQ samples consumed over all streams. */
 struct hd_host_iqfiles;
 int hd_ingest_run(hd_engine* e, struct hd_host_iqfiles* src, uint64_t max_rounds, uint64_t* samples_done);
@@ -295,6 +317,11 @@ int  hd_survey_push_device(hd_survey* sv, const void* d_iq, uint64_t n);
 /* The same from host memory, pageable or page-locked, staged through a device slab in pieces of whole runs -- segmentation and run structure are those
  * of the one push, so the result is byte-identical to hd_survey_push_device of the same samples.  The buffer is the caller's again on return. */
 int  hd_survey_push_host(hd_survey* sv, const float* iq, uint64_t n);
+/* The same pushes of packed IQ (HD_IQ_*; n in complex samples): host and device pushes alike go through the 4 MiB slab loop of hd_survey_push_host on the
+ * survey's queue, each slab's whole runs unpacked into it in front of the transform -- byte-identical to hd_survey_push_host of the converted floats.
+ * Both return when the buffer is the caller's again.  HD_IQ_CF32 is the plain call; an unknown fmt or a base off its sample boundary: HD_ERR_INVALID. */
+int  hd_survey_push_host_fmt(hd_survey* sv, int fmt, const void* iq, uint64_t n);
+int  hd_survey_push_device_fmt(hd_survey* sv, int fmt, const void* d_iq, uint64_t n);
 /* Waits for the survey's own queue only.  p[i] = acc[i] / (segments * sum w^2) (the sum in double over the float table) belongs to
  * f = (i - 2048) fs / 4096: white noise of complex variance s^2 reads about s^2.  No segments yet: zeros.  Returns the bins written (4096), 0 when
  * cap < 4096 (nothing written), or a negative HD_ERR_*; *segments (optional) = segments accumulated since creation or the last reset. */

@@ -122,6 +122,18 @@ uint64_t hd_host_iqfiles_rewinds(const hd_host_iqfiles*, uint32_t stream);
 /* One round: slab[s*stride .. ] (stride in complex samples, >= chunk) receives stream s's samples, n_per_stream[s] how many
  * (a multiple of granule).  Returns the number of streams that read anything (0: all files exhausted and not looping). */
 uint32_t hd_host_iqfiles_next(hd_host_iqfiles*, float* slab, size_t stride, uint32_t* n_per_stream);
+/* Packed files (HD_IQ_*, include/habdec_amd.h): the same reader over raw cs16 / cs8 / cu8 files -- count = file size / bytes per sample; reads, the
+ * granule carry and rewinds are counted in samples and hold packed bytes.  hd_host_iqfiles_open is hd_host_iqfiles_open_fmt(..., HD_IQ_CF32); NULL for an
+ * unknown fmt.  hd_host_iqfiles_next on a packed batch delivers the converted floats (hd_host_iq_convert); hd_host_iqfiles_next_raw fills the slab with the
+ * file's own bytes (stride still in complex samples: stream s starts at byte s * stride * hd_host_iq_bytes(fmt)) -- what hd_ingest_run hands on packed.
+ * Either call advances the batch by one round. */
+hd_host_iqfiles* hd_host_iqfiles_open_fmt(const char* const* paths, uint32_t n_files, int loop, uint32_t chunk, uint32_t granule,
+                                          double realtime_rate, int fmt);
+uint32_t hd_host_iqfiles_next_raw(hd_host_iqfiles*, void* slab, size_t stride, uint32_t* n_per_stream);
+/* The packed formats on the host, for checks without a GPU: bytes per complex sample (0 = unknown fmt), and the conversion the GPU performs --
+ * `n` complex samples at `src` (any alignment; exactly n * bytes are read) to 2 n floats at `out`.  An unknown fmt writes nothing. */
+size_t hd_host_iq_bytes(int fmt);
+void hd_host_iq_convert(int fmt, const void* src, size_t n, float* out);
 
 /* ---- per-stream digital tuning (hd_stream_set_tune, include/habdec_amd.h): the arithmetic the kernels run, for checks without a GPU ----
  * hd_host_tune_step: step = (uint32_t)(int64_t)nearbyint(-(offset_hz / decimated_rate) * 2^32), rounded half to even; HD_ERR_INVALID (-1) unless
