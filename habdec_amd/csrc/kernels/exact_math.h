@@ -5,8 +5,11 @@
 // algorithms evaluated in plain float arithmetic (argument reduction to one of four intervals, an odd/even
 // split degree-11 polynomial, hi/lo constants).  Restated below with the same operation order and compiled
 // with -ffp-contract=off, every result is bit-identical to the host libm (checked on 4e8 inputs incl.
-// NaN/Inf/denormal bit patterns in tests/test_host_logic.py::test_atan2_restatement_matches_libm and on the
-// GPU in tests/test_gpu_parity.py).  That makes the demodulated floats, and therefore every flip point,
+// NaN/Inf/denormal bit patterns in tests/test_host_logic.py::test_atan2_restatement_matches_libm as host code; the
+// device compile -- its own division expansion, denormal mode and select lowering -- in
+// tests/test_gpu_discriminator_domain.py::test_exact_discriminator_matches_the_cpu_chain_over_the_whole_domain, which drives
+// all twenty cells of the straight-line function and the special classes of the general one through every kernel that
+// inlines this header).  That makes the demodulated floats, and therefore every flip point,
 // bit and character downstream, identical to the CPU path by construction instead of "almost always".
 #pragma once
 #include <stdint.h>

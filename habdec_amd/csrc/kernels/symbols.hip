@@ -276,8 +276,12 @@ __global__ __launch_bounds__(kSymLanes) void k_symbols(const float* __restrict__
             if (lo == 0xFFFFFFFFu) break;
             const uint32_t hi = find_flag_lds(lmask, st.base, rmask, lo + 1, limit, false);
             if (hi == 0xFFFFFFFFu) { frontier = lo; break; }      // an edge zone is open: the next flip lies at or after lo
-            // first maximum of the weight over [lo, hi): key = (weight bits, ~index) -- weights are >= 0, so their bit patterns
-            // order like the values, and among equal weights the smaller index has the larger key
+            // first maximum of the weight over [lo, hi) as the reference finds it (it takes lo, then replaces its best only on `w > bestw`): key =
+            // (weight bits, ~index).  The weights are |d| or (float)|int|: never negative and never -0, so the bit patterns of the numbers among them
+            // (+Inf included) order like the values, and among equal weights the smaller index has the larger key.  A NaN weight (a NaN or Inf - Inf
+            // among the window sums) compares false both ways there: it never replaces a best, and a best that is NaN -- only lo's can be -- is never
+            // replaced; its bit pattern (0x7fc00000 or above) would beat every number instead, so it is keyed as 0 behind lo and as the maximum at lo
+            // (tests/test_gpu_discriminator_domain.py::test_flip_search_beside_nan_and_inf_samples)
             unsigned long long key = 0ull;
             constexpr int ZB = 4;                             // 256 zone positions per round trip (a zone is about R long)
             for (uint32_t i0 = lo + lane; i0 < hi; i0 += 64 * ZB) {
@@ -294,7 +298,9 @@ __global__ __launch_bounds__(kSymLanes) void k_symbols(const float* __restrict__
                     if (i < hi) {
                         const float d = wr_[u] / (float)R - wl_[u] / (float)R;   // avg_r - avg_l
                         const float w = q.float_abs ? __builtin_fabsf(d) : (float)abs((int)d);
-                        const unsigned long long k = ((unsigned long long)__builtin_bit_cast(uint32_t, w) << 32) | (uint32_t)~i;
+                        uint32_t wb = __builtin_bit_cast(uint32_t, w);
+                        if (wb > 0x7f800000u) wb = i == lo ? 0xFFFFFFFFu : 0u;   // a NaN weight never wins (`w > bestw` is false), unless the zone starts with it
+                        const unsigned long long k = ((unsigned long long)wb << 32) | (uint32_t)~i;
                         key = k > key ? k : key;
                     }
                 }

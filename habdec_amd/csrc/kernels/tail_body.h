@@ -838,7 +838,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
             if (lo == 0xFFFFFFFFu) break;
             const uint32_t hi = find_flag_rel(lmask, st.base, wr0, lo + 1, limit, false);
             if (hi == 0xFFFFFFFFu) { frontier = lo; break; }            // an edge zone is open: the next flip lies at or after lo
-            unsigned long long key = 0ull;                              // first maximum of the weight over [lo, hi): (weight bits, ~index)
+            unsigned long long key = 0ull;                              // first maximum of the weight over [lo, hi): (weight bits, ~index); NaN weights as in symbols.hip
             constexpr int ZB = 4;
             for (uint32_t i0 = lo + lane; i0 < hi; i0 += 64 * ZB) {
                 float wr_[ZB], wl_[ZB];
@@ -854,7 +854,9 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
                     if (i < hi) {
                         const float d = wr_[u] / (float)R - wl_[u] / (float)R;   // avg_r - avg_l
                         const float w = q.float_abs ? __builtin_fabsf(d) : (float)abs((int)d);
-                        const unsigned long long k = ((unsigned long long)__builtin_bit_cast(uint32_t, w) << 32) | (uint32_t)~i;
+                        uint32_t wb = __builtin_bit_cast(uint32_t, w);
+                        if (wb > 0x7f800000u) wb = i == lo ? 0xFFFFFFFFu : 0u;   // a NaN weight never wins (`w > bestw` is false), unless the zone starts with it
+                        const unsigned long long k = ((unsigned long long)wb << 32) | (uint32_t)~i;
                         key = k > key ? k : key;
                     }
                 }
