@@ -49,6 +49,34 @@ class hd_survey_candidate(C.Structure):
     _fields_ = [("offset_hz", C.c_double), ("snr_db", C.c_double), ("width_hz", C.c_double), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32)]
 
 
+PROBE_CANDIDATES, PROBE_SCALES, TRIAL_FORMATS = 1024, 9, 4
+PROBE_WINDOWS = (1, 3, 7, 15, 31, 63, 127, 255, 511)
+
+
+class hd_baud_probe_params(C.Structure):
+    _fields_ = [("baud_lo", C.c_double), ("baud_hi", C.c_double), ("min_coherence", C.c_double)]
+
+
+class hd_baud_estimate(C.Structure):
+    _fields_ = [("baud", C.c_double), ("nominal", C.c_double), ("rho", C.c_double), ("rho_max", C.c_double), ("samples", C.c_uint64),
+                ("edges", C.c_uint64), ("k", C.c_uint32), ("settled", C.c_int32), ("valid", C.c_int32), ("_pad", C.c_uint32)]
+
+
+class hd_baud_probe_stream_state(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("edges", C.c_uint64 * PROBE_SCALES), ("history", C.c_uint64 * 8), ("majority", C.c_uint32 * PROBE_SCALES),
+                ("n_candidates", C.c_uint32)]
+
+
+# one hd_baud_probe_candidate
+PROBE_CANDIDATE_DTYPE = np.dtype([("P", "<u8"), ("Q", "<u8"), ("NB", "<u4"), ("re", "<i4"), ("im", "<i4"), ("n", "<u4"), ("cur_block", "<u4"), ("_pad", "<u4")])
+
+
+class hd_format_trial_result(C.Structure):
+    _fields_ = [("best", C.c_int32), ("best_bits", C.c_uint32), ("best_stops", C.c_float), ("bits", C.c_uint32 * TRIAL_FORMATS),
+                ("stops", C.c_float * TRIAL_FORMATS), ("_pad", C.c_uint32), ("sentences_ok", C.c_uint64 * TRIAL_FORMATS),
+                ("matches", C.c_uint64 * TRIAL_FORMATS), ("printable", C.c_uint64 * TRIAL_FORMATS)]
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -134,6 +162,17 @@ ENGINE_API = {
     "hd_survey_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
     "hd_survey_params_default": (None, [C.POINTER(hd_survey_params)]),
     "hd_survey_detect": (_int, [_vp, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
+    "hd_baud_probe_params_default": (None, [C.POINTER(hd_baud_probe_params)]),
+    "hd_baud_probe_create": (_int, [_vp, C.POINTER(hd_baud_probe_params), C.POINTER(_vp)]),
+    "hd_baud_probe_destroy": (None, [_vp]),
+    "hd_baud_probe_reset": (_int, [_vp, _u32]),
+    "hd_baud_probe_push_engine": (_int, [_vp]),
+    "hd_baud_probe_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_baud_probe_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_baud_probe_estimate": (_int, [_vp, _u32, C.POINTER(hd_baud_estimate)]),
+    "hd_baud_probe_state": (_int, [_vp, _u32, C.POINTER(hd_baud_probe_stream_state), _vp, _sz]),
+    "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
+    "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
 # every symbol declared in include/habdec_amd_host.h
 HOST_API = {
@@ -187,6 +226,16 @@ HOST_API = {
     "hd_host_tune_rotate": (None, [_f32p, _sz, C.c_uint32, C.c_uint32, _f32p]),
     "hd_host_survey_window": (None, [_f32p]),
     "hd_host_survey_detect": (_int, [_f64p, C.c_uint64, _dbl, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
+    "hd_host_baud_probe_new": (_vp, [_dbl, C.POINTER(hd_baud_probe_params)]),
+    "hd_host_baud_probe_free": (None, [_vp]),
+    "hd_host_baud_probe_reset": (None, [_vp]),
+    "hd_host_baud_probe_push": (None, [_vp, _f32p, _sz]),
+    "hd_host_baud_probe_state": (_int, [_vp, C.POINTER(hd_baud_probe_stream_state), _vp, _sz]),
+    "hd_host_baud_probe_estimate": (_int, [_vp, C.POINTER(hd_baud_estimate)]),
+    "hd_host_format_trial_new": (_vp, []),
+    "hd_host_format_trial_free": (None, [_vp]),
+    "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),
+    "hd_host_format_trial_get": (None, [_vp, C.POINTER(hd_format_trial_result)]),
 }
 
 

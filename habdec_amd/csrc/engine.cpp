@@ -31,6 +31,8 @@
 #include "host/iq_convert.hpp"
 #include "host/iq_file_batch.hpp"
 #include "host/survey.hpp"
+#include "host/baud_probe.hpp"
+#include "host/format_trial.hpp"
 #include "host/text_stage.hpp"
 #include "host/tune_host.hpp"
 #include "kernels/launch.h"
@@ -138,6 +140,8 @@ struct StreamHost {
     double front_hz = 0;
     uint32_t front_step = 0;
     uint64_t front_from = 0;                  // first call of the current offset
+    // framing trial (hd_stream_set_format_trial): four text stages beside `text`, fed the same bits at delivery; null while off
+    std::shared_ptr<hd::FormatTrial> trial;     // (shared: a StreamHost is copied where a setter tries a value out)
 };
 
 }  // namespace
@@ -866,6 +870,7 @@ int collect(hd_engine* e, hd_engine::CallSlot& sl)
         st.last_words.assign(words, words + (hdr->nbits + 31) / 32);
         if (!c.fir_m) continue;
         if (hdr->nbits) st.text.framer.push_packed(words, hdr->nbits);
+        if (st.trial) st.trial->push_packed(words, hdr->nbits);
         const std::string chars = st.text.run(hdr->nbits != 0, [&](const hd::SentenceMatch& m) {
             ++e->sentences_ok;
             if (e->sentence_cb) { e->in_callback = true; e->sentence_cb(e->sentence_user, s, m.callsign.c_str(), m.data.c_str(), m.crc.c_str()); e->in_callback = false; }
@@ -2296,6 +2301,282 @@ int hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candida
     if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "hd_survey_detect needs at least 16 segments and a floor above zero (" + std::to_string(segs) + " segments so far)");
     if (rc) return fail(rc, "hd_survey_detect: bad parameters or a NaN / negative power");
     return HD_OK;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- framing trial (host/format_trial.hpp) ------------------------------- */
+
+extern "C" {
+
+int hd_stream_set_format_trial(hd_engine* e, uint32_t s, int on)
+{
+    if (check_stream(e, s)) return HD_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    e->st[s].trial.reset(on ? new hd::FormatTrial : nullptr);
+    return HD_OK;
+}
+
+int hd_stream_format_trial(hd_engine* e, uint32_t s, hd_format_trial_result* out)
+{
+    if (check_stream(e, s)) return HD_ERR_INVALID;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    if (!e->st[s].trial) return fail(HD_ERR_INVALID, "the stream's framing trial is off (hd_stream_set_format_trial)");
+    e->st[s].trial->get(out);
+    return HD_OK;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- baud-rate probe (kernels/baud_probe.hip) ----------------------------- */
+
+struct hd_baud_probe {
+    hd_engine* e = nullptr;
+    hd_baud_probe_params prm{};
+    hd::BaudProbeTables t;
+    uint32_t S = 0;
+    hd_baud_probe_stream_state* hdr = nullptr;   // [S]
+    unsigned long long* acc64 = nullptr;         // [S][2][1024]: P, Q
+    uint32_t* acc32 = nullptr;                   // [S][5][1024]: NB, re, im, n, cur_block
+    uint32_t *F = nullptr, *scale = nullptr;
+    int32_t* ctab = nullptr;
+    float* slab = nullptr;                       // hd_baud_probe_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::ProbeSrc> src;                    // [S]: the push's descriptors, read by the kernel in place (a push returns when its kernel is done)
+    uint64_t pushed_calls = 0;                   // hd_baud_probe_push_engine: e->calls at the last push (the call delivered last is calls - 1)
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launch
+    ~hd_baud_probe()
+    {
+        for (void* p : {(void*)hdr, (void*)acc64, (void*)acc32, (void*)F, (void*)scale, (void*)ctab, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+int probe_enter(hd_baud_probe* p)
+{
+    if (p->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + p->e->fail_cause + ") -- destroy the engine");
+    HD_HIP(hipSetDevice(p->e->cfg.device));
+    return HD_OK;
+}
+
+// The descriptors are written: one launch for all streams on the engine's first queue, and the wait for it.
+int probe_launch(hd_baud_probe* p)
+{
+    std::atomic_thread_fence(std::memory_order_release);
+    if (p->t0) HD_HIP(hipEventRecord(p->t0, p->e->qa));
+    hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr, p->acc64, p->acc32, p->F, p->scale, p->ctab);
+    if (p->t1) HD_HIP(hipEventRecord(p->t1, p->e->qa));
+    HD_HIP(hipGetLastError());
+    HD_HIP(hipStreamSynchronize(p->e->qa));
+    return HD_OK;
+}
+
+int probe_clear(hd_baud_probe* p, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = p->e->qa;
+    HD_HIP(hipMemsetAsync(p->hdr + s0, 0, (size_t)ns * sizeof(hd_baud_probe_stream_state), q));
+    HD_HIP(hipMemsetAsync(p->acc64 + (size_t)s0 * 2 * hd::kProbeCand, 0, (size_t)ns * 2 * hd::kProbeCand * sizeof(unsigned long long), q));
+    HD_HIP(hipMemsetAsync(p->acc32 + (size_t)s0 * 5 * hd::kProbeCand, 0, (size_t)ns * 5 * hd::kProbeCand * sizeof(uint32_t), q));
+    HD_HIP(hipStreamSynchronize(q));
+    return HD_OK;
+}
+
+int probe_check_rows(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, uint32_t* max_n, size_t* total)
+{
+    if (!p) return fail(HD_ERR_INVALID, "null probe");
+    if (!rows) return fail(HD_ERR_INVALID, "null rows");
+    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
+    *max_n = 0; *total = 0;
+    for (uint32_t s = 0; s < p->S; ++s) {
+        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
+        *max_n = std::max(*max_n, ns); *total += ns;
+    }
+    if (p->S > 1 && *max_n > stride) return fail(HD_ERR_INVALID, "a row is longer than the stride");
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_baud_probe_params_default(hd_baud_probe_params* p) { if (p) hd::baud_probe_params_default(p); }
+
+int hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* params, hd_baud_probe** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_baud_probe> p(new hd_baud_probe);
+    p->e = e; p->S = e->S;
+    hd::baud_probe_params_default(&p->prm);
+    if (params) p->prm = *params;
+    if (!hd::baud_probe_params_ok(&p->prm, e->fsd))
+        return fail(HD_ERR_INVALID, "baud probe parameters: 0 < baud_lo < baud_hi <= decimated rate / 3.5 (" + std::to_string(e->fsd / 3.5) + ") and min_coherence >= 0");
+    if (const int rc = probe_enter(p.get())) return rc;
+    p->t.make(e->fsd, p->prm);
+    std::vector<uint32_t> sc(hd::kProbeCand);
+    for (uint32_t k = 0; k < hd::kProbeCand; ++k) sc[k] = p->t.scale[k];
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->hdr), (size_t)p->S * sizeof(hd_baud_probe_stream_state)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc64), (size_t)p->S * 2 * hd::kProbeCand * sizeof(unsigned long long)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc32), (size_t)p->S * 5 * hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->F), hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->scale), hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->ctab), 1024 * sizeof(int32_t)));
+    HD_HIP(p->src.alloc(p->S));
+    HD_HIP(hipMemcpyAsync(p->F, p->t.F, hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->scale, sc.data(), hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->ctab, p->t.C, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, e->qa));
+    if (const int rc = probe_clear(p.get(), 0, p->S)) return rc;       // (waits for the queue: `sc` is a local)
+    p->pushed_calls = 0;
+    *out = p.release();
+    return HD_OK;
+}
+
+void hd_baud_probe_destroy(hd_baud_probe* p)
+{
+    if (!p) return;
+    hd_engine* e = p->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    (void)hipSetDevice(e->cfg.device);
+    delete p;
+}
+
+int hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream)
+{
+    if (!p) return fail(HD_ERR_INVALID, "null probe");
+    if (stream != UINT32_MAX && stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    return stream == UINT32_MAX ? probe_clear(p, 0, p->S) : probe_clear(p, stream, 1);
+}
+
+int hd_baud_probe_push_engine(hd_baud_probe* p)
+{
+    if (!p) return fail(HD_ERR_INVALID, "null probe");
+    hd_engine* e = p->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    if (e->in_callback) return fail(HD_ERR_INVALID, "hd_baud_probe_push_engine cannot be called from a sentence / character callback");
+    if (const int rc = flush_locked(e)) return rc;                     // like the data getters: the call in flight is delivered first
+    if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + ") -- destroy the engine");
+    if (e->calls == p->pushed_calls) return HD_OK;                     // no call since the last push
+    p->pushed_calls = e->calls;
+    bool any = false;
+    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
+        const SizeState& sz = e->mirror[s];
+        hd::ProbeSrc& d = p->src.p[s];
+        d.n = sz.last_m;
+        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
+        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
+        any |= d.n != 0;
+    }
+    return any ? probe_launch(p) : HD_OK;
+}
+
+int hd_baud_probe_push_device(hd_baud_probe* p, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    uint32_t max_n = 0; size_t total = 0;
+    if (const int rc = probe_check_rows(p, d_rows, stride, n_per_stream, n, &max_n, &total)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    if (!total) return HD_OK;
+    {   // what the kernel reads must be memory the GPU can address
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
+                                                                   !(at.type == hipMemoryTypeHost && at.devicePointer))) {
+            (void)hipGetLastError();
+            return fail(HD_ERR_INVALID, "rows are not device memory (hd_baud_probe_push_host takes host memory)");
+        }
+    }
+    for (uint32_t s = 0; s < p->S; ++s) {
+        hd::ProbeSrc& d = p->src.p[s];
+        d.p = d_rows + (size_t)s * stride; d.sym = nullptr; d.ring_mask = 0; d.n = n_per_stream ? n_per_stream[s] : n;
+    }
+    return probe_launch(p);
+}
+
+int hd_baud_probe_push_host(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    uint32_t max_n = 0; size_t total = 0;
+    if (const int rc = probe_check_rows(p, rows, stride, n_per_stream, n, &max_n, &total)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    if (!total) return HD_OK;
+    if (total > p->slab_n) {
+        if (p->slab) { (void)hipFree(p->slab); p->slab = nullptr; p->slab_n = 0; }
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->slab), total * sizeof(float)));
+        p->slab_n = total;
+    }
+    size_t at = 0;
+    for (uint32_t s = 0; s < p->S; ++s) {
+        hd::ProbeSrc& d = p->src.p[s];
+        d.n = n_per_stream ? n_per_stream[s] : n;
+        d.p = p->slab + at; d.sym = nullptr; d.ring_mask = 0;
+        if (d.n) HD_HIP(hipMemcpyAsync(p->slab + at, rows + (size_t)s * stride, (size_t)d.n * sizeof(float), hipMemcpyHostToDevice, p->e->qa));
+        at += d.n;
+    }
+    return probe_launch(p);
+}
+
+int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* cand, size_t cap)
+{
+    if (!p) return fail(HD_ERR_INVALID, "null probe");
+    if (stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (cap < hd::kProbeCand) return (int)hd::kProbeCand;              // nothing is written
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    hd_baud_probe_stream_state h;
+    std::vector<unsigned long long> a64(2 * hd::kProbeCand);
+    std::vector<uint32_t> a32(5 * hd::kProbeCand);
+    HD_HIP(hipMemcpy(&h, p->hdr + stream, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a64.data(), p->acc64 + (size_t)stream * a64.size(), a64.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a32.data(), p->acc32 + (size_t)stream * a32.size(), a32.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h.n_candidates = hd::kProbeCand;
+    if (hdr) *hdr = h;
+    for (uint32_t k = 0; cand && k < hd::kProbeCand; ++k) {
+        hd_baud_probe_candidate& c = cand[k];
+        c.P = a64[k]; c.Q = a64[hd::kProbeCand + k];
+        c.NB = a32[k]; c.re = (int32_t)a32[hd::kProbeCand + k]; c.im = (int32_t)a32[2 * hd::kProbeCand + k];
+        c.n = a32[3 * hd::kProbeCand + k]; c.cur_block = a32[4 * hd::kProbeCand + k]; c._pad = 0;
+    }
+    return (int)hd::kProbeCand;
+}
+
+int hd_baud_probe_estimate(hd_baud_probe* p, uint32_t stream, hd_baud_estimate* out)
+{
+    if (!p) return fail(HD_ERR_INVALID, "null probe");
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    hd_baud_probe_stream_state h;
+    std::vector<hd_baud_probe_candidate> c(hd::kProbeCand);
+    const int n = hd_baud_probe_state(p, stream, &h, c.data(), c.size());
+    if (n < 0) return n;
+    hd::baud_probe_estimate(p->t, p->prm, h, c.data(), out);
+    return HD_OK;
+}
+
+// Measurement hook (tools/micro/probe_rate.py; not part of the ABI): the kernel of hd_baud_probe_push_engine between two HIP events, and the host
+// time of the whole call in microseconds.
+int hd_debug_baud_probe_push_timed(hd_baud_probe* p, float* kernel_ms, double* host_us)
+{
+    if (!p || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    hd_engine* e = p->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = probe_enter(p)) return rc;
+    if (const int rc = flush_locked(e)) return rc;
+    HD_HIP(hipEventCreate(&p->t0));
+    HD_HIP(hipEventCreate(&p->t1));
+    const uint64_t before = p->pushed_calls;
+    const auto w0 = std::chrono::steady_clock::now();
+    const int rc = hd_baud_probe_push_engine(p);
+    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+    *kernel_ms = 0;
+    if (rc == HD_OK && p->pushed_calls != before && hipEventQuery(p->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, p->t0, p->t1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(p->t0); (void)hipEventDestroy(p->t1);
+    p->t0 = p->t1 = nullptr;
+    return rc;
 }
 
 }  // extern "C"

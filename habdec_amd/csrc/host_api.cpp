@@ -5,8 +5,10 @@
 
 #include "../../include/habdec_amd_host.h"
 #include "host/afc_tracker.hpp"
+#include "host/baud_probe.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
+#include "host/format_trial.hpp"
 #include "host/gui_payload.hpp"
 #include "host/telemetry.hpp"
 #include "host/sondehub.hpp"
@@ -279,5 +281,47 @@ int hd_host_survey_detect(const double* power, uint64_t segments, double samplin
 {
     return hd::survey_detect(power, segments, sampling_rate, p, out, cap, found);
 }
+
+/* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */
+struct hd_host_baud_probe {
+    hd_baud_probe_params prm;
+    hd::BaudProbeTables t;
+    hd::BaudProbeStream s;
+};
+hd_host_baud_probe* hd_host_baud_probe_new(double decimated_rate, const hd_baud_probe_params* params)
+{
+    hd_baud_probe_params prm;
+    hd::baud_probe_params_default(&prm);
+    if (params) prm = *params;
+    if (!hd::baud_probe_params_ok(&prm, decimated_rate)) return nullptr;
+    auto* h = new hd_host_baud_probe;
+    h->prm = prm;
+    h->t.make(decimated_rate, prm);
+    return h;
+}
+void hd_host_baud_probe_free(hd_host_baud_probe* h) { delete h; }
+void hd_host_baud_probe_reset(hd_host_baud_probe* h) { if (h) h->s.reset(); }
+void hd_host_baud_probe_push(hd_host_baud_probe* h, const float* d, size_t n) { if (h && d && n) h->s.push(h->t, d, n); }
+int hd_host_baud_probe_state(const hd_host_baud_probe* h, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* candidates, size_t cap)
+{
+    if (!h) return HD_ERR_INVALID;
+    if (cap < hd::kProbeCand) return (int)hd::kProbeCand;
+    if (hdr) *hdr = h->s.h;
+    if (candidates) std::memcpy(candidates, h->s.c.data(), hd::kProbeCand * sizeof(hd_baud_probe_candidate));
+    return (int)hd::kProbeCand;
+}
+int hd_host_baud_probe_estimate(const hd_host_baud_probe* h, hd_baud_estimate* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    hd::baud_probe_estimate(h->t, h->prm, h->s.h, h->s.c.data(), out);
+    return HD_OK;
+}
+
+/* ---- framing trial (see host/format_trial.hpp) ---- */
+struct hd_host_format_trial { hd::FormatTrial f; };
+hd_host_format_trial* hd_host_format_trial_new(void) { return new hd_host_format_trial; }
+void hd_host_format_trial_free(hd_host_format_trial* h) { delete h; }
+void hd_host_format_trial_push_bits(hd_host_format_trial* h, const uint8_t* bits, size_t n) { if (h && (bits || !n)) h->f.push_bits(bits, n); }
+void hd_host_format_trial_get(const hd_host_format_trial* h, hd_format_trial_result* out) { if (h && out) h->f.get(out); }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../dev_types.h"
+#include "../../../include/habdec_amd.h"
 #include "../host/ring_schedule.hpp"
 
 namespace hd {
@@ -76,6 +77,18 @@ void launch_spectrum_wave(hipStream_t st, uint32_t n_streams, const float2* fft_
 // n_rows = 1 with both strides unused.  A cs16 row may start on any 4-byte boundary, a cs8 / cu8 row on any 2-byte boundary.  false: unknown fmt.
 bool launch_iq_unpack(hipStream_t st, int fmt, uint32_t n_rows, uint32_t max_n, const void* src, size_t src_stride, const uint32_t* n_per_row,
                       uint32_t n_uniform, float2* dst, size_t dst_stride);
+
+// Baud-rate probe (baud_probe.hip), one workgroup of 1024 threads per stream.  src[s]: where stream s's discriminator output of this push lies -- n floats
+// at p, or (ring_mask != 0) the n floats in front of the append position base + held of *sym in the symbol ring at p, indices taken & ring_mask; n = 0:
+// the stream is not touched.  hdr [S], acc64 [S][2][1024] (P, Q), acc32 [S][5][1024] (NB, re, im, n, cur_block); F, scale, ctab: the 1024-entry tables of
+// host/baud_probe.hpp (BaudProbeTables).
+struct ProbeSrc {
+    const float* p;
+    const SymState* sym;
+    uint32_t n, ring_mask;
+};
+void launch_baud_probe(hipStream_t st, uint32_t n_streams, const ProbeSrc* src, hd_baud_probe_stream_state* hdr, unsigned long long* acc64, uint32_t* acc32,
+                       const uint32_t* F, const uint32_t* scale, const int32_t* ctab);
 
 // ---- launchers of the mode-dependent kernels, once per arithmetic mode (arith.h)
 namespace exact {

@@ -51,9 +51,9 @@ class Engine:
         self._cbs = []
 
     def close(self):
-        for sv in getattr(self, "_surveys", []):       # (a survey uses its engine's device, twiddles and mutex: it goes first)
+        for sv in getattr(self, "_surveys", []) + getattr(self, "_probes", []):       # (a survey or a probe uses its engine's device and mutex: it goes first)
             sv.close()
-        self._surveys = []
+        self._surveys, self._probes = [], []
         if getattr(self, "h", None):
             self.L.hd_engine_destroy(self.h)
             self.h = None
@@ -232,6 +232,178 @@ class Engine:
         sv = Survey(self)
         self._surveys = getattr(self, "_surveys", []) + [sv]
         return sv
+
+    def baud_probe(self, **params) -> "BaudProbe":
+        """A baud-rate probe on this engine's streams (hd_baud_probe_*; params as hd_baud_probe_params): close it before the engine."""
+        p = BaudProbe(self, **params)
+        self._probes = getattr(self, "_probes", []) + [p]
+        return p
+
+    def set_format_trial(self, s, on=True):
+        """Tee the bits delivered for stream s into a framing trial (hd_stream_set_format_trial); turning it on resets it."""
+        check(self.L.hd_stream_set_format_trial(self.h, s, int(on)))
+
+    def format_trial(self, s=0) -> dict:
+        r = capi.hd_format_trial_result()
+        check(self.L.hd_stream_format_trial(self.h, s, C.byref(r)))
+        return _trial_result(r)
+
+
+def _trial_result(r) -> dict:
+    return {"best": r.best, "best_bits": r.best_bits, "best_stops": r.best_stops, "bits": list(r.bits), "stops": list(r.stops),
+            "sentences_ok": list(r.sentences_ok), "matches": list(r.matches), "printable": list(r.printable)}
+
+
+def _estimate(e) -> dict:
+    return {"baud": e.baud, "nominal": e.nominal, "rho": e.rho, "rho_max": e.rho_max, "samples": e.samples, "edges": e.edges, "k": e.k,
+            "settled": bool(e.settled), "valid": bool(e.valid)}
+
+
+def _probe_state(h, cand) -> dict:
+    """A stream's raw accumulators as numpy arrays: what the parity tests compare integer for integer."""
+    out = {k: cand[k].copy() for k in ("P", "Q", "NB", "re", "im", "n", "cur_block")}
+    out.update(samples=int(h.samples), edges=np.array(list(h.edges), np.uint64), history=np.array(list(h.history), np.uint64),
+               majority=np.array(list(h.majority), np.uint32))
+    return out
+
+
+class _ProbeRows:
+    """rows: float32 [S, stride] (or [n] for one stream); n_per_stream: None = every row whole."""
+
+    @staticmethod
+    def args(rows, S, n_per_stream):
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim == 1:
+            rows = rows[None, :]
+        assert rows.shape[0] == S, rows.shape
+        n = np.full(S, rows.shape[1], np.uint32) if n_per_stream is None else np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+        assert n.shape == (S,) and (S == 1 or int(n.max(initial=0)) <= rows.shape[1])
+        return rows, n
+
+
+class BaudProbe:
+    """Baud-rate probe of an engine's streams (hd_baud_probe_*, include/habdec_amd.h): push discriminator output, read an estimate."""
+
+    def __init__(self, eng: Engine, **params):
+        self.L, self.eng, self.S = eng.L, eng, eng.S
+        p = capi.hd_baud_probe_params()
+        self.L.hd_baud_probe_params_default(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, float(v))
+        h = C.c_void_p()
+        check(self.L.hd_baud_probe_create(eng.h, C.byref(p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_baud_probe_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_engine(self):
+        """Add every stream's discriminator output of the call delivered last (drains the pipeline first, like the data getters)."""
+        check(self.L.hd_baud_probe_push_engine(self.h))
+
+    def push_host(self, rows, n_per_stream=None):
+        rows, n = _ProbeRows.args(rows, self.S, n_per_stream)
+        check(self.L.hd_baud_probe_push_host(self.h, rows.ctypes.data, rows.shape[1], n.ctypes.data, 0))
+
+    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
+        """float32 rows at a device address, row s at dev_ptr + 4 * s * stride."""
+        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+        assert n.shape == (self.S,)
+        check(self.L.hd_baud_probe_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+
+    def estimate(self, s=0) -> dict:
+        e = capi.hd_baud_estimate()
+        check(self.L.hd_baud_probe_estimate(self.h, s, C.byref(e)))
+        return _estimate(e)
+
+    def state(self, s=0) -> dict:
+        h, cand = capi.hd_baud_probe_stream_state(), np.zeros(capi.PROBE_CANDIDATES, capi.PROBE_CANDIDATE_DTYPE)
+        n = self.L.hd_baud_probe_state(self.h, s, C.byref(h), cand.ctypes.data, cand.size)
+        if n != capi.PROBE_CANDIDATES:
+            check(n if n < 0 else -1)
+        return _probe_state(h, cand)
+
+    def reset(self, s=None):
+        check(self.L.hd_baud_probe_reset(self.h, 0xFFFFFFFF if s is None else s))
+
+
+class HostBaudProbe:
+    """One stream of the probe in plain C++ on the host (hd_host_baud_probe_*): the restatement the kernel is held to, no GPU."""
+
+    def __init__(self, decimated_rate: float, **params):
+        self.L = lib()
+        p = capi.hd_baud_probe_params()
+        self.L.hd_baud_probe_params_default(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, float(v))
+        self.h = self.L.hd_host_baud_probe_new(float(decimated_rate), C.byref(p))
+        if not self.h:
+            raise HabdecError("hd_host_baud_probe_new: 0 < baud_lo < baud_hi <= decimated_rate / 3.5 and min_coherence >= 0")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_host_baud_probe_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, d):
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+        self.L.hd_host_baud_probe_push(self.h, d, d.size)
+
+    def reset(self):
+        self.L.hd_host_baud_probe_reset(self.h)
+
+    def estimate(self) -> dict:
+        e = capi.hd_baud_estimate()
+        check(self.L.hd_host_baud_probe_estimate(self.h, C.byref(e)))
+        return _estimate(e)
+
+    def state(self) -> dict:
+        h, cand = capi.hd_baud_probe_stream_state(), np.zeros(capi.PROBE_CANDIDATES, capi.PROBE_CANDIDATE_DTYPE)
+        n = self.L.hd_host_baud_probe_state(self.h, C.byref(h), cand.ctypes.data, cand.size)
+        assert n == capi.PROBE_CANDIDATES, n
+        return _probe_state(h, cand)
+
+
+class HostFormatTrial:
+    """Four text stages (7N1, 7N2, 8N1, 8N2) over the same bits on the host (hd_host_format_trial_*)."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = self.L.hd_host_format_trial_new()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_host_format_trial_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_bits(self, bits):
+        bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
+        self.L.hd_host_format_trial_push_bits(self.h, bits, bits.size)
+
+    def get(self) -> dict:
+        r = capi.hd_format_trial_result()
+        self.L.hd_host_format_trial_get(self.h, C.byref(r))
+        return _trial_result(r)
 
 
 def _candidates(out, n) -> list:

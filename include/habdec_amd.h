@@ -343,6 +343,96 @@ void hd_survey_params_default(hd_survey_params* p);
  * are written, strongest first.  Fewer than 16 segments: HD_ERR_UNSUPPORTED. */
 int  hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap, uint32_t* found);
 
+/* ---- baud-rate probe: what is a stream's symbol rate? (not in the reference, which is told it: Decoder::baud()) ----
+ * survey -> front tune -> AFC -> PROBE -> hd_stream_set_baud -> framing trial (below) -> hd_stream_set_rtty.  A probe is attached to an engine like a
+ * survey (its device and mutex; destroy it before the engine) and accumulates, per stream, integer statistics of the discriminator output
+ * (hd_stream_demodulated) over as many calls as are pushed; an estimate is read from them on the host.  fsd = hd_engine_decimated_rate(e).
+ *  - Candidates: HD_PROBE_CANDIDATES of them, b_k = baud_lo (baud_hi / baud_lo)^(k / 1023) in double, F_k = (uint64)floor(b_k / fsd 2^32 + 0.5).
+ *    hd_baud_probe_create is HD_ERR_INVALID unless 0 < baud_lo < baud_hi <= fsd / 3.5 (and min_coherence >= 0).
+ *  - Sign bits: b[i] = d[i] > 0.0f (NaN gives 0), b[j] = 0 in front of the stream's first sample since the last reset; i = the stream's absolute sample
+ *    index since the last reset, uint64.
+ *  - Scales: W in {1, 3, 7, 15, 31, 63, 127, 255, 511}; m_W[i] = popcount(b[i-W+1 .. i]) > (W-1)/2; an edge of scale W stands at i when i >= W and
+ *    m_W[i] != m_W[i-1].  Candidate k listens to the largest W <= max(1, T_k / 4), T_k = 2^32 / F_k in double.
+ *  - Per edge and candidate: p = i F_k mod 2^64, idx = (p >> 22) & 1023, block = (uint32)(p >> 38) (the group of 64 candidate periods the edge falls
+ *    into).  block != cur_block_k: the block is dumped and cur_block_k = block.  Then n_k += 1 and, while n_k <= 4096, re_k += C[idx],
+ *    im_k += C[(idx + 768) & 1023], C[a] = (int32)nearbyint(32767 cos(2 pi a / 1024)).
+ *  - Dump: if 8 <= n_k <= 4096 then P_k += re_k^2 + im_k^2, Q_k += n_k^2, NB_k += 1; then re_k = im_k = n_k = 0.
+ *  - Estimate (host, double; on a copy of the state whose open blocks are dumped by the same rule): rho_k = NB_k >= 4 ? P_k / (32767^2 Q_k) : 0 -- 1 when
+ *    every edge of every block sits at one phase of the candidate's period, about 1 / n for random edges.  settled = ((i F_0) >> 38) >= 4: four whole
+ *    blocks of the lowest candidate, 6.4 s at baud_lo = 40.  valid = settled && rho_max >= min_coherence.  k* = the lowest k with rho_k >= rho_max / 2,
+ *    moved up while rho_{k+1} > rho_k (the baud line and its harmonics all read about 1: the fundamental is the lowest; sub-harmonics at the character
+ *    rate are coherent for the start-bit edges only).  baud = the vertex of the parabola through (ln b, rho) at k*-1, k*, k*+1, clamped to
+ *    [b_{k*-1}, b_{k*+1}]; b_{k*} at the grid's ends.  nominal = the entry of {45.45, 50, 75, 100, 110, 134.5, 150, 200, 300, 600, 1200} nearest in
+ *    ratio if within 1.5 %, else 0.
+ *  - A stream that repeats one sparse character is periodic at its character rate, and the answer may be that rate.
+ *  - Queue: launches run on the engine's first queue; every push returns when its kernel is done.  Calls are serialised by the engine's mutex.
+ *  - Errors: null arguments and bad parameters are HD_ERR_INVALID; an engine in its failed state is HD_ERR_DEVICE. */
+#define HD_PROBE_CANDIDATES 1024
+#define HD_PROBE_SCALES 9
+typedef struct hd_baud_probe hd_baud_probe;
+typedef struct hd_baud_probe_params {
+    double baud_lo, baud_hi;   /* the candidate grid's ends; defaults 40 and 1300 */
+    double min_coherence;      /* an estimate is valid at rho_max >= this; default 0.5 */
+} hd_baud_probe_params;
+typedef struct hd_baud_estimate {
+    double baud, nominal;      /* nominal = 0: no standard rate within 1.5 % */
+    double rho, rho_max;       /* coherence of candidate k, and the largest of all candidates */
+    uint64_t samples;          /* i: samples pushed since the last reset */
+    uint64_t edges;            /* edges of the scale candidate k listens to */
+    uint32_t k;                /* k* */
+    int32_t  settled, valid;
+    uint32_t _pad;
+} hd_baud_estimate;
+/* The raw accumulators (parity tests).  history: bit (j & 63) of word ((j >> 6) & 7) is the sign bit of the newest sample j' < i with j' = j mod 512. */
+typedef struct hd_baud_probe_stream_state {
+    uint64_t samples;                       /* i */
+    uint64_t edges[HD_PROBE_SCALES];        /* edges seen per scale */
+    uint64_t history[8];
+    uint32_t majority[HD_PROBE_SCALES];     /* m_W[i-1] per scale */
+    uint32_t n_candidates;                  /* HD_PROBE_CANDIDATES */
+} hd_baud_probe_stream_state;
+typedef struct hd_baud_probe_candidate {
+    uint64_t P, Q;
+    uint32_t NB;
+    int32_t  re, im;
+    uint32_t n, cur_block, _pad;
+} hd_baud_probe_candidate;
+void hd_baud_probe_params_default(hd_baud_probe_params* p);
+int  hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* p /* null: the defaults */, hd_baud_probe** out);
+void hd_baud_probe_destroy(hd_baud_probe* p);
+int  hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream /* UINT32_MAX: all */);
+/* Adds, for every stream, the discriminator output of the call delivered last (what hd_stream_demodulated returns), read where the call left it: one
+ * launch for all streams behind a drain of the pipeline, like the data getters (not from inside a callback).  A call that was pushed already, and a
+ * stream whose call produced no output, add nothing: HD_OK. */
+int  hd_baud_probe_push_engine(hd_baud_probe* p);
+/* Rows of any discriminator output: stream s adds n_per_stream[s] (null: n) floats at rows + s * stride, from device memory on the engine's GPU (4-byte
+ * aligned) or from host memory.  The buffer is the caller's again on return. */
+int  hd_baud_probe_push_device(hd_baud_probe* p, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_baud_probe_push_host(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* A copy of the stream's state followed by hd_host_baud_probe's estimate (habdec_amd_host.h). */
+int  hd_baud_probe_estimate(hd_baud_probe* p, uint32_t stream, hd_baud_estimate* out);
+/* Returns HD_PROBE_CANDIDATES; *hdr (optional) is written, and the candidates when cap >= HD_PROBE_CANDIDATES -- with a smaller cap nothing at all is
+ * written.  Negative: HD_ERR_*. */
+int  hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* candidates, size_t cap);
+
+/* ---- framing trial: 7 or 8 data bits, 1 or 2 stop bits? (not in the reference) ----
+ * Once the baud rate is set the bits flow; while a stream's trial is on, the bits delivered for it are also pushed into four text stages (7N1, 7N2, 8N1,
+ * 8N2: formats 0..3) beside its own, in every pipeline mode.  The stream's own text stage, callbacks and getters are untouched.  Turning the trial on
+ * resets it; turning it off drops it.  best = -1 while no format has a CRC-valid sentence; else, among the formats whose sentences_ok is the largest,
+ * the one with the most stop bits, then the most data bits (a one-stop framer also frames a two-stop signal: the stricter format that loses nothing). */
+#define HD_TRIAL_FORMATS 4
+typedef struct hd_format_trial_result {
+    int32_t  best;                 /* format index or -1 */
+    uint32_t best_bits;            /* what hd_stream_set_rtty takes (0 when best = -1) */
+    float    best_stops;
+    uint32_t bits[HD_TRIAL_FORMATS];
+    float    stops[HD_TRIAL_FORMATS];
+    uint32_t _pad;
+    uint64_t sentences_ok[HD_TRIAL_FORMATS], matches[HD_TRIAL_FORMATS], printable[HD_TRIAL_FORMATS];
+} hd_format_trial_result;
+int hd_stream_set_format_trial(hd_engine* e, uint32_t stream, int on);
+int hd_stream_format_trial(hd_engine* e, uint32_t stream, hd_format_trial_result* out);   /* HD_ERR_INVALID while the trial is off */
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,25 @@ void hd_host_survey_window(float w[4096]);
 int  hd_host_survey_detect(const double* power, uint64_t segments, double sampling_rate, const hd_survey_params* p, hd_survey_candidate* out,
                            uint32_t cap, uint32_t* found);
 
+/* ---- baud-rate probe (hd_baud_probe_*, include/habdec_amd.h has the definition): one stream of it in plain C++, sample by sample ----
+ * The same structs and the same integers as the kernel: hd_host_baud_probe_state of the same pushes equals hd_baud_probe_state bit for bit, and
+ * hd_baud_probe_estimate is a copy of the device state followed by the estimate of this file.  `decimated_rate` = fsd; params null: the defaults;
+ * NULL for parameters hd_baud_probe_create refuses.  hd_host_baud_probe_state returns HD_PROBE_CANDIDATES and writes nothing at all when cap is smaller. */
+typedef struct hd_host_baud_probe hd_host_baud_probe;
+hd_host_baud_probe* hd_host_baud_probe_new(double decimated_rate, const hd_baud_probe_params* params);
+void hd_host_baud_probe_free(hd_host_baud_probe*);
+void hd_host_baud_probe_reset(hd_host_baud_probe*);
+void hd_host_baud_probe_push(hd_host_baud_probe*, const float* d, size_t n);
+int  hd_host_baud_probe_state(const hd_host_baud_probe*, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* candidates, size_t cap);
+int  hd_host_baud_probe_estimate(const hd_host_baud_probe*, hd_baud_estimate* out);
+
+/* ---- framing trial (hd_stream_set_format_trial, include/habdec_amd.h): four hd_host_text chains (7N1, 7N2, 8N1, 8N2) over the same bits ---- */
+typedef struct hd_host_format_trial hd_host_format_trial;
+hd_host_format_trial* hd_host_format_trial_new(void);
+void hd_host_format_trial_free(hd_host_format_trial*);
+void hd_host_format_trial_push_bits(hd_host_format_trial*, const uint8_t* bits, size_t n);
+void hd_host_format_trial_get(const hd_host_format_trial*, hd_format_trial_result* out);
+
 #ifdef __cplusplus
 }
 #endif
