@@ -49,6 +49,33 @@ class hd_survey_candidate(C.Structure):
     _fields_ = [("offset_hz", C.c_double), ("snr_db", C.c_double), ("width_hz", C.c_double), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32)]
 
 
+WATERFALL_WORDS, WF_SHORT, WF_BAD, WF_NO_FLOOR = 128, 1, 2, 4
+
+
+class hd_waterfall_params(C.Structure):
+    _fields_ = [("slot_segments", C.c_uint32), ("rows_cap", C.c_uint32), ("threshold_db", C.c_double), ("dc_guard_hz", C.c_double)]
+
+
+class hd_waterfall_row(C.Structure):
+    _fields_ = [("first_sample", C.c_uint64), ("segments", C.c_uint32), ("flags", C.c_uint32), ("floor", C.c_float), ("level", C.c_float),
+                ("n_marked", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# one hd_waterfall_row
+WATERFALL_ROW_DTYPE = np.dtype([("first_sample", "<u8"), ("segments", "<u4"), ("flags", "<u4"), ("floor", "<f4"), ("level", "<f4"), ("n_marked", "<u4"),
+                                ("_pad", "<u4")])
+
+
+class hd_waterfall_track_params(C.Structure):
+    _fields_ = [("merge_hz", C.c_double), ("max_width_hz", C.c_double), ("gap_rows", C.c_uint32), ("min_rows", C.c_uint32)]
+
+
+class hd_waterfall_track(C.Structure):
+    _fields_ = [("first_sample", C.c_uint64), ("end_sample", C.c_uint64), ("first_row", C.c_uint64), ("last_row", C.c_uint64), ("marks", C.c_uint64),
+                ("offset_hz", C.c_double), ("width_hz", C.c_double), ("rows_hit", C.c_uint32), ("bin_lo", C.c_uint32), ("bin_hi", C.c_uint32),
+                ("open", C.c_int32)]
+
+
 PROBE_CANDIDATES, PROBE_SCALES, TRIAL_FORMATS = 1024, 9, 4
 PROBE_WINDOWS = (1, 3, 7, 15, 31, 63, 127, 255, 511)
 
@@ -162,6 +189,22 @@ ENGINE_API = {
     "hd_survey_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
     "hd_survey_params_default": (None, [C.POINTER(hd_survey_params)]),
     "hd_survey_detect": (_int, [_vp, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
+    "hd_waterfall_params_default": (None, [C.POINTER(hd_waterfall_params)]),
+    "hd_waterfall_track_params_default": (None, [C.POINTER(hd_waterfall_track_params)]),
+    "hd_waterfall_create": (_int, [_vp, C.POINTER(hd_waterfall_params), C.POINTER(_vp)]),
+    "hd_waterfall_destroy": (None, [_vp]),
+    "hd_waterfall_reset": (_int, [_vp]),
+    "hd_waterfall_push_device": (_int, [_vp, _vp, C.c_uint64]),
+    "hd_waterfall_push_host": (_int, [_vp, _vp, C.c_uint64]),
+    "hd_waterfall_push_device_fmt": (_int, [_vp, _int, _vp, C.c_uint64]),
+    "hd_waterfall_push_host_fmt": (_int, [_vp, _int, _vp, C.c_uint64]),
+    "hd_waterfall_push_rows": (_int, [_vp, _vp, _vp, _u32, _int]),
+    "hd_waterfall_rows_total": (C.c_uint64, [_vp]),
+    "hd_waterfall_headers": (_int, [_vp, C.c_uint64, _u32, _vp]),
+    "hd_waterfall_marks": (_int, [_vp, C.c_uint64, _u32, _vp]),
+    "hd_waterfall_rows": (_int, [_vp, C.c_uint64, _u32, _vp]),
+    "hd_waterfall_hits": (_int, [_vp, _vp, C.POINTER(C.c_uint64)]),
+    "hd_waterfall_tracks": (_int, [_vp, C.POINTER(hd_waterfall_track_params), C.POINTER(hd_waterfall_track), _u32, C.POINTER(_u32)]),
     "hd_baud_probe_params_default": (None, [C.POINTER(hd_baud_probe_params)]),
     "hd_baud_probe_create": (_int, [_vp, C.POINTER(hd_baud_probe_params), C.POINTER(_vp)]),
     "hd_baud_probe_destroy": (None, [_vp]),
@@ -226,6 +269,9 @@ HOST_API = {
     "hd_host_tune_rotate": (None, [_f32p, _sz, C.c_uint32, C.c_uint32, _f32p]),
     "hd_host_survey_window": (None, [_f32p]),
     "hd_host_survey_detect": (_int, [_f64p, C.c_uint64, _dbl, C.POINTER(hd_survey_params), C.POINTER(hd_survey_candidate), _u32, C.POINTER(_u32)]),
+    "hd_host_waterfall_params_default": (None, [C.POINTER(hd_waterfall_params)]),
+    "hd_host_waterfall_detect_row": (_int, [_vp, _u32, _dbl, C.POINTER(hd_waterfall_params), _vp, _vp]),
+    "hd_host_waterfall_tracks": (_int, [_vp, _vp, C.c_uint64, _dbl, C.POINTER(hd_waterfall_track_params), C.POINTER(hd_waterfall_track), _u32, C.POINTER(_u32)]),
     "hd_host_baud_probe_new": (_vp, [_dbl, C.POINTER(hd_baud_probe_params)]),
     "hd_host_baud_probe_free": (None, [_vp]),
     "hd_host_baud_probe_reset": (None, [_vp]),

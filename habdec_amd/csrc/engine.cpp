@@ -38,6 +38,8 @@
 #include "kernels/launch.h"
 #include "kernels/spectrum_math.h"
 #include "kernels/survey.h"
+#include "kernels/waterfall.h"
+#include "host/waterfall.hpp"
 
 // A launcher (or layout helper) of the kernels that exist once per arithmetic mode (kernels/arith.h): hd::exact::fn or hd::fast::fn by the engine's mode.
 #define HDK(fn, ...) (e->fast ? hd::fast::fn(__VA_ARGS__) : hd::exact::fn(__VA_ARGS__))
@@ -2300,6 +2302,364 @@ int hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candida
     const int rc = hd::survey_detect(pw.data(), segs, sv->e->fs, p, out, cap, found);
     if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "hd_survey_detect needs at least 16 segments and a floor above zero (" + std::to_string(segs) + " segments so far)");
     if (rc) return fail(rc, "hd_survey_detect: bad parameters or a NaN / negative power");
+    return HD_OK;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- waterfall (kernels/waterfall.hip, host/waterfall.hpp) ----------------- */
+
+struct hd_waterfall {
+    hd_engine* e = nullptr;
+    hipStream_t q = nullptr;               // the waterfall's own queue: launches, staging copies and the read-backs
+    hd_waterfall_params par{};
+    uint32_t guard_lo = 0, guard_hi = 0;   // the bins dc_guard_hz takes out
+    const float2* tw = nullptr;            // the engine's twiddles, or own_tw where the engine computes no spectra
+    float2* own_tw = nullptr;
+    float* win = nullptr;                  // [4096] the survey's window table
+    float* factor = nullptr;               // [65] F[s]
+    float* ring = nullptr;                 // [rows_cap][4096]: row r lives at slot r % rows_cap
+    uint32_t* hits = nullptr;              // [4096]
+    hd::WaterfallRec* rec = nullptr;       // [kChunkRows] the detector's records of the chunk in flight
+    hd::WaterfallRec* h_rec = nullptr;     // their page-locked landing place
+    uint32_t* d_seg = nullptr;             // [kChunkRows] hd_waterfall_push_rows: the chunk's segment counts
+    uint32_t* h_hits = nullptr;            // page-locked landing place of hd_waterfall_hits
+    float2* slab = nullptr;                // host and packed pushes: staging for kSlabSegs segments, allocated by the first such push
+    unsigned char* pslab = nullptr;        // packed host pushes: the same segments packed (sized for cs16)
+    uint64_t samples = 0;                  // pushed since creation or reset
+    uint64_t rows_counted = 0;             // unflagged rows
+    std::vector<hd_waterfall_row> headers; // of all rows since creation or reset
+    std::vector<uint32_t> marks;           // [rows][128]
+    static constexpr uint32_t kSlabSegs = 256;    // as hd_survey: (256 + 1) hops = 4 MiB + 16 KiB
+    static constexpr uint32_t kChunkRows = 1024;  // most rows per launch and read-back (528 KiB of records): one k_survey wave per SIMD of the chip
+    uint32_t chunk_rows = kChunkRows;             // HD_WATERFALL_CHUNK, read at creation: fewer, so that short pushes reach the several-launch shapes
+    ~hd_waterfall()
+    {
+        for (void* p : {(void*)own_tw, (void*)win, (void*)factor, (void*)ring, (void*)hits, (void*)rec, (void*)d_seg, (void*)slab, (void*)pslab}) if (p) (void)hipFree(p);
+        if (h_rec) (void)hipHostFree(h_rec);
+        if (h_hits) (void)hipHostFree(h_hits);
+        if (q) (void)hipStreamDestroy(q);
+    }
+};
+
+namespace {
+
+int waterfall_enter(hd_waterfall* wf)
+{
+    if (wf->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + wf->e->fail_cause + ") -- destroy the engine");
+    HD_HIP(hipSetDevice(wf->e->cfg.device));
+    return HD_OK;
+}
+
+bool waterfall_is_device_pointer(const void* p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
+                                                          !(at.type == hipMemoryTypeHost && at.devicePointer))) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return true;
+}
+
+// The detector, the hit counters and the read-back for the n rows a launch has just put into the ring at `slot`; waits for the waterfall's queue and
+// appends headers and marks.  d_seg: the rows' segment counts on the device (null: seg_full each, the last one seg_last); first[b], seg[b]: the same
+// rows' first samples and segment counts for the headers.
+int waterfall_detect_chunk(hd_waterfall* wf, uint32_t slot, uint32_t n, const uint32_t* d_seg, uint32_t seg_full, uint32_t seg_last, const uint64_t* first,
+                           const uint32_t* seg)
+{
+    hd::launch_waterfall_detect(wf->q, n, wf->ring + (size_t)slot * hd::kWaterfallBins, d_seg, seg_full, seg_last, wf->guard_lo, wf->guard_hi, wf->factor, wf->rec);
+    hd::launch_waterfall_hits(wf->q, wf->rec, n, wf->hits);
+    HD_HIP(hipGetLastError());
+    HD_HIP(hipMemcpyAsync(wf->h_rec, wf->rec, (size_t)n * sizeof(hd::WaterfallRec), hipMemcpyDeviceToHost, wf->q));
+    HD_HIP(hipStreamSynchronize(wf->q));
+    for (uint32_t b = 0; b < n; ++b) {
+        const hd::WaterfallRec& r = wf->h_rec[b];
+        hd_waterfall_row h{};
+        h.first_sample = first[b]; h.segments = seg[b]; h.flags = r.flags; h.floor = r.floor; h.level = r.level; h.n_marked = r.n_marked;
+        wf->headers.push_back(h);
+        wf->marks.insert(wf->marks.end(), r.marks, r.marks + hd::kWaterfallWords);
+        if (!r.flags) ++wf->rows_counted;
+    }
+    return HD_OK;
+}
+
+// Rows of segments [seg0, seg1) of a push, read from x (x[0] = sample 2048 base_seg of the push; seg0 - base_seg is a multiple of L): launches of the
+// survey's kernel with run_len = L straight into the ring, cut where the ring wraps and at chunk_rows, each followed by its detector.
+int waterfall_enqueue(hd_waterfall* wf, const float2* x, uint64_t base_seg, uint64_t seg0, uint64_t seg1)
+{
+    const uint32_t L = wf->par.slot_segments;
+    uint64_t first[hd_waterfall::kChunkRows];
+    uint32_t seg[hd_waterfall::kChunkRows];
+    for (uint64_t s = seg0; s < seg1;) {
+        const uint64_t rows_left = (seg1 - s + L - 1) / L;
+        const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
+        const uint32_t n = (uint32_t)std::min<uint64_t>(rows_left, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
+        hd::launch_survey(wf->q, n, x, wf->win, wf->tw, wf->ring + (size_t)slot * hd::kWaterfallBins, s - base_seg, seg1 - base_seg, L);
+        const uint64_t s_end = std::min<uint64_t>(seg1, s + (uint64_t)n * L);
+        const uint32_t seg_last = (uint32_t)(s_end - (s + (uint64_t)(n - 1) * L));
+        for (uint32_t b = 0; b < n; ++b) { first[b] = wf->samples + (s + (uint64_t)b * L) * hd::kSurveyHop; seg[b] = b + 1 == n ? seg_last : L; }
+        if (const int rc = waterfall_detect_chunk(wf, slot, n, nullptr, L, seg_last, first, seg)) return rc;
+        s = s_end;
+    }
+    return HD_OK;
+}
+
+// A push through the staging slab: host cf32 (fmt = HD_IQ_CF32, device = false) or packed IQ from host or device memory.  A slab carries whole rows,
+// so every wave sums the segments it would have summed in one device push.
+int waterfall_push_slabs(hd_waterfall* wf, int fmt, const void* iq, uint64_t n, bool device)
+{
+    const size_t bps = hd::iq_bytes(fmt);
+    const bool packed = fmt != HD_IQ_CF32;
+    const uint64_t n_seg = hd::survey_segments(n);
+    if (n_seg) {
+        if (device && !waterfall_is_device_pointer(iq)) return fail(HD_ERR_INVALID, "IQ pointer is not device memory (the _host calls take host memory)");
+        const size_t slab_samples = (size_t)(hd_waterfall::kSlabSegs + 1) * hd::kSurveyHop;
+        if (!wf->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->slab), slab_samples * sizeof(float2)));
+        if (packed && !device && !wf->pslab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->pslab), slab_samples * 4u));
+        const uint32_t L = wf->par.slot_segments;
+        const uint64_t per_slab = (uint64_t)(hd_waterfall::kSlabSegs / L) * L;
+        const unsigned char* p = static_cast<const unsigned char*>(iq);
+        for (uint64_t s = 0; s < n_seg; s += per_slab) {
+            const uint64_t s1 = std::min(n_seg, s + per_slab);
+            const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
+            const unsigned char* from = p + (size_t)s * hd::kSurveyHop * bps;
+            if (!packed) {
+                HD_HIP(hipMemcpyAsync(wf->slab, from, samples * sizeof(float2), hipMemcpyHostToDevice, wf->q));
+            } else {
+                if (!device) {
+                    HD_HIP(hipMemcpyAsync(wf->pslab, from, samples * bps, hipMemcpyHostToDevice, wf->q));
+                    from = wf->pslab;
+                }
+                if (!hd::launch_iq_unpack(wf->q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, wf->slab, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
+            }
+            if (const int rc = waterfall_enqueue(wf, wf->slab, s, s, s1)) return rc;   // (waits for the queue: the slab is free for the next piece)
+        }
+    }
+    wf->samples += n;
+    return HD_OK;
+}
+
+int waterfall_push_packed(hd_waterfall* wf, int fmt, const void* iq, uint64_t n, bool device)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    const size_t bps = hd::iq_bytes(fmt);
+    if (!bps || fmt == HD_IQ_CF32) return fail(HD_ERR_INVALID, "unknown IQ format (HD_IQ_CF32, HD_IQ_CS16, HD_IQ_CS8, HD_IQ_CU8)");
+    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(HD_ERR_INVALID, "packed IQ base must be aligned to one sample (4 bytes cs16, 2 bytes cs8 / cu8)");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    return waterfall_push_slabs(wf, fmt, iq, n, device);
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_waterfall_params_default(hd_waterfall_params* p) { if (p) hd::waterfall_params_default(p); }
+void hd_waterfall_track_params_default(hd_waterfall_track_params* p) { if (p) hd::waterfall_track_params_default(p); }
+
+int hd_waterfall_create(hd_engine* e, const hd_waterfall_params* p, hd_waterfall** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_waterfall> wf(new hd_waterfall);
+    wf->e = e;
+    if (p) wf->par = *p; else hd::waterfall_params_default(&wf->par);
+    if (!hd::waterfall_params_ok(&wf->par)) return fail(HD_ERR_INVALID, "hd_waterfall_params: slot_segments 16..64, rows_cap >= 1, threshold_db and dc_guard_hz >= 0");
+    if (!hd::waterfall_guard_range(e->fs, wf->par.dc_guard_hz, &wf->guard_lo, &wf->guard_hi)) return fail(HD_ERR_INVALID, "dc_guard_hz leaves no bin");
+    if (const int rc = waterfall_enter(wf.get())) return rc;
+    if (const char* v = getenv("HD_WATERFALL_CHUNK")) wf->chunk_rows = (uint32_t)std::min(std::max(atol(v), 1L), (long)hd_waterfall::kChunkRows);
+    HD_HIP(hipStreamCreateWithFlags(&wf->q, hipStreamNonBlocking));
+    std::vector<float> w(hd::kSurveyBins), f(hd::kWaterfallMaxSeg + 1, 0.0f);
+    hd::survey_window(w.data());
+    for (uint32_t s = 1; s <= hd::kWaterfallMaxSeg; ++s) f[s] = hd::waterfall_factor(wf->par.threshold_db, s);
+    // (plain allocations, filled on the waterfall's queue: nothing here runs on the null stream or waits for the engine's queues)
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->win), w.size() * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->factor), f.size() * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->ring), (size_t)wf->par.rows_cap * hd::kWaterfallBins * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->hits), hd::kWaterfallBins * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->d_seg), hd_waterfall::kChunkRows * sizeof(uint32_t)));
+    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec), hipHostMallocDefault));
+    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_hits), hd::kWaterfallBins * sizeof(uint32_t), hipHostMallocDefault));
+    std::vector<float2> tw;
+    wf->tw = e->fft_tw.p;
+    if (!wf->tw) {   // an engine without spectra holds no twiddles: the same table, the waterfall's own
+        tw.resize(hd::kFftBins);
+        hd::specwave::fft_twiddles(tw.data());
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->own_tw), tw.size() * sizeof(float2)));
+        HD_HIP(hipMemcpyAsync(wf->own_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, wf->q));
+        wf->tw = wf->own_tw;
+    }
+    HD_HIP(hipMemcpyAsync(wf->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, wf->q));
+    HD_HIP(hipMemcpyAsync(wf->factor, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, wf->q));
+    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->q));
+    HD_HIP(hipStreamSynchronize(wf->q));   // (the tables above are locals)
+    *out = wf.release();
+    return HD_OK;
+}
+
+void hd_waterfall_destroy(hd_waterfall* wf)
+{
+    if (!wf) return;
+    hd_engine* e = wf->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    (void)hipSetDevice(e->cfg.device);
+    if (wf->q) (void)hipStreamSynchronize(wf->q);
+    delete wf;
+}
+
+int hd_waterfall_reset(hd_waterfall* wf)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->q));
+    HD_HIP(hipStreamSynchronize(wf->q));
+    wf->headers.clear();
+    wf->marks.clear();
+    wf->samples = 0;
+    wf->rows_counted = 0;
+    return HD_OK;
+}
+
+int hd_waterfall_push_device(hd_waterfall* wf, const void* d_iq, uint64_t n)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (!d_iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    if (reinterpret_cast<uintptr_t>(d_iq) & 7) return fail(HD_ERR_INVALID, "IQ base must be 8-byte aligned");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    const uint64_t n_seg = hd::survey_segments(n);
+    if (n_seg) {
+        // what the kernel reads must be memory the GPU can address: a host pointer HIP does not know never reaches a launch
+        if (!waterfall_is_device_pointer(d_iq)) return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_waterfall_push_host takes host memory)");
+        if (const int rc = waterfall_enqueue(wf, static_cast<const float2*>(d_iq), 0, 0, n_seg)) return rc;
+    }
+    wf->samples += n;
+    return HD_OK;
+}
+
+int hd_waterfall_push_host(hd_waterfall* wf, const float* iq, uint64_t n)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    return waterfall_push_slabs(wf, HD_IQ_CF32, iq, n, false);
+}
+
+int hd_waterfall_push_device_fmt(hd_waterfall* wf, int fmt, const void* d_iq, uint64_t n)
+{
+    if (fmt == HD_IQ_CF32) return hd_waterfall_push_device(wf, d_iq, n);
+    return waterfall_push_packed(wf, fmt, d_iq, n, true);
+}
+
+int hd_waterfall_push_host_fmt(hd_waterfall* wf, int fmt, const void* iq, uint64_t n)
+{
+    if (fmt == HD_IQ_CF32) return hd_waterfall_push_host(wf, static_cast<const float*>(iq), n);
+    return waterfall_push_packed(wf, fmt, iq, n, false);
+}
+
+int hd_waterfall_push_rows(hd_waterfall* wf, const float* rows, const uint32_t* segments, uint32_t n_rows, int device)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (!rows || !segments) return fail(HD_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
+    for (uint32_t r = 0; r < n_rows; ++r)
+        if (segments[r] < 1 || segments[r] > hd::kWaterfallMaxSeg) return fail(HD_ERR_INVALID, "segments[r] must be 1..64");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    if (!n_rows) return HD_OK;
+    if (device && !waterfall_is_device_pointer(rows)) return fail(HD_ERR_INVALID, "rows pointer is not device memory (device = 0 takes host memory)");
+    uint64_t first[hd_waterfall::kChunkRows];
+    for (uint32_t r = 0; r < n_rows;) {
+        const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
+        const uint32_t n = std::min(n_rows - r, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
+        HD_HIP(hipMemcpyAsync(wf->ring + (size_t)slot * hd::kWaterfallBins, rows + (size_t)r * hd::kWaterfallBins, (size_t)n * hd::kWaterfallBins * sizeof(float),
+                              device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, wf->q));
+        HD_HIP(hipMemcpyAsync(wf->d_seg, segments + r, n * sizeof(uint32_t), hipMemcpyHostToDevice, wf->q));
+        uint64_t at = wf->samples;
+        for (uint32_t b = 0; b < n; ++b) { first[b] = at; at += (uint64_t)segments[r + b] * hd::kSurveyHop; }
+        if (const int rc = waterfall_detect_chunk(wf, slot, n, wf->d_seg, 0, 0, first, segments + r)) return rc;
+        wf->samples = at;
+        r += n;
+    }
+    return HD_OK;
+}
+
+uint64_t hd_waterfall_rows_total(hd_waterfall* wf)
+{
+    if (!wf) return 0;
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    return wf->headers.size();
+}
+
+int hd_waterfall_headers(hd_waterfall* wf, uint64_t first_row, uint32_t n, hd_waterfall_row* out)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (n && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (first_row > wf->headers.size() || n > wf->headers.size() - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
+    if (n) std::memcpy(out, wf->headers.data() + first_row, (size_t)n * sizeof(hd_waterfall_row));
+    return HD_OK;
+}
+
+int hd_waterfall_marks(hd_waterfall* wf, uint64_t first_row, uint32_t n, uint32_t* out)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (n && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (first_row > wf->headers.size() || n > wf->headers.size() - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
+    if (n) std::memcpy(out, wf->marks.data() + first_row * hd::kWaterfallWords, (size_t)n * hd::kWaterfallWords * sizeof(uint32_t));
+    return HD_OK;
+}
+
+int hd_waterfall_rows(hd_waterfall* wf, uint64_t first_row, uint32_t n, float* out)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (n && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    const uint64_t total = wf->headers.size(), cap = wf->par.rows_cap;
+    if (first_row > total || n > total - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
+    if (n && first_row + cap < total) return fail(HD_ERR_INVALID, "the first of these rows has left the ring (rows_cap = " + std::to_string(cap) + ")");
+    for (uint32_t r = 0; r < n;) {           // at most two pieces: the ring wraps once inside rows_cap rows
+        const uint32_t slot = (uint32_t)((first_row + r) % cap);
+        const uint32_t k = (uint32_t)std::min<uint64_t>(n - r, cap - slot);
+        HD_HIP(hipMemcpyAsync(out + (size_t)r * hd::kWaterfallBins, wf->ring + (size_t)slot * hd::kWaterfallBins, (size_t)k * hd::kWaterfallBins * sizeof(float),
+                              hipMemcpyDeviceToHost, wf->q));
+        r += k;
+    }
+    HD_HIP(hipStreamSynchronize(wf->q));
+    return HD_OK;
+}
+
+int hd_waterfall_hits(hd_waterfall* wf, uint32_t hits[4096], uint64_t* rows_counted)
+{
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (!hits) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (const int rc = waterfall_enter(wf)) return rc;
+    HD_HIP(hipMemcpyAsync(wf->h_hits, wf->hits, hd::kWaterfallBins * sizeof(uint32_t), hipMemcpyDeviceToHost, wf->q));
+    HD_HIP(hipStreamSynchronize(wf->q));
+    std::memcpy(hits, wf->h_hits, hd::kWaterfallBins * sizeof(uint32_t));
+    if (rows_counted) *rows_counted = wf->rows_counted;
+    return HD_OK;
+}
+
+int hd_waterfall_tracks(hd_waterfall* wf, const hd_waterfall_track_params* p, hd_waterfall_track* out, uint32_t cap, uint32_t* found)
+{
+    if (found) *found = 0;
+    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
+    if (!found || (cap && !out)) return fail(HD_ERR_INVALID, "null argument");
+    hd_waterfall_track_params def;
+    hd::waterfall_track_params_default(&def);
+    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
+    if (hd::waterfall_tracks(wf->headers.data(), wf->marks.data(), wf->headers.size(), wf->e->fs, p ? p : &def, out, cap, found))
+        return fail(HD_ERR_INVALID, "hd_waterfall_tracks: merge_hz and max_width_hz must be >= 0");
     return HD_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "host/iq_file_batch.hpp"
 #include "host/survey.hpp"
 #include "host/tune_host.hpp"
+#include "host/waterfall.hpp"
 #include "kernels/exact_math.h"
 
 struct hd_host_rtty { hd::RttyFramer f; };
@@ -280,6 +281,19 @@ int hd_host_survey_detect(const double* power, uint64_t segments, double samplin
                           uint32_t* found)
 {
     return hd::survey_detect(power, segments, sampling_rate, p, out, cap, found);
+}
+
+/* ---- waterfall (kernels/waterfall.hip; see host/waterfall.hpp) ---- */
+void hd_host_waterfall_params_default(hd_waterfall_params* p) { if (p) hd::waterfall_params_default(p); }
+int hd_host_waterfall_detect_row(const float* row, uint32_t segments, double sampling_rate, const hd_waterfall_params* p, hd_waterfall_row* hdr,
+                                 uint32_t* marks)
+{
+    return hd::waterfall_detect_row(row, segments, sampling_rate, p, hdr, marks);
+}
+int hd_host_waterfall_tracks(const hd_waterfall_row* headers, const uint32_t* marks, uint64_t n_rows, double sampling_rate,
+                             const hd_waterfall_track_params* p, hd_waterfall_track* out, uint32_t cap, uint32_t* found)
+{
+    return hd::waterfall_tracks(headers, marks, n_rows, sampling_rate, p, out, cap, found);
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

@@ -233,6 +233,12 @@ class Engine:
         self._surveys = getattr(self, "_surveys", []) + [sv]
         return sv
 
+    def waterfall(self, **params) -> "Waterfall":
+        """A waterfall on this engine's GPU and sampling rate (hd_waterfall_*; params as hd_waterfall_params): close it before the engine."""
+        wf = Waterfall(self, **params)
+        self._surveys = getattr(self, "_surveys", []) + [wf]
+        return wf
+
     def baud_probe(self, **params) -> "BaudProbe":
         """A baud-rate probe on this engine's streams (hd_baud_probe_*; params as hd_baud_probe_params): close it before the engine."""
         p = BaudProbe(self, **params)
@@ -488,6 +494,142 @@ class Survey:
 
     def reset(self):
         check(self.L.hd_survey_reset(self.h))
+
+
+def _tracks(out, n) -> list:
+    keys = ("first_sample", "end_sample", "first_row", "last_row", "marks", "offset_hz", "width_hz", "rows_hit", "bin_lo", "bin_hi", "open")
+    return [{k: getattr(t, k) for k in keys} for t in out[:n]]
+
+
+def _track_params(L, params):
+    p = capi.hd_waterfall_track_params()
+    L.hd_waterfall_track_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, int(v) if k in ("gap_rows", "min_rows") else float(v))
+    return p
+
+
+def waterfall_tracks(headers: np.ndarray, marks: np.ndarray, sampling_rate: float, cap: int = 64, **params) -> list:
+    """hd_host_waterfall_tracks over headers (capi.WATERFALL_ROW_DTYPE [n]) and marks (uint32 [n, 128]) (no GPU): tracks as dicts, ordered by
+    first_sample, then offset_hz; params as hd_waterfall_track_params."""
+    L = lib()
+    p = _track_params(L, params)
+    headers = np.ascontiguousarray(headers, capi.WATERFALL_ROW_DTYPE)
+    marks = np.ascontiguousarray(marks, np.uint32).reshape(len(headers), capi.WATERFALL_WORDS)
+    out, found = (capi.hd_waterfall_track * max(cap, 1))(), C.c_uint32(0)
+    rc = L.hd_host_waterfall_tracks(headers.ctypes.data, marks.ctypes.data, len(headers), float(sampling_rate), C.byref(p), out, cap, C.byref(found))
+    if rc:
+        raise HabdecError(f"habdec_amd error {rc}: hd_host_waterfall_tracks")
+    if found.value > cap:
+        return waterfall_tracks(headers, marks, sampling_rate, found.value, **params)
+    return _tracks(out, found.value)
+
+
+class Waterfall:
+    """The survey's rows over time, the per-row detector on the GPU and the tracks on top of its marks (hd_waterfall_*, include/habdec_amd.h)."""
+
+    def __init__(self, eng: Engine, **params):
+        self.L, self.eng = eng.L, eng
+        p = capi.hd_waterfall_params()
+        self.L.hd_waterfall_params_default(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, int(v) if k in ("slot_segments", "rows_cap") else float(v))
+        h = C.c_void_p()
+        check(self.L.hd_waterfall_create(eng.h, C.byref(p), C.byref(h)))
+        self.h, self.params = h, p
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_waterfall_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push_device(self, dev_ptr: int, n: int, fmt=None):
+        """n cf32 samples at a device address, or with fmt n packed ones; returns when the new rows' headers and marks are on the host."""
+        if fmt is not None:
+            check(self.L.hd_waterfall_push_device_fmt(self.h, capi.iq_fmt(fmt), dev_ptr, n))
+            return
+        check(self.L.hd_waterfall_push_device(self.h, dev_ptr, n))
+
+    def push_host(self, iq: np.ndarray, fmt=None):
+        """fmt: iq is packed, an integer array [n, 2] (or flat, I then Q) of the format's dtype (hd_waterfall_push_host_fmt)."""
+        if fmt is not None and capi.iq_fmt(fmt) != capi.IQ_CF32:
+            fmt = capi.iq_fmt(fmt)
+            iq = np.ascontiguousarray(iq).reshape(-1)
+            if fmt in capi.IQ_DTYPES and iq.dtype != capi.IQ_DTYPES[fmt]:
+                raise HabdecError(f"IQ format {fmt} wants dtype {capi.IQ_DTYPES[fmt]}, not {iq.dtype}")
+            check(self.L.hd_waterfall_push_host_fmt(self.h, fmt, iq.ctypes.data, iq.size // 2))
+            return
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        check(self.L.hd_waterfall_push_host(self.h, iq.ctypes.data, iq.size))
+
+    def push_rows(self, rows, segments, n_rows: int | None = None):
+        """Rows of float sums made elsewhere: a float32 array [n, 4096] with segments [n], or a device address with n_rows (hd_waterfall_push_rows)."""
+        seg = np.ascontiguousarray(segments, np.uint32).reshape(-1)
+        if isinstance(rows, int):
+            check(self.L.hd_waterfall_push_rows(self.h, rows, seg.ctypes.data, len(seg) if n_rows is None else n_rows, 1))
+            return
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 4096)
+        assert len(rows) == len(seg), (rows.shape, seg.shape)
+        check(self.L.hd_waterfall_push_rows(self.h, rows.ctypes.data, seg.ctypes.data, len(rows), 0))
+
+    def rows_total(self) -> int:
+        return int(self.L.hd_waterfall_rows_total(self.h))
+
+    def _range(self, first, n):
+        return (first, self.rows_total() - first) if n is None else (first, n)
+
+    def headers(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """A structured array (capi.WATERFALL_ROW_DTYPE) of rows [first, first + n); n = None: all from `first` on."""
+        first, n = self._range(first, n)
+        out = np.zeros(max(n, 0), capi.WATERFALL_ROW_DTYPE)
+        check(self.L.hd_waterfall_headers(self.h, first, n, out.ctypes.data))
+        return out
+
+    def marks(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """uint32 [n, 128]: bit i & 31 of word i >> 5 is bin i."""
+        first, n = self._range(first, n)
+        out = np.zeros((max(n, 0), capi.WATERFALL_WORDS), np.uint32)
+        check(self.L.hd_waterfall_marks(self.h, first, n, out.ctypes.data))
+        return out
+
+    def marks_bool(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """bool [n, 4096]"""
+        m = self.marks(first, n)
+        return ((m[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(len(m), 4096)
+
+    def rows(self, first: int, n: int, normalised: bool = False) -> np.ndarray:
+        """float32 [n, 4096] raw sums of rows still in the ring; normalised: float64, divided by segments * sum w^2 (the survey's scale)."""
+        out = np.zeros((n, 4096), np.float32)
+        check(self.L.hd_waterfall_rows(self.h, first, n, out.ctypes.data))
+        if not normalised:
+            return out
+        w = np.zeros(4096, np.float32)
+        self.L.hd_host_survey_window(w)
+        return out.astype(np.float64) / (self.headers(first, n)["segments"].astype(np.float64)[:, None] * float(np.sum(w.astype(np.float64) ** 2)))
+
+    def hits(self):
+        """(uint32[4096], rows_counted)"""
+        h, k = np.zeros(4096, np.uint32), C.c_uint64(0)
+        check(self.L.hd_waterfall_hits(self.h, h.ctypes.data, C.byref(k)))
+        return h, int(k.value)
+
+    def tracks(self, cap: int = 64, **params) -> list:
+        """Tracks as dicts (offset_hz is what Engine.set_front_tune takes); params as hd_waterfall_track_params."""
+        p = _track_params(self.L, params)
+        out, found = (capi.hd_waterfall_track * max(cap, 1))(), C.c_uint32(0)
+        check(self.L.hd_waterfall_tracks(self.h, C.byref(p), out, cap, C.byref(found)))
+        if found.value > cap:
+            return self.tracks(found.value, **params)
+        return _tracks(out, found.value)
+
+    def reset(self):
+        check(self.L.hd_waterfall_reset(self.h))
 
 
 class IqFiles:

@@ -343,6 +343,104 @@ void hd_survey_params_default(hd_survey_params* p);
  * are written, strongest first.  Fewer than 16 segments: HD_ERR_UNSUPPORTED. */
 int  hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap, uint32_t* found);
 
+/* ---- waterfall: WHEN does a payload transmit? (not in the reference) ----
+ * The survey sums a whole capture into one spectrum; the waterfall keeps the float rows the survey's kernel forms per run of segments, runs the survey's
+ * marking rule on every row on the GPU, counts hits per bin there, and links the marks into tracks on the host: offset_hz (what
+ * hd_stream_set_front_tune takes), first_sample and end_sample (when to hd_baud_probe_reset a stream, and when a stream is free again).
+ *  - Segments: the survey's.  A push of n samples has n < 4096 ? 0 : 1 + (n - 4096) / 2048 segments; segment s is samples [2048 s, 2048 s + 4096) of THAT
+ *    push.  Segments never straddle pushes.  A push shorter than 4096 samples adds no row, but its samples still count towards first_sample of later rows.
+ *  - Rows: with L = slot_segments, row j of a push is the float sum, in segment order, of re^2 + im^2 per bin over segments [j L, min((j + 1) L, n_seg)) --
+ *    per segment the survey's window, in-wave transform and fftshifted store: exactly what one wave of the survey's kernel produces for a run of L.
+ *    first_sample = samples pushed before this push + 2048 j L.  The last row of a push may hold fewer than L segments; below 16 it is flagged
+ *    HD_WF_SHORT.  Rows are raw sums: divide by segments * sum w^2 (hd_host_survey_window) for the survey's scale.  So push pieces of
+ *    4096 + (k L - 1) * 2048 samples (k whole rows and no sample unused), or much larger ones.
+ *  - Detector, per row, on the GPU, all in float, every operation rounded once (hd_host_waterfall_detect_row is the same in plain C++):
+ *     1. If any of the 4096 bins has a bit pattern above 0x7F800000 (a NaN or a set sign bit) the row is HD_WF_BAD.
+ *     2. Eligible bins: those with |f_i| >= dc_guard_hz, f_i = (i - 2048) fs / 4096.  A guard that leaves no bin: hd_waterfall_create is HD_ERR_INVALID.
+ *     3. floor = the median of the m eligible values: s[m / 2] for m odd, 0.5f * (s[m / 2 - 1] + s[m / 2]) for m even, s in ascending order (for the
+ *        patterns step 1 admits, the order of the patterns read as unsigned integers).  floor == 0 or floor == +inf: the row is HD_WF_NO_FLOOR.
+ *     4. level = floor * F[segments], F[s] = (float)max(10^(threshold_db / 10), 1 + 8 / sqrt(s)), computed in double on the host.
+ *     5. Bit i & 31 of word i >> 5 is set when bin i is eligible and row[i] >= level; n_marked is the popcount.
+ *     6. A flagged row has no marks and does not count for hits.  floor and level are 0 in a BAD or NO_FLOOR row; a row that is only SHORT has both.
+ *  - Hits: hits[i] = the unflagged rows since creation or reset in which bin i is marked, counted on the GPU in integers; rows_counted = those rows.
+ *  - Tracks (hd_host_waterfall_tracks is the function; g = ceil(merge_hz / (fs / 4096)) as in the survey):
+ *     1. Rows are processed in order; a flagged row is a row without marks.
+ *     2. A row's clusters are the survey's: runs of marked bins with at most g unmarked bins between neighbours, no wrap-around; each carries
+ *        (lo, hi, n, sum of indices).
+ *     3. In ascending lo, a cluster joins the first open track, in order of creation, with lo <= t.hi + g && hi + g >= t.lo (t.lo, t.hi: the track's
+ *        cumulative range, which the cluster widens); a cluster that joins none opens a track.
+ *     4. After row r a track with r - last_row > gap_rows is closed.
+ *    Tracks with rows_hit < min_rows, or wider than max_width_hz when that is > 0, are dropped; the rest come ordered by first_sample, then offset_hz.
+ *    *found = tracks, the first min(found, cap) are written.
+ *  - Queue and lifetime: like the survey -- a HIP stream of its own, the engine's device, sampling rate, twiddles and mutex; it never waits for, drains or
+ *    reorders the engine's pipeline; destroy it before the engine.  Every push returns when the caller's buffer is theirs again and the new rows' headers
+ *    and marks are in host memory (528 bytes per row read back on the waterfall's queue).  A push is worked off in launches of at most 1024 rows (environment
+ *    HD_WATERFALL_CHUNK, read by hd_waterfall_create; rows, headers and marks do not depend on it), cut also where the ring wraps.  The float rows stay in a device ring of rows_cap rows;
+ *    headers and marks of all rows since creation or reset are kept on the host.
+ *  - Same rows from every source: host and packed pushes go through a staging slab that carries whole rows; rows, headers and marks are byte-identical
+ *    to one hd_waterfall_push_device of the same samples (packed: of hd_host_iq_convert's floats).
+ *  - hd_waterfall_push_rows: n_rows rows of 4096 float sums made elsewhere, of segments[r] segments each (1..64; a host array), from host (device = 0) or
+ *    device memory (4-byte aligned); they are copied into the ring and go through the same detector.  Row r's first_sample is the sample count so
+ *    far, which the row advances by 2048 segments[r].
+ *  - Errors: null arguments, slot_segments outside 16..64, rows_cap == 0, negative or NaN parameters, a cf32 base off 8 bytes or a packed base off its
+ *    sample boundary, a pointer that is not device memory where one is wanted, segments[r] outside 1..64, rows outside the kept range are
+ *    HD_ERR_INVALID; an engine in its failed state is HD_ERR_DEVICE. */
+#define HD_WATERFALL_WORDS 128          /* 4096 mark bits per row */
+#define HD_WF_SHORT    1u               /* fewer than 16 segments: no marks */
+#define HD_WF_BAD      2u               /* some bin of the row is NaN or has its sign bit set: no marks */
+#define HD_WF_NO_FLOOR 4u               /* floor == 0 or floor == +inf: no marks */
+typedef struct hd_waterfall hd_waterfall;
+typedef struct hd_waterfall_params {
+    uint32_t slot_segments;   /* L: segments summed per row, 16..64; default 16 */
+    uint32_t rows_cap;        /* float rows kept on the device (a ring), >= 1; default 1024 (16 MiB) */
+    double   threshold_db;    /* as hd_survey_params; default 6 */
+    double   dc_guard_hz;     /* as hd_survey_params; default 0 */
+} hd_waterfall_params;
+typedef struct hd_waterfall_row {       /* 32 bytes */
+    uint64_t first_sample;    /* absolute index, since creation / reset, of the row's first sample */
+    uint32_t segments;        /* 1..L */
+    uint32_t flags;           /* HD_WF_* */
+    float    floor, level;    /* 0 where the flags leave them undefined */
+    uint32_t n_marked, _pad;
+} hd_waterfall_row;
+typedef struct hd_waterfall_track_params {
+    double   merge_hz;        /* as hd_survey_params, within a row and between a cluster and a track; default 1500 */
+    double   max_width_hz;    /* > 0: tracks wider than this are dropped; default 0 */
+    uint32_t gap_rows;        /* a track survives this many rows without a mark; default 1 */
+    uint32_t min_rows;        /* tracks marked in fewer rows are dropped; default 3 */
+} hd_waterfall_track_params;
+typedef struct hd_waterfall_track {     /* 72 bytes */
+    uint64_t first_sample;    /* first_sample of first_row */
+    uint64_t end_sample;      /* first_sample of last_row + (segments of last_row + 1) * 2048: one past the last sample of the last marked row */
+    uint64_t first_row, last_row;
+    uint64_t marks;           /* marked bins over all its rows */
+    double   offset_hz;       /* (sum of marked indices / marks - 2048) fs / 4096: what hd_stream_set_front_tune takes */
+    double   width_hz;        /* (bin_hi - bin_lo + 1) fs / 4096 */
+    uint32_t rows_hit;        /* distinct rows with a mark of the track */
+    uint32_t bin_lo, bin_hi;  /* cumulative range */
+    int32_t  open;            /* 1: still open after the last row (the payload may be going on) */
+} hd_waterfall_track;
+void hd_waterfall_params_default(hd_waterfall_params* p);
+void hd_waterfall_track_params_default(hd_waterfall_track_params* p);
+int  hd_waterfall_create(hd_engine* e, const hd_waterfall_params* p /* null: defaults */, hd_waterfall** out);
+void hd_waterfall_destroy(hd_waterfall* wf);
+int  hd_waterfall_reset(hd_waterfall* wf);                 /* rows, hits and the sample count = 0 */
+/* n cf32 samples in device memory (as hd_survey_push_device) / in host memory; packed IQ (HD_IQ_*) from either.  All four return when the buffer is the
+ * caller's again and the push's headers and marks are in host memory. */
+int  hd_waterfall_push_device(hd_waterfall* wf, const void* d_iq, uint64_t n);
+int  hd_waterfall_push_host(hd_waterfall* wf, const float* iq, uint64_t n);
+int  hd_waterfall_push_device_fmt(hd_waterfall* wf, int fmt, const void* d_iq, uint64_t n);
+int  hd_waterfall_push_host_fmt(hd_waterfall* wf, int fmt, const void* iq, uint64_t n);
+/* rows of float sums made elsewhere (and the detector's test door): n_rows rows of 4096 floats, segments[r] each, host or device memory */
+int  hd_waterfall_push_rows(hd_waterfall* wf, const float* rows, const uint32_t* segments, uint32_t n_rows, int device);
+uint64_t hd_waterfall_rows_total(hd_waterfall* wf);        /* rows since creation or reset (0 for a null waterfall) */
+/* rows [first_row, first_row + n) must exist (n may be 0) */
+int  hd_waterfall_headers(hd_waterfall* wf, uint64_t first_row, uint32_t n, hd_waterfall_row* out);
+int  hd_waterfall_marks(hd_waterfall* wf, uint64_t first_row, uint32_t n, uint32_t* out /* n * 128 words */);
+int  hd_waterfall_rows(hd_waterfall* wf, uint64_t first_row, uint32_t n, float* out /* n * 4096 */);   /* only rows still in the ring, else HD_ERR_INVALID */
+int  hd_waterfall_hits(hd_waterfall* wf, uint32_t hits[4096], uint64_t* rows_counted);
+int  hd_waterfall_tracks(hd_waterfall* wf, const hd_waterfall_track_params* p /* null: defaults */, hd_waterfall_track* out, uint32_t cap, uint32_t* found);
+
 /* ---- baud-rate probe: what is a stream's symbol rate? (not in the reference, which is told it: Decoder::baud()) ----
  * survey -> front tune -> AFC -> PROBE -> hd_stream_set_baud -> framing trial (below) -> hd_stream_set_rtty.  A probe is attached to an engine like a
  * survey (its device and mutex; destroy it before the engine) and accumulates, per stream, integer statistics of the discriminator output

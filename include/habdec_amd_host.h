@@ -161,6 +161,20 @@ void hd_host_survey_window(float w[4096]);
 int  hd_host_survey_detect(const double* power, uint64_t segments, double sampling_rate, const hd_survey_params* p, hd_survey_candidate* out,
                            uint32_t cap, uint32_t* found);
 
+/* ---- waterfall (hd_waterfall_*, include/habdec_amd.h has the contract): the row detector and the tracker in plain C++ ----
+ * hd_host_waterfall_detect_row: the detector's steps 1-6 on one row of 4096 float sums of `segments` (1..64) segments; of p only threshold_db and
+ *   dc_guard_hz are looked at.  Writes hdr->segments, flags, floor, level and n_marked (first_sample and _pad = 0) and the 128 mark words -- bit for bit
+ *   what the GPU's detector leaves for the same row.  Null arguments, segments outside 1..64, sampling_rate <= 0, a negative or NaN parameter or a guard
+ *   that leaves no bin: HD_ERR_INVALID.
+ * hd_host_waterfall_tracks: the tracker over headers[n_rows] and marks[n_rows][128] (hd_waterfall_tracks calls it with the rows it keeps).  Null
+ *   arguments (out may be null when cap is 0; headers and marks when n_rows is 0), sampling_rate <= 0, a negative or NaN merge_hz or max_width_hz:
+ *   HD_ERR_INVALID. */
+void hd_host_waterfall_params_default(hd_waterfall_params* p);
+int  hd_host_waterfall_detect_row(const float* row, uint32_t segments, double sampling_rate, const hd_waterfall_params* p, hd_waterfall_row* hdr,
+                                  uint32_t* marks);
+int  hd_host_waterfall_tracks(const hd_waterfall_row* headers, const uint32_t* marks, uint64_t n_rows, double sampling_rate,
+                              const hd_waterfall_track_params* p, hd_waterfall_track* out, uint32_t cap, uint32_t* found);
+
 /* ---- baud-rate probe (hd_baud_probe_*, include/habdec_amd.h has the definition): one stream of it in plain C++, sample by sample ----
  * The same structs and the same integers as the kernel: hd_host_baud_probe_state of the same pushes equals hd_baud_probe_state bit for bit, and
  * hd_baud_probe_estimate is a copy of the device state followed by the estimate of this file.  `decimated_rate` = fsd; params null: the defaults;
