@@ -104,6 +104,20 @@ class hd_format_trial_result(C.Structure):
                 ("matches", C.c_uint64 * TRIAL_FORMATS), ("printable", C.c_uint64 * TRIAL_FORMATS)]
 
 
+class hd_clocked_params(C.Structure):
+    _fields_ = [("record_cap", C.c_uint32), ("repair_bits", C.c_uint32), ("repair_flips", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class hd_clocked_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("samples", "cursor", "characters", "rejects", "dropped", "matches_failed", "sentences_plain", "sentences_repaired")]
+
+
+# one hd_clocked_record, one hd_clocked_sentence
+CLOCKED_RECORD_DTYPE = np.dtype([("pos", "<u8"), ("data", "<i4", (8,)), ("start", "<i4"), ("stop", "<i4"), ("stop2", "<i4"), ("ch", "<u4")])
+CLOCKED_SENTENCE_DTYPE = np.dtype([("pos", "<u8"), ("flips", "<u4"), ("len", "<u4"), ("text", "S496")])
+CLOCKED_MAX_SPB, CLOCKED_RING, CLOCKED_CHUNK = 2048, 32768, 4096
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -214,6 +228,17 @@ ENGINE_API = {
     "hd_baud_probe_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
     "hd_baud_probe_estimate": (_int, [_vp, _u32, C.POINTER(hd_baud_estimate)]),
     "hd_baud_probe_state": (_int, [_vp, _u32, C.POINTER(hd_baud_probe_stream_state), _vp, _sz]),
+    "hd_clocked_params_default": (None, [C.POINTER(hd_clocked_params)]),
+    "hd_clocked_create": (_int, [_vp, C.POINTER(hd_clocked_params), C.POINTER(_vp)]),
+    "hd_clocked_destroy": (None, [_vp]),
+    "hd_clocked_reset": (_int, [_vp, _u32]),
+    "hd_clocked_set_modem": (_int, [_vp, _u32, _dbl, _u32, _u32, _int]),
+    "hd_clocked_push_engine": (_int, [_vp]),
+    "hd_clocked_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_clocked_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_clocked_records": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_clocked_take_sentences": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_clocked_stats": (_int, [_vp, _u32, C.POINTER(hd_clocked_counters)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -278,6 +303,15 @@ HOST_API = {
     "hd_host_baud_probe_push": (None, [_vp, _f32p, _sz]),
     "hd_host_baud_probe_state": (_int, [_vp, C.POINTER(hd_baud_probe_stream_state), _vp, _sz]),
     "hd_host_baud_probe_estimate": (_int, [_vp, C.POINTER(hd_baud_estimate)]),
+    "hd_host_clocked_new": (_vp, [_dbl, C.POINTER(hd_clocked_params)]),
+    "hd_host_clocked_free": (None, [_vp]),
+    "hd_host_clocked_reset": (None, [_vp]),
+    "hd_host_clocked_set_modem": (_int, [_vp, _dbl, _u32, _u32, _int]),
+    "hd_host_clocked_push": (None, [_vp, _f32p, _sz]),
+    "hd_host_clocked_records": (_int, [_vp, _vp, _sz]),
+    "hd_host_clocked_take_sentences": (_int, [_vp, _vp, _sz]),
+    "hd_host_clocked_stats": (_int, [_vp, C.POINTER(hd_clocked_counters)]),
+    "hd_host_chase_repair": (_int, [C.c_char_p, _sz, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

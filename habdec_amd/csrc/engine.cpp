@@ -32,6 +32,7 @@
 #include "host/iq_file_batch.hpp"
 #include "host/survey.hpp"
 #include "host/baud_probe.hpp"
+#include "host/clocked.hpp"
 #include "host/format_trial.hpp"
 #include "host/text_stage.hpp"
 #include "host/tune_host.hpp"
@@ -2937,6 +2938,331 @@ int hd_debug_baud_probe_push_timed(hd_baud_probe* p, float* kernel_ms, double* h
     (void)hipEventDestroy(p->t0); (void)hipEventDestroy(p->t1);
     p->t0 = p->t1 = nullptr;
     return rc;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- clocked decoder (kernels/clocked.hip) -------------------------------- */
+
+struct hd_clocked {
+    hd_engine* e = nullptr;
+    hd_clocked_params prm{};
+    uint32_t S = 0;
+    hd::ClockedState* st = nullptr;              // [S]
+    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_CLOCKED_RING running sums | guard
+    uint32_t* rec = nullptr;                     // [S][rec_stride]: guard | record_cap records | guard
+    size_t ring_stride = 0, rec_stride = 0;
+    float* slab = nullptr;                       // hd_clocked_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::ClockedSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    std::vector<hd::ClockedState> modem;         // [S]: the state a reset gives the stream (F = 0: off)
+    std::vector<hd::ClockedText> tx;             // [S]
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
+    ~hd_clocked()
+    {
+        for (void* p : {(void*)st, (void*)ring, (void*)rec, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+int clocked_enter(hd_clocked* c)
+{
+    if (c->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + c->e->fail_cause + ") -- destroy the engine");
+    HD_HIP(hipSetDevice(c->e->cfg.device));
+    return HD_OK;
+}
+
+// src[s].p, sym, ring_mask and n_total are written: one launch per HD_CLOCKED_CHUNK samples of the longest row, each waited for.
+int clocked_launch(hd_clocked* c, uint32_t max_n)
+{
+    hipStream_t q = c->e->qa;
+    if (c->t0) HD_HIP(hipEventRecord(c->t0, q));
+    for (uint32_t off = 0; off < max_n; off += HD_CLOCKED_CHUNK) {
+        uint32_t lds_words = 64;
+        for (uint32_t s = 0; s < c->S; ++s) {
+            hd::ClockedSrc& d = c->src.p[s];
+            d.off = off;
+            d.n = d.n_total > off ? std::min<uint32_t>(HD_CLOCKED_CHUNK, d.n_total - off) : 0u;
+            if (c->modem[s].F) lds_words = std::max(lds_words, hd::clocked_window_words(c->modem[s], d.n));
+        }
+        std::atomic_thread_fence(std::memory_order_release);
+        if (!hd::launch_clocked(q, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, lds_words))
+            return fail(HD_ERR_DEVICE, "clocked decoder: the launch's window does not fit the LDS");
+        HD_HIP(hipGetLastError());
+        if (c->t1 && off + HD_CLOCKED_CHUNK >= max_n) HD_HIP(hipEventRecord(c->t1, q));
+        HD_HIP(hipStreamSynchronize(q));
+    }
+    return HD_OK;
+}
+
+int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = c->e->qa;
+    HD_HIP(hipMemcpyAsync(c->st + s0, c->modem.data() + s0, (size_t)ns * sizeof(hd::ClockedState), hipMemcpyHostToDevice, q));
+    HD_HIP(hipMemset2DAsync(c->ring + (size_t)s0 * c->ring_stride + hd::kClockedGuard, c->ring_stride * sizeof(uint32_t), 0,
+                            (size_t)HD_CLOCKED_RING * sizeof(uint32_t), ns, q));
+    HD_HIP(hipStreamSynchronize(q));
+    for (uint32_t s = s0; s < s0 + ns; ++s) { c->tx[s].reset(); c->tx[s].nbits = c->modem[s].nbits; }
+    return HD_OK;
+}
+
+int clocked_check_rows(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, uint32_t* max_n, size_t* total)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (!rows) return fail(HD_ERR_INVALID, "null rows");
+    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
+    *max_n = 0; *total = 0;
+    for (uint32_t s = 0; s < c->S; ++s) {
+        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
+        *max_n = std::max(*max_n, ns); *total += ns;
+    }
+    if (c->S > 1 && *max_n > stride) return fail(HD_ERR_INVALID, "a row is longer than the stride");
+    return HD_OK;
+}
+
+// The stream's waiting records leave the ring through its text stage; up to cap of them are copied to out (out null: none are kept).
+int clocked_drain(hd_clocked* c, uint32_t s, hd_clocked_record* out, size_t cap, size_t* n_out)
+{
+    hd::ClockedState h;
+    HD_HIP(hipMemcpy(&h, c->st + s, sizeof h, hipMemcpyDeviceToHost));
+    const uint64_t have = h.written - h.taken, rc = c->prm.record_cap;
+    const size_t k = out ? (size_t)std::min<uint64_t>(have, cap) : (size_t)have;
+    *n_out = k;
+    if (!k) return HD_OK;
+    std::vector<hd_clocked_record> tmp(k);
+    const uint32_t* base = c->rec + (size_t)s * c->rec_stride + hd::kClockedGuard;
+    for (size_t i = 0; i < k;) {             // at most two pieces: the ring wraps once inside record_cap records
+        const uint64_t slot = (h.taken + i) % rc;
+        const size_t m = (size_t)std::min<uint64_t>(k - i, rc - slot);
+        HD_HIP(hipMemcpy(tmp.data() + i, base + slot * hd::kClockedRecWords, m * sizeof(hd_clocked_record), hipMemcpyDeviceToHost));
+        i += m;
+    }
+    h.taken += k;
+    HD_HIP(hipMemcpy(reinterpret_cast<char*>(c->st + s) + offsetof(hd::ClockedState, taken), &h.taken, sizeof h.taken, hipMemcpyHostToDevice));
+    c->tx[s].feed(tmp.data(), k);
+    if (out) std::memcpy(out, tmp.data(), k * sizeof(hd_clocked_record));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_clocked_params_default(hd_clocked_params* p) { if (p) hd::clocked_params_default(p); }
+
+int hd_clocked_create(hd_engine* e, const hd_clocked_params* params, hd_clocked** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_clocked> c(new hd_clocked);
+    c->e = e; c->S = e->S;
+    hd::clocked_params_default(&c->prm);
+    if (params) c->prm = *params;
+    if (!hd::clocked_params_ok(&c->prm)) return fail(HD_ERR_INVALID, "clocked decoder parameters: 16 <= record_cap <= 2^20, repair_bits <= 16, repair_flips <= 4");
+    if (const int rc = clocked_enter(c.get())) return rc;
+    c->modem.resize(c->S);
+    c->tx.resize(c->S);
+    for (uint32_t s = 0; s < c->S; ++s) {
+        const uint32_t nbits = (uint32_t)e->st[s].text.framer.nbits;
+        const double nstops = (double)e->st[s].text.framer.nstops;
+        const uint32_t F = hd::clocked_modem_F(e->fsd, e->st[s].baud, nbits, nstops);
+        hd::clocked_state_reset(c->modem[s], F, F ? nbits : 0u, F ? (uint32_t)nstops : 0u, 0u);
+        c->tx[s].repair_bits = c->prm.repair_bits; c->tx[s].repair_flips = c->prm.repair_flips;
+    }
+    c->ring_stride = (size_t)HD_CLOCKED_RING + 2 * hd::kClockedGuard;
+    c->rec_stride = (size_t)c->prm.record_cap * hd::kClockedRecWords + 2 * hd::kClockedGuard;
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->st), (size_t)c->S * sizeof(hd::ClockedState)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)c->S * c->ring_stride * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rec), (size_t)c->S * c->rec_stride * sizeof(uint32_t)));
+    HD_HIP(c->src.alloc(c->S));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kClockedGuardWord, (size_t)c->S * c->ring_stride, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rec), (int)hd::kClockedGuardWord, (size_t)c->S * c->rec_stride, e->qa));
+    if (const int rc = clocked_clear(c.get(), 0, c->S)) return rc;
+    *out = c.release();
+    return HD_OK;
+}
+
+void hd_clocked_destroy(hd_clocked* c)
+{
+    if (!c) return;
+    hd_engine* e = c->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    (void)hipSetDevice(e->cfg.device);
+    delete c;
+}
+
+int hd_clocked_reset(hd_clocked* c, uint32_t stream)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (stream != UINT32_MAX && stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    return stream == UINT32_MAX ? clocked_clear(c, 0, c->S) : clocked_clear(c, stream, 1);
+}
+
+int hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t nbits, uint32_t nstops, int invert)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    const uint32_t F = hd::clocked_modem_F(c->e->fsd, baud, nbits, (double)nstops);
+    if (!F) return fail(HD_ERR_UNSUPPORTED, "clocked decoder: 3.5 <= decimated rate / baud <= " + std::to_string(HD_CLOCKED_MAX_SPB) + ", 7 or 8 data bits, 1 or 2 stop bits");
+    if (const int rc = clocked_enter(c)) return rc;
+    hd::clocked_state_reset(c->modem[stream], F, nbits, nstops, invert ? 1u : 0u);
+    return clocked_clear(c, stream, 1);
+}
+
+int hd_clocked_push_engine(hd_clocked* c)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    hd_engine* e = c->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    if (e->in_callback) return fail(HD_ERR_INVALID, "hd_clocked_push_engine cannot be called from a sentence / character callback");
+    if (const int rc = flush_locked(e)) return rc;                     // like the data getters: the call in flight is delivered first
+    if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + ") -- destroy the engine");
+    if (e->calls == c->pushed_calls) return HD_OK;                     // no call since the last push
+    c->pushed_calls = e->calls;
+    uint32_t max_n = 0;
+    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
+        const SizeState& sz = e->mirror[s];
+        hd::ClockedSrc& d = c->src.p[s];
+        d.n_total = sz.last_m;
+        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
+        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
+        max_n = std::max(max_n, d.n_total);
+    }
+    return clocked_launch(c, max_n);
+}
+
+int hd_clocked_push_device(hd_clocked* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    uint32_t max_n = 0; size_t total = 0;
+    if (const int rc = clocked_check_rows(c, d_rows, stride, n_per_stream, n, &max_n, &total)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    if (!total) return HD_OK;
+    {   // what the kernel reads must be memory the GPU can address
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
+                                                                   !(at.type == hipMemoryTypeHost && at.devicePointer))) {
+            (void)hipGetLastError();
+            return fail(HD_ERR_INVALID, "rows are not device memory (hd_clocked_push_host takes host memory)");
+        }
+    }
+    for (uint32_t s = 0; s < c->S; ++s) {
+        hd::ClockedSrc& d = c->src.p[s];
+        d.p = d_rows + (size_t)s * stride; d.sym = nullptr; d.ring_mask = 0; d.n_total = n_per_stream ? n_per_stream[s] : n;
+    }
+    return clocked_launch(c, max_n);
+}
+
+int hd_clocked_push_host(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    uint32_t max_n = 0; size_t total = 0;
+    if (const int rc = clocked_check_rows(c, rows, stride, n_per_stream, n, &max_n, &total)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    if (!total) return HD_OK;
+    if (total > c->slab_n) {
+        if (c->slab) { (void)hipFree(c->slab); c->slab = nullptr; c->slab_n = 0; }
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->slab), total * sizeof(float)));
+        c->slab_n = total;
+    }
+    size_t at = 0;
+    for (uint32_t s = 0; s < c->S; ++s) {
+        hd::ClockedSrc& d = c->src.p[s];
+        d.n_total = n_per_stream ? n_per_stream[s] : n;
+        d.p = c->slab + at; d.sym = nullptr; d.ring_mask = 0;
+        if (d.n_total) HD_HIP(hipMemcpyAsync(c->slab + at, rows + (size_t)s * stride, (size_t)d.n_total * sizeof(float), hipMemcpyHostToDevice, c->e->qa));
+        at += d.n_total;
+    }
+    return clocked_launch(c, max_n);
+}
+
+int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, size_t cap)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    if (!out) {
+        hd::ClockedState h;
+        HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+        return (int)(h.written - h.taken);
+    }
+    size_t n = 0;
+    if (const int rc = clocked_drain(c, stream, out, cap, &n)) return rc;
+    return (int)n;
+}
+
+int hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    size_t n = 0;
+    if (const int rc = clocked_drain(c, stream, nullptr, 0, &n)) return rc;
+    return (int)c->tx[stream].take(out, cap);
+}
+
+int hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out)
+{
+    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    hd::ClockedState h;
+    HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+    const hd::ClockedText& t = c->tx[stream];
+    *out = hd_clocked_counters{h.n, h.p, h.chars, h.rejects, h.dropped, t.matches_failed, t.plain, t.repaired};
+    return HD_OK;
+}
+
+// Measurement hook (tools/micro/clocked_rate.py; not part of the ABI): the kernels of hd_clocked_push_engine between two HIP events, and the host time
+// of the whole call in microseconds.
+int hd_debug_clocked_push_timed(hd_clocked* c, float* kernel_ms, double* host_us)
+{
+    if (!c || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    hd_engine* e = c->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    if (const int rc = flush_locked(e)) return rc;
+    HD_HIP(hipEventCreate(&c->t0));
+    HD_HIP(hipEventCreate(&c->t1));
+    const uint64_t before = c->pushed_calls;
+    const auto w0 = std::chrono::steady_clock::now();
+    const int rc = hd_clocked_push_engine(c);
+    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+    *kernel_ms = 0;
+    if (rc == HD_OK && c->pushed_calls != before && hipEventQuery(c->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, c->t0, c->t1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(c->t0); (void)hipEventDestroy(c->t1);
+    c->t0 = c->t1 = nullptr;
+    return rc;
+}
+
+// Test hook (tests/test_gpu_clocked.py; not part of the ABI): how many of the guard words around the stream's two rings no longer hold their pattern.
+int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
+{
+    if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = clocked_enter(c)) return rc;
+    uint32_t g[4][hd::kClockedGuard];
+    const uint32_t* at[4] = {c->ring + (size_t)stream * c->ring_stride, c->ring + (size_t)(stream + 1) * c->ring_stride - hd::kClockedGuard,
+                             c->rec + (size_t)stream * c->rec_stride, c->rec + (size_t)(stream + 1) * c->rec_stride - hd::kClockedGuard};
+    int bad = 0;
+    for (int i = 0; i < 4; ++i) {
+        HD_HIP(hipMemcpy(g[i], at[i], sizeof g[i], hipMemcpyDeviceToHost));
+        for (uint32_t w : g[i]) bad += w != hd::kClockedGuardWord;
+    }
+    return bad;
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "../../include/habdec_amd_host.h"
 #include "host/afc_tracker.hpp"
 #include "host/baud_probe.hpp"
+#include "host/clocked.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
 #include "host/format_trial.hpp"
@@ -294,6 +295,77 @@ int hd_host_waterfall_tracks(const hd_waterfall_row* headers, const uint32_t* ma
                              const hd_waterfall_track_params* p, hd_waterfall_track* out, uint32_t cap, uint32_t* found)
 {
     return hd::waterfall_tracks(headers, marks, n_rows, sampling_rate, p, out, cap, found);
+}
+
+/* ---- clocked decoder (kernels/clocked.hip; see host/clocked.hpp, host/chase_repair.hpp) ---- */
+struct hd_host_clocked {
+    double fsd;
+    hd::ClockedStream st;
+    hd::ClockedText tx;
+    hd_host_clocked(double rate, uint32_t cap) : fsd(rate), st(cap) {}
+    void drain(hd_clocked_record* out, size_t cap, size_t* n)
+    {
+        std::vector<hd_clocked_record> tmp(out ? std::min<size_t>(cap, st.take(nullptr, 0)) : st.take(nullptr, 0));
+        const size_t k = st.take(tmp.data(), tmp.size());
+        tx.feed(tmp.data(), k);
+        if (out && k) std::memcpy(out, tmp.data(), k * sizeof(hd_clocked_record));
+        *n = k;
+    }
+};
+hd_host_clocked* hd_host_clocked_new(double decimated_rate, const hd_clocked_params* params)
+{
+    hd_clocked_params prm;
+    hd::clocked_params_default(&prm);
+    if (params) prm = *params;
+    if (!hd::clocked_params_ok(&prm) || !(decimated_rate > 0)) return nullptr;
+    auto* h = new hd_host_clocked(decimated_rate, prm.record_cap);
+    h->tx.repair_bits = prm.repair_bits; h->tx.repair_flips = prm.repair_flips;
+    return h;
+}
+void hd_host_clocked_free(hd_host_clocked* h) { delete h; }
+void hd_host_clocked_reset(hd_host_clocked* h) { if (h) { h->st.reset(); h->tx.reset(); } }
+int hd_host_clocked_set_modem(hd_host_clocked* h, double baud, uint32_t nbits, uint32_t nstops, int invert)
+{
+    if (!h) return HD_ERR_INVALID;
+    const uint32_t F = hd::clocked_modem_F(h->fsd, baud, nbits, (double)nstops);
+    if (!F) return HD_ERR_UNSUPPORTED;
+    h->st.set_modem(F, nbits, nstops, invert ? 1u : 0u);
+    h->tx.reset(); h->tx.nbits = nbits;
+    return HD_OK;
+}
+void hd_host_clocked_push(hd_host_clocked* h, const float* d, size_t n) { if (h && d && n) h->st.push(d, n); }
+int hd_host_clocked_records(hd_host_clocked* h, hd_clocked_record* out, size_t cap)
+{
+    if (!h) return HD_ERR_INVALID;
+    if (!out) return (int)h->st.take(nullptr, 0);
+    size_t n = 0;
+    h->drain(out, cap, &n);
+    return (int)n;
+}
+int hd_host_clocked_take_sentences(hd_host_clocked* h, hd_clocked_sentence* out, size_t cap)
+{
+    if (!h || (cap && !out)) return HD_ERR_INVALID;
+    size_t n = 0;
+    h->drain(nullptr, 0, &n);
+    return (int)h->tx.take(out, cap);
+}
+int hd_host_clocked_stats(const hd_host_clocked* h, hd_clocked_counters* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    const hd::ClockedState& s = h->st.s;
+    *out = hd_clocked_counters{s.n, s.p, s.chars, s.rejects, s.dropped, h->tx.matches_failed, h->tx.plain, h->tx.repaired};
+    return HD_OK;
+}
+int hd_host_chase_repair(const char* span, size_t n, const int32_t* data, uint32_t nbits, uint32_t repair_bits, uint32_t repair_flips, char* out,
+                         uint32_t* flips)
+{
+    if (!span || !data || !out || !flips || (nbits != 7 && nbits != 8) || repair_bits > hd::kChaseMaxBits || repair_flips > hd::kChaseMaxFlips) return HD_ERR_INVALID;
+    std::string fixed;
+    hd::SentenceMatch m;
+    *flips = hd::chase_repair(std::string(span, n), data, nbits, repair_bits, repair_flips, fixed, m);
+    if (!*flips) return 0;
+    std::memcpy(out, fixed.data(), n);
+    return 1;
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

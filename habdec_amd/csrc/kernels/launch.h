@@ -6,6 +6,7 @@
 
 #include "../dev_types.h"
 #include "../../../include/habdec_amd.h"
+#include "../host/clocked_state.hpp"
 #include "../host/ring_schedule.hpp"
 
 namespace hd {
@@ -89,6 +90,19 @@ struct ProbeSrc {
 };
 void launch_baud_probe(hipStream_t st, uint32_t n_streams, const ProbeSrc* src, hd_baud_probe_stream_state* hdr, unsigned long long* acc64, uint32_t* acc32,
                        const uint32_t* F, const uint32_t* scale, const int32_t* ctab);
+
+// Clocked decoder (clocked.hip), one wave per stream.  src[s]: the probe's descriptor with a window -- of the n_total floats of the push this launch
+// takes the n from index off on (n <= HD_CLOCKED_CHUNK; n = 0: nothing is appended, and nothing can be decided that was not decided before).
+// st [S]; ring [S][ring_stride] uint32, a stream's HD_CLOCKED_RING running sums behind kClockedGuard guard words; rec [S][rec_stride] uint32, its
+// record_cap records of 14 words (hd_clocked_record) behind kClockedGuard guard words.
+struct ClockedSrc {
+    const float* p;
+    const SymState* sym;
+    uint32_t n_total, ring_mask, off, n;
+};
+// lds_words: words of LDS per wave, at least look + h + n of every stream that is on (host/clocked.hpp: clocked_window_words); false: more than the CU has.
+bool launch_clocked(hipStream_t st, uint32_t n_streams, const ClockedSrc* src, ClockedState* state, uint32_t* ring, size_t ring_stride, uint32_t* rec,
+                    size_t rec_stride, uint32_t record_cap, uint32_t lds_words);
 
 // ---- launchers of the mode-dependent kernels, once per arithmetic mode (arith.h)
 namespace exact {

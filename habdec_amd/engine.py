@@ -245,6 +245,12 @@ class Engine:
         self._probes = getattr(self, "_probes", []) + [p]
         return p
 
+    def clocked(self, **params) -> "Clocked":
+        """A clocked decoder on this engine's streams (hd_clocked_*; params as hd_clocked_params): close it before the engine."""
+        c = Clocked(self, **params)
+        self._probes = getattr(self, "_probes", []) + [c]
+        return c
+
     def set_format_trial(self, s, on=True):
         """Tee the bits delivered for stream s into a framing trial (hd_stream_set_format_trial); turning it on resets it."""
         check(self.L.hd_stream_set_format_trial(self.h, s, int(on)))
@@ -382,6 +388,155 @@ class HostBaudProbe:
         n = self.L.hd_host_baud_probe_state(self.h, C.byref(h), cand.ctypes.data, cand.size)
         assert n == capi.PROBE_CANDIDATES, n
         return _probe_state(h, cand)
+
+
+def _clocked_params(L, params):
+    p = capi.hd_clocked_params()
+    L.hd_clocked_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, int(v))
+    return p
+
+
+def _clocked_counters(c) -> dict:
+    return {k: int(getattr(c, k)) for k, _ in capi.hd_clocked_counters._fields_}
+
+
+def _clocked_sentences(a) -> list:
+    """[(pos, flips, 'callsign,data*CRC')]"""
+    return [(int(r["pos"]), int(r["flips"]), r["text"].decode("latin-1")) for r in a]
+
+
+class Clocked:
+    """Clocked soft-decision decoder of an engine's streams (hd_clocked_*, include/habdec_amd.h): push discriminator output, take records and sentences."""
+
+    def __init__(self, eng: Engine, **params):
+        self.L, self.eng, self.S = eng.L, eng, eng.S
+        p = _clocked_params(self.L, params)
+        h = C.c_void_p()
+        check(self.L.hd_clocked_create(eng.h, C.byref(p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_clocked_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_modem(self, s, baud, bits, stops, invert=False):
+        """Give stream s its modem (resets the stream)."""
+        check(self.L.hd_clocked_set_modem(self.h, s, float(baud), int(bits), int(stops), int(invert)))
+
+    def reset(self, s=None):
+        check(self.L.hd_clocked_reset(self.h, 0xFFFFFFFF if s is None else s))
+
+    def push_engine(self):
+        """Add every stream's discriminator output of the call delivered last (drains the pipeline first, like the data getters)."""
+        check(self.L.hd_clocked_push_engine(self.h))
+
+    def push_host(self, rows, n_per_stream=None):
+        rows, n = _ProbeRows.args(rows, self.S, n_per_stream)
+        check(self.L.hd_clocked_push_host(self.h, rows.ctypes.data, rows.shape[1], n.ctypes.data, 0))
+
+    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
+        """float32 rows at a device address, row s at dev_ptr + 4 * s * stride."""
+        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+        assert n.shape == (self.S,)
+        check(self.L.hd_clocked_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+
+    def waiting(self, s=0) -> int:
+        n = self.L.hd_clocked_records(self.h, s, None, 0)
+        check(min(n, 0))
+        return n
+
+    def records(self, s=0, cap=None) -> np.ndarray:
+        """Take the stream's waiting records (at most cap), oldest first: an array of capi.CLOCKED_RECORD_DTYPE."""
+        out = np.zeros(self.waiting(s) if cap is None else cap, capi.CLOCKED_RECORD_DTYPE)
+        n = self.L.hd_clocked_records(self.h, s, out.ctypes.data, out.size) if out.size else 0
+        check(min(n, 0))
+        return out[:n]
+
+    def take_sentences(self, s=0, cap=64) -> list:
+        out = np.zeros(cap, capi.CLOCKED_SENTENCE_DTYPE)
+        n = self.L.hd_clocked_take_sentences(self.h, s, out.ctypes.data, out.size)
+        check(min(n, 0))
+        return _clocked_sentences(out[:n])
+
+    def stats(self, s=0) -> dict:
+        c = capi.hd_clocked_counters()
+        check(self.L.hd_clocked_stats(self.h, s, C.byref(c)))
+        return _clocked_counters(c)
+
+
+class HostClocked:
+    """One stream of the clocked decoder in plain C++ on the host (hd_host_clocked_*): the restatement the kernel is held to, no GPU."""
+
+    def __init__(self, decimated_rate: float, baud=None, bits=8, stops=2, invert=False, **params):
+        self.L = lib()
+        p = _clocked_params(self.L, params)
+        self.h = self.L.hd_host_clocked_new(float(decimated_rate), C.byref(p))
+        if not self.h:
+            raise HabdecError("hd_host_clocked_new: 16 <= record_cap <= 2^20, repair_bits <= 16, repair_flips <= 4, decimated_rate > 0")
+        if baud is not None:
+            self.set_modem(baud, bits, stops, invert)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_host_clocked_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_modem(self, baud, bits, stops, invert=False):
+        rc = self.L.hd_host_clocked_set_modem(self.h, float(baud), int(bits), int(stops), int(invert))
+        if rc:
+            raise HabdecError("hd_host_clocked_set_modem: %d (3.5 <= samples per bit <= 2048, 7 or 8 data bits, 1 or 2 stop bits)" % rc)
+
+    def reset(self):
+        self.L.hd_host_clocked_reset(self.h)
+
+    def push(self, d):
+        d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+        self.L.hd_host_clocked_push(self.h, d, d.size)
+
+    def waiting(self) -> int:
+        return self.L.hd_host_clocked_records(self.h, None, 0)
+
+    def records(self, cap=None) -> np.ndarray:
+        out = np.zeros(self.waiting() if cap is None else cap, capi.CLOCKED_RECORD_DTYPE)
+        n = self.L.hd_host_clocked_records(self.h, out.ctypes.data, out.size) if out.size else 0
+        return out[:n]
+
+    def take_sentences(self, cap=64) -> list:
+        out = np.zeros(cap, capi.CLOCKED_SENTENCE_DTYPE)
+        n = self.L.hd_host_clocked_take_sentences(self.h, out.ctypes.data, out.size)
+        return _clocked_sentences(out[:n])
+
+    def stats(self) -> dict:
+        c = capi.hd_clocked_counters()
+        check(self.L.hd_host_clocked_stats(self.h, C.byref(c)))
+        return _clocked_counters(c)
+
+
+def chase_repair(span: str, data, nbits=8, repair_bits=8, repair_flips=3):
+    """hd_host_chase_repair: (repaired span, flips) or None.  data: int32 [len(span), 8], the data_k of every character."""
+    L = lib()
+    b = span.encode("latin-1")
+    data = np.ascontiguousarray(data, dtype=np.int32)
+    assert data.shape == (len(b), 8), data.shape
+    out, flips = C.create_string_buffer(len(b) + 1), C.c_uint32(0)
+    rc = L.hd_host_chase_repair(b, len(b), data.ctypes.data, nbits, repair_bits, repair_flips, out, C.byref(flips))
+    check(min(rc, 0))
+    return (out.raw[:len(b)].decode("latin-1"), flips.value) if rc == 1 else None
 
 
 class HostFormatTrial:

@@ -531,6 +531,89 @@ typedef struct hd_format_trial_result {
 int hd_stream_set_format_trial(hd_engine* e, uint32_t stream, int on);
 int hd_stream_format_trial(hd_engine* e, uint32_t stream, hd_format_trial_result* out);   /* HD_ERR_INVALID while the trial is off */
 
+/* ---- clocked soft-decision decoder with CRC-guided repair: for weak signals (not in the reference) ----
+ * probe -> hd_stream_set_baud -> trial -> hd_stream_set_rtty -> hd_clocked_set_modem.  The engine's own chain (flip points of quarter-bit means, run
+ * lengths rounded to bits, a framer hunting for start and stop bits) is the reference's and stays; a discriminator click costs it a bit and with the bit
+ * the character alignment of a sentence.  A clocked decoder is attached to an engine like a probe and reads the same rows (hd_stream_demodulated).  Per
+ * stream it starts a bit clock at every start edge, takes one decision per bit from the sum over the whole bit, and keeps the sums as soft values; a
+ * host stage runs the sentence scan and CRC of the ordinary text stage over the characters and, where a match's CRC fails, flips the least confident
+ * bits.  All of it is integer arithmetic: kernel, host restatement (hd_host_clocked_*) and a numpy model agree bit for bit.
+ *  - Indices are absolute sample indices of a stream since its last reset (uint64); how a stream is cut into pushes cannot matter.
+ *  - Quantised sample: q_i = 0 for NaN, else (int32)(clamp(v_i, -4, 4) * 1024) truncated toward zero; negated when the stream's `invert` is set (tones
+ *    swapped).  S(a, b) = the exact sum of q_i, a <= i < b.
+ *  - Clock: F = (int64)floor(fsd / baud * 65536 + 0.5); full = (F + 32768) >> 16; h = max(2, (F + 65536) >> 17); bit boundary k of a character whose
+ *    start edge is x: B_k = x + ((k F + 32768) >> 16).  K = 1 + nbits + nstops bits per character; look = h + ((K F + 32768) >> 16).
+ *    hd_clocked_set_modem is HD_ERR_UNSUPPORTED unless 3.5 <= fsd / baud <= HD_CLOCKED_MAX_SPB (2048), nbits is 7 or 8 and nstops 1 or 2.
+ *  - Scan: the cursor p starts at h.  Position p is decided once p + look <= n, n = samples pushed -- every sample any decision at p can read exists
+ *    then; else the stream waits for the next push.  (One rule for every kind of decision: the state after n samples is a function of those samples.)
+ *    Edge test at p: S(p-h, p) > 0 && S(p, p+h) < 0.  False: p += 1.  True: x = the smallest x in [p, p+h] that minimises S(x, x+full) - S(x-h, x);
+ *    start = S(B_0, B_1), data_k = S(B_{1+k}, B_{2+k}) for k < nbits, stop = S(B_{1+nbits}, B_{2+nbits}), stop2 = S(B_{2+nbits}, B_{3+nbits}) with two
+ *    stop bits (else 0; recorded, no condition).  Accepted iff start < 0 && stop > 0: a record {pos = x, ch = sum over k of (data_k > 0) << k, data,
+ *    start, stop, stop2} is appended, characters += 1 and p = x + (((2 (1 + nbits) + 1) F + 65536) >> 17), the middle of the first stop bit.
+ *    Rejected: rejects += 1, p += 1.
+ *  - Records lie in a per-stream ring of record_cap entries on the GPU until hd_clocked_records or hd_clocked_take_sentences takes them; a record
+ *    appended to a full ring overwrites the oldest untaken one, dropped += 1.
+ *  - Text (host; what the engine's text stage does behind its framer): characters 32..126 and '\n' are appended to the stream's text with their
+ *    records; while the text is longer than 20 characters the sentence scan runs; a match with the right CRC16 is a plain sentence (flips = 0); the
+ *    text is cut as the text stage cuts it (4 characters behind the terminator; above 1000 characters at the last '$').
+ *  - Repair, for a match whose CRC fails (matches_failed += 1): the span is the match from its first '$' to the CRC's last character.  The repair_bits
+ *    (default 8) data bits of the span with the smallest |data_k| -- ties: the earlier character, then the lower bit -- are the list; all subsets of size
+ *    1, then 2, ... up to repair_flips (default 3) are tried in the list's lexicographic order (92 trials).  A trial flips its bits (ch bit k of the
+ *    character); it counts if every character it changed is in 32..126 afterwards, the sentence scan on the changed span alone matches the whole span
+ *    (from its first character to its last) and the CRC16 agrees.  The first trial that counts wins: a repaired sentence with flips = the subset's
+ *    size.  Either limit 0: no repair.
+ *  - False accepts: a trial on a span that is not the transmitted sentence passes the CRC16 with probability 2^-16, so a failed match yields a
+ *    sentence that was not sent with probability at most 92 * 2^-16 = 0.14 % at the default limits, before the printable and shape filters.
+ *  - Sentences, plain and repaired, leave through hd_clocked_take_sentences only: never through hd_set_sentence_callback, hd_engine_sentences_ok or
+ *    any getter of the engine.
+ *  - Queue, errors: as the probe's.  One launch per push for all streams (a push of more than HD_CLOCKED_CHUNK samples for a stream: one launch per
+ *    chunk); every push returns when its kernels are done. */
+#define HD_CLOCKED_MAX_SPB 2048
+#define HD_CLOCKED_RING 32768      /* per-stream sample history on the GPU, kept as running sums */
+#define HD_CLOCKED_CHUNK 4096      /* samples per stream and launch */
+typedef struct hd_clocked hd_clocked;
+typedef struct hd_clocked_params {
+    uint32_t record_cap;       /* records per stream the ring holds; default 4096, at least 16 */
+    uint32_t repair_bits;      /* default 8, at most 16 */
+    uint32_t repair_flips;     /* default 3, at most 4 */
+    uint32_t _pad;
+} hd_clocked_params;
+typedef struct hd_clocked_record {
+    uint64_t pos;              /* x */
+    int32_t  data[8];          /* data_k; data[7] = 0 with 7 data bits */
+    int32_t  start, stop, stop2;
+    uint32_t ch;
+} hd_clocked_record;
+typedef struct hd_clocked_sentence {
+    uint64_t pos;              /* pos of the record of the sentence's first '$' */
+    uint32_t flips;            /* 0: plain */
+    uint32_t len;              /* strlen of callsign,data*CRC (text holds at most 495 characters of it, NUL-terminated) */
+    char     text[496];
+} hd_clocked_sentence;
+typedef struct hd_clocked_counters {
+    uint64_t samples, cursor;  /* n and p */
+    uint64_t characters, rejects, dropped;
+    uint64_t matches_failed, sentences_plain, sentences_repaired;
+} hd_clocked_counters;
+void hd_clocked_params_default(hd_clocked_params* p);
+/* Every stream takes the engine stream's current baud rate and framing; a stream whose settings hd_clocked_set_modem would refuse is off (pushes pass
+ * it by) until it is given a modem. */
+int  hd_clocked_create(hd_engine* e, const hd_clocked_params* p /* null: the defaults */, hd_clocked** out);
+void hd_clocked_destroy(hd_clocked* c);
+/* Samples, cursor, records, text and counters of the stream start again; sentences not yet taken stay. */
+int  hd_clocked_reset(hd_clocked* c, uint32_t stream /* UINT32_MAX: all */);
+int  hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t nbits, uint32_t nstops, int invert);   /* resets the stream */
+/* The three routes of the probe, with its rules (hd_baud_probe_push_*). */
+int  hd_clocked_push_engine(hd_clocked* c);
+int  hd_clocked_push_device(hd_clocked* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_clocked_push_host(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* Takes up to cap of the stream's oldest untaken records off the ring (they pass through the text stage on their way) and returns how many were
+ * written; out null: takes none and returns how many wait.  Negative: HD_ERR_*. */
+int  hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, size_t cap);
+/* Takes all waiting records into the text stage, then hands out up to cap of the stream's sentences, oldest first; returns how many were written. */
+int  hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap);
+int  hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out);
+
 #ifdef __cplusplus
 }
 #endif

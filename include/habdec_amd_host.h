@@ -194,6 +194,24 @@ void hd_host_format_trial_free(hd_host_format_trial*);
 void hd_host_format_trial_push_bits(hd_host_format_trial*, const uint8_t* bits, size_t n);
 void hd_host_format_trial_get(const hd_host_format_trial*, hd_format_trial_result* out);
 
+/* ---- clocked decoder (hd_clocked_*, include/habdec_amd.h has the definition): one stream of it in plain C++, position by position ----
+ * The same structs and the same integers as the kernel: the records of the same pushes equal hd_clocked_records byte for byte, and the text stage and
+ * the repair behind them are the code the engine's object runs.  hd_host_clocked_new: NULL for parameters hd_clocked_create refuses; the stream is off
+ * until hd_host_clocked_set_modem (HD_ERR_UNSUPPORTED where hd_clocked_set_modem is) gives it a modem.  The other calls as their hd_clocked_* namesakes.
+ * hd_host_chase_repair: the repair alone on a span of n characters with data[n][8] their data_k -- 1 and out[n], *flips when a trial counts, 0 when
+ * none does (out untouched), HD_ERR_INVALID for null arguments, nbits other than 7 or 8, repair_bits > 16 or repair_flips > 4. */
+typedef struct hd_host_clocked hd_host_clocked;
+hd_host_clocked* hd_host_clocked_new(double decimated_rate, const hd_clocked_params* params);
+void hd_host_clocked_free(hd_host_clocked*);
+void hd_host_clocked_reset(hd_host_clocked*);
+int  hd_host_clocked_set_modem(hd_host_clocked*, double baud, uint32_t nbits, uint32_t nstops, int invert);
+void hd_host_clocked_push(hd_host_clocked*, const float* d, size_t n);
+int  hd_host_clocked_records(hd_host_clocked*, hd_clocked_record* out, size_t cap);
+int  hd_host_clocked_take_sentences(hd_host_clocked*, hd_clocked_sentence* out, size_t cap);
+int  hd_host_clocked_stats(const hd_host_clocked*, hd_clocked_counters* out);
+int  hd_host_chase_repair(const char* span, size_t n, const int32_t* data, uint32_t nbits, uint32_t repair_bits, uint32_t repair_flips, char* out,
+                          uint32_t* flips);
+
 #ifdef __cplusplus
 }
 #endif
