@@ -1,0 +1,498 @@
+// The objects that read the streams' discriminator output beside the decode pipeline: the baud-rate probe (kernels/baud_probe.hip, host/baud_probe.hpp)
+// and the clocked decoder (kernels/clocked.hip, host/clocked.hpp).  Both take one float row per stream through the same three doors -- the engine's last
+// call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream descriptors, launch on the engine's
+// first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc) and in what they launch; the rest is the helpers below.
+#include <atomic>
+#include <chrono>
+#include <cstddef>
+
+#include "engine_state.h"
+#include "host/baud_probe.hpp"
+#include "host/clocked.hpp"
+
+using hd::eng::enter;
+using hd::eng::is_device_pointer;
+
+namespace {
+
+// A row's length in its descriptor.  (The clocked decoder's n is the part of the row one launch takes: clocked_launch.)
+uint32_t& src_len(hd::ProbeSrc& d) { return d.n; }
+uint32_t& src_len(hd::ClockedSrc& d) { return d.n_total; }
+
+// The helpers take either object: both carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names.
+
+// hd_*_push_engine.  null_msg: the error for a null object; fn: the door's name for the message.  launch(max_n): the descriptors are written and
+// the longest row has max_n samples.
+template <typename Obj, typename Launch>
+int push_engine(Obj* o, const char* null_msg, const char* fn, Launch launch)
+{
+    if (!o) return fail(HD_ERR_INVALID, null_msg);
+    hd_engine* e = o->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = enter(e)) return rc;
+    if (e->in_callback) return fail(HD_ERR_INVALID, std::string(fn) + " cannot be called from a sentence / character callback");
+    if (const int rc = flush_locked(e)) return rc;                     // like the data getters: the call in flight is delivered first
+    if (e->device_failed) return hd::eng::failed_state(e);            // (the delivery may have found the give-up word set)
+    if (e->calls == o->pushed_calls) return HD_OK;                     // no call since the last push
+    o->pushed_calls = e->calls;
+    uint32_t max_n = 0;
+    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
+        const SizeState& sz = e->mirror[s];
+        auto& d = o->src.p[s];
+        src_len(d) = sz.last_m;
+        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
+        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
+        max_n = std::max(max_n, sz.last_m);
+    }
+    return launch(max_n);
+}
+
+// hd_*_push_device (device = true: row s is read in place at rows + s * stride) and hd_*_push_host (the rows are packed end to end into the slab,
+// grown on demand, one copy per row on the engine's first queue).
+template <typename Obj, typename Launch>
+int push_rows(Obj* o, const char* null_msg, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, bool device, Launch launch)
+{
+    if (!o) return fail(HD_ERR_INVALID, null_msg);
+    if (!rows) return fail(HD_ERR_INVALID, "null rows");
+    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
+    uint32_t max_n = 0; size_t total = 0;
+    for (uint32_t s = 0; s < o->S; ++s) {
+        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
+        max_n = std::max(max_n, ns); total += ns;
+    }
+    if (o->S > 1 && max_n > stride) return fail(HD_ERR_INVALID, "a row is longer than the stride");
+    std::lock_guard<std::recursive_mutex> lock(o->e->mtx);
+    if (const int rc = enter(o->e)) return rc;
+    if (!total) return HD_OK;                  // nothing to read: before the device-pointer check
+    if (device && !is_device_pointer(rows)) return fail(HD_ERR_INVALID, "rows are not device memory (the _host call takes host memory)");
+    if (!device && total > o->slab_n) {
+        if (o->slab) { (void)hipFree(o->slab); o->slab = nullptr; o->slab_n = 0; }
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&o->slab), total * sizeof(float)));
+        o->slab_n = total;
+    }
+    size_t at = 0;
+    for (uint32_t s = 0; s < o->S; ++s) {
+        auto& d = o->src.p[s];
+        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
+        src_len(d) = ns; d.sym = nullptr; d.ring_mask = 0;
+        d.p = device ? rows + (size_t)s * stride : o->slab + at;
+        if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab + at, rows + (size_t)s * stride, (size_t)ns * sizeof(float), hipMemcpyHostToDevice, o->e->qa));
+        at += ns;
+    }
+    return launch(max_n);
+}
+
+// The measurement hooks (tools/micro/probe_rate.py, clocked_rate.py; not part of the ABI): the kernels of push() -- the object's hd_*_push_engine, whose
+// launch records t0 and t1 where they are set -- between two HIP events, and the host time of the whole call in microseconds.
+template <typename Obj, typename Push>
+int push_timed(Obj* o, float* kernel_ms, double* host_us, Push push)
+{
+    if (!o || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    hd_engine* e = o->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    if (const int rc = enter(e)) return rc;
+    if (const int rc = flush_locked(e)) return rc;
+    HD_HIP(hipEventCreate(&o->t0));
+    HD_HIP(hipEventCreate(&o->t1));
+    const uint64_t before = o->pushed_calls;
+    const auto w0 = std::chrono::steady_clock::now();
+    const int rc = push(o);
+    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+    *kernel_ms = 0;
+    if (rc == HD_OK && o->pushed_calls != before && hipEventQuery(o->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, o->t0, o->t1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(o->t0); (void)hipEventDestroy(o->t1);
+    o->t0 = o->t1 = nullptr;
+    return rc;
+}
+
+// hd_*_destroy.  (No queue to wait for: every push has waited for its launches.)
+template <typename Obj>
+void destroy(Obj* o)
+{
+    if (!o) return;
+    hd_engine* e = o->e;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    (void)hipSetDevice(e->cfg.device);
+    delete o;
+}
+
+}  // namespace
+
+/* ---------------------------------------------------------------- baud-rate probe (kernels/baud_probe.hip) ----------------------------- */
+
+struct hd_baud_probe {
+    hd_engine* e = nullptr;
+    hd_baud_probe_params prm{};
+    hd::BaudProbeTables t;
+    uint32_t S = 0;
+    hd_baud_probe_stream_state* hdr = nullptr;   // [S]
+    unsigned long long* acc64 = nullptr;         // [S][2][1024]: P, Q
+    uint32_t* acc32 = nullptr;                   // [S][5][1024]: NB, re, im, n, cur_block
+    uint32_t *F = nullptr, *scale = nullptr;
+    int32_t* ctab = nullptr;
+    float* slab = nullptr;                       // hd_baud_probe_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::ProbeSrc> src;                    // [S]: the push's descriptors, read by the kernel in place (a push returns when its kernel is done)
+    uint64_t pushed_calls = 0;                   // hd_baud_probe_push_engine: e->calls at the last push (the call delivered last is calls - 1)
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launch
+    ~hd_baud_probe()
+    {
+        for (void* p : {(void*)hdr, (void*)acc64, (void*)acc32, (void*)F, (void*)scale, (void*)ctab, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+const char kNullProbe[] = "null probe";
+
+// The descriptors are written: one launch for all streams on the engine's first queue, and the wait for it.
+int probe_launch(hd_baud_probe* p)
+{
+    std::atomic_thread_fence(std::memory_order_release);
+    if (p->t0) HD_HIP(hipEventRecord(p->t0, p->e->qa));
+    hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr, p->acc64, p->acc32, p->F, p->scale, p->ctab);
+    if (p->t1) HD_HIP(hipEventRecord(p->t1, p->e->qa));
+    HD_HIP(hipGetLastError());
+    HD_HIP(hipStreamSynchronize(p->e->qa));
+    return HD_OK;
+}
+
+int probe_clear(hd_baud_probe* p, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = p->e->qa;
+    HD_HIP(hipMemsetAsync(p->hdr + s0, 0, (size_t)ns * sizeof(hd_baud_probe_stream_state), q));
+    HD_HIP(hipMemsetAsync(p->acc64 + (size_t)s0 * 2 * hd::kProbeCand, 0, (size_t)ns * 2 * hd::kProbeCand * sizeof(unsigned long long), q));
+    HD_HIP(hipMemsetAsync(p->acc32 + (size_t)s0 * 5 * hd::kProbeCand, 0, (size_t)ns * 5 * hd::kProbeCand * sizeof(uint32_t), q));
+    HD_HIP(hipStreamSynchronize(q));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_baud_probe_params_default(hd_baud_probe_params* p) { if (p) hd::baud_probe_params_default(p); }
+
+int hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* params, hd_baud_probe** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_baud_probe> p(new hd_baud_probe);
+    p->e = e; p->S = e->S;
+    hd::baud_probe_params_default(&p->prm);
+    if (params) p->prm = *params;
+    if (!hd::baud_probe_params_ok(&p->prm, e->fsd))
+        return fail(HD_ERR_INVALID, "baud probe parameters: 0 < baud_lo < baud_hi <= decimated rate / 3.5 (" + std::to_string(e->fsd / 3.5) + ") and min_coherence >= 0");
+    if (const int rc = enter(e)) return rc;
+    p->t.make(e->fsd, p->prm);
+    std::vector<uint32_t> sc(hd::kProbeCand);
+    for (uint32_t k = 0; k < hd::kProbeCand; ++k) sc[k] = p->t.scale[k];
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->hdr), (size_t)p->S * sizeof(hd_baud_probe_stream_state)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc64), (size_t)p->S * 2 * hd::kProbeCand * sizeof(unsigned long long)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc32), (size_t)p->S * 5 * hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->F), hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->scale), hd::kProbeCand * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->ctab), 1024 * sizeof(int32_t)));
+    HD_HIP(p->src.alloc(p->S));
+    HD_HIP(hipMemcpyAsync(p->F, p->t.F, hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->scale, sc.data(), hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->ctab, p->t.C, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, e->qa));
+    if (const int rc = probe_clear(p.get(), 0, p->S)) return rc;       // (waits for the queue: `sc` is a local)
+    p->pushed_calls = 0;
+    *out = p.release();
+    return HD_OK;
+}
+
+void hd_baud_probe_destroy(hd_baud_probe* p) { destroy(p); }
+
+int hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream)
+{
+    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
+    if (stream != UINT32_MAX && stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = enter(p->e)) return rc;
+    return stream == UINT32_MAX ? probe_clear(p, 0, p->S) : probe_clear(p, stream, 1);
+}
+
+int hd_baud_probe_push_engine(hd_baud_probe* p)
+{
+    // The probe launches nothing when every stream's row is empty.  (The clocked decoder's chunk loop simply runs zero times.)
+    return push_engine(p, kNullProbe, "hd_baud_probe_push_engine", [p](uint32_t max_n) { return max_n ? probe_launch(p) : HD_OK; });
+}
+
+int hd_baud_probe_push_device(hd_baud_probe* p, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(p, kNullProbe, d_rows, stride, n_per_stream, n, true, [p](uint32_t) { return probe_launch(p); });
+}
+
+int hd_baud_probe_push_host(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(p, kNullProbe, rows, stride, n_per_stream, n, false, [p](uint32_t) { return probe_launch(p); });
+}
+
+int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* cand, size_t cap)
+{
+    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
+    if (stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (cap < hd::kProbeCand) return (int)hd::kProbeCand;              // nothing is written
+    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
+    if (const int rc = enter(p->e)) return rc;
+    hd_baud_probe_stream_state h;
+    std::vector<unsigned long long> a64(2 * hd::kProbeCand);
+    std::vector<uint32_t> a32(5 * hd::kProbeCand);
+    HD_HIP(hipMemcpy(&h, p->hdr + stream, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a64.data(), p->acc64 + (size_t)stream * a64.size(), a64.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a32.data(), p->acc32 + (size_t)stream * a32.size(), a32.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h.n_candidates = hd::kProbeCand;
+    if (hdr) *hdr = h;
+    for (uint32_t k = 0; cand && k < hd::kProbeCand; ++k) {
+        hd_baud_probe_candidate& c = cand[k];
+        c.P = a64[k]; c.Q = a64[hd::kProbeCand + k];
+        c.NB = a32[k]; c.re = (int32_t)a32[hd::kProbeCand + k]; c.im = (int32_t)a32[2 * hd::kProbeCand + k];
+        c.n = a32[3 * hd::kProbeCand + k]; c.cur_block = a32[4 * hd::kProbeCand + k]; c._pad = 0;
+    }
+    return (int)hd::kProbeCand;
+}
+
+int hd_baud_probe_estimate(hd_baud_probe* p, uint32_t stream, hd_baud_estimate* out)
+{
+    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    hd_baud_probe_stream_state h;
+    std::vector<hd_baud_probe_candidate> c(hd::kProbeCand);
+    const int n = hd_baud_probe_state(p, stream, &h, c.data(), c.size());
+    if (n < 0) return n;
+    hd::baud_probe_estimate(p->t, p->prm, h, c.data(), out);
+    return HD_OK;
+}
+
+int hd_debug_baud_probe_push_timed(hd_baud_probe* p, float* kernel_ms, double* host_us) { return push_timed(p, kernel_ms, host_us, hd_baud_probe_push_engine); }
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- clocked decoder (kernels/clocked.hip) -------------------------------- */
+
+struct hd_clocked {
+    hd_engine* e = nullptr;
+    hd_clocked_params prm{};
+    uint32_t S = 0;
+    hd::ClockedState* st = nullptr;              // [S]
+    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_CLOCKED_RING running sums | guard
+    uint32_t* rec = nullptr;                     // [S][rec_stride]: guard | record_cap records | guard
+    size_t ring_stride = 0, rec_stride = 0;
+    float* slab = nullptr;                       // hd_clocked_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::ClockedSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    std::vector<hd::ClockedState> modem;         // [S]: the state a reset gives the stream (F = 0: off)
+    std::vector<hd::ClockedText> tx;             // [S]
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
+    ~hd_clocked()
+    {
+        for (void* p : {(void*)st, (void*)ring, (void*)rec, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+const char kNullClocked[] = "null clocked decoder";
+
+// src[s].p, sym, ring_mask and n_total are written: one launch per HD_CLOCKED_CHUNK samples of the longest row, each waited for.
+int clocked_launch(hd_clocked* c, uint32_t max_n)
+{
+    hipStream_t q = c->e->qa;
+    if (c->t0) HD_HIP(hipEventRecord(c->t0, q));
+    for (uint32_t off = 0; off < max_n; off += HD_CLOCKED_CHUNK) {
+        uint32_t lds_words = 64;
+        for (uint32_t s = 0; s < c->S; ++s) {
+            hd::ClockedSrc& d = c->src.p[s];
+            d.off = off;
+            d.n = d.n_total > off ? std::min<uint32_t>(HD_CLOCKED_CHUNK, d.n_total - off) : 0u;
+            if (c->modem[s].F) lds_words = std::max(lds_words, hd::clocked_window_words(c->modem[s], d.n));
+        }
+        std::atomic_thread_fence(std::memory_order_release);
+        if (!hd::launch_clocked(q, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, lds_words))
+            return fail(HD_ERR_DEVICE, "clocked decoder: the launch's window does not fit the LDS");
+        HD_HIP(hipGetLastError());
+        if (c->t1 && off + HD_CLOCKED_CHUNK >= max_n) HD_HIP(hipEventRecord(c->t1, q));
+        HD_HIP(hipStreamSynchronize(q));
+    }
+    return HD_OK;
+}
+
+int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = c->e->qa;
+    HD_HIP(hipMemcpyAsync(c->st + s0, c->modem.data() + s0, (size_t)ns * sizeof(hd::ClockedState), hipMemcpyHostToDevice, q));
+    HD_HIP(hipMemset2DAsync(c->ring + (size_t)s0 * c->ring_stride + hd::kClockedGuard, c->ring_stride * sizeof(uint32_t), 0,
+                            (size_t)HD_CLOCKED_RING * sizeof(uint32_t), ns, q));
+    HD_HIP(hipStreamSynchronize(q));
+    for (uint32_t s = s0; s < s0 + ns; ++s) { c->tx[s].reset(); c->tx[s].nbits = c->modem[s].nbits; }
+    return HD_OK;
+}
+
+// The stream's waiting records leave the ring through its text stage; up to cap of them are copied to out (out null: none are kept).
+int clocked_drain(hd_clocked* c, uint32_t s, hd_clocked_record* out, size_t cap, size_t* n_out)
+{
+    hd::ClockedState h;
+    HD_HIP(hipMemcpy(&h, c->st + s, sizeof h, hipMemcpyDeviceToHost));
+    const uint64_t have = h.written - h.taken, rc = c->prm.record_cap;
+    const size_t k = out ? (size_t)std::min<uint64_t>(have, cap) : (size_t)have;
+    *n_out = k;
+    if (!k) return HD_OK;
+    std::vector<hd_clocked_record> tmp(k);
+    const uint32_t* base = c->rec + (size_t)s * c->rec_stride + hd::kClockedGuard;
+    for (size_t i = 0; i < k;) {             // at most two pieces: the ring wraps once inside record_cap records
+        const uint64_t slot = (h.taken + i) % rc;
+        const size_t m = (size_t)std::min<uint64_t>(k - i, rc - slot);
+        HD_HIP(hipMemcpy(tmp.data() + i, base + slot * hd::kClockedRecWords, m * sizeof(hd_clocked_record), hipMemcpyDeviceToHost));
+        i += m;
+    }
+    h.taken += k;
+    HD_HIP(hipMemcpy(reinterpret_cast<char*>(c->st + s) + offsetof(hd::ClockedState, taken), &h.taken, sizeof h.taken, hipMemcpyHostToDevice));
+    c->tx[s].feed(tmp.data(), k);
+    if (out) std::memcpy(out, tmp.data(), k * sizeof(hd_clocked_record));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_clocked_params_default(hd_clocked_params* p) { if (p) hd::clocked_params_default(p); }
+
+int hd_clocked_create(hd_engine* e, const hd_clocked_params* params, hd_clocked** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_clocked> c(new hd_clocked);
+    c->e = e; c->S = e->S;
+    hd::clocked_params_default(&c->prm);
+    if (params) c->prm = *params;
+    if (!hd::clocked_params_ok(&c->prm)) return fail(HD_ERR_INVALID, "clocked decoder parameters: 16 <= record_cap <= 2^20, repair_bits <= 16, repair_flips <= 4");
+    if (const int rc = enter(e)) return rc;
+    c->modem.resize(c->S);
+    c->tx.resize(c->S);
+    for (uint32_t s = 0; s < c->S; ++s) {
+        const uint32_t nbits = (uint32_t)e->st[s].text.framer.nbits;
+        const double nstops = (double)e->st[s].text.framer.nstops;
+        const uint32_t F = hd::clocked_modem_F(e->fsd, e->st[s].baud, nbits, nstops);
+        hd::clocked_state_reset(c->modem[s], F, F ? nbits : 0u, F ? (uint32_t)nstops : 0u, 0u);
+        c->tx[s].repair_bits = c->prm.repair_bits; c->tx[s].repair_flips = c->prm.repair_flips;
+    }
+    c->ring_stride = (size_t)HD_CLOCKED_RING + 2 * hd::kClockedGuard;
+    c->rec_stride = (size_t)c->prm.record_cap * hd::kClockedRecWords + 2 * hd::kClockedGuard;
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->st), (size_t)c->S * sizeof(hd::ClockedState)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)c->S * c->ring_stride * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rec), (size_t)c->S * c->rec_stride * sizeof(uint32_t)));
+    HD_HIP(c->src.alloc(c->S));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kClockedGuardWord, (size_t)c->S * c->ring_stride, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rec), (int)hd::kClockedGuardWord, (size_t)c->S * c->rec_stride, e->qa));
+    if (const int rc = clocked_clear(c.get(), 0, c->S)) return rc;
+    *out = c.release();
+    return HD_OK;
+}
+
+void hd_clocked_destroy(hd_clocked* c) { destroy(c); }
+
+int hd_clocked_reset(hd_clocked* c, uint32_t stream)
+{
+    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
+    if (stream != UINT32_MAX && stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    return stream == UINT32_MAX ? clocked_clear(c, 0, c->S) : clocked_clear(c, stream, 1);
+}
+
+int hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t nbits, uint32_t nstops, int invert)
+{
+    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    const uint32_t F = hd::clocked_modem_F(c->e->fsd, baud, nbits, (double)nstops);
+    if (!F) return fail(HD_ERR_UNSUPPORTED, "clocked decoder: 3.5 <= decimated rate / baud <= " + std::to_string(HD_CLOCKED_MAX_SPB) + ", 7 or 8 data bits, 1 or 2 stop bits");
+    if (const int rc = enter(c->e)) return rc;
+    hd::clocked_state_reset(c->modem[stream], F, nbits, nstops, invert ? 1u : 0u);
+    return clocked_clear(c, stream, 1);
+}
+
+int hd_clocked_push_engine(hd_clocked* c)
+{
+    return push_engine(c, kNullClocked, "hd_clocked_push_engine", [c](uint32_t max_n) { return clocked_launch(c, max_n); });
+}
+
+int hd_clocked_push_device(hd_clocked* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(c, kNullClocked, d_rows, stride, n_per_stream, n, true, [c](uint32_t max_n) { return clocked_launch(c, max_n); });
+}
+
+int hd_clocked_push_host(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(c, kNullClocked, rows, stride, n_per_stream, n, false, [c](uint32_t max_n) { return clocked_launch(c, max_n); });
+}
+
+int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, size_t cap)
+{
+    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    if (!out) {
+        hd::ClockedState h;
+        HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+        return (int)(h.written - h.taken);
+    }
+    size_t n = 0;
+    if (const int rc = clocked_drain(c, stream, out, cap, &n)) return rc;
+    return (int)n;
+}
+
+int hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap)
+{
+    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    size_t n = 0;
+    if (const int rc = clocked_drain(c, stream, nullptr, 0, &n)) return rc;
+    return (int)c->tx[stream].take(out, cap);
+}
+
+int hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out)
+{
+    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
+    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    hd::ClockedState h;
+    HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+    const hd::ClockedText& t = c->tx[stream];
+    *out = hd_clocked_counters{h.n, h.p, h.chars, h.rejects, h.dropped, t.matches_failed, t.plain, t.repaired};
+    return HD_OK;
+}
+
+int hd_debug_clocked_push_timed(hd_clocked* c, float* kernel_ms, double* host_us) { return push_timed(c, kernel_ms, host_us, hd_clocked_push_engine); }
+
+// Test hook (tests/test_gpu_clocked.py; not part of the ABI): how many of the guard words around the stream's two rings no longer hold their pattern.
+int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
+{
+    if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    uint32_t g[4][hd::kClockedGuard];
+    const uint32_t* at[4] = {c->ring + (size_t)stream * c->ring_stride, c->ring + (size_t)(stream + 1) * c->ring_stride - hd::kClockedGuard,
+                             c->rec + (size_t)stream * c->rec_stride, c->rec + (size_t)(stream + 1) * c->rec_stride - hd::kClockedGuard};
+    int bad = 0;
+    for (int i = 0; i < 4; ++i) {
+        HD_HIP(hipMemcpy(g[i], at[i], sizeof g[i], hipMemcpyDeviceToHost));
+        for (uint32_t w : g[i]) bad += w != hd::kClockedGuardWord;
+    }
+    return bad;
+}
+
+}  // extern "C"

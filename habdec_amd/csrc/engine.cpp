@@ -6,288 +6,39 @@
 // kernels over all streams on one HIP stream, fetch the packed bits and spectrum statistics, and run the host
 // text stage (RTTY framing, sentence extraction, CRC, callbacks: Decoder.h:559-637) and the AFC state machine.
 // There is no CPU fallback: without a gfx950 device and the kernels in this library hd_engine_create fails.
-#include <hip/hip_runtime.h>
-#include <rocfft/rocfft.h>
-
-#include <algorithm>
+//
+// The engine's state (struct hd_engine and what it is made of) is in engine_state.h, shared with the objects that work beside the pipeline:
+// wideband.cpp (survey, waterfall) and demod_rows.cpp (baud-rate probe, clocked decoder).
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <memory>
 #include <condition_variable>
-#include <mutex>
 #include <thread>
-#include <string>
-#include <vector>
 
-#include "../../include/habdec_amd.h"
-#include "dev_types.h"
-#include "host/afc_tracker.hpp"
-#include "host/decim_plan.hpp"
-#include "host/fir_design.hpp"
+#include "engine_state.h"
 #include "host/iq_convert.hpp"
 #include "host/iq_file_batch.hpp"
-#include "host/survey.hpp"
-#include "host/baud_probe.hpp"
-#include "host/clocked.hpp"
-#include "host/format_trial.hpp"
-#include "host/text_stage.hpp"
 #include "host/tune_host.hpp"
-#include "kernels/launch.h"
 #include "kernels/spectrum_math.h"
-#include "kernels/survey.h"
-#include "kernels/waterfall.h"
-#include "host/waterfall.hpp"
 
 // A launcher (or layout helper) of the kernels that exist once per arithmetic mode (kernels/arith.h): hd::exact::fn or hd::fast::fn by the engine's mode.
 #define HDK(fn, ...) (e->fast ? hd::fast::fn(__VA_ARGS__) : hd::exact::fn(__VA_ARGS__))
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HD_HIP(call)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (call);                                                                        \
-        if (e_ != hipSuccess) return fail(HD_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        n = count;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) e = hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
-        return e;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-template <typename T>
-struct PinBuf {
-    T* p = nullptr;
-    T* dev = nullptr;      // the same memory as the GPU addresses it (kernels write results straight into it)
-    size_t n = 0;
-    hipError_t alloc(size_t count)
-    {
-        n = count;
-        hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocMapped | hipHostMallocCoherent);
-        if (e == hipSuccess) std::memset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), p, 0);
-        return e;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
-
-// The size bookkeeping mirrored from the reference that one call advances.  plan_call computes every stream's next state into
-// hd_engine::mirror_next; commit_call makes it the current one (hd_engine::mirror) once the call is enqueued -- a refused call leaves it as it was.
-struct SizeState {
-    size_t stage_buf[2] = {0, 0};   // Decimator::p_buff_.size()
-    size_t pending = 0;             // iq_samples_decimated_.size()
-    size_t fft_fill = 0;            // freq_in_.size()
-    size_t fir_buf = 0;             // FirFilter::buff_.size()
-    uint32_t fir_T_run = 0;         // tap count of the last low-pass run (FirHistory, dev_types.h)
-    uint32_t head_n = 0;            // FirHistory head, lazily: how many samples of the last run's input a later run may ask for ...
-    uint64_t head_call = ~0ull;     // ... the call that run was in (its input sits in THAT call's low-pass buffer until the buffer's turn comes again) ...
-    bool head_aside = false;        // ... or: the head has been copied to the side buffer (the stream did not run in the call behind its last run)
-    uint32_t tune_phase = 0;        // tuning phase of the next call to be submitted
-    uint32_t front_phase = 0;       // ... and the phase of the tuning at the input rate (hd_stream_set_front_tune)
-    uint32_t win_ub = 0, inflight_m = 0;   // upper bound of backlog samples without final window results; low-pass outputs of undelivered calls (collect() learns them back)
-    uint32_t last_n2 = 0, last_pend_before = 0, last_m = 0;   // last call (for the getters)
-    int last_buf = 0;
-    uint8_t fft_buf = 0;            // which of the stream's two spectrum collection buffers the next call appends to (dev_types.h sc_fft_buf; always 0 unless hd_engine::lazy_spectra)
-    uint8_t spec_buf = 0;           // ... and the one that completed last
-    bool spec_stale = false;        // the spectrum of that buffer has not been stored into `spec` / `power`: the tail that transformed it kept the statistics only (refresh_spectra)
-    bool demod_in_ring = false;     // the last call's discriminator output was not stored into `demod`: it is the newest last_m samples of the symbol ring (fill_tail)
-};
-
-struct StreamHost {
-    // control plane
-    double baud = 300;
-    float lp_bw = 1500, lp_trans = 0.025f;
-    bool dc = false;
-    hd::LowpassDesigner lp;
-    bool taps_dirty = false;
-    uint32_t tune_step = 0;         // tuning step of the next call to be submitted (hd_stream_set_tune; its phase: SizeState::tune_phase)
-    // data-dependent state learned back from the device
-    uint32_t held = 0;
-    bool sym_reset = true;          // symbol parameters changed since the window cache was built
-    // host stages
-    hd::TextStage text;
-    hd::AfcTracker afc;
-    hd::SpectrumStats stats{};
-    bool have_spectrum = false;     // freq_out_.size() == 4096
-    uint64_t spectra = 0;
-    // last call delivered (for the getters)
-    uint32_t last_nbits = 0, last_nflips = 0;
-    uint64_t flip_list_full = 0;   // calls in which the device's flip list filled up (kMaxFlipsPerCall) and the search went on a call later
-    uint64_t bits_total = 0;
-    std::vector<uint32_t> last_words;
-    uint32_t demod_ck[2] = {0, 0}, demod_ck_n = 0xFFFFFFFFu;   // discriminator checksum of the call delivered last (BitsHeader::demod_ck)
-    uint64_t demod_ck_call = 0;                               // ... and that call's index (0 = the engine's first hd_process_* call)
-    uint64_t demod_ck_hash = 0xCBF29CE484222325ull;           // every delivered call's (n, ck[0], ck[1]) folded into one word (hd_stream_demod_checksum_total)
-    uint64_t demod_ck_calls = 0, demod_ck_unknown = 0;        // calls folded in / calls whose slot carried no checksum (0: every route fills it)
-    // digital tuning of the decimated chunk (hd_stream_set_tune, kernels/tune.h) and the closed loop over it (hd_stream_set_auto_afc)
-    double tune_hz = 0;
-    uint64_t tune_from = 0, retunes = 0;      // first call of the current offset; automatic retunes so far
-    bool auto_afc = false;
-    double afc_hold_s = 6.0, afc_min_hz = 100.0;
-    uint64_t afc_elapsed = 0;                 // input samples delivered since the loop was set or last retuned
-    // tuning at the input rate, in front of the first decimation stage (hd_stream_set_front_tune; its phase: SizeState::front_phase)
-    double front_hz = 0;
-    uint32_t front_step = 0;
-    uint64_t front_from = 0;                  // first call of the current offset
-    // framing trial (hd_stream_set_format_trial): four text stages beside `text`, fed the same bits at delivery; null while off
-    std::shared_ptr<hd::FormatTrial> trial;     // (shared: a StreamHost is copied where a setter tries a value out)
-};
+thread_local std::string g_err;     // hd_last_error: one per thread, whichever translation unit refused the call
 
 }  // namespace
 
-struct hd_engine {
-    hd_engine_config cfg{};
-    double fs = 0, fsd = 0;
-    std::vector<hd::DecimStage> stages;
-    uint32_t S = 0, D = 1;
-    uint32_t n1_cap = 0, n2_cap = 0;        // per-call capacities after stage 1 / last stage
-    uint32_t taps_cap = 0, fir_hist_cap = 0; // low-pass tap capacity, history slots in front of the pending samples
-    size_t fbuf_stride = 0;
-    uint32_t tail_cap = 0, backlog_cap = 0, slot_words = 0, flips_cap = 0, max_R = 0, min_R = 4;
-    int bins_sep = 8;
-    bool decode_enabled = true;
-    bool fast = false;         // hd_engine_config.arith == HD_ARITH_FAST: the hd::fast kernels (fused multiply-add in every FIR; tolerance 1e-5, not bit-identical floats)
-    bool one_stream = false;
-    bool lazy_spectra = false; // batch mode: the stream tails store a spectrum's AFC statistics only; `spec` / `power` are filled when a getter asks (refresh_spectra).  HD_EAGER_SPECTRA=1: stored by every tail
-    bool no_tail = false;      // HD_NO_TAIL: never use the one-wave stream tail (kernels/tail_body.h); A/B measurements
-    uint32_t tail_max_n2 = 2048;   // HD_TAIL_MAX_N2: most decimated samples per call for which the stream tail is used
-    int last_route = -1;       // route of the previous call (Route; the routes use the stage-2 buffers on different queues)
-    // Step mode (batch decoding, kernels/decimate.hip k_step): the stream tails of call k ride in the stage-1 launch of call k+1.
-    struct PendingTail { bool valid = false; hd::TailArgs ta{}; int slot = 0; int r2 = 0, t2 = 0; } pend;
-    DevBuf<float2> fft_tw;     // [64][64] the transform's twiddles, lane-major (kernels/spectrum_math.h: fft_twiddles), rounded once from double
-    bool no_claim = false;     // HD_NO_CLAIM: step launches with fixed shares of tiles (A/B measurements)
-    uint32_t step_run = 0;     // HD_STEP_RUN: tiles per drawn run (default 4, minimum 2)
-    bool no_cu_step = false;   // HD_NO_CU_STEP: step launches as single-wave workgroups (k_step) instead of one workgroup per CU (k_step_cu)
-    uint32_t ring_run = 0;     // HD_RING_RUN: tiles per drawn run of the per-CU ring kernels (default: pick_ring_run)
-    uint32_t ring_chain = 1;   // HD_RING_CHAIN: 0 = the /32 worker waves' tiles all stand alone (the plain schedule: 64 - HR outputs per tile); default: chained runs (host/ring_schedule.hpp)
-    uint32_t ring_short_pct = 25;   // HD_RING_SHORT_PCT: share of an XCD's tiles the worker waves draw as SINGLE tiles at the end of a launch (guided hand-out; 0 = whole runs to the end)
-    bool ring_short_set = false;    // ... was given.  Not given, chained launches take an eighth of the streams, not a quarter (make_claim)
-#ifndef HD_S1_SLOTS_BATCH
-#define HD_S1_SLOTS_BATCH 4
-#endif
-    static constexpr uint32_t kS1Slots = HD_S1_SLOTS_BATCH;     // tile slots of k_stage1_cu in batch mode on the separate-kernels path: four leave half of a CU's LDS to the back-half
-                                                // workgroups of the previous call on the other queue (/16: 0.334-0.343 ms per step against 0.342-0.351 with eight)
-    PinBuf<unsigned int> ring_gave_up;     // mapped host word a wave of k_step_cu / k_stage1_cu sets when a bounded wait runs out (never in a correct run)
-    std::string fail_cause;                // what put the engine into its failed state (reported again by every later call)
-    bool device_failed = false;            // ... after which the engine stays failed: the launch that gave up left stage-1 output incomplete, and up to
-                                           // three calls are undelivered by the time a collect() sees the word -- which of them it was cannot be told
-    uint64_t step_launches = 0;
-    DevBuf<unsigned int> step_ctr;         // two sets of per-XCD run counters ([2][16][32] u32), alternating per step launch
-    uint32_t pend_max_taps = 0;
-    bool dec_wgs_forced = false;   // HD_DEC_WGS_PER_CU was given (tests of the linear split)
-    // Timing experiments (results wrong: step launches without their tails -- 1 -- or without stage 1 -- 2; tools/micro/joules.py) exist in a VARIANT build only
-    // (-DHD_TIMING_EXPERIMENT, HD_BUILD_VARIANT=timingexp: reads HD_CU_EXP): no environment variable makes the product library skip the result-slot tag
-    // check or deliver wrong results.
-#ifdef HD_TIMING_EXPERIMENT
-    int cu_exp = 0;
-#else
-    static constexpr int cu_exp = 0;
-#endif
-    uint32_t n_cus = 0, dec_wgs_per_cu = 0;   // stage-1 linear split: workgroups per CU (0 = classic grid), see kernels/decimate.hip
-    hipStream_t qa = nullptr, qb = nullptr, qc = nullptr;   // front (decimation, spectrum) and back (FIR, symbols, results) HIP streams
-    // hd_process_host: copies run on their own stream into two alternating slabs; a call returns once ITS copy has landed, so the
-    // caller may reuse (or free) the buffer at once, like Decoder::pushSamples' copy -- whatever the engine still has queued.
-    hipStream_t qh = nullptr;
-    DevBuf<float2> staging2;
-    hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_staging_free[2] = {nullptr, nullptr};
-    bool staging_used[2] = {false, false};
-    uint64_t host_calls = 0, host_calls_in_place = 0;   // hd_process_host calls through the staging slabs / served in place from page-locked memory
-    // hd_process_*_fmt: a packed call is unpacked into the staging slab of its turn (kernels/iq_unpack.hip) and goes on as a cf32 call on that slab -- on
-    // qh, or on a synchronous engine's own queue where there is nothing to copy.  packed[j]: where the packed bytes of a pageable (or batch-mode) host
-    // buffer land first, [S][max_chunk] samples of the widest format seen so far, allocated on first use; unpack_n: the call's per-stream counts for the
-    // kernel (one array: the unpack that read it is done when its call returns).
-    unsigned char* packed[2] = {nullptr, nullptr};
-    size_t packed_bytes[2] = {0, 0};
-    DevBuf<uint32_t> unpack_n;
-    uint32_t timing_every = 8;   // HIP-event timing on every Nth call (0 = off): each event record is a barrier packet worth ~6 us of queue time
-    hd_timing last_timing{};
-    // Fast mode, long low-pass filters (>= kLpFftMinTaps taps: configs[4]'s 4097): the filter as transforms (kernels/fir_demod.hip: k_lp_gather / k_lp_mul around
-    // rocFFT, k_fir_demod with the filtered samples handed in).  Two transform lengths, the smaller one where [history | inputs] of every stream fits it.
-    static constexpr uint32_t kLpFftMinTaps = 1024;
-    uint32_t lpf_N[2] = {0, 0};
-    rocfft_plan lpf_fwd[2] = {nullptr, nullptr}, lpf_inv[2] = {nullptr, nullptr};
-    rocfft_execution_info lpf_info = nullptr;
-    DevBuf<char> lpf_workbuf;
-    DevBuf<float2> lpf_x, lpf_k;           // [S][lpf_N[1]]: the input images / filtered samples of the call in the back half; the taps' spectra
-    PinBuf<uint32_t> lpf_ntaps;            // [S]: tap counts the spectra in lpf_k were made from
-    uint32_t lpf_k_N = 0;                  // ... and the transform length (0: none yet)
-    bool lpf_k_stale = true;
-    uint64_t lpf_calls = 0;
+int hd::eng::fail(int code, const std::string& msg) { g_err = msg; return code; }
 
-    DevBuf<float2> staging, dec1, dec1b, dec1c, hist1[2], hist2[2], fbuf[3], fft_in, spec, filtered;   // dec1/b/c: stage-1 output, rotating per call
-    DevBuf<float> stage_taps[2], lp_taps, power, demod, tail, weight;
-    DevBuf<unsigned long long> flipmask;
-    DevBuf<uint32_t> flips_dbg;
-    DevBuf<hd::SymState> d_symstate;
-    DevBuf<hd::DemodCarry> carry[2];
-    DevBuf<float2> fir_head;          // [S][head_cap]: FirHistory heads moved aside -- the first samples of a stream's last low-pass run's input, copied here by the first call in
-                                      // which the stream did not run (dev_types.h: the head, lazily); a stream that ran in the previous call finds them in that call's buffer
-    DevBuf<float> tune_tab;           // the phasor tables [C | F] of the per-stream tuning (kernels/tune.h), 2 x 256 (cos, sin)
-    DevBuf<uint32_t> demod_ck_acc;    // [S][2]: the discriminator checksum of the call in the back half of the separate-kernels path (k_fir_demod adds, k_symbols collects and clears)
-    uint32_t head_cap = 0;
-    DevBuf<hd::SymbolParams> d_sym;
-    PinBuf<hd::SymbolParams> h_sym;
-    PinBuf<hd::StreamCall> h_spec_call;   // [S], lazy_spectra: the parameter block of the spectrum launch a getter triggers (only fft_run is set: which streams, which buffer)
-    // Everything a call in flight owns, double-buffered so call k+1 can be enqueued (and its front half can run)
-    // while call k's back half is still executing and its results have not been read yet.
-    static constexpr int kSlots = 4;   // calls whose host-visible blocks (parameters, result slots, spectrum statistics) may be in use at once: in flight + being delivered
-    struct CallSlot {
-        DevBuf<hd::StreamCall> d_call;
-        PinBuf<hd::StreamCall> h_call;
-        PinBuf<uint32_t> h_slots;                 // written by the symbol scan kernel over PCIe (zero-copy), read after ev_done
-        PinBuf<hd::SpectrumStatsDev> h_stats;    // written by the spectrum kernel
-        PinBuf<uint2> h_tune;                     // (step, phase) of every stream for this call, read by the kernels in place; passed only when some stream is tuned
-        PinBuf<uint2> h_front;                    // the same for the tuning at the input rate: read in place by k_decimate_tuned, which runs only when some stream has one
-        bool timed = false, timed_step = false;   // this call carries the timing events (a step call: only the two around its one launch)
-        hipEvent_t ev_front = nullptr, ev_done = nullptr, ev_params = nullptr, ev_spec = nullptr, t0 = nullptr, t1 = nullptr, t2 = nullptr, t3 = nullptr;
-        bool busy = false;
-        uint32_t seq = 0;                         // this call's tag: what every result slot's BitsHeader::seq must read before the slot is taken as delivered
-        uint64_t total_in = 0;
-        uint32_t r1 = 1;
-        ~CallSlot() { for (hipEvent_t ev : {ev_front, ev_done, ev_params, ev_spec, t0, t1, t2, t3}) if (ev) (void)hipEventDestroy(ev); }
-    } slot[kSlots];
-    uint64_t calls = 0;
-    uint64_t delivered = 0;   // calls whose results have been delivered; calls - delivered <= 2 (pipelined mode)
-    int cur = 0;          // which fbuf receives this call's chunk (three take turns: the one a call writes was last read by the back half of call k-3, which the host has collected)
-    int hist_cur = 0;     // which stage-history buffers are read this call (the others are written)
-    int carry_cur = 0;
-    bool sym_dirty = true;
-
-    std::vector<StreamHost> st;
-    std::vector<SizeState> mirror, mirror_next;   // [S]: the streams' size bookkeeping; the call being planned (swapped in by commit_call)
-    std::recursive_mutex mtx;   // recursive: a sentence / character callback (fired under it, on the calling thread) may call the text getters
-    bool in_callback = false;   // ... but not the data getters that would have to flush the pipeline from inside a delivery
-    hd_sentence_cb sentence_cb = nullptr; void* sentence_user = nullptr;
-    hd_match_cb match_cb = nullptr; void* match_user = nullptr;
-    hd_chars_cb chars_cb = nullptr; void* chars_user = nullptr;
-    uint64_t sentences_ok = 0;
-
-    ~hd_engine()
-    {
-        for (rocfft_plan pl : {lpf_fwd[0], lpf_fwd[1], lpf_inv[0], lpf_inv[1]}) if (pl) rocfft_plan_destroy(pl);
-        if (lpf_info) rocfft_execution_info_destroy(lpf_info);
-        if (qa) (void)hipStreamDestroy(qa);
-        if (qb && qb != qa) (void)hipStreamDestroy(qb);
-        if (qc && qc != qa) (void)hipStreamDestroy(qc);
-        if (qh) (void)hipStreamDestroy(qh);
-        for (unsigned char* pk : packed) if (pk) (void)hipFree(pk);
-        for (hipEvent_t ev : {ev_copy[0], ev_copy[1], ev_staging_free[0], ev_staging_free[1]}) if (ev) (void)hipEventDestroy(ev);
-    }
-};
+int hd::eng::check_stream(const hd_engine* e, uint32_t s)
+{
+    if (!e) return fail(HD_ERR_INVALID, "null engine");
+    if (s >= e->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    return HD_OK;
+}
 
 namespace {
 
@@ -311,13 +62,6 @@ hd::SymbolParams symbol_params(const hd_engine* e, const StreamHost& s)
 }
 
 float cutoff_rel(const hd_engine* e, const StreamHost& s) { return (float)(s.lp_bw / e->fsd); }
-
-int check_stream(const hd_engine* e, uint32_t s)
-{
-    if (!e) return fail(HD_ERR_INVALID, "null engine");
-    if (s >= e->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    return HD_OK;
-}
 
 }  // namespace
 
@@ -748,6 +492,25 @@ int hd_stream_tune(hd_engine* e, uint32_t s, hd_tune_info* out)
     return HD_OK;
 }
 
+// framing trial (host/format_trial.hpp)
+int hd_stream_set_format_trial(hd_engine* e, uint32_t s, int on)
+{
+    if (check_stream(e, s)) return HD_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    e->st[s].trial.reset(on ? new hd::FormatTrial : nullptr);
+    return HD_OK;
+}
+
+int hd_stream_format_trial(hd_engine* e, uint32_t s, hd_format_trial_result* out)
+{
+    if (check_stream(e, s)) return HD_ERR_INVALID;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> l(e->mtx);
+    if (!e->st[s].trial) return fail(HD_ERR_INVALID, "the stream's framing trial is off (hd_stream_set_format_trial)");
+    e->st[s].trial->get(out);
+    return HD_OK;
+}
+
 }  // extern "C"
 
 /* ---------------------------------------------------------------- data path ------------------------------------ */
@@ -898,12 +661,16 @@ int deliver(hd_engine* e, uint64_t depth)
     return rc;
 }
 
-int flush_locked(hd_engine* e)
+}  // namespace
+
+int hd::eng::flush_locked(hd_engine* e)
 {
     // step mode: the newest call's tails have not been launched yet -- start them before the host spends time on the older call's text
     if (e->delivered < e->calls) { if (const int r = run_pending_tail(e)) return r; }
     return deliver(e, 0);
 }
+
+namespace {
 
 /* One hd_process_device call, in stages:
  *   plan_call    sizes and the reference's bookkeeping: the slot's StreamCall / tuning entries, a summary (CallPlan), the mirror after the call;
@@ -1731,6 +1498,31 @@ int hd_process_device_fmt(hd_engine* e, int fmt, const void* d_iq, size_t stride
     return process_packed(e, fmt, d_iq, stride, n_per_stream, n_uniform, true);
 }
 
+// Measurement and test hook (tools/micro/iq_format_rate.py, tests/test_gpu_iq_formats.py; not part of the ABI): one unpack launch straight into a buffer
+// of the caller's, between two HIP events on the host-copy queue -- row r reads d_n[r] (a device array; null: n_uniform) samples at
+// d_src + r * src_stride * bps and writes them at d_dst + r * dst_stride.  With fmt = HD_IQ_CF32: a device-to-device copy of rows * n_uniform * 8 bytes.
+int hd_debug_iq_unpack_timed(hd_engine* e, int fmt, const void* d_src, size_t src_stride, const uint32_t* d_n, uint32_t n_uniform, uint32_t max_n,
+                             uint32_t rows, void* d_dst, size_t dst_stride, float* ms)
+{
+    if (!e || !d_src || !d_dst || !ms) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    HD_HIP(hipSetDevice(e->cfg.device));
+    if (!e->qh) HD_HIP(hipStreamCreateWithFlags(&e->qh, hipStreamNonBlocking));
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    HD_HIP(hipEventCreate(&t0));
+    HD_HIP(hipEventCreate(&t1));
+    HD_HIP(hipEventRecord(t0, e->qh));
+    bool ok = true;
+    if (fmt == HD_IQ_CF32) HD_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)rows * n_uniform * sizeof(float2), hipMemcpyDeviceToDevice, e->qh));
+    else ok = hd::launch_iq_unpack(e->qh, fmt, rows, max_n, d_src, src_stride, d_n, n_uniform, static_cast<float2*>(d_dst), dst_stride);
+    HD_HIP(hipEventRecord(t1, e->qh));
+    HD_HIP(hipEventSynchronize(t1));
+    HD_HIP(hipEventElapsedTime(ms, t0, t1));
+    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
+    HD_HIP(hipGetLastError());
+    return ok ? HD_OK : fail(HD_ERR_INVALID, "unknown IQ format");
+}
+
 /* ---------------------------------------------------------------- batched file ingest -------------------------- */
 
 int hd_ingest_run(hd_engine* e, hd_host_iqfiles* src, uint64_t max_rounds, uint64_t* samples_done)
@@ -2012,1257 +1804,3 @@ uint32_t hd_stream_symbol_backlog(hd_engine* e, uint32_t s)
 
 }  // extern "C"
 
-/* ---------------------------------------------------------------- wideband survey (kernels/survey.hip) -------------------------- */
-
-struct hd_survey {
-    hd_engine* e = nullptr;
-    hipStream_t q = nullptr;               // the survey's own queue: launches, staging copies and the read-back
-    uint32_t runs_per_launch = 1024;       // HD_SURVEY_RUNS, read at creation
-    const float2* tw = nullptr;            // the engine's twiddles, or own_tw where the engine computes no spectra
-    float2* own_tw = nullptr;
-    float* win = nullptr;                  // [4096] the window table
-    float* partial = nullptr;              // [runs_per_launch][4096] float rows of the launch in flight (launches of one queue run in order)
-    double* acc = nullptr;                 // [4096], for the life of the survey
-    float2* slab = nullptr;                // hd_survey_push_host: staging for kSlabSegs segments, allocated by the first host push
-    unsigned char* pslab = nullptr;        // hd_survey_push_host_fmt: the same segments packed (sized for cs16), in front of the unpack into `slab`
-    double* h_acc = nullptr;               // page-locked landing place of the read-back
-    double sum_w2 = 0;                     // sum of w^2, in double over the float table
-    uint64_t segments = 0;
-    static constexpr uint32_t kSlabSegs = 256;   // whole segments one staging copy carries ((256 + 1) hops = 4 MiB + 16 KiB)
-    ~hd_survey()
-    {
-        for (void* p : {(void*)own_tw, (void*)win, (void*)partial, (void*)acc, (void*)slab, (void*)pslab}) if (p) (void)hipFree(p);
-        if (h_acc) (void)hipHostFree(h_acc);
-        if (q) (void)hipStreamDestroy(q);
-    }
-};
-
-namespace {
-
-// Segments [seg0, seg1) of a push whose run length is r, read from x (x[0] = the push's first sample when base_seg = 0, else sample 2048 base_seg):
-// launches of at most runs_per_launch runs, each followed by its reduction.  seg0 - base_seg is a multiple of r.
-int survey_enqueue(hd_survey* sv, const float2* x, uint64_t base_seg, uint64_t seg0, uint64_t seg1, uint32_t r)
-{
-    for (uint64_t s = seg0; s < seg1;) {
-        const uint64_t runs_left = (seg1 - s + r - 1) / r;
-        const uint32_t runs = (uint32_t)std::min<uint64_t>(runs_left, sv->runs_per_launch);
-        hd::launch_survey(sv->q, runs, x, sv->win, sv->tw, sv->partial, s - base_seg, seg1 - base_seg, r);
-        hd::launch_survey_reduce(sv->q, sv->partial, runs, sv->acc);
-        HD_HIP(hipGetLastError());
-        s += (uint64_t)runs * r;
-    }
-    return HD_OK;
-}
-
-int survey_enter(hd_survey* sv)
-{
-    if (sv->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + sv->e->fail_cause + ") -- destroy the engine");
-    HD_HIP(hipSetDevice(sv->e->cfg.device));
-    return HD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hd_survey_create(hd_engine* e, hd_survey** out)
-{
-    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    std::unique_ptr<hd_survey> sv(new hd_survey);
-    sv->e = e;
-    if (const int rc = survey_enter(sv.get())) return rc;
-    if (const char* v = getenv("HD_SURVEY_RUNS")) sv->runs_per_launch = (uint32_t)std::min(std::max(atol(v), 1L), 4096L);
-    HD_HIP(hipStreamCreateWithFlags(&sv->q, hipStreamNonBlocking));
-    std::vector<float> w(hd::kSurveyBins);
-    hd::survey_window(w.data());
-    for (float v : w) sv->sum_w2 += (double)v * (double)v;
-    // (plain allocations, filled on the survey's queue: nothing here runs on the null stream or waits for the engine's queues)
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->win), hd::kSurveyBins * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->partial), (size_t)sv->runs_per_launch * hd::kSurveyBins * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->acc), hd::kSurveyBins * sizeof(double)));
-    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&sv->h_acc), hd::kSurveyBins * sizeof(double), hipHostMallocDefault));
-    std::vector<float2> tw;
-    sv->tw = e->fft_tw.p;
-    if (!sv->tw) {   // an engine without spectra holds no twiddles: the same table, the survey's own
-        tw.resize(hd::kFftBins);
-        hd::specwave::fft_twiddles(tw.data());
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->own_tw), tw.size() * sizeof(float2)));
-        HD_HIP(hipMemcpyAsync(sv->own_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, sv->q));
-        sv->tw = sv->own_tw;
-    }
-    HD_HIP(hipMemcpyAsync(sv->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, sv->q));
-    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->q));
-    HD_HIP(hipStreamSynchronize(sv->q));   // (the tables above are locals)
-    *out = sv.release();
-    return HD_OK;
-}
-
-void hd_survey_destroy(hd_survey* sv)
-{
-    if (!sv) return;
-    hd_engine* e = sv->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    (void)hipSetDevice(e->cfg.device);
-    if (sv->q) (void)hipStreamSynchronize(sv->q);
-    delete sv;
-}
-
-int hd_survey_reset(hd_survey* sv)
-{
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->q));
-    HD_HIP(hipStreamSynchronize(sv->q));   // (what was pushed before is done with its buffers)
-    sv->segments = 0;
-    return HD_OK;
-}
-
-int hd_survey_push_device(hd_survey* sv, const void* d_iq, uint64_t n)
-{
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    if (!d_iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    if (reinterpret_cast<uintptr_t>(d_iq) & 7) return fail(HD_ERR_INVALID, "IQ base must be 8-byte aligned");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    const uint64_t n_seg = hd::survey_segments(n);
-    if (!n_seg) return HD_OK;
-    {   // what the kernel reads must be memory the GPU can address: a host pointer HIP does not know never reaches a launch
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_iq) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
-                                                                 !(at.type == hipMemoryTypeHost && at.devicePointer))) {
-            (void)hipGetLastError();
-            return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_survey_push_host takes host memory)");
-        }
-    }
-    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);
-    if (const int rc = survey_enqueue(sv, static_cast<const float2*>(d_iq), 0, 0, n_seg, r)) return rc;
-    sv->segments += n_seg;
-    return HD_OK;
-}
-
-int hd_survey_push_host(hd_survey* sv, const float* iq, uint64_t n)
-{
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    const uint64_t n_seg = hd::survey_segments(n);
-    if (!n_seg) return HD_OK;
-    if (!sv->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->slab), (size_t)(hd_survey::kSlabSegs + 1) * hd::kSurveyHop * sizeof(float2)));
-    // The run length is the whole push's; a slab carries whole runs of it (at least one: r <= 64 segments), so every wave sums the segments it would
-    // have summed in one device push, and the rows reach the accumulators in the same order.  Copies and launches share the queue: a slab is
-    // overwritten only behind the launch that read it.
-    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);
-    const uint64_t per_slab = (uint64_t)(hd_survey::kSlabSegs / r) * r;
-    for (uint64_t s = 0; s < n_seg; s += per_slab) {
-        const uint64_t s1 = std::min(n_seg, s + per_slab);
-        const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
-        HD_HIP(hipMemcpyAsync(sv->slab, iq + 2 * (size_t)s * hd::kSurveyHop, samples * sizeof(float2), hipMemcpyHostToDevice, sv->q));
-        if (const int rc = survey_enqueue(sv, sv->slab, s, s, s1, r)) return rc;
-    }
-    HD_HIP(hipStreamSynchronize(sv->q));   // from here on the caller's buffer is theirs again
-    sv->segments += n_seg;
-    return HD_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// A packed push, host or device: the slab loop of hd_survey_push_host with an unpack in front of every slab's launches.
-int survey_push_packed(hd_survey* sv, int fmt, const void* iq, uint64_t n, bool device)
-{
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    const size_t bps = hd::iq_bytes(fmt);
-    if (!bps || fmt == HD_IQ_CF32) return fail(HD_ERR_INVALID, "unknown IQ format (HD_IQ_CF32, HD_IQ_CS16, HD_IQ_CS8, HD_IQ_CU8)");
-    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(HD_ERR_INVALID, "packed IQ base must be aligned to one sample (4 bytes cs16, 2 bytes cs8 / cu8)");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    const uint64_t n_seg = hd::survey_segments(n);
-    if (!n_seg) return HD_OK;
-    if (device) {   // what the kernel reads must be memory the GPU can address
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, iq) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
-                                                               !(at.type == hipMemoryTypeHost && at.devicePointer))) {
-            (void)hipGetLastError();
-            return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_survey_push_host_fmt takes host memory)");
-        }
-    }
-    const size_t slab_samples = (size_t)(hd_survey::kSlabSegs + 1) * hd::kSurveyHop;
-    if (!sv->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->slab), slab_samples * sizeof(float2)));
-    if (!device && !sv->pslab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->pslab), slab_samples * 4u));
-    const uint32_t r = hd::survey_run_len(n_seg, sv->runs_per_launch);     // the whole push's run length; a slab carries whole runs (hd_survey_push_host)
-    const uint64_t per_slab = (uint64_t)(hd_survey::kSlabSegs / r) * r;
-    const unsigned char* p = static_cast<const unsigned char*>(iq);
-    for (uint64_t s = 0; s < n_seg; s += per_slab) {
-        const uint64_t s1 = std::min(n_seg, s + per_slab);
-        const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
-        const unsigned char* from = p + (size_t)s * hd::kSurveyHop * bps;
-        if (!device) {
-            HD_HIP(hipMemcpyAsync(sv->pslab, from, samples * bps, hipMemcpyHostToDevice, sv->q));
-            from = sv->pslab;
-        }
-        if (!hd::launch_iq_unpack(sv->q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, sv->slab, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
-        if (const int rc = survey_enqueue(sv, sv->slab, s, s, s1, r)) return rc;
-    }
-    HD_HIP(hipStreamSynchronize(sv->q));   // from here on the caller's buffer is theirs again
-    sv->segments += n_seg;
-    return HD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hd_survey_push_host_fmt(hd_survey* sv, int fmt, const void* iq, uint64_t n)
-{
-    if (fmt == HD_IQ_CF32) return hd_survey_push_host(sv, static_cast<const float*>(iq), n);
-    return survey_push_packed(sv, fmt, iq, n, false);
-}
-
-int hd_survey_push_device_fmt(hd_survey* sv, int fmt, const void* d_iq, uint64_t n)
-{
-    if (fmt == HD_IQ_CF32) return hd_survey_push_device(sv, d_iq, n);
-    return survey_push_packed(sv, fmt, d_iq, n, true);
-}
-
-int hd_survey_power(hd_survey* sv, double* p, size_t cap, uint64_t* segments)
-{
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    if (!p) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    if (segments) *segments = sv->segments;
-    if (cap < hd::kSurveyBins) return 0;
-    HD_HIP(hipMemcpyAsync(sv->h_acc, sv->acc, hd::kSurveyBins * sizeof(double), hipMemcpyDeviceToHost, sv->q));
-    HD_HIP(hipStreamSynchronize(sv->q));
-    const double norm = (double)sv->segments * sv->sum_w2;
-    for (uint32_t i = 0; i < hd::kSurveyBins; ++i) p[i] = sv->segments ? sv->h_acc[i] / norm : 0.0;
-    return (int)hd::kSurveyBins;
-}
-
-// Measurement hook (tools/micro/survey_rate.py; not part of the ABI): hd_survey_push_device between two HIP events on the survey's queue.
-int hd_debug_survey_push_timed(hd_survey* sv, const void* d_iq, uint64_t n, float* ms)
-{
-    if (!sv || !ms) return fail(HD_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    if (const int rc = survey_enter(sv)) return rc;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    HD_HIP(hipEventCreate(&t0));
-    HD_HIP(hipEventCreate(&t1));
-    HD_HIP(hipEventRecord(t0, sv->q));
-    const int rc = hd_survey_push_device(sv, d_iq, n);
-    HD_HIP(hipEventRecord(t1, sv->q));
-    HD_HIP(hipEventSynchronize(t1));
-    HD_HIP(hipEventElapsedTime(ms, t0, t1));
-    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
-    return rc;
-}
-
-// Measurement and test hook (tools/micro/iq_format_rate.py, tests/test_gpu_iq_formats.py; not part of the ABI): one unpack launch straight into a buffer
-// of the caller's, between two HIP events on the host-copy queue -- row r reads d_n[r] (a device array; null: n_uniform) samples at
-// d_src + r * src_stride * bps and writes them at d_dst + r * dst_stride.  With fmt = HD_IQ_CF32: a device-to-device copy of rows * n_uniform * 8 bytes.
-int hd_debug_iq_unpack_timed(hd_engine* e, int fmt, const void* d_src, size_t src_stride, const uint32_t* d_n, uint32_t n_uniform, uint32_t max_n,
-                             uint32_t rows, void* d_dst, size_t dst_stride, float* ms)
-{
-    if (!e || !d_src || !d_dst || !ms) return fail(HD_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    HD_HIP(hipSetDevice(e->cfg.device));
-    if (!e->qh) HD_HIP(hipStreamCreateWithFlags(&e->qh, hipStreamNonBlocking));
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    HD_HIP(hipEventCreate(&t0));
-    HD_HIP(hipEventCreate(&t1));
-    HD_HIP(hipEventRecord(t0, e->qh));
-    bool ok = true;
-    if (fmt == HD_IQ_CF32) HD_HIP(hipMemcpyAsync(d_dst, d_src, (size_t)rows * n_uniform * sizeof(float2), hipMemcpyDeviceToDevice, e->qh));
-    else ok = hd::launch_iq_unpack(e->qh, fmt, rows, max_n, d_src, src_stride, d_n, n_uniform, static_cast<float2*>(d_dst), dst_stride);
-    HD_HIP(hipEventRecord(t1, e->qh));
-    HD_HIP(hipEventSynchronize(t1));
-    HD_HIP(hipEventElapsedTime(ms, t0, t1));
-    (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
-    HD_HIP(hipGetLastError());
-    return ok ? HD_OK : fail(HD_ERR_INVALID, "unknown IQ format");
-}
-
-void hd_survey_params_default(hd_survey_params* p) { if (p) hd::survey_params_default(p); }
-
-int hd_survey_detect(hd_survey* sv, const hd_survey_params* p, hd_survey_candidate* out, uint32_t cap, uint32_t* found)
-{
-    if (found) *found = 0;
-    if (!sv) return fail(HD_ERR_INVALID, "null survey");
-    if (!p || !found || (cap && !out)) return fail(HD_ERR_INVALID, "null argument");
-    std::lock_guard<std::recursive_mutex> lock(sv->e->mtx);
-    std::vector<double> pw(hd::kSurveyBins);
-    uint64_t segs = 0;
-    const int n = hd_survey_power(sv, pw.data(), pw.size(), &segs);
-    if (n < 0) return n;
-    const int rc = hd::survey_detect(pw.data(), segs, sv->e->fs, p, out, cap, found);
-    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "hd_survey_detect needs at least 16 segments and a floor above zero (" + std::to_string(segs) + " segments so far)");
-    if (rc) return fail(rc, "hd_survey_detect: bad parameters or a NaN / negative power");
-    return HD_OK;
-}
-
-}  // extern "C"
-
-/* ---------------------------------------------------------------- waterfall (kernels/waterfall.hip, host/waterfall.hpp) ----------------- */
-
-struct hd_waterfall {
-    hd_engine* e = nullptr;
-    hipStream_t q = nullptr;               // the waterfall's own queue: launches, staging copies and the read-backs
-    hd_waterfall_params par{};
-    uint32_t guard_lo = 0, guard_hi = 0;   // the bins dc_guard_hz takes out
-    const float2* tw = nullptr;            // the engine's twiddles, or own_tw where the engine computes no spectra
-    float2* own_tw = nullptr;
-    float* win = nullptr;                  // [4096] the survey's window table
-    float* factor = nullptr;               // [65] F[s]
-    float* ring = nullptr;                 // [rows_cap][4096]: row r lives at slot r % rows_cap
-    uint32_t* hits = nullptr;              // [4096]
-    hd::WaterfallRec* rec = nullptr;       // [kChunkRows] the detector's records of the chunk in flight
-    hd::WaterfallRec* h_rec = nullptr;     // their page-locked landing place
-    uint32_t* d_seg = nullptr;             // [kChunkRows] hd_waterfall_push_rows: the chunk's segment counts
-    uint32_t* h_hits = nullptr;            // page-locked landing place of hd_waterfall_hits
-    float2* slab = nullptr;                // host and packed pushes: staging for kSlabSegs segments, allocated by the first such push
-    unsigned char* pslab = nullptr;        // packed host pushes: the same segments packed (sized for cs16)
-    uint64_t samples = 0;                  // pushed since creation or reset
-    uint64_t rows_counted = 0;             // unflagged rows
-    std::vector<hd_waterfall_row> headers; // of all rows since creation or reset
-    std::vector<uint32_t> marks;           // [rows][128]
-    static constexpr uint32_t kSlabSegs = 256;    // as hd_survey: (256 + 1) hops = 4 MiB + 16 KiB
-    static constexpr uint32_t kChunkRows = 1024;  // most rows per launch and read-back (528 KiB of records): one k_survey wave per SIMD of the chip
-    uint32_t chunk_rows = kChunkRows;             // HD_WATERFALL_CHUNK, read at creation: fewer, so that short pushes reach the several-launch shapes
-    ~hd_waterfall()
-    {
-        for (void* p : {(void*)own_tw, (void*)win, (void*)factor, (void*)ring, (void*)hits, (void*)rec, (void*)d_seg, (void*)slab, (void*)pslab}) if (p) (void)hipFree(p);
-        if (h_rec) (void)hipHostFree(h_rec);
-        if (h_hits) (void)hipHostFree(h_hits);
-        if (q) (void)hipStreamDestroy(q);
-    }
-};
-
-namespace {
-
-int waterfall_enter(hd_waterfall* wf)
-{
-    if (wf->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + wf->e->fail_cause + ") -- destroy the engine");
-    HD_HIP(hipSetDevice(wf->e->cfg.device));
-    return HD_OK;
-}
-
-bool waterfall_is_device_pointer(const void* p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
-                                                          !(at.type == hipMemoryTypeHost && at.devicePointer))) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return true;
-}
-
-// The detector, the hit counters and the read-back for the n rows a launch has just put into the ring at `slot`; waits for the waterfall's queue and
-// appends headers and marks.  d_seg: the rows' segment counts on the device (null: seg_full each, the last one seg_last); first[b], seg[b]: the same
-// rows' first samples and segment counts for the headers.
-int waterfall_detect_chunk(hd_waterfall* wf, uint32_t slot, uint32_t n, const uint32_t* d_seg, uint32_t seg_full, uint32_t seg_last, const uint64_t* first,
-                           const uint32_t* seg)
-{
-    hd::launch_waterfall_detect(wf->q, n, wf->ring + (size_t)slot * hd::kWaterfallBins, d_seg, seg_full, seg_last, wf->guard_lo, wf->guard_hi, wf->factor, wf->rec);
-    hd::launch_waterfall_hits(wf->q, wf->rec, n, wf->hits);
-    HD_HIP(hipGetLastError());
-    HD_HIP(hipMemcpyAsync(wf->h_rec, wf->rec, (size_t)n * sizeof(hd::WaterfallRec), hipMemcpyDeviceToHost, wf->q));
-    HD_HIP(hipStreamSynchronize(wf->q));
-    for (uint32_t b = 0; b < n; ++b) {
-        const hd::WaterfallRec& r = wf->h_rec[b];
-        hd_waterfall_row h{};
-        h.first_sample = first[b]; h.segments = seg[b]; h.flags = r.flags; h.floor = r.floor; h.level = r.level; h.n_marked = r.n_marked;
-        wf->headers.push_back(h);
-        wf->marks.insert(wf->marks.end(), r.marks, r.marks + hd::kWaterfallWords);
-        if (!r.flags) ++wf->rows_counted;
-    }
-    return HD_OK;
-}
-
-// Rows of segments [seg0, seg1) of a push, read from x (x[0] = sample 2048 base_seg of the push; seg0 - base_seg is a multiple of L): launches of the
-// survey's kernel with run_len = L straight into the ring, cut where the ring wraps and at chunk_rows, each followed by its detector.
-int waterfall_enqueue(hd_waterfall* wf, const float2* x, uint64_t base_seg, uint64_t seg0, uint64_t seg1)
-{
-    const uint32_t L = wf->par.slot_segments;
-    uint64_t first[hd_waterfall::kChunkRows];
-    uint32_t seg[hd_waterfall::kChunkRows];
-    for (uint64_t s = seg0; s < seg1;) {
-        const uint64_t rows_left = (seg1 - s + L - 1) / L;
-        const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
-        const uint32_t n = (uint32_t)std::min<uint64_t>(rows_left, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
-        hd::launch_survey(wf->q, n, x, wf->win, wf->tw, wf->ring + (size_t)slot * hd::kWaterfallBins, s - base_seg, seg1 - base_seg, L);
-        const uint64_t s_end = std::min<uint64_t>(seg1, s + (uint64_t)n * L);
-        const uint32_t seg_last = (uint32_t)(s_end - (s + (uint64_t)(n - 1) * L));
-        for (uint32_t b = 0; b < n; ++b) { first[b] = wf->samples + (s + (uint64_t)b * L) * hd::kSurveyHop; seg[b] = b + 1 == n ? seg_last : L; }
-        if (const int rc = waterfall_detect_chunk(wf, slot, n, nullptr, L, seg_last, first, seg)) return rc;
-        s = s_end;
-    }
-    return HD_OK;
-}
-
-// A push through the staging slab: host cf32 (fmt = HD_IQ_CF32, device = false) or packed IQ from host or device memory.  A slab carries whole rows,
-// so every wave sums the segments it would have summed in one device push.
-int waterfall_push_slabs(hd_waterfall* wf, int fmt, const void* iq, uint64_t n, bool device)
-{
-    const size_t bps = hd::iq_bytes(fmt);
-    const bool packed = fmt != HD_IQ_CF32;
-    const uint64_t n_seg = hd::survey_segments(n);
-    if (n_seg) {
-        if (device && !waterfall_is_device_pointer(iq)) return fail(HD_ERR_INVALID, "IQ pointer is not device memory (the _host calls take host memory)");
-        const size_t slab_samples = (size_t)(hd_waterfall::kSlabSegs + 1) * hd::kSurveyHop;
-        if (!wf->slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->slab), slab_samples * sizeof(float2)));
-        if (packed && !device && !wf->pslab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->pslab), slab_samples * 4u));
-        const uint32_t L = wf->par.slot_segments;
-        const uint64_t per_slab = (uint64_t)(hd_waterfall::kSlabSegs / L) * L;
-        const unsigned char* p = static_cast<const unsigned char*>(iq);
-        for (uint64_t s = 0; s < n_seg; s += per_slab) {
-            const uint64_t s1 = std::min(n_seg, s + per_slab);
-            const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
-            const unsigned char* from = p + (size_t)s * hd::kSurveyHop * bps;
-            if (!packed) {
-                HD_HIP(hipMemcpyAsync(wf->slab, from, samples * sizeof(float2), hipMemcpyHostToDevice, wf->q));
-            } else {
-                if (!device) {
-                    HD_HIP(hipMemcpyAsync(wf->pslab, from, samples * bps, hipMemcpyHostToDevice, wf->q));
-                    from = wf->pslab;
-                }
-                if (!hd::launch_iq_unpack(wf->q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, wf->slab, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
-            }
-            if (const int rc = waterfall_enqueue(wf, wf->slab, s, s, s1)) return rc;   // (waits for the queue: the slab is free for the next piece)
-        }
-    }
-    wf->samples += n;
-    return HD_OK;
-}
-
-int waterfall_push_packed(hd_waterfall* wf, int fmt, const void* iq, uint64_t n, bool device)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    const size_t bps = hd::iq_bytes(fmt);
-    if (!bps || fmt == HD_IQ_CF32) return fail(HD_ERR_INVALID, "unknown IQ format (HD_IQ_CF32, HD_IQ_CS16, HD_IQ_CS8, HD_IQ_CU8)");
-    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    if (reinterpret_cast<uintptr_t>(iq) & (bps - 1)) return fail(HD_ERR_INVALID, "packed IQ base must be aligned to one sample (4 bytes cs16, 2 bytes cs8 / cu8)");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    return waterfall_push_slabs(wf, fmt, iq, n, device);
-}
-
-}  // namespace
-
-extern "C" {
-
-void hd_waterfall_params_default(hd_waterfall_params* p) { if (p) hd::waterfall_params_default(p); }
-void hd_waterfall_track_params_default(hd_waterfall_track_params* p) { if (p) hd::waterfall_track_params_default(p); }
-
-int hd_waterfall_create(hd_engine* e, const hd_waterfall_params* p, hd_waterfall** out)
-{
-    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    std::unique_ptr<hd_waterfall> wf(new hd_waterfall);
-    wf->e = e;
-    if (p) wf->par = *p; else hd::waterfall_params_default(&wf->par);
-    if (!hd::waterfall_params_ok(&wf->par)) return fail(HD_ERR_INVALID, "hd_waterfall_params: slot_segments 16..64, rows_cap >= 1, threshold_db and dc_guard_hz >= 0");
-    if (!hd::waterfall_guard_range(e->fs, wf->par.dc_guard_hz, &wf->guard_lo, &wf->guard_hi)) return fail(HD_ERR_INVALID, "dc_guard_hz leaves no bin");
-    if (const int rc = waterfall_enter(wf.get())) return rc;
-    if (const char* v = getenv("HD_WATERFALL_CHUNK")) wf->chunk_rows = (uint32_t)std::min(std::max(atol(v), 1L), (long)hd_waterfall::kChunkRows);
-    HD_HIP(hipStreamCreateWithFlags(&wf->q, hipStreamNonBlocking));
-    std::vector<float> w(hd::kSurveyBins), f(hd::kWaterfallMaxSeg + 1, 0.0f);
-    hd::survey_window(w.data());
-    for (uint32_t s = 1; s <= hd::kWaterfallMaxSeg; ++s) f[s] = hd::waterfall_factor(wf->par.threshold_db, s);
-    // (plain allocations, filled on the waterfall's queue: nothing here runs on the null stream or waits for the engine's queues)
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->win), w.size() * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->factor), f.size() * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->ring), (size_t)wf->par.rows_cap * hd::kWaterfallBins * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->hits), hd::kWaterfallBins * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->d_seg), hd_waterfall::kChunkRows * sizeof(uint32_t)));
-    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec), hipHostMallocDefault));
-    HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_hits), hd::kWaterfallBins * sizeof(uint32_t), hipHostMallocDefault));
-    std::vector<float2> tw;
-    wf->tw = e->fft_tw.p;
-    if (!wf->tw) {   // an engine without spectra holds no twiddles: the same table, the waterfall's own
-        tw.resize(hd::kFftBins);
-        hd::specwave::fft_twiddles(tw.data());
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->own_tw), tw.size() * sizeof(float2)));
-        HD_HIP(hipMemcpyAsync(wf->own_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, wf->q));
-        wf->tw = wf->own_tw;
-    }
-    HD_HIP(hipMemcpyAsync(wf->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, wf->q));
-    HD_HIP(hipMemcpyAsync(wf->factor, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, wf->q));
-    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->q));
-    HD_HIP(hipStreamSynchronize(wf->q));   // (the tables above are locals)
-    *out = wf.release();
-    return HD_OK;
-}
-
-void hd_waterfall_destroy(hd_waterfall* wf)
-{
-    if (!wf) return;
-    hd_engine* e = wf->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    (void)hipSetDevice(e->cfg.device);
-    if (wf->q) (void)hipStreamSynchronize(wf->q);
-    delete wf;
-}
-
-int hd_waterfall_reset(hd_waterfall* wf)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->q));
-    HD_HIP(hipStreamSynchronize(wf->q));
-    wf->headers.clear();
-    wf->marks.clear();
-    wf->samples = 0;
-    wf->rows_counted = 0;
-    return HD_OK;
-}
-
-int hd_waterfall_push_device(hd_waterfall* wf, const void* d_iq, uint64_t n)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (!d_iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    if (reinterpret_cast<uintptr_t>(d_iq) & 7) return fail(HD_ERR_INVALID, "IQ base must be 8-byte aligned");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    const uint64_t n_seg = hd::survey_segments(n);
-    if (n_seg) {
-        // what the kernel reads must be memory the GPU can address: a host pointer HIP does not know never reaches a launch
-        if (!waterfall_is_device_pointer(d_iq)) return fail(HD_ERR_INVALID, "IQ pointer is not device memory (hd_waterfall_push_host takes host memory)");
-        if (const int rc = waterfall_enqueue(wf, static_cast<const float2*>(d_iq), 0, 0, n_seg)) return rc;
-    }
-    wf->samples += n;
-    return HD_OK;
-}
-
-int hd_waterfall_push_host(hd_waterfall* wf, const float* iq, uint64_t n)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (!iq) return fail(HD_ERR_INVALID, "null IQ pointer");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    return waterfall_push_slabs(wf, HD_IQ_CF32, iq, n, false);
-}
-
-int hd_waterfall_push_device_fmt(hd_waterfall* wf, int fmt, const void* d_iq, uint64_t n)
-{
-    if (fmt == HD_IQ_CF32) return hd_waterfall_push_device(wf, d_iq, n);
-    return waterfall_push_packed(wf, fmt, d_iq, n, true);
-}
-
-int hd_waterfall_push_host_fmt(hd_waterfall* wf, int fmt, const void* iq, uint64_t n)
-{
-    if (fmt == HD_IQ_CF32) return hd_waterfall_push_host(wf, static_cast<const float*>(iq), n);
-    return waterfall_push_packed(wf, fmt, iq, n, false);
-}
-
-int hd_waterfall_push_rows(hd_waterfall* wf, const float* rows, const uint32_t* segments, uint32_t n_rows, int device)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (!rows || !segments) return fail(HD_ERR_INVALID, "null argument");
-    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
-    for (uint32_t r = 0; r < n_rows; ++r)
-        if (segments[r] < 1 || segments[r] > hd::kWaterfallMaxSeg) return fail(HD_ERR_INVALID, "segments[r] must be 1..64");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    if (!n_rows) return HD_OK;
-    if (device && !waterfall_is_device_pointer(rows)) return fail(HD_ERR_INVALID, "rows pointer is not device memory (device = 0 takes host memory)");
-    uint64_t first[hd_waterfall::kChunkRows];
-    for (uint32_t r = 0; r < n_rows;) {
-        const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
-        const uint32_t n = std::min(n_rows - r, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
-        HD_HIP(hipMemcpyAsync(wf->ring + (size_t)slot * hd::kWaterfallBins, rows + (size_t)r * hd::kWaterfallBins, (size_t)n * hd::kWaterfallBins * sizeof(float),
-                              device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, wf->q));
-        HD_HIP(hipMemcpyAsync(wf->d_seg, segments + r, n * sizeof(uint32_t), hipMemcpyHostToDevice, wf->q));
-        uint64_t at = wf->samples;
-        for (uint32_t b = 0; b < n; ++b) { first[b] = at; at += (uint64_t)segments[r + b] * hd::kSurveyHop; }
-        if (const int rc = waterfall_detect_chunk(wf, slot, n, wf->d_seg, 0, 0, first, segments + r)) return rc;
-        wf->samples = at;
-        r += n;
-    }
-    return HD_OK;
-}
-
-uint64_t hd_waterfall_rows_total(hd_waterfall* wf)
-{
-    if (!wf) return 0;
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    return wf->headers.size();
-}
-
-int hd_waterfall_headers(hd_waterfall* wf, uint64_t first_row, uint32_t n, hd_waterfall_row* out)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (n && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (first_row > wf->headers.size() || n > wf->headers.size() - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
-    if (n) std::memcpy(out, wf->headers.data() + first_row, (size_t)n * sizeof(hd_waterfall_row));
-    return HD_OK;
-}
-
-int hd_waterfall_marks(hd_waterfall* wf, uint64_t first_row, uint32_t n, uint32_t* out)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (n && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (first_row > wf->headers.size() || n > wf->headers.size() - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
-    if (n) std::memcpy(out, wf->marks.data() + first_row * hd::kWaterfallWords, (size_t)n * hd::kWaterfallWords * sizeof(uint32_t));
-    return HD_OK;
-}
-
-int hd_waterfall_rows(hd_waterfall* wf, uint64_t first_row, uint32_t n, float* out)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (n && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    const uint64_t total = wf->headers.size(), cap = wf->par.rows_cap;
-    if (first_row > total || n > total - first_row) return fail(HD_ERR_INVALID, "rows outside [0, hd_waterfall_rows_total)");
-    if (n && first_row + cap < total) return fail(HD_ERR_INVALID, "the first of these rows has left the ring (rows_cap = " + std::to_string(cap) + ")");
-    for (uint32_t r = 0; r < n;) {           // at most two pieces: the ring wraps once inside rows_cap rows
-        const uint32_t slot = (uint32_t)((first_row + r) % cap);
-        const uint32_t k = (uint32_t)std::min<uint64_t>(n - r, cap - slot);
-        HD_HIP(hipMemcpyAsync(out + (size_t)r * hd::kWaterfallBins, wf->ring + (size_t)slot * hd::kWaterfallBins, (size_t)k * hd::kWaterfallBins * sizeof(float),
-                              hipMemcpyDeviceToHost, wf->q));
-        r += k;
-    }
-    HD_HIP(hipStreamSynchronize(wf->q));
-    return HD_OK;
-}
-
-int hd_waterfall_hits(hd_waterfall* wf, uint32_t hits[4096], uint64_t* rows_counted)
-{
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (!hits) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (const int rc = waterfall_enter(wf)) return rc;
-    HD_HIP(hipMemcpyAsync(wf->h_hits, wf->hits, hd::kWaterfallBins * sizeof(uint32_t), hipMemcpyDeviceToHost, wf->q));
-    HD_HIP(hipStreamSynchronize(wf->q));
-    std::memcpy(hits, wf->h_hits, hd::kWaterfallBins * sizeof(uint32_t));
-    if (rows_counted) *rows_counted = wf->rows_counted;
-    return HD_OK;
-}
-
-int hd_waterfall_tracks(hd_waterfall* wf, const hd_waterfall_track_params* p, hd_waterfall_track* out, uint32_t cap, uint32_t* found)
-{
-    if (found) *found = 0;
-    if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
-    if (!found || (cap && !out)) return fail(HD_ERR_INVALID, "null argument");
-    hd_waterfall_track_params def;
-    hd::waterfall_track_params_default(&def);
-    std::lock_guard<std::recursive_mutex> lock(wf->e->mtx);
-    if (hd::waterfall_tracks(wf->headers.data(), wf->marks.data(), wf->headers.size(), wf->e->fs, p ? p : &def, out, cap, found))
-        return fail(HD_ERR_INVALID, "hd_waterfall_tracks: merge_hz and max_width_hz must be >= 0");
-    return HD_OK;
-}
-
-}  // extern "C"
-
-/* ---------------------------------------------------------------- framing trial (host/format_trial.hpp) ------------------------------- */
-
-extern "C" {
-
-int hd_stream_set_format_trial(hd_engine* e, uint32_t s, int on)
-{
-    if (check_stream(e, s)) return HD_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> l(e->mtx);
-    e->st[s].trial.reset(on ? new hd::FormatTrial : nullptr);
-    return HD_OK;
-}
-
-int hd_stream_format_trial(hd_engine* e, uint32_t s, hd_format_trial_result* out)
-{
-    if (check_stream(e, s)) return HD_ERR_INVALID;
-    if (!out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> l(e->mtx);
-    if (!e->st[s].trial) return fail(HD_ERR_INVALID, "the stream's framing trial is off (hd_stream_set_format_trial)");
-    e->st[s].trial->get(out);
-    return HD_OK;
-}
-
-}  // extern "C"
-
-/* ---------------------------------------------------------------- baud-rate probe (kernels/baud_probe.hip) ----------------------------- */
-
-struct hd_baud_probe {
-    hd_engine* e = nullptr;
-    hd_baud_probe_params prm{};
-    hd::BaudProbeTables t;
-    uint32_t S = 0;
-    hd_baud_probe_stream_state* hdr = nullptr;   // [S]
-    unsigned long long* acc64 = nullptr;         // [S][2][1024]: P, Q
-    uint32_t* acc32 = nullptr;                   // [S][5][1024]: NB, re, im, n, cur_block
-    uint32_t *F = nullptr, *scale = nullptr;
-    int32_t* ctab = nullptr;
-    float* slab = nullptr;                       // hd_baud_probe_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
-    PinBuf<hd::ProbeSrc> src;                    // [S]: the push's descriptors, read by the kernel in place (a push returns when its kernel is done)
-    uint64_t pushed_calls = 0;                   // hd_baud_probe_push_engine: e->calls at the last push (the call delivered last is calls - 1)
-    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launch
-    ~hd_baud_probe()
-    {
-        for (void* p : {(void*)hdr, (void*)acc64, (void*)acc32, (void*)F, (void*)scale, (void*)ctab, (void*)slab}) if (p) (void)hipFree(p);
-    }
-};
-
-namespace {
-
-int probe_enter(hd_baud_probe* p)
-{
-    if (p->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + p->e->fail_cause + ") -- destroy the engine");
-    HD_HIP(hipSetDevice(p->e->cfg.device));
-    return HD_OK;
-}
-
-// The descriptors are written: one launch for all streams on the engine's first queue, and the wait for it.
-int probe_launch(hd_baud_probe* p)
-{
-    std::atomic_thread_fence(std::memory_order_release);
-    if (p->t0) HD_HIP(hipEventRecord(p->t0, p->e->qa));
-    hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr, p->acc64, p->acc32, p->F, p->scale, p->ctab);
-    if (p->t1) HD_HIP(hipEventRecord(p->t1, p->e->qa));
-    HD_HIP(hipGetLastError());
-    HD_HIP(hipStreamSynchronize(p->e->qa));
-    return HD_OK;
-}
-
-int probe_clear(hd_baud_probe* p, uint32_t s0, uint32_t ns)
-{
-    hipStream_t q = p->e->qa;
-    HD_HIP(hipMemsetAsync(p->hdr + s0, 0, (size_t)ns * sizeof(hd_baud_probe_stream_state), q));
-    HD_HIP(hipMemsetAsync(p->acc64 + (size_t)s0 * 2 * hd::kProbeCand, 0, (size_t)ns * 2 * hd::kProbeCand * sizeof(unsigned long long), q));
-    HD_HIP(hipMemsetAsync(p->acc32 + (size_t)s0 * 5 * hd::kProbeCand, 0, (size_t)ns * 5 * hd::kProbeCand * sizeof(uint32_t), q));
-    HD_HIP(hipStreamSynchronize(q));
-    return HD_OK;
-}
-
-int probe_check_rows(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, uint32_t* max_n, size_t* total)
-{
-    if (!p) return fail(HD_ERR_INVALID, "null probe");
-    if (!rows) return fail(HD_ERR_INVALID, "null rows");
-    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
-    *max_n = 0; *total = 0;
-    for (uint32_t s = 0; s < p->S; ++s) {
-        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
-        *max_n = std::max(*max_n, ns); *total += ns;
-    }
-    if (p->S > 1 && *max_n > stride) return fail(HD_ERR_INVALID, "a row is longer than the stride");
-    return HD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-void hd_baud_probe_params_default(hd_baud_probe_params* p) { if (p) hd::baud_probe_params_default(p); }
-
-int hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* params, hd_baud_probe** out)
-{
-    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    std::unique_ptr<hd_baud_probe> p(new hd_baud_probe);
-    p->e = e; p->S = e->S;
-    hd::baud_probe_params_default(&p->prm);
-    if (params) p->prm = *params;
-    if (!hd::baud_probe_params_ok(&p->prm, e->fsd))
-        return fail(HD_ERR_INVALID, "baud probe parameters: 0 < baud_lo < baud_hi <= decimated rate / 3.5 (" + std::to_string(e->fsd / 3.5) + ") and min_coherence >= 0");
-    if (const int rc = probe_enter(p.get())) return rc;
-    p->t.make(e->fsd, p->prm);
-    std::vector<uint32_t> sc(hd::kProbeCand);
-    for (uint32_t k = 0; k < hd::kProbeCand; ++k) sc[k] = p->t.scale[k];
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->hdr), (size_t)p->S * sizeof(hd_baud_probe_stream_state)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc64), (size_t)p->S * 2 * hd::kProbeCand * sizeof(unsigned long long)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc32), (size_t)p->S * 5 * hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->F), hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->scale), hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->ctab), 1024 * sizeof(int32_t)));
-    HD_HIP(p->src.alloc(p->S));
-    HD_HIP(hipMemcpyAsync(p->F, p->t.F, hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemcpyAsync(p->scale, sc.data(), hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemcpyAsync(p->ctab, p->t.C, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, e->qa));
-    if (const int rc = probe_clear(p.get(), 0, p->S)) return rc;       // (waits for the queue: `sc` is a local)
-    p->pushed_calls = 0;
-    *out = p.release();
-    return HD_OK;
-}
-
-void hd_baud_probe_destroy(hd_baud_probe* p)
-{
-    if (!p) return;
-    hd_engine* e = p->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    (void)hipSetDevice(e->cfg.device);
-    delete p;
-}
-
-int hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream)
-{
-    if (!p) return fail(HD_ERR_INVALID, "null probe");
-    if (stream != UINT32_MAX && stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    return stream == UINT32_MAX ? probe_clear(p, 0, p->S) : probe_clear(p, stream, 1);
-}
-
-int hd_baud_probe_push_engine(hd_baud_probe* p)
-{
-    if (!p) return fail(HD_ERR_INVALID, "null probe");
-    hd_engine* e = p->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    if (e->in_callback) return fail(HD_ERR_INVALID, "hd_baud_probe_push_engine cannot be called from a sentence / character callback");
-    if (const int rc = flush_locked(e)) return rc;                     // like the data getters: the call in flight is delivered first
-    if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + ") -- destroy the engine");
-    if (e->calls == p->pushed_calls) return HD_OK;                     // no call since the last push
-    p->pushed_calls = e->calls;
-    bool any = false;
-    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
-        const SizeState& sz = e->mirror[s];
-        hd::ProbeSrc& d = p->src.p[s];
-        d.n = sz.last_m;
-        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
-        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
-        any |= d.n != 0;
-    }
-    return any ? probe_launch(p) : HD_OK;
-}
-
-int hd_baud_probe_push_device(hd_baud_probe* p, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
-{
-    uint32_t max_n = 0; size_t total = 0;
-    if (const int rc = probe_check_rows(p, d_rows, stride, n_per_stream, n, &max_n, &total)) return rc;
-    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    if (!total) return HD_OK;
-    {   // what the kernel reads must be memory the GPU can address
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
-                                                                   !(at.type == hipMemoryTypeHost && at.devicePointer))) {
-            (void)hipGetLastError();
-            return fail(HD_ERR_INVALID, "rows are not device memory (hd_baud_probe_push_host takes host memory)");
-        }
-    }
-    for (uint32_t s = 0; s < p->S; ++s) {
-        hd::ProbeSrc& d = p->src.p[s];
-        d.p = d_rows + (size_t)s * stride; d.sym = nullptr; d.ring_mask = 0; d.n = n_per_stream ? n_per_stream[s] : n;
-    }
-    return probe_launch(p);
-}
-
-int hd_baud_probe_push_host(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
-{
-    uint32_t max_n = 0; size_t total = 0;
-    if (const int rc = probe_check_rows(p, rows, stride, n_per_stream, n, &max_n, &total)) return rc;
-    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    if (!total) return HD_OK;
-    if (total > p->slab_n) {
-        if (p->slab) { (void)hipFree(p->slab); p->slab = nullptr; p->slab_n = 0; }
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->slab), total * sizeof(float)));
-        p->slab_n = total;
-    }
-    size_t at = 0;
-    for (uint32_t s = 0; s < p->S; ++s) {
-        hd::ProbeSrc& d = p->src.p[s];
-        d.n = n_per_stream ? n_per_stream[s] : n;
-        d.p = p->slab + at; d.sym = nullptr; d.ring_mask = 0;
-        if (d.n) HD_HIP(hipMemcpyAsync(p->slab + at, rows + (size_t)s * stride, (size_t)d.n * sizeof(float), hipMemcpyHostToDevice, p->e->qa));
-        at += d.n;
-    }
-    return probe_launch(p);
-}
-
-int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* cand, size_t cap)
-{
-    if (!p) return fail(HD_ERR_INVALID, "null probe");
-    if (stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    if (cap < hd::kProbeCand) return (int)hd::kProbeCand;              // nothing is written
-    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    hd_baud_probe_stream_state h;
-    std::vector<unsigned long long> a64(2 * hd::kProbeCand);
-    std::vector<uint32_t> a32(5 * hd::kProbeCand);
-    HD_HIP(hipMemcpy(&h, p->hdr + stream, sizeof h, hipMemcpyDeviceToHost));
-    HD_HIP(hipMemcpy(a64.data(), p->acc64 + (size_t)stream * a64.size(), a64.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HD_HIP(hipMemcpy(a32.data(), p->acc32 + (size_t)stream * a32.size(), a32.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    h.n_candidates = hd::kProbeCand;
-    if (hdr) *hdr = h;
-    for (uint32_t k = 0; cand && k < hd::kProbeCand; ++k) {
-        hd_baud_probe_candidate& c = cand[k];
-        c.P = a64[k]; c.Q = a64[hd::kProbeCand + k];
-        c.NB = a32[k]; c.re = (int32_t)a32[hd::kProbeCand + k]; c.im = (int32_t)a32[2 * hd::kProbeCand + k];
-        c.n = a32[3 * hd::kProbeCand + k]; c.cur_block = a32[4 * hd::kProbeCand + k]; c._pad = 0;
-    }
-    return (int)hd::kProbeCand;
-}
-
-int hd_baud_probe_estimate(hd_baud_probe* p, uint32_t stream, hd_baud_estimate* out)
-{
-    if (!p) return fail(HD_ERR_INVALID, "null probe");
-    if (!out) return fail(HD_ERR_INVALID, "null output");
-    hd_baud_probe_stream_state h;
-    std::vector<hd_baud_probe_candidate> c(hd::kProbeCand);
-    const int n = hd_baud_probe_state(p, stream, &h, c.data(), c.size());
-    if (n < 0) return n;
-    hd::baud_probe_estimate(p->t, p->prm, h, c.data(), out);
-    return HD_OK;
-}
-
-// Measurement hook (tools/micro/probe_rate.py; not part of the ABI): the kernel of hd_baud_probe_push_engine between two HIP events, and the host
-// time of the whole call in microseconds.
-int hd_debug_baud_probe_push_timed(hd_baud_probe* p, float* kernel_ms, double* host_us)
-{
-    if (!p || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
-    hd_engine* e = p->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    if (const int rc = probe_enter(p)) return rc;
-    if (const int rc = flush_locked(e)) return rc;
-    HD_HIP(hipEventCreate(&p->t0));
-    HD_HIP(hipEventCreate(&p->t1));
-    const uint64_t before = p->pushed_calls;
-    const auto w0 = std::chrono::steady_clock::now();
-    const int rc = hd_baud_probe_push_engine(p);
-    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
-    *kernel_ms = 0;
-    if (rc == HD_OK && p->pushed_calls != before && hipEventQuery(p->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, p->t0, p->t1);
-    (void)hipGetLastError();
-    (void)hipEventDestroy(p->t0); (void)hipEventDestroy(p->t1);
-    p->t0 = p->t1 = nullptr;
-    return rc;
-}
-
-}  // extern "C"
-
-/* ---------------------------------------------------------------- clocked decoder (kernels/clocked.hip) -------------------------------- */
-
-struct hd_clocked {
-    hd_engine* e = nullptr;
-    hd_clocked_params prm{};
-    uint32_t S = 0;
-    hd::ClockedState* st = nullptr;              // [S]
-    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_CLOCKED_RING running sums | guard
-    uint32_t* rec = nullptr;                     // [S][rec_stride]: guard | record_cap records | guard
-    size_t ring_stride = 0, rec_stride = 0;
-    float* slab = nullptr;                       // hd_clocked_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
-    PinBuf<hd::ClockedSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
-    std::vector<hd::ClockedState> modem;         // [S]: the state a reset gives the stream (F = 0: off)
-    std::vector<hd::ClockedText> tx;             // [S]
-    uint64_t pushed_calls = 0;
-    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
-    ~hd_clocked()
-    {
-        for (void* p : {(void*)st, (void*)ring, (void*)rec, (void*)slab}) if (p) (void)hipFree(p);
-    }
-};
-
-namespace {
-
-int clocked_enter(hd_clocked* c)
-{
-    if (c->e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + c->e->fail_cause + ") -- destroy the engine");
-    HD_HIP(hipSetDevice(c->e->cfg.device));
-    return HD_OK;
-}
-
-// src[s].p, sym, ring_mask and n_total are written: one launch per HD_CLOCKED_CHUNK samples of the longest row, each waited for.
-int clocked_launch(hd_clocked* c, uint32_t max_n)
-{
-    hipStream_t q = c->e->qa;
-    if (c->t0) HD_HIP(hipEventRecord(c->t0, q));
-    for (uint32_t off = 0; off < max_n; off += HD_CLOCKED_CHUNK) {
-        uint32_t lds_words = 64;
-        for (uint32_t s = 0; s < c->S; ++s) {
-            hd::ClockedSrc& d = c->src.p[s];
-            d.off = off;
-            d.n = d.n_total > off ? std::min<uint32_t>(HD_CLOCKED_CHUNK, d.n_total - off) : 0u;
-            if (c->modem[s].F) lds_words = std::max(lds_words, hd::clocked_window_words(c->modem[s], d.n));
-        }
-        std::atomic_thread_fence(std::memory_order_release);
-        if (!hd::launch_clocked(q, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, lds_words))
-            return fail(HD_ERR_DEVICE, "clocked decoder: the launch's window does not fit the LDS");
-        HD_HIP(hipGetLastError());
-        if (c->t1 && off + HD_CLOCKED_CHUNK >= max_n) HD_HIP(hipEventRecord(c->t1, q));
-        HD_HIP(hipStreamSynchronize(q));
-    }
-    return HD_OK;
-}
-
-int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
-{
-    hipStream_t q = c->e->qa;
-    HD_HIP(hipMemcpyAsync(c->st + s0, c->modem.data() + s0, (size_t)ns * sizeof(hd::ClockedState), hipMemcpyHostToDevice, q));
-    HD_HIP(hipMemset2DAsync(c->ring + (size_t)s0 * c->ring_stride + hd::kClockedGuard, c->ring_stride * sizeof(uint32_t), 0,
-                            (size_t)HD_CLOCKED_RING * sizeof(uint32_t), ns, q));
-    HD_HIP(hipStreamSynchronize(q));
-    for (uint32_t s = s0; s < s0 + ns; ++s) { c->tx[s].reset(); c->tx[s].nbits = c->modem[s].nbits; }
-    return HD_OK;
-}
-
-int clocked_check_rows(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, uint32_t* max_n, size_t* total)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (!rows) return fail(HD_ERR_INVALID, "null rows");
-    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
-    *max_n = 0; *total = 0;
-    for (uint32_t s = 0; s < c->S; ++s) {
-        const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
-        *max_n = std::max(*max_n, ns); *total += ns;
-    }
-    if (c->S > 1 && *max_n > stride) return fail(HD_ERR_INVALID, "a row is longer than the stride");
-    return HD_OK;
-}
-
-// The stream's waiting records leave the ring through its text stage; up to cap of them are copied to out (out null: none are kept).
-int clocked_drain(hd_clocked* c, uint32_t s, hd_clocked_record* out, size_t cap, size_t* n_out)
-{
-    hd::ClockedState h;
-    HD_HIP(hipMemcpy(&h, c->st + s, sizeof h, hipMemcpyDeviceToHost));
-    const uint64_t have = h.written - h.taken, rc = c->prm.record_cap;
-    const size_t k = out ? (size_t)std::min<uint64_t>(have, cap) : (size_t)have;
-    *n_out = k;
-    if (!k) return HD_OK;
-    std::vector<hd_clocked_record> tmp(k);
-    const uint32_t* base = c->rec + (size_t)s * c->rec_stride + hd::kClockedGuard;
-    for (size_t i = 0; i < k;) {             // at most two pieces: the ring wraps once inside record_cap records
-        const uint64_t slot = (h.taken + i) % rc;
-        const size_t m = (size_t)std::min<uint64_t>(k - i, rc - slot);
-        HD_HIP(hipMemcpy(tmp.data() + i, base + slot * hd::kClockedRecWords, m * sizeof(hd_clocked_record), hipMemcpyDeviceToHost));
-        i += m;
-    }
-    h.taken += k;
-    HD_HIP(hipMemcpy(reinterpret_cast<char*>(c->st + s) + offsetof(hd::ClockedState, taken), &h.taken, sizeof h.taken, hipMemcpyHostToDevice));
-    c->tx[s].feed(tmp.data(), k);
-    if (out) std::memcpy(out, tmp.data(), k * sizeof(hd_clocked_record));
-    return HD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-void hd_clocked_params_default(hd_clocked_params* p) { if (p) hd::clocked_params_default(p); }
-
-int hd_clocked_create(hd_engine* e, const hd_clocked_params* params, hd_clocked** out)
-{
-    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
-    *out = nullptr;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    std::unique_ptr<hd_clocked> c(new hd_clocked);
-    c->e = e; c->S = e->S;
-    hd::clocked_params_default(&c->prm);
-    if (params) c->prm = *params;
-    if (!hd::clocked_params_ok(&c->prm)) return fail(HD_ERR_INVALID, "clocked decoder parameters: 16 <= record_cap <= 2^20, repair_bits <= 16, repair_flips <= 4");
-    if (const int rc = clocked_enter(c.get())) return rc;
-    c->modem.resize(c->S);
-    c->tx.resize(c->S);
-    for (uint32_t s = 0; s < c->S; ++s) {
-        const uint32_t nbits = (uint32_t)e->st[s].text.framer.nbits;
-        const double nstops = (double)e->st[s].text.framer.nstops;
-        const uint32_t F = hd::clocked_modem_F(e->fsd, e->st[s].baud, nbits, nstops);
-        hd::clocked_state_reset(c->modem[s], F, F ? nbits : 0u, F ? (uint32_t)nstops : 0u, 0u);
-        c->tx[s].repair_bits = c->prm.repair_bits; c->tx[s].repair_flips = c->prm.repair_flips;
-    }
-    c->ring_stride = (size_t)HD_CLOCKED_RING + 2 * hd::kClockedGuard;
-    c->rec_stride = (size_t)c->prm.record_cap * hd::kClockedRecWords + 2 * hd::kClockedGuard;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->st), (size_t)c->S * sizeof(hd::ClockedState)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)c->S * c->ring_stride * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rec), (size_t)c->S * c->rec_stride * sizeof(uint32_t)));
-    HD_HIP(c->src.alloc(c->S));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kClockedGuardWord, (size_t)c->S * c->ring_stride, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rec), (int)hd::kClockedGuardWord, (size_t)c->S * c->rec_stride, e->qa));
-    if (const int rc = clocked_clear(c.get(), 0, c->S)) return rc;
-    *out = c.release();
-    return HD_OK;
-}
-
-void hd_clocked_destroy(hd_clocked* c)
-{
-    if (!c) return;
-    hd_engine* e = c->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    (void)hipSetDevice(e->cfg.device);
-    delete c;
-}
-
-int hd_clocked_reset(hd_clocked* c, uint32_t stream)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (stream != UINT32_MAX && stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    return stream == UINT32_MAX ? clocked_clear(c, 0, c->S) : clocked_clear(c, stream, 1);
-}
-
-int hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t nbits, uint32_t nstops, int invert)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    const uint32_t F = hd::clocked_modem_F(c->e->fsd, baud, nbits, (double)nstops);
-    if (!F) return fail(HD_ERR_UNSUPPORTED, "clocked decoder: 3.5 <= decimated rate / baud <= " + std::to_string(HD_CLOCKED_MAX_SPB) + ", 7 or 8 data bits, 1 or 2 stop bits");
-    if (const int rc = clocked_enter(c)) return rc;
-    hd::clocked_state_reset(c->modem[stream], F, nbits, nstops, invert ? 1u : 0u);
-    return clocked_clear(c, stream, 1);
-}
-
-int hd_clocked_push_engine(hd_clocked* c)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    hd_engine* e = c->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    if (e->in_callback) return fail(HD_ERR_INVALID, "hd_clocked_push_engine cannot be called from a sentence / character callback");
-    if (const int rc = flush_locked(e)) return rc;                     // like the data getters: the call in flight is delivered first
-    if (e->device_failed) return fail(HD_ERR_DEVICE, "this engine is in its failed state (" + e->fail_cause + ") -- destroy the engine");
-    if (e->calls == c->pushed_calls) return HD_OK;                     // no call since the last push
-    c->pushed_calls = e->calls;
-    uint32_t max_n = 0;
-    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
-        const SizeState& sz = e->mirror[s];
-        hd::ClockedSrc& d = c->src.p[s];
-        d.n_total = sz.last_m;
-        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
-        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
-        max_n = std::max(max_n, d.n_total);
-    }
-    return clocked_launch(c, max_n);
-}
-
-int hd_clocked_push_device(hd_clocked* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
-{
-    uint32_t max_n = 0; size_t total = 0;
-    if (const int rc = clocked_check_rows(c, d_rows, stride, n_per_stream, n, &max_n, &total)) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    if (!total) return HD_OK;
-    {   // what the kernel reads must be memory the GPU can address
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, d_rows) != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged &&
-                                                                   !(at.type == hipMemoryTypeHost && at.devicePointer))) {
-            (void)hipGetLastError();
-            return fail(HD_ERR_INVALID, "rows are not device memory (hd_clocked_push_host takes host memory)");
-        }
-    }
-    for (uint32_t s = 0; s < c->S; ++s) {
-        hd::ClockedSrc& d = c->src.p[s];
-        d.p = d_rows + (size_t)s * stride; d.sym = nullptr; d.ring_mask = 0; d.n_total = n_per_stream ? n_per_stream[s] : n;
-    }
-    return clocked_launch(c, max_n);
-}
-
-int hd_clocked_push_host(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
-{
-    uint32_t max_n = 0; size_t total = 0;
-    if (const int rc = clocked_check_rows(c, rows, stride, n_per_stream, n, &max_n, &total)) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    if (!total) return HD_OK;
-    if (total > c->slab_n) {
-        if (c->slab) { (void)hipFree(c->slab); c->slab = nullptr; c->slab_n = 0; }
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->slab), total * sizeof(float)));
-        c->slab_n = total;
-    }
-    size_t at = 0;
-    for (uint32_t s = 0; s < c->S; ++s) {
-        hd::ClockedSrc& d = c->src.p[s];
-        d.n_total = n_per_stream ? n_per_stream[s] : n;
-        d.p = c->slab + at; d.sym = nullptr; d.ring_mask = 0;
-        if (d.n_total) HD_HIP(hipMemcpyAsync(c->slab + at, rows + (size_t)s * stride, (size_t)d.n_total * sizeof(float), hipMemcpyHostToDevice, c->e->qa));
-        at += d.n_total;
-    }
-    return clocked_launch(c, max_n);
-}
-
-int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, size_t cap)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    if (!out) {
-        hd::ClockedState h;
-        HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
-        return (int)(h.written - h.taken);
-    }
-    size_t n = 0;
-    if (const int rc = clocked_drain(c, stream, out, cap, &n)) return rc;
-    return (int)n;
-}
-
-int hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    size_t n = 0;
-    if (const int rc = clocked_drain(c, stream, nullptr, 0, &n)) return rc;
-    return (int)c->tx[stream].take(out, cap);
-}
-
-int hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out)
-{
-    if (!c) return fail(HD_ERR_INVALID, "null clocked decoder");
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    if (!out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    hd::ClockedState h;
-    HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
-    const hd::ClockedText& t = c->tx[stream];
-    *out = hd_clocked_counters{h.n, h.p, h.chars, h.rejects, h.dropped, t.matches_failed, t.plain, t.repaired};
-    return HD_OK;
-}
-
-// Measurement hook (tools/micro/clocked_rate.py; not part of the ABI): the kernels of hd_clocked_push_engine between two HIP events, and the host time
-// of the whole call in microseconds.
-int hd_debug_clocked_push_timed(hd_clocked* c, float* kernel_ms, double* host_us)
-{
-    if (!c || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
-    hd_engine* e = c->e;
-    std::lock_guard<std::recursive_mutex> lock(e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    if (const int rc = flush_locked(e)) return rc;
-    HD_HIP(hipEventCreate(&c->t0));
-    HD_HIP(hipEventCreate(&c->t1));
-    const uint64_t before = c->pushed_calls;
-    const auto w0 = std::chrono::steady_clock::now();
-    const int rc = hd_clocked_push_engine(c);
-    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
-    *kernel_ms = 0;
-    if (rc == HD_OK && c->pushed_calls != before && hipEventQuery(c->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, c->t0, c->t1);
-    (void)hipGetLastError();
-    (void)hipEventDestroy(c->t0); (void)hipEventDestroy(c->t1);
-    c->t0 = c->t1 = nullptr;
-    return rc;
-}
-
-// Test hook (tests/test_gpu_clocked.py; not part of the ABI): how many of the guard words around the stream's two rings no longer hold their pattern.
-int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
-{
-    if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = clocked_enter(c)) return rc;
-    uint32_t g[4][hd::kClockedGuard];
-    const uint32_t* at[4] = {c->ring + (size_t)stream * c->ring_stride, c->ring + (size_t)(stream + 1) * c->ring_stride - hd::kClockedGuard,
-                             c->rec + (size_t)stream * c->rec_stride, c->rec + (size_t)(stream + 1) * c->rec_stride - hd::kClockedGuard};
-    int bad = 0;
-    for (int i = 0; i < 4; ++i) {
-        HD_HIP(hipMemcpy(g[i], at[i], sizeof g[i], hipMemcpyDeviceToHost));
-        for (uint32_t w : g[i]) bad += w != hd::kClockedGuardWord;
-    }
-    return bad;
-}
-
-}  // extern "C"

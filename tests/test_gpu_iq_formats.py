@@ -303,8 +303,11 @@ def test_ingest_of_cs16_files_decodes_like_the_same_files_as_cf32(hd, tmp_path):
 
 
 # ---- 5. survey
-@pytest.mark.parametrize("n", [6144, 260 * 2048], ids=["2_segments", "259_segments"])
-def test_survey_of_cs8_pushes_is_the_survey_of_the_converted_floats(hd, torch, n):
+@pytest.mark.parametrize("n,runs", [(6144, None), (260 * 2048, None), (260 * 2048, 2)], ids=["2_segments", "259_segments", "259_segments_RUNS=2"])
+def test_survey_of_cs8_pushes_is_the_survey_of_the_converted_floats(hd, torch, monkeypatch, n, runs):
+    """(259 segments at the default run count: r = 1; at HD_SURVEY_RUNS=2: r = 64, a slab of four runs and one of one)"""
+    if runs:
+        monkeypatch.setenv("HD_SURVEY_RUNS", str(runs))        # (read when a survey is created)
     fs = 2.048e6
     k = np.arange(n)
     nz = synth._noise(n, 11)
