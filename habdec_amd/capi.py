@@ -118,6 +118,17 @@ CLOCKED_SENTENCE_DTYPE = np.dtype([("pos", "<u8"), ("flips", "<u4"), ("len", "<u
 CLOCKED_MAX_SPB, CLOCKED_RING, CLOCKED_CHUNK = 2048, 32768, 4096
 
 
+class hd_tones_params(C.Structure):
+    _fields_ = [("max_push", C.c_uint32), ("window_q8", C.c_uint32)]
+
+
+class hd_tones_info(C.Structure):
+    _fields_ = [("samples", C.c_uint64)] + [(k, C.c_uint32) for k in ("F", "full", "W", "L", "step_hi", "step_lo")]
+
+
+TONES_MAX_SPB, TONES_CHUNK = 2048, 4096
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -239,6 +250,18 @@ ENGINE_API = {
     "hd_clocked_records": (_int, [_vp, _u32, _vp, _sz]),
     "hd_clocked_take_sentences": (_int, [_vp, _u32, _vp, _sz]),
     "hd_clocked_stats": (_int, [_vp, _u32, C.POINTER(hd_clocked_counters)]),
+    "hd_tones_params_default": (None, [C.POINTER(hd_tones_params)]),
+    "hd_tones_create": (_int, [_vp, C.POINTER(hd_tones_params), C.POINTER(_vp)]),
+    "hd_tones_destroy": (None, [_vp]),
+    "hd_tones_reset": (_int, [_vp, _u32]),
+    "hd_tones_set_modem": (_int, [_vp, _u32, _dbl, _dbl, _dbl]),
+    "hd_tones_set_modem_from_afc": (_int, [_vp, _u32, _dbl]),
+    "hd_tones_push_engine": (_int, [_vp]),
+    "hd_tones_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_tones_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_tones_rows": (_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _vp]),
+    "hd_tones_output": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_tones_stats": (_int, [_vp, _u32, C.POINTER(hd_tones_info)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -312,6 +335,12 @@ HOST_API = {
     "hd_host_clocked_take_sentences": (_int, [_vp, _vp, _sz]),
     "hd_host_clocked_stats": (_int, [_vp, C.POINTER(hd_clocked_counters)]),
     "hd_host_chase_repair": (_int, [C.c_char_p, _sz, _vp, _u32, _u32, _u32, _vp, C.POINTER(_u32)]),
+    "hd_host_tones_new": (_vp, [_dbl, C.POINTER(hd_tones_params)]),
+    "hd_host_tones_free": (None, [_vp]),
+    "hd_host_tones_reset": (None, [_vp]),
+    "hd_host_tones_set_modem": (_int, [_vp, _dbl, _dbl, _dbl]),
+    "hd_host_tones_push": (_sz, [_vp, _vp, _sz, _vp]),
+    "hd_host_tones_stats": (_int, [_vp, C.POINTER(hd_tones_info)]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

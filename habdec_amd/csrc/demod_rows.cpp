@@ -1,7 +1,9 @@
-// The objects that read the streams' discriminator output beside the decode pipeline: the baud-rate probe (kernels/baud_probe.hip, host/baud_probe.hpp)
-// and the clocked decoder (kernels/clocked.hip, host/clocked.hpp).  Both take one float row per stream through the same three doors -- the engine's last
-// call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream descriptors, launch on the engine's
-// first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc) and in what they launch; the rest is the helpers below.
+// The objects that read the streams' signal beside the decode pipeline: the baud-rate probe (kernels/baud_probe.hip, host/baud_probe.hpp) and the clocked
+// decoder (kernels/clocked.hip, host/clocked.hpp), which read the discriminator output, and the tone-filter demodulator (kernels/tones.hip,
+// host/tones.hpp), which reads the decimated IQ and writes a row the other two can take.  All take one row per stream through the same three doors -- the
+// engine's last call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream descriptors, launch on
+// the engine's first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc, TonesSrc), in the rows' element (float, or
+// float2 for cf32) and in what they launch; the rest is the helpers below.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -9,6 +11,7 @@
 #include "engine_state.h"
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
+#include "host/tones.hpp"
 
 using hd::eng::enter;
 using hd::eng::is_device_pointer;
@@ -19,7 +22,30 @@ namespace {
 uint32_t& src_len(hd::ProbeSrc& d) { return d.n; }
 uint32_t& src_len(hd::ClockedSrc& d) { return d.n_total; }
 
-// The helpers take either object: both carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names.
+// A descriptor for n elements in linear memory at p.
+template <typename Src>
+void src_set(Src& d, const float* p, uint32_t n) { src_len(d) = n; d.p = p; d.sym = nullptr; d.ring_mask = 0; }
+void src_set(hd::TonesSrc& d, const float2* p, uint32_t n) { d.n_total = n; d.p = p; }
+
+// A descriptor for what the engine's last call left for stream s, and that row's length: what hd_stream_demodulated knows -- the linear demod row, or the
+// newest last_m samples of the symbol ring -- or, for the tones, what hd_stream_decimated knows.
+template <typename Src>
+uint32_t src_from_engine(hd_engine* e, uint32_t s, Src& d)
+{
+    const SizeState& sz = e->mirror[s];
+    src_len(d) = sz.last_m;
+    if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
+    else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
+    return sz.last_m;
+}
+uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::TonesSrc& d)
+{
+    const SizeState& sz = e->mirror[s];
+    src_set(d, e->fbuf[sz.last_buf].p + (size_t)s * e->fbuf_stride + e->fir_hist_cap + sz.last_pend_before, sz.last_n2);
+    return sz.last_n2;
+}
+
+// The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names.
 
 // hd_*_push_engine.  null_msg: the error for a null object; fn: the door's name for the message.  launch(max_n): the descriptors are written and
 // the longest row has max_n samples.
@@ -36,25 +62,18 @@ int push_engine(Obj* o, const char* null_msg, const char* fn, Launch launch)
     if (e->calls == o->pushed_calls) return HD_OK;                     // no call since the last push
     o->pushed_calls = e->calls;
     uint32_t max_n = 0;
-    for (uint32_t s = 0; s < e->S; ++s) {      // what hd_stream_demodulated knows: the linear demod row, or the newest last_m samples of the symbol ring
-        const SizeState& sz = e->mirror[s];
-        auto& d = o->src.p[s];
-        src_len(d) = sz.last_m;
-        if (sz.demod_in_ring) { d.p = e->tail.p + (size_t)s * e->tail_cap; d.sym = e->d_symstate.p + s; d.ring_mask = e->tail_cap - 1u; }
-        else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
-        max_n = std::max(max_n, sz.last_m);
-    }
+    for (uint32_t s = 0; s < e->S; ++s) max_n = std::max(max_n, src_from_engine(e, s, o->src.p[s]));
     return launch(max_n);
 }
 
 // hd_*_push_device (device = true: row s is read in place at rows + s * stride) and hd_*_push_host (the rows are packed end to end into the slab,
-// grown on demand, one copy per row on the engine's first queue).
-template <typename Obj, typename Launch>
-int push_rows(Obj* o, const char* null_msg, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, bool device, Launch launch)
+// grown on demand, one copy per row on the engine's first queue).  T: a row's element, float or float2.
+template <typename Obj, typename T, typename Launch>
+int push_rows(Obj* o, const char* null_msg, const T* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, bool device, Launch launch)
 {
     if (!o) return fail(HD_ERR_INVALID, null_msg);
     if (!rows) return fail(HD_ERR_INVALID, "null rows");
-    if (reinterpret_cast<uintptr_t>(rows) & 3) return fail(HD_ERR_INVALID, "rows must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(rows) & (alignof(T) - 1)) return fail(HD_ERR_INVALID, "rows must be " + std::to_string(alignof(T)) + "-byte aligned");
     uint32_t max_n = 0; size_t total = 0;
     for (uint32_t s = 0; s < o->S; ++s) {
         const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
@@ -67,16 +86,15 @@ int push_rows(Obj* o, const char* null_msg, const float* rows, size_t stride, co
     if (device && !is_device_pointer(rows)) return fail(HD_ERR_INVALID, "rows are not device memory (the _host call takes host memory)");
     if (!device && total > o->slab_n) {
         if (o->slab) { (void)hipFree(o->slab); o->slab = nullptr; o->slab_n = 0; }
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&o->slab), total * sizeof(float)));
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&o->slab), total * sizeof(T)));
         o->slab_n = total;
     }
     size_t at = 0;
     for (uint32_t s = 0; s < o->S; ++s) {
         auto& d = o->src.p[s];
         const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
-        src_len(d) = ns; d.sym = nullptr; d.ring_mask = 0;
-        d.p = device ? rows + (size_t)s * stride : o->slab + at;
-        if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab + at, rows + (size_t)s * stride, (size_t)ns * sizeof(float), hipMemcpyHostToDevice, o->e->qa));
+        src_set(d, device ? rows + (size_t)s * stride : o->slab + at, ns);
+        if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab + at, rows + (size_t)s * stride, (size_t)ns * sizeof(T), hipMemcpyHostToDevice, o->e->qa));
         at += ns;
     }
     return launch(max_n);
@@ -491,6 +509,244 @@ int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
     for (int i = 0; i < 4; ++i) {
         HD_HIP(hipMemcpy(g[i], at[i], sizeof g[i], hipMemcpyDeviceToHost));
         for (uint32_t w : g[i]) bad += w != hd::kClockedGuardWord;
+    }
+    return bad;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- tone-filter demodulator (kernels/tones.hip) -------------------------- */
+
+struct hd_tones {
+    hd_engine* e = nullptr;
+    hd_tones_params prm{};
+    uint32_t S = 0;
+    hd::TonesState* st = nullptr;                // [S]
+    uint32_t* ring32 = nullptr;                  // [S][4][ring32_stride]: guard | kTonesRing32 running sums | guard
+    unsigned long long* ring64 = nullptr;        // [S][ring64_stride]: guard | kTonesRing64 running sums | guard
+    int32_t* ctab = nullptr;                     // [1024]
+    float* rows = nullptr;                       // [S][row_stride]: guard | max_push floats | guard
+    size_t ring32_stride = 0, ring64_stride = 0, row_stride = 0;
+    float2* slab = nullptr;                      // hd_tones_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::TonesSrc> src;                    // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    std::vector<hd::TonesState> modem;           // [S]: the state a reset gives the stream (F = 0: no modem)
+    std::vector<double> baud;                    // [S]: the engine stream's baud rate when the object was made
+    std::vector<uint32_t> row_n;                 // [S]: the rows' lengths after the last push
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
+    ~hd_tones()
+    {
+        for (void* p : {(void*)st, (void*)ring32, (void*)ring64, (void*)ctab, (void*)rows, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+const char kNullTones[] = "null tones object";
+
+// src[s].p and n_total are written: a stream without a modem is passed by; one launch per HD_TONES_CHUNK samples of the longest row, each waited for.
+int tones_launch(hd_tones* t, uint32_t max_n)
+{
+    hipStream_t q = t->e->qa;
+    max_n = 0;
+    for (uint32_t s = 0; s < t->S; ++s) {
+        hd::TonesSrc& d = t->src.p[s];
+        if (!t->modem[s].F) d.n_total = 0;
+        if (d.n_total > t->prm.max_push)
+            return fail(HD_ERR_CAPACITY, "hd_tones: a push of " + std::to_string(d.n_total) + " samples, max_push is " + std::to_string(t->prm.max_push));
+        max_n = std::max(max_n, d.n_total);
+    }
+    for (uint32_t s = 0; s < t->S; ++s) t->row_n[s] = t->src.p[s].n_total;
+    if (t->t0) HD_HIP(hipEventRecord(t->t0, q));
+    for (uint32_t off = 0; off < max_n; off += HD_TONES_CHUNK) {
+        uint32_t cap = 0;
+        for (uint32_t s = 0; s < t->S; ++s) {
+            hd::TonesSrc& d = t->src.p[s];
+            d.off = off;
+            d.n = d.n_total > off ? std::min<uint32_t>(HD_TONES_CHUNK, d.n_total - off) : 0u;
+            cap = std::max(cap, d.n);
+        }
+        std::atomic_thread_fence(std::memory_order_release);
+        if (!hd::launch_tones(q, t->S, cap, t->src.dev, t->st, t->ring32, t->ring32_stride, t->ring64, t->ring64_stride, t->ctab, t->rows, t->row_stride,
+                              t->prm.max_push))
+            return fail(HD_ERR_DEVICE, "tones: the launch's chunk does not fit the LDS");
+        HD_HIP(hipGetLastError());
+        if (t->t1 && off + HD_TONES_CHUNK >= max_n) HD_HIP(hipEventRecord(t->t1, q));
+        HD_HIP(hipStreamSynchronize(q));
+    }
+    return HD_OK;
+}
+
+// (The rings need no clearing: nothing in front of a stream's index 0 is read.)
+int tones_clear(hd_tones* t, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = t->e->qa;
+    HD_HIP(hipMemcpyAsync(t->st + s0, t->modem.data() + s0, (size_t)ns * sizeof(hd::TonesState), hipMemcpyHostToDevice, q));
+    HD_HIP(hipStreamSynchronize(q));
+    for (uint32_t s = s0; s < s0 + ns; ++s) t->row_n[s] = 0;
+    return HD_OK;
+}
+
+int tones_check(hd_tones* t, uint32_t stream)
+{
+    if (!t) return fail(HD_ERR_INVALID, kNullTones);
+    if (stream >= t->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_tones_params_default(hd_tones_params* p) { if (p) hd::tones_params_default(p); }
+
+int hd_tones_create(hd_engine* e, const hd_tones_params* params, hd_tones** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_tones> t(new hd_tones);
+    t->e = e; t->S = e->S;
+    hd::tones_params_default(&t->prm);
+    if (params) t->prm = *params;
+    if (!hd::tones_window_ok(t->prm.window_q8)) return fail(HD_ERR_UNSUPPORTED, "tones parameters: 32 <= window_q8 <= 256");
+    if (!t->prm.max_push) t->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
+    if (t->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "tones parameters: max_push <= 2^28");
+    if (const int rc = enter(e)) return rc;
+    t->modem.resize(t->S);
+    t->baud.resize(t->S);
+    t->row_n.assign(t->S, 0u);
+    for (uint32_t s = 0; s < t->S; ++s) {
+        hd::tones_state_reset(t->modem[s], 0, 0, 0, 0);
+        t->baud[s] = e->st[s].baud;
+    }
+    t->ring32_stride = (size_t)hd::kTonesRing32 + 2 * hd::kTonesGuard;
+    t->ring64_stride = (size_t)hd::kTonesRing64 + hd::kTonesGuard;             // (its guards are kTonesGuard / 2 64-bit words each)
+    t->row_stride = (size_t)t->prm.max_push + 2 * hd::kTonesGuard;
+    int32_t C[1024];
+    hd::tones_table(C);
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->st), (size_t)t->S * sizeof(hd::TonesState)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ring32), (size_t)t->S * 4 * t->ring32_stride * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ring64), (size_t)t->S * t->ring64_stride * sizeof(unsigned long long)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->rows), (size_t)t->S * t->row_stride * sizeof(float)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ctab), sizeof C));
+    HD_HIP(t->src.alloc(t->S));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->ring32), (int)hd::kTonesGuardWord, (size_t)t->S * 4 * t->ring32_stride, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->ring64), (int)hd::kTonesGuardWord, (size_t)t->S * t->ring64_stride * 2, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->rows), (int)hd::kTonesGuardWord, (size_t)t->S * t->row_stride, e->qa));
+    HD_HIP(hipMemcpyAsync(t->ctab, C, sizeof C, hipMemcpyHostToDevice, e->qa));
+    if (const int rc = tones_clear(t.get(), 0, t->S)) return rc;       // (waits for the queue: `C` is a local)
+    *out = t.release();
+    return HD_OK;
+}
+
+void hd_tones_destroy(hd_tones* t) { destroy(t); }
+
+int hd_tones_reset(hd_tones* t, uint32_t stream)
+{
+    if (!t) return fail(HD_ERR_INVALID, kNullTones);
+    if (stream != UINT32_MAX && stream >= t->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    if (const int rc = enter(t->e)) return rc;
+    return stream == UINT32_MAX ? tones_clear(t, 0, t->S) : tones_clear(t, stream, 1);
+}
+
+int hd_tones_set_modem(hd_tones* t, uint32_t stream, double baud, double f_hi_hz, double f_lo_hz)
+{
+    if (const int rc = tones_check(t, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    hd::TonesState m;
+    const int rc = hd::tones_modem(m, t->e->fsd, baud == 0 ? t->baud[stream] : baud, f_hi_hz, f_lo_hz, t->prm.window_q8);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "tones: 3.5 <= decimated rate / baud <= " + std::to_string(HD_TONES_MAX_SPB) + " and 32 <= window_q8 <= 256");
+    if (rc) return fail(rc, "tones: |tone| < decimated rate / 2 and f_hi above f_lo");
+    if (const int rc2 = enter(t->e)) return rc2;
+    t->modem[stream] = m;
+    return tones_clear(t, stream, 1);
+}
+
+int hd_tones_set_modem_from_afc(hd_tones* t, uint32_t stream, double baud)
+{
+    if (const int rc = tones_check(t, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    hd_afc_info a;
+    if (const int rc = hd_stream_afc(t->e, stream, &a)) return rc;
+    if (a.peak_left <= 0 || a.peak_right <= 0) return fail(HD_ERR_INVALID, "tones: the stream's AFC has no two valid peaks");
+    const double bin = t->e->fsd / 4096.0;
+    return hd_tones_set_modem(t, stream, baud, (a.peak_right - 2048) * bin, (a.peak_left - 2048) * bin);
+}
+
+int hd_tones_push_engine(hd_tones* t)
+{
+    return push_engine(t, kNullTones, "hd_tones_push_engine", [t](uint32_t max_n) { return tones_launch(t, max_n); });
+}
+
+int hd_tones_push_device(hd_tones* t, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(t, kNullTones, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, [t](uint32_t max_n) { return tones_launch(t, max_n); });
+}
+
+int hd_tones_push_host(hd_tones* t, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(t, kNullTones, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, [t](uint32_t max_n) { return tones_launch(t, max_n); });
+}
+
+int hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
+{
+    if (!t) return fail(HD_ERR_INVALID, kNullTones);
+    if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    *d_rows = t->rows + hd::kTonesGuard;
+    *stride = t->row_stride;
+    std::memcpy(n_per_stream, t->row_n.data(), (size_t)t->S * sizeof(uint32_t));
+    return HD_OK;
+}
+
+int hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap)
+{
+    if (const int rc = tones_check(t, stream)) return rc;
+    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    if (const int rc = enter(t->e)) return rc;
+    const size_t k = std::min<size_t>(t->row_n[stream], cap);
+    if (k) HD_HIP(hipMemcpy(out, t->rows + (size_t)stream * t->row_stride + hd::kTonesGuard, k * sizeof(float), hipMemcpyDeviceToHost));
+    return (int)t->row_n[stream];
+}
+
+int hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out)
+{
+    if (const int rc = tones_check(t, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    if (const int rc = enter(t->e)) return rc;
+    hd::TonesState h;
+    HD_HIP(hipMemcpy(&h, t->st + stream, sizeof h, hipMemcpyDeviceToHost));
+    *out = hd_tones_info{h.n, h.F, h.full, h.W, h.L, h.phi[0], h.phi[1]};
+    return HD_OK;
+}
+
+int hd_debug_tones_push_timed(hd_tones* t, float* kernel_ms, double* host_us) { return push_timed(t, kernel_ms, host_us, hd_tones_push_engine); }
+
+// Test hook (tests/test_gpu_tones.py; not part of the ABI): how many of the guard words around the stream's five rings and its row no longer hold their pattern.
+int hd_debug_tones_guards(hd_tones* t, uint32_t stream)
+{
+    if (!t || stream >= t->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
+    if (const int rc = enter(t->e)) return rc;
+    const uint32_t* r64 = reinterpret_cast<const uint32_t*>(t->ring64);       // (its guards as 32-bit words: kTonesGuard on either side)
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(t->rows);
+    const uint32_t* at[12];
+    for (uint32_t k = 0; k < 4; ++k) {
+        at[2 * k] = t->ring32 + ((size_t)stream * 4 + k) * t->ring32_stride;
+        at[2 * k + 1] = at[2 * k] + t->ring32_stride - hd::kTonesGuard;
+    }
+    at[8] = r64 + (size_t)stream * t->ring64_stride * 2; at[9] = at[8] + t->ring64_stride * 2 - hd::kTonesGuard;
+    at[10] = row + (size_t)stream * t->row_stride; at[11] = at[10] + t->row_stride - hd::kTonesGuard;
+    int bad = 0;
+    for (const uint32_t* p : at) {
+        uint32_t g[hd::kTonesGuard];
+        HD_HIP(hipMemcpy(g, p, sizeof g, hipMemcpyDeviceToHost));
+        for (uint32_t w : g) bad += w != hd::kTonesGuardWord;
     }
     return bad;
 }

@@ -7,6 +7,7 @@
 #include "host/afc_tracker.hpp"
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
+#include "host/tones.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
 #include "host/format_trial.hpp"
@@ -366,6 +367,38 @@ int hd_host_chase_repair(const char* span, size_t n, const int32_t* data, uint32
     if (!*flips) return 0;
     std::memcpy(out, fixed.data(), n);
     return 1;
+}
+
+/* ---- tone-filter demodulator (kernels/tones.hip; see host/tones.hpp) ---- */
+struct hd_host_tones {
+    double fsd;
+    uint32_t window_q8;
+    hd::TonesStream st;
+};
+hd_host_tones* hd_host_tones_new(double decimated_rate, const hd_tones_params* params)
+{
+    hd_tones_params prm;
+    hd::tones_params_default(&prm);
+    if (params) prm = *params;
+    if (!(decimated_rate > 0)) return nullptr;
+    auto* h = new hd_host_tones;
+    h->fsd = decimated_rate; h->window_q8 = prm.window_q8;
+    return h;
+}
+void hd_host_tones_free(hd_host_tones* h) { delete h; }
+void hd_host_tones_reset(hd_host_tones* h) { if (h) h->st.reset(); }
+int hd_host_tones_set_modem(hd_host_tones* h, double baud, double f_hi_hz, double f_lo_hz)
+{
+    if (!h) return HD_ERR_INVALID;
+    return hd::tones_modem(h->st.s, h->fsd, baud, f_hi_hz, f_lo_hz, h->window_q8);
+}
+size_t hd_host_tones_push(hd_host_tones* h, const float* iq, size_t n, float* out) { return h && iq && out && n ? h->st.push(iq, n, out) : 0; }
+int hd_host_tones_stats(const hd_host_tones* h, hd_tones_info* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    const hd::TonesState& s = h->st.s;
+    *out = hd_tones_info{s.n, s.F, s.full, s.W, s.L, s.phi[0], s.phi[1]};
+    return HD_OK;
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

@@ -8,6 +8,7 @@
 #include "../../../include/habdec_amd.h"
 #include "../host/clocked_state.hpp"
 #include "../host/ring_schedule.hpp"
+#include "../host/tones_state.hpp"
 
 namespace hd {
 
@@ -103,6 +104,18 @@ struct ClockedSrc {
 // lds_words: words of LDS per wave, at least look + h + n of every stream that is on (host/clocked.hpp: clocked_window_words); false: more than the CU has.
 bool launch_clocked(hipStream_t st, uint32_t n_streams, const ClockedSrc* src, ClockedState* state, uint32_t* ring, size_t ring_stride, uint32_t* rec,
                     size_t rec_stride, uint32_t record_cap, uint32_t lds_words);
+
+// Tone-filter demodulator (tones.hip), one workgroup per stream.  src[s]: of the n_total cf32 samples of the push at p this launch takes the n from index
+// off on (n <= cap <= HD_TONES_CHUNK; n = 0, or a stream without a modem: not touched) and writes as many floats from index off on into the stream's row.
+// st [S]; ring32 [S][4][ring32_stride] uint32, a stream's four rings of kTonesRing32 running sums, each behind kTonesGuard guard words; ring64
+// [S][ring64_stride] uint64, its kTonesRing64 running sums of the normaliser behind kTonesGuard / 2 guard words; ctab: the probe's cosine table; rows
+// [S][row_stride] float, row_cap floats behind kTonesGuard guard words.  cap: the longest n of the launch, which sizes the LDS; false: more than the CU has.
+struct TonesSrc {
+    const float2* p;
+    uint32_t n_total, off, n, _pad;
+};
+bool launch_tones(hipStream_t st, uint32_t n_streams, uint32_t cap, const TonesSrc* src, TonesState* state, uint32_t* ring32, size_t ring32_stride,
+                  unsigned long long* ring64, size_t ring64_stride, const int32_t* ctab, float* rows, size_t row_stride, uint32_t row_cap);
 
 // ---- launchers of the mode-dependent kernels, once per arithmetic mode (arith.h)
 namespace exact {

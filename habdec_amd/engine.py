@@ -251,6 +251,12 @@ class Engine:
         self._probes = getattr(self, "_probes", []) + [c]
         return c
 
+    def tones(self, **params) -> "Tones":
+        """A tone-filter demodulator on this engine's streams (hd_tones_*; params as hd_tones_params): close it before the engine."""
+        t = Tones(self, **params)
+        self._probes = getattr(self, "_probes", []) + [t]
+        return t
+
     def set_format_trial(self, s, on=True):
         """Tee the bits delivered for stream s into a framing trial (hd_stream_set_format_trial); turning it on resets it."""
         check(self.L.hd_stream_set_format_trial(self.h, s, int(on)))
@@ -449,6 +455,11 @@ class Clocked:
         assert n.shape == (self.S,)
         check(self.L.hd_clocked_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
 
+    def push_tones(self, tones: "Tones"):
+        """Add the rows of the tone-filter demodulator's last push (hd_tones_rows), read in place in device memory."""
+        ptr, stride, n = tones.rows()
+        check(self.L.hd_clocked_push_device(self.h, ptr, stride, n.ctypes.data, 0))
+
     def waiting(self, s=0) -> int:
         n = self.L.hd_clocked_records(self.h, s, None, 0)
         check(min(n, 0))
@@ -525,6 +536,139 @@ class HostClocked:
         c = capi.hd_clocked_counters()
         check(self.L.hd_host_clocked_stats(self.h, C.byref(c)))
         return _clocked_counters(c)
+
+
+def _tones_params(L, params):
+    p = capi.hd_tones_params()
+    L.hd_tones_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, int(v))
+    return p
+
+
+def _tones_info(i) -> dict:
+    return {k: int(getattr(i, k)) for k, _ in capi.hd_tones_info._fields_}
+
+
+def _iq_rows(iq, S, n_per_stream):
+    """iq: complex64 [S, stride] (or [n] for one stream); n_per_stream: None = every row whole."""
+    iq = np.ascontiguousarray(iq, dtype=np.complex64)
+    if iq.ndim == 1:
+        iq = iq[None, :]
+    assert iq.shape[0] == S, iq.shape
+    n = np.full(S, iq.shape[1], np.uint32) if n_per_stream is None else np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+    assert n.shape == (S,) and (S == 1 or int(n.max(initial=0)) <= iq.shape[1])
+    return iq, n
+
+
+class Tones:
+    """Tone-filter demodulator of an engine's streams (hd_tones_*, include/habdec_amd.h): push decimated IQ, get one float row per stream in device memory
+    for Clocked.push_tones or BaudProbe.push_device."""
+
+    def __init__(self, eng: Engine, **params):
+        self.L, self.eng, self.S = eng.L, eng, eng.S
+        p = _tones_params(self.L, params)
+        h = C.c_void_p()
+        check(self.L.hd_tones_create(eng.h, C.byref(p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_tones_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_modem(self, s, baud, f_hi, f_lo):
+        """Give stream s its modem (resets the stream); baud 0: the engine stream's."""
+        check(self.L.hd_tones_set_modem(self.h, s, float(baud), float(f_hi), float(f_lo)))
+
+    def set_modem_from_afc(self, s, baud=0.0):
+        check(self.L.hd_tones_set_modem_from_afc(self.h, s, float(baud)))
+
+    def reset(self, s=None):
+        check(self.L.hd_tones_reset(self.h, 0xFFFFFFFF if s is None else s))
+
+    def push_engine(self):
+        """Demodulate every stream's decimated IQ of the call delivered last (drains the pipeline first, like the data getters)."""
+        check(self.L.hd_tones_push_engine(self.h))
+
+    def push_host(self, iq, n_per_stream=None):
+        iq, n = _iq_rows(iq, self.S, n_per_stream)
+        check(self.L.hd_tones_push_host(self.h, iq.ctypes.data, iq.shape[1], n.ctypes.data, 0))
+
+    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
+        """cf32 rows at a device address, row s at dev_ptr + 8 * s * stride."""
+        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+        assert n.shape == (self.S,)
+        check(self.L.hd_tones_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+
+    def rows(self):
+        """(device address of row 0, stride in floats, the rows' lengths) of the last push: valid until the next push or reset."""
+        ptr, stride, n = C.c_void_p(), C.c_size_t(), np.zeros(self.S, np.uint32)
+        check(self.L.hd_tones_rows(self.h, C.byref(ptr), C.byref(stride), n.ctypes.data))
+        return ptr.value, stride.value, n
+
+    def output(self, s=0) -> np.ndarray:
+        """A host copy of stream s's row of the last push."""
+        n = self.L.hd_tones_output(self.h, s, None, 0)
+        check(min(n, 0))
+        out = np.zeros(n, np.float32)
+        if n:
+            check(min(self.L.hd_tones_output(self.h, s, out.ctypes.data, out.size), 0))
+        return out
+
+    def stats(self, s=0) -> dict:
+        i = capi.hd_tones_info()
+        check(self.L.hd_tones_stats(self.h, s, C.byref(i)))
+        return _tones_info(i)
+
+
+class HostTones:
+    """One stream of the tone-filter demodulator in plain C++ on the host (hd_host_tones_*): the restatement the kernel is held to, no GPU."""
+
+    def __init__(self, decimated_rate: float, baud=None, f_hi=None, f_lo=None, **params):
+        self.L = lib()
+        p = _tones_params(self.L, params)
+        self.h = self.L.hd_host_tones_new(float(decimated_rate), C.byref(p))
+        if not self.h:
+            raise HabdecError("hd_host_tones_new: decimated_rate > 0")
+        if baud is not None:
+            self.set_modem(baud, f_hi, f_lo)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_host_tones_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_modem(self, baud, f_hi, f_lo):
+        rc = self.L.hd_host_tones_set_modem(self.h, float(baud), float(f_hi), float(f_lo))
+        if rc:
+            raise HabdecError("hd_host_tones_set_modem: %d (3.5 <= samples per bit <= 2048, 32 <= window_q8 <= 256; |tone| < rate / 2, f_hi above f_lo)" % rc)
+
+    def reset(self):
+        self.L.hd_host_tones_reset(self.h)
+
+    def push(self, iq) -> np.ndarray:
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        out = np.zeros(iq.size, np.float32)
+        n = self.L.hd_host_tones_push(self.h, iq.ctypes.data, iq.size, out.ctypes.data) if iq.size else 0
+        return out[:n]
+
+    def stats(self) -> dict:
+        i = capi.hd_tones_info()
+        check(self.L.hd_host_tones_stats(self.h, C.byref(i)))
+        return _tones_info(i)
 
 
 def chase_repair(span: str, data, nbits=8, repair_bits=8, repair_flips=3):

@@ -614,6 +614,69 @@ int  hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, 
 int  hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap);
 int  hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out);
 
+/* ---- tone-filter demodulator: a row for the clocked decoder and the probe below the discriminator's threshold (not in the reference) ----
+ * probe -> trial -> TONES -> hd_clocked_push_device.  The polar discriminator (hd_stream_demodulated) differentiates phase; once the noise makes the phase
+ * jump, its row carries nothing for any decoder.  The receiver for that level correlates the IQ against the two tones over about a bit and compares the
+ * envelopes: noncoherent FSK detection, mark and space filters.  A tones object is attached to an engine like a probe (its device, mutex and first queue;
+ * destroy it before the engine), reads each stream's tuned decimated IQ (hd_stream_decimated) and writes one float row per stream in device memory, which
+ * hd_clocked_push_device and hd_baud_probe_push_device take as they take any row.  Integer arithmetic behind the quantisation: kernel, host restatement
+ * (hd_host_tones_*) and a numpy model agree byte for byte.  fsd = hd_engine_decimated_rate(e).
+ *  - Modem of a stream: baud, the upper and the lower tone f_hi, f_lo in Hz at the decimated rate, and the object's window_q8.
+ *    F = (int64)floor(fsd / baud * 65536 + 0.5), full = (F + 32768) >> 16 (the clocked decoder's F and full), W = max(1, (F window_q8 + 2^23) >> 24),
+ *    L = 8 full, Phi_t = (uint32)(int64)nearbyint(f_t / fsd * 2^32), ties to even.  hd_tones_set_modem is HD_ERR_UNSUPPORTED unless
+ *    3.5 <= fsd / baud <= HD_TONES_MAX_SPB (2048) and 32 <= window_q8 <= 256, HD_ERR_INVALID for |f_t| >= fsd / 2 or an f_hi that is not above f_lo.
+ *  - i = the stream's absolute sample index since its last reset, uint64; how a stream is cut into pushes cannot matter; samples in front of index 0
+ *    are zero.
+ *  - Quantise, per component of the cf32 sample: q = 0 for NaN, else (int32)(clamp(v, -8, 8) * 256) truncated toward zero.
+ *  - Rotate, per tone t: theta = (i Phi_t) mod 2^32, a = theta >> 22, c = C[a], s = C[(a + 768) & 1023], C[a] = (int32)nearbyint(32767 cos(2 pi a / 1024))
+ *    (the probe's table); r_re = (q_re c + q_im s) >> 15, r_im = (q_im c - q_re s) >> 15, arithmetic shifts (floor).
+ *  - Window: s_re(i) = the sum of r_re(j), max(0, i + 1 - W) <= j <= i, s_im likewise.  Envelope: A_t(i) = floor(sqrt(s_re^2 + s_im^2)), the exact integer
+ *    root.
+ *  - Normaliser: T(i) = A_hi(i) + A_lo(i); N(i) = the sum of T(j), max(0, i + 1 - L) <= j <= i.
+ *  - Output: o = ((A_hi - A_lo) * 1024 * L) / max(1, N), int64 division truncated toward zero, clamped to [-4096, 4096]; the float written is o / 1024.0f,
+ *    exact, and the clocked decoder's quantisation of it gives back o.  Positive means the upper tone, the discriminator's sign: `invert` of
+ *    hd_clocked_set_modem means the same with either row.
+ *  - After hd_tones_create no stream has a modem: a stream without one is passed by and its row has length 0.  Every stream remembers the engine stream's
+ *    baud rate of that moment; baud = 0 in hd_tones_set_modem stands for it.
+ *  - The tones: the AFC's peaks (hd_stream_afc) are unreliable at the levels this object is for -- at sigma 1.1 on the 300 baud signal of NOTES.md the
+ *    reference's AFC reports peaks 420 Hz and 74 Hz off.  Take the tones while the signal is strong (hd_tones_set_modem_from_afc), or from the nominal
+ *    shift around a known centre.  The object does no tone search of its own.
+ *  - Queue, errors: as the probe's.  One launch for all streams per HD_TONES_CHUNK samples of the longest row; every push returns when its kernels are
+ *    done.  A push of more than max_push samples for a stream is HD_ERR_CAPACITY. */
+#define HD_TONES_MAX_SPB 2048
+#define HD_TONES_CHUNK 4096        /* samples per stream and launch */
+typedef struct hd_tones hd_tones;
+typedef struct hd_tones_params {
+    uint32_t max_push;         /* samples per stream and push the rows hold; default (0): the engine's largest decimated chunk per call, at least 4096 */
+    uint32_t window_q8;        /* the tone filters' length in 1/256 bit; default 160, 32 .. 256 */
+} hd_tones_params;
+typedef struct hd_tones_info {
+    uint64_t samples;          /* i: samples pushed since the last reset */
+    uint32_t F, full, W, L;    /* F = 0: the stream has no modem */
+    uint32_t step_hi, step_lo; /* Phi_hi, Phi_lo */
+} hd_tones_info;
+void hd_tones_params_default(hd_tones_params* p);
+int  hd_tones_create(hd_engine* e, const hd_tones_params* p /* null: the defaults */, hd_tones** out);   /* HD_ERR_UNSUPPORTED: window_q8 */
+void hd_tones_destroy(hd_tones* t);
+int  hd_tones_reset(hd_tones* t, uint32_t stream /* UINT32_MAX: all */);     /* the sample index starts again; the modem stays; the rows have length 0 */
+int  hd_tones_set_modem(hd_tones* t, uint32_t stream, double baud, double f_hi_hz, double f_lo_hz);       /* resets the stream */
+/* The tones from the stream's AFC: tone = (peak bin - 2048) * fsd / 4096 of hd_afc_info's peak_right and peak_left.  HD_ERR_INVALID unless both peaks
+ * are valid (positive). */
+int  hd_tones_set_modem_from_afc(hd_tones* t, uint32_t stream, double baud);
+/* Takes, for every stream with a modem, the tuned decimated IQ of the call delivered last (what hd_stream_decimated returns), read where the call left
+ * it, behind a drain of the pipeline (not from inside a callback).  A call that was pushed already adds nothing and leaves the rows as they are: HD_OK. */
+int  hd_tones_push_engine(hd_tones* t);
+/* Rows of cf32: stream s takes n_per_stream[s] (null: n) complex samples at d_iq + 2 * s * stride floats (stride in complex samples), from device
+ * memory on the engine's GPU (8-byte aligned) or from host memory.  The buffer is the caller's again on return. */
+int  hd_tones_push_device(hd_tones* t, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_tones_push_host(hd_tones* t, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* The device rows of the last push: row s is n_per_stream[s] floats at *d_rows + s * *stride (n_per_stream: S entries, written by the call).  They are
+ * valid until the next push or reset; what hd_clocked_push_device and hd_baud_probe_push_device take. */
+int  hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n_per_stream);
+/* A host copy of one row of the last push: returns its length and writes min(length, cap) floats.  Negative: HD_ERR_*. */
+int  hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap);
+int  hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out);
+
 #ifdef __cplusplus
 }
 #endif

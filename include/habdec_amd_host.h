@@ -212,6 +212,19 @@ int  hd_host_clocked_stats(const hd_host_clocked*, hd_clocked_counters* out);
 int  hd_host_chase_repair(const char* span, size_t n, const int32_t* data, uint32_t nbits, uint32_t repair_bits, uint32_t repair_flips, char* out,
                           uint32_t* flips);
 
+/* ---- tone-filter demodulator (hd_tones_*, include/habdec_amd.h has the definition): one stream of it in plain C++, sample by sample ----
+ * The same integers as the kernel: the rows of the same pushes equal the device rows byte for byte.  hd_host_tones_new: NULL unless decimated_rate > 0
+ * (params null: the defaults); the stream has no modem until hd_host_tones_set_modem gives it one, with the errors of hd_tones_set_modem.
+ * hd_host_tones_push takes n cf32 samples at iq (2 n floats), writes n floats to out and returns n; without a modem it writes nothing and returns 0.
+ * hd_host_tones_stats as hd_tones_stats. */
+typedef struct hd_host_tones hd_host_tones;
+hd_host_tones* hd_host_tones_new(double decimated_rate, const hd_tones_params* params);
+void   hd_host_tones_free(hd_host_tones*);
+void   hd_host_tones_reset(hd_host_tones*);
+int    hd_host_tones_set_modem(hd_host_tones*, double baud, double f_hi_hz, double f_lo_hz);
+size_t hd_host_tones_push(hd_host_tones*, const float* iq, size_t n, float* out);
+int    hd_host_tones_stats(const hd_host_tones*, hd_tones_info* out);
+
 #ifdef __cplusplus
 }
 #endif
