@@ -129,6 +129,26 @@ class hd_tones_info(C.Structure):
 TONES_MAX_SPB, TONES_CHUNK = 2048, 4096
 
 
+class hd_tone_search_params(C.Structure):
+    _fields_ = [("max_push", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class hd_tone_search_info(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("carry", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class hd_tone_search_detect_params(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("baud", "shift_lo_hz", "shift_hi_hz", "min_quality")]
+
+
+class hd_tone_search_result(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("f_hi_hz", "f_lo_hz", "quality", "floor")] + [("segments", C.c_uint64)] + \
+        [(k, C.c_uint32) for k in ("bin_lo", "shift_bins", "w", "valid")]
+
+
+TONE_SEARCH_BINS, TONE_SEARCH_HOP, TONE_SEARCH_CHUNK = 4096, 2048, 65536
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -262,6 +282,17 @@ ENGINE_API = {
     "hd_tones_rows": (_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _vp]),
     "hd_tones_output": (_int, [_vp, _u32, _vp, _sz]),
     "hd_tones_stats": (_int, [_vp, _u32, C.POINTER(hd_tones_info)]),
+    "hd_tone_search_params_default": (None, [C.POINTER(hd_tone_search_params)]),
+    "hd_tone_search_detect_params_default": (None, [C.POINTER(hd_tone_search_detect_params)]),
+    "hd_tone_search_create": (_int, [_vp, C.POINTER(hd_tone_search_params), C.POINTER(_vp)]),
+    "hd_tone_search_destroy": (None, [_vp]),
+    "hd_tone_search_reset": (_int, [_vp, _u32]),
+    "hd_tone_search_push_engine": (_int, [_vp]),
+    "hd_tone_search_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_tone_search_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_tone_search_power": (_int, [_vp, _u32, _vp, _sz, C.POINTER(C.c_uint64)]),
+    "hd_tone_search_stats": (_int, [_vp, _u32, C.POINTER(hd_tone_search_info)]),
+    "hd_tone_search_detect": (_int, [_vp, _u32, C.POINTER(hd_tone_search_detect_params), C.POINTER(hd_tone_search_result)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -341,6 +372,12 @@ HOST_API = {
     "hd_host_tones_set_modem": (_int, [_vp, _dbl, _dbl, _dbl]),
     "hd_host_tones_push": (_sz, [_vp, _vp, _sz, _vp]),
     "hd_host_tones_stats": (_int, [_vp, C.POINTER(hd_tones_info)]),
+    "hd_host_tone_search_detect": (_int, [_vp, C.c_uint64, _dbl, C.POINTER(hd_tone_search_detect_params), C.POINTER(hd_tone_search_result)]),
+    "hd_host_tone_search_create": (_vp, []),
+    "hd_host_tone_search_destroy": (None, [_vp]),
+    "hd_host_tone_search_reset": (None, [_vp]),
+    "hd_host_tone_search_push": (None, [_vp, _vp, _sz]),
+    "hd_host_tone_search_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

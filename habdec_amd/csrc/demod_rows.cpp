@@ -1,9 +1,10 @@
 // The objects that read the streams' signal beside the decode pipeline: the baud-rate probe (kernels/baud_probe.hip, host/baud_probe.hpp) and the clocked
 // decoder (kernels/clocked.hip, host/clocked.hpp), which read the discriminator output, and the tone-filter demodulator (kernels/tones.hip,
-// host/tones.hpp), which reads the decimated IQ and writes a row the other two can take.  All take one row per stream through the same three doors -- the
-// engine's last call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream descriptors, launch on
-// the engine's first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc, TonesSrc), in the rows' element (float, or
-// float2 for cf32) and in what they launch; the rest is the helpers below.
+// host/tones.hpp), which reads the decimated IQ and writes a row the other two can take, and the tone search (kernels/tone_search.hip,
+// host/tone_search.hpp), which reads the decimated IQ too and keeps a long-averaged spectrum per stream.  All take one row per stream through the same
+// three doors -- the engine's last call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream
+// descriptors, launch on the engine's first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc, TonesSrc;
+// tone_search.h: ToneSearchSrc), in the rows' element (float, or float2 for cf32) and in what they launch; the rest is the helpers below.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -12,6 +13,9 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/tones.hpp"
+#include "host/tone_search.hpp"
+#include "kernels/spectrum_math.h"
+#include "kernels/tone_search.h"
 
 using hd::eng::enter;
 using hd::eng::is_device_pointer;
@@ -25,7 +29,8 @@ uint32_t& src_len(hd::ClockedSrc& d) { return d.n_total; }
 // A descriptor for n elements in linear memory at p.
 template <typename Src>
 void src_set(Src& d, const float* p, uint32_t n) { src_len(d) = n; d.p = p; d.sym = nullptr; d.ring_mask = 0; }
-void src_set(hd::TonesSrc& d, const float2* p, uint32_t n) { d.n_total = n; d.p = p; }
+template <typename Src>
+void src_set(Src& d, const float2* p, uint32_t n) { d.n_total = n; d.p = p; }            // the cf32 descriptors: TonesSrc, ToneSearchSrc
 
 // A descriptor for what the engine's last call left for stream s, and that row's length: what hd_stream_demodulated knows -- the linear demod row, or the
 // newest last_m samples of the symbol ring -- or, for the tones, what hd_stream_decimated knows.
@@ -38,12 +43,15 @@ uint32_t src_from_engine(hd_engine* e, uint32_t s, Src& d)
     else { d.p = e->demod.p + (size_t)s * (e->demod.n / e->S); d.sym = nullptr; d.ring_mask = 0; }
     return sz.last_m;
 }
-uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::TonesSrc& d)
+template <typename Src>
+uint32_t src_from_engine_iq(hd_engine* e, uint32_t s, Src& d)
 {
     const SizeState& sz = e->mirror[s];
     src_set(d, e->fbuf[sz.last_buf].p + (size_t)s * e->fbuf_stride + e->fir_hist_cap + sz.last_pend_before, sz.last_n2);
     return sz.last_n2;
 }
+uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::TonesSrc& d) { return src_from_engine_iq(e, s, d); }
+uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::ToneSearchSrc& d) { return src_from_engine_iq(e, s, d); }
 
 // The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names.
 
@@ -747,6 +755,234 @@ int hd_debug_tones_guards(hd_tones* t, uint32_t stream)
         uint32_t g[hd::kTonesGuard];
         HD_HIP(hipMemcpy(g, p, sizeof g, hipMemcpyDeviceToHost));
         for (uint32_t w : g) bad += w != hd::kTonesGuardWord;
+    }
+    return bad;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- tone search (kernels/tone_search.hip) -------------------------------- */
+
+struct hd_tone_search {
+    hd_engine* e = nullptr;
+    hd_tone_search_params prm{};
+    uint32_t S = 0;
+    double* acc = nullptr;                       // [S][acc_stride]: guard | 4096 fftshifted sums | guard
+    float2* carry = nullptr;                     // [S][2][carry_stride]: guard | 4096 samples | guard -- the stream's two carry buffers (kernels/tone_search.hip)
+    float* win = nullptr;                        // [4096] the survey's window table
+    float2* own_tw = nullptr;                    // the twiddles where the engine computes no spectra and holds none
+    const float2* tw = nullptr;
+    size_t acc_stride = 0, carry_stride = 0;
+    double sum_w2 = 0;                           // sum of w^2, in double over the float table
+    float2* slab = nullptr;                      // hd_tone_search_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::ToneSearchSrc> src;               // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    std::vector<uint64_t> samples, segments;     // [S]: since the stream's last reset
+    std::vector<uint32_t> carry_n, flip;         // [S]: the carry's length, and which of the two buffers holds it
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
+    ~hd_tone_search()
+    {
+        for (void* p : {(void*)acc, (void*)carry, (void*)win, (void*)own_tw, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+const char kNullToneSearch[] = "null tone search";
+
+// src[s].p and n_total are written: one launch per HD_TONE_SEARCH_CHUNK samples of the longest row, each waited for; the streams' counts move on behind
+// every launch.  A row above max_push refuses the whole push before anything is launched.
+int tone_search_launch(hd_tone_search* ts, uint32_t max_n)
+{
+    hipStream_t q = ts->e->qa;
+    max_n = 0;
+    for (uint32_t s = 0; s < ts->S; ++s) {
+        const uint32_t n = ts->src.p[s].n_total;
+        if (n > ts->prm.max_push)
+            return fail(HD_ERR_CAPACITY, "hd_tone_search: a push of " + std::to_string(n) + " samples, max_push is " + std::to_string(ts->prm.max_push));
+        max_n = std::max(max_n, n);
+    }
+    if (ts->t0) HD_HIP(hipEventRecord(ts->t0, q));
+    for (uint32_t off = 0; off < max_n; off += HD_TONE_SEARCH_CHUNK) {
+        for (uint32_t s = 0; s < ts->S; ++s) {
+            hd::ToneSearchSrc& d = ts->src.p[s];
+            d.off = off;
+            d.n = d.n_total > off ? std::min<uint32_t>(HD_TONE_SEARCH_CHUNK, d.n_total - off) : 0u;
+            d.carry = ts->carry_n[s];
+            d.segs = hd::tone_search_segments(d.carry, d.n);
+            d.flip = ts->flip[s];
+        }
+        std::atomic_thread_fence(std::memory_order_release);
+        hd::launch_tone_search(q, ts->S, ts->src.dev, ts->win, ts->tw, ts->acc, ts->acc_stride, ts->carry, ts->carry_stride);
+        HD_HIP(hipGetLastError());
+        if (ts->t1 && off + HD_TONE_SEARCH_CHUNK >= max_n) HD_HIP(hipEventRecord(ts->t1, q));
+        HD_HIP(hipStreamSynchronize(q));
+        for (uint32_t s = 0; s < ts->S; ++s) {
+            const hd::ToneSearchSrc& d = ts->src.p[s];
+            ts->samples[s] += d.n;
+            ts->segments[s] += d.segs;
+            ts->carry_n[s] = d.carry + d.n - d.segs * hd::kToneSearchStep;
+            if (d.segs) ts->flip[s] ^= 1u;
+        }
+    }
+    return HD_OK;
+}
+
+// (The carry buffers need no clearing: nothing behind a stream's carry length is read.)
+int tone_search_clear(hd_tone_search* ts, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = ts->e->qa;
+    HD_HIP(hipMemset2DAsync(ts->acc + (size_t)s0 * ts->acc_stride + hd::kToneSearchGuard / 2, ts->acc_stride * sizeof(double), 0,
+                            (size_t)hd::kToneSearchSeg * sizeof(double), ns, q));
+    HD_HIP(hipStreamSynchronize(q));
+    for (uint32_t s = s0; s < s0 + ns; ++s) { ts->samples[s] = ts->segments[s] = 0; ts->carry_n[s] = ts->flip[s] = 0; }
+    return HD_OK;
+}
+
+int tone_search_check(hd_tone_search* ts, uint32_t stream)
+{
+    if (!ts) return fail(HD_ERR_INVALID, kNullToneSearch);
+    if (stream >= ts->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_tone_search_params_default(hd_tone_search_params* p) { if (p) *p = hd_tone_search_params{0u, 0u}; }
+void hd_tone_search_detect_params_default(hd_tone_search_detect_params* p) { if (p) hd::tone_search_detect_params_default(p); }
+
+int hd_tone_search_create(hd_engine* e, const hd_tone_search_params* params, hd_tone_search** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_tone_search> ts(new hd_tone_search);
+    ts->e = e; ts->S = e->S;
+    if (params) ts->prm = *params;
+    if (!ts->prm.max_push) ts->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
+    if (ts->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "tone search parameters: max_push <= 2^28");
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = ts->S;
+    ts->samples.assign(S, 0); ts->segments.assign(S, 0); ts->carry_n.assign(S, 0u); ts->flip.assign(S, 0u);
+    ts->acc_stride = (size_t)hd::kToneSearchSeg + hd::kToneSearchGuard;          // (kToneSearchGuard / 2 doubles, or samples, on either side)
+    ts->carry_stride = (size_t)hd::kToneSearchSeg + hd::kToneSearchGuard;
+    std::vector<float> w(hd::kToneSearchSeg);
+    hd::survey_window(w.data());
+    for (float v : w) ts->sum_w2 += (double)v * (double)v;
+    std::vector<float2> tw_host;
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->acc), (size_t)S * ts->acc_stride * sizeof(double)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->carry), (size_t)S * 2 * ts->carry_stride * sizeof(float2)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->win), w.size() * sizeof(float)));
+    HD_HIP(ts->src.alloc(S));
+    ts->tw = e->fft_tw.p;
+    if (!ts->tw) {   // an engine without spectra holds no twiddles: the same table, the object's own
+        tw_host.resize(hd::kFftBins);
+        hd::specwave::fft_twiddles(tw_host.data());
+        HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->own_tw), tw_host.size() * sizeof(float2)));
+        HD_HIP(hipMemcpyAsync(ts->own_tw, tw_host.data(), tw_host.size() * sizeof(float2), hipMemcpyHostToDevice, e->qa));
+        ts->tw = ts->own_tw;
+    }
+    HD_HIP(hipMemcpyAsync(ts->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ts->acc), (int)hd::kToneSearchGuardWord, (size_t)S * ts->acc_stride * 2, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ts->carry), (int)hd::kToneSearchGuardWord, (size_t)S * 2 * ts->carry_stride * 2, e->qa));
+    if (const int rc = tone_search_clear(ts.get(), 0, S)) return rc;   // (waits for the queue: the tables are locals)
+    *out = ts.release();
+    return HD_OK;
+}
+
+void hd_tone_search_destroy(hd_tone_search* ts) { destroy(ts); }
+
+int hd_tone_search_reset(hd_tone_search* ts, uint32_t stream)
+{
+    if (!ts) return fail(HD_ERR_INVALID, kNullToneSearch);
+    if (stream != UINT32_MAX && stream >= ts->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
+    if (const int rc = enter(ts->e)) return rc;
+    return stream == UINT32_MAX ? tone_search_clear(ts, 0, ts->S) : tone_search_clear(ts, stream, 1);
+}
+
+int hd_tone_search_push_engine(hd_tone_search* ts)
+{
+    return push_engine(ts, kNullToneSearch, "hd_tone_search_push_engine", [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
+}
+
+int hd_tone_search_push_device(hd_tone_search* ts, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(ts, kNullToneSearch, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true,
+                     [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
+}
+
+int hd_tone_search_push_host(hd_tone_search* ts, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(ts, kNullToneSearch, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false,
+                     [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
+}
+
+int hd_tone_search_power(hd_tone_search* ts, uint32_t stream, double* p, size_t cap, uint64_t* segments)
+{
+    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (!p) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
+    if (const int rc = enter(ts->e)) return rc;
+    const uint64_t segs = ts->segments[stream];
+    if (segments) *segments = segs;
+    if (cap < hd::kToneSearchSeg) return 0;
+    // (no queue to wait for: every push has waited for its launches)
+    HD_HIP(hipMemcpy(p, ts->acc + (size_t)stream * ts->acc_stride + hd::kToneSearchGuard / 2, hd::kToneSearchSeg * sizeof(double), hipMemcpyDeviceToHost));
+    const double norm = (double)segs * ts->sum_w2;
+    for (uint32_t i = 0; i < hd::kToneSearchSeg; ++i) p[i] = segs ? p[i] / norm : 0.0;
+    return (int)hd::kToneSearchSeg;
+}
+
+int hd_tone_search_stats(hd_tone_search* ts, uint32_t stream, hd_tone_search_info* out)
+{
+    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
+    *out = hd_tone_search_info{ts->samples[stream], ts->segments[stream], ts->carry_n[stream], 0u};
+    return HD_OK;
+}
+
+int hd_tone_search_detect(hd_tone_search* ts, uint32_t stream, const hd_tone_search_detect_params* p, hd_tone_search_result* out)
+{
+    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (!p || !out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
+    std::vector<double> pw(hd::kToneSearchSeg);
+    uint64_t segs = 0;
+    const int n = hd_tone_search_power(ts, stream, pw.data(), pw.size(), &segs);
+    if (n < 0) return n;
+    const int rc = hd::tone_search_detect(pw.data(), segs, ts->e->fsd, p, out);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "hd_tone_search_detect needs at least 8 segments (" + std::to_string(segs) + " so far)");
+    if (rc) return fail(rc, "hd_tone_search_detect: baud > 0, 0 < shift_lo_hz <= shift_hi_hz, and a tone spacing that fits the spectrum");
+    return HD_OK;
+}
+
+int hd_debug_tone_search_push_timed(hd_tone_search* ts, float* kernel_ms, double* host_us) { return push_timed(ts, kernel_ms, host_us, hd_tone_search_push_engine); }
+
+// Test hook (tests/test_gpu_tone_search.py; not part of the ABI): how many of the guard words around the stream's accumulator and its two carry buffers no
+// longer hold their pattern.
+int hd_debug_tone_search_guards(hd_tone_search* ts, uint32_t stream)
+{
+    if (!ts || stream >= ts->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
+    if (const int rc = enter(ts->e)) return rc;
+    const uint32_t* a32 = reinterpret_cast<const uint32_t*>(ts->acc);
+    const uint32_t* c32 = reinterpret_cast<const uint32_t*>(ts->carry);
+    const uint32_t* at[6];
+    at[0] = a32 + (size_t)stream * ts->acc_stride * 2; at[1] = at[0] + ts->acc_stride * 2 - hd::kToneSearchGuard;
+    for (uint32_t k = 0; k < 2; ++k) {
+        at[2 + 2 * k] = c32 + ((size_t)stream * 2 + k) * ts->carry_stride * 2;
+        at[3 + 2 * k] = at[2 + 2 * k] + ts->carry_stride * 2 - hd::kToneSearchGuard;
+    }
+    int bad = 0;
+    for (const uint32_t* p : at) {
+        uint32_t g[hd::kToneSearchGuard];
+        HD_HIP(hipMemcpy(g, p, sizeof g, hipMemcpyDeviceToHost));
+        for (uint32_t w : g) bad += w != hd::kToneSearchGuardWord;
     }
     return bad;
 }

@@ -8,6 +8,7 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/tones.hpp"
+#include "host/tone_search.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
 #include "host/format_trial.hpp"
@@ -399,6 +400,27 @@ int hd_host_tones_stats(const hd_host_tones* h, hd_tones_info* out)
     const hd::TonesState& s = h->st.s;
     *out = hd_tones_info{s.n, s.F, s.full, s.W, s.L, s.phi[0], s.phi[1]};
     return HD_OK;
+}
+
+/* ---- tone search (kernels/tone_search.hip; see host/tone_search.hpp) ---- */
+struct hd_host_tone_search {
+    hd::ToneSearchStream st;
+};
+int hd_host_tone_search_detect(const double* p, uint64_t segments, double fsd, const hd_tone_search_detect_params* params, hd_tone_search_result* out)
+{
+    return hd::tone_search_detect(p, segments, fsd, params, out);
+}
+hd_host_tone_search* hd_host_tone_search_create(void) { return new hd_host_tone_search; }
+void hd_host_tone_search_destroy(hd_host_tone_search* h) { delete h; }
+void hd_host_tone_search_reset(hd_host_tone_search* h) { if (h) h->st.reset(); }
+void hd_host_tone_search_push(hd_host_tone_search* h, const float* iq, size_t n) { if (h && iq && n) h->st.push(iq, n); }
+int hd_host_tone_search_power(const hd_host_tone_search* h, double* p, size_t cap, uint64_t* segments)
+{
+    if (!h || !p) return HD_ERR_INVALID;
+    if (segments) *segments = h->st.segments;
+    if (cap < hd::kToneSearchBins) return 0;
+    h->st.power(p);
+    return (int)hd::kToneSearchBins;
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

@@ -257,6 +257,12 @@ class Engine:
         self._probes = getattr(self, "_probes", []) + [t]
         return t
 
+    def tone_search(self, **params) -> "ToneSearch":
+        """A tone search on this engine's streams (hd_tone_search_*; params as hd_tone_search_params): close it before the engine."""
+        t = ToneSearch(self, **params)
+        self._probes = getattr(self, "_probes", []) + [t]
+        return t
+
     def set_format_trial(self, s, on=True):
         """Tee the bits delivered for stream s into a framing trial (hd_stream_set_format_trial); turning it on resets it."""
         check(self.L.hd_stream_set_format_trial(self.h, s, int(on)))
@@ -669,6 +675,130 @@ class HostTones:
         i = capi.hd_tones_info()
         check(self.L.hd_host_tones_stats(self.h, C.byref(i)))
         return _tones_info(i)
+
+
+def _tone_search_detect_params(L, params):
+    p = capi.hd_tone_search_detect_params()
+    L.hd_tone_search_detect_params_default(C.byref(p))
+    for k, v in params.items():
+        setattr(p, k, float(v))
+    return p
+
+
+def _tone_search_result(r) -> dict:
+    return {k: getattr(r, k) for k, _ in capi.hd_tone_search_result._fields_}
+
+
+def tone_search_detect(power: np.ndarray, segments: int, fsd: float, **params) -> dict:
+    """hd_host_tone_search_detect on a 4096-bin averaged power spectrum (no GPU): the result as a dict (f_hi_hz and f_lo_hz are what Tones.set_modem
+    takes); params as hd_tone_search_detect_params, baud required."""
+    L = lib()
+    power = np.ascontiguousarray(power, np.float64)
+    assert power.shape == (4096,), power.shape
+    p, r = _tone_search_detect_params(L, params), capi.hd_tone_search_result()
+    rc = L.hd_host_tone_search_detect(power.ctypes.data, int(segments), float(fsd), C.byref(p), C.byref(r))
+    if rc:
+        raise HabdecError(f"habdec_amd error {rc}: hd_host_tone_search_detect")
+    return _tone_search_result(r)
+
+
+class ToneSearch:
+    """Long-averaged power spectrum of every stream's decimated IQ and the two-tone detector on top of it (hd_tone_search_*, include/habdec_amd.h)."""
+
+    def __init__(self, eng: Engine, **params):
+        self.L, self.eng, self.S = eng.L, eng, eng.S
+        p = capi.hd_tone_search_params()
+        self.L.hd_tone_search_params_default(C.byref(p))
+        for k, v in params.items():
+            setattr(p, k, int(v))
+        h = C.c_void_p()
+        check(self.L.hd_tone_search_create(eng.h, C.byref(p), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_tone_search_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, s=None):
+        check(self.L.hd_tone_search_reset(self.h, 0xFFFFFFFF if s is None else s))
+
+    def push_engine(self):
+        """Take every stream's decimated IQ of the call delivered last (drains the pipeline first, like the data getters)."""
+        check(self.L.hd_tone_search_push_engine(self.h))
+
+    def push_host(self, iq, n_per_stream=None):
+        iq, n = _iq_rows(iq, self.S, n_per_stream)
+        check(self.L.hd_tone_search_push_host(self.h, iq.ctypes.data, iq.shape[1], n.ctypes.data, 0))
+
+    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
+        """cf32 rows at a device address, row s at dev_ptr + 8 * s * stride."""
+        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+        assert n.shape == (self.S,)
+        check(self.L.hd_tone_search_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+
+    def power(self, s=0):
+        """(float64[4096], segments) of stream s: p[k] belongs to (k - 2048) * decimated rate / 4096."""
+        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
+        n = self.L.hd_tone_search_power(self.h, s, p.ctypes.data, p.size, C.byref(seg))
+        if n != 4096:
+            check(n if n < 0 else -1)
+        return p, int(seg.value)
+
+    def stats(self, s=0) -> dict:
+        i = capi.hd_tone_search_info()
+        check(self.L.hd_tone_search_stats(self.h, s, C.byref(i)))
+        return {"samples": int(i.samples), "segments": int(i.segments), "carry": int(i.carry)}
+
+    def detect(self, s=0, **params) -> dict:
+        """The stream's two tones as a dict; params as hd_tone_search_detect_params, baud required."""
+        p, r = _tone_search_detect_params(self.L, params), capi.hd_tone_search_result()
+        check(self.L.hd_tone_search_detect(self.h, s, C.byref(p), C.byref(r)))
+        return _tone_search_result(r)
+
+
+class HostToneSearch:
+    """One stream of the tone search's spectrum in plain C++ on the host (hd_host_tone_search_*): double-precision transform, no GPU."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = self.L.hd_host_tone_search_create()
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.hd_host_tone_search_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self.L.hd_host_tone_search_reset(self.h)
+
+    def push(self, iq):
+        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
+        if iq.size:
+            self.L.hd_host_tone_search_push(self.h, iq.ctypes.data, iq.size)
+
+    def power(self):
+        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
+        n = self.L.hd_host_tone_search_power(self.h, p.ctypes.data, p.size, C.byref(seg))
+        if n != 4096:
+            raise HabdecError(f"habdec_amd error {n}: hd_host_tone_search_power")
+        return p, int(seg.value)
+
+    def detect(self, fsd, **params) -> dict:
+        p, seg = self.power()
+        return tone_search_detect(p, seg, fsd, **params)
 
 
 def chase_repair(span: str, data, nbits=8, repair_bits=8, repair_flips=3):

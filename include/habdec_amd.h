@@ -640,7 +640,8 @@ int  hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out);
  *    baud rate of that moment; baud = 0 in hd_tones_set_modem stands for it.
  *  - The tones: the AFC's peaks (hd_stream_afc) are unreliable at the levels this object is for -- at sigma 1.1 on the 300 baud signal of NOTES.md the
  *    reference's AFC reports peaks 420 Hz and 74 Hz off.  Take the tones while the signal is strong (hd_tones_set_modem_from_afc), or from the nominal
- *    shift around a known centre.  The object does no tone search of its own.
+ *    shift around a known centre.  A payload that was never strong has its tones found by the tone search below (hd_tone_search_*), whose result is
+ *    what hd_tones_set_modem takes.
  *  - Queue, errors: as the probe's.  One launch for all streams per HD_TONES_CHUNK samples of the longest row; every push returns when its kernels are
  *    done.  A push of more than max_push samples for a stream is HD_ERR_CAPACITY. */
 #define HD_TONES_MAX_SPB 2048
@@ -676,6 +677,75 @@ int  hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* 
 /* A host copy of one row of the last push: returns its length and writes min(length, cap) floats.  Negative: HD_ERR_*. */
 int  hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap);
 int  hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out);
+
+/* ---- tone search: the two FSK tones of a stream that was never strong, from a long-averaged spectrum (not in the reference) ----
+ * survey -> front tune -> probe -> trial -> TONE SEARCH -> tones -> hd_clocked_push_device.  The tone filters need both tones to a few per cent of the baud
+ * rate; the engine's only per-stream spectrum is one 4096-sample snapshot per spectrum call, and its peaks are what the AFC misjudges on a weak signal.
+ * What finds them is long integration: a Welch-averaged power spectrum per stream at the decimated rate, kept over many calls, and a two-tone detector
+ * on top of it (habdec_amd_host.h: hd_host_tone_search_detect).  A tone search is attached to an engine like a tones object (its device, mutex and first
+ * queue; destroy it before the engine) and reads what that one reads: each stream's tuned decimated IQ in cf32 (hd_stream_decimated).  Per stream it
+ * keeps 4096 double accumulators (fftshifted), a segment count, the absolute sample index and a carry of the samples that do not yet fill a segment.
+ * fsd = hd_engine_decimated_rate(e).
+ *  - i = the stream's absolute sample index since its last reset, uint64.  Segment j is samples [2048 j, 2048 j + 4096) of the STREAM, not of a push:
+ *    segments straddle pushes (the engine's calls leave 1024 to 4000 decimated samples each; the survey's rule, segments that never straddle pushes,
+ *    would lose every one of them).  How a stream is cut into pushes does not matter, byte for byte.
+ *  - Per completed segment, the survey's arithmetic: the periodic Hann float table of hd_host_survey_window, one rounded multiply per part; the engine's
+ *    4096-point in-wave transform; re^2 + im^2 per bin in float, every product and sum rounded separately; the half swap, so that bin k belongs to
+ *    (k - 2048) fsd / 4096.  Then acc[k] += (double)p[k], in segment order.  No float sums across segments and no floating-point atomics: this is what
+ *    makes the result independent of the cut.
+ *  - A NaN or Inf sample makes its segments' bins non-finite, and the accumulator stays non-finite until the stream is reset; hd_tone_search_detect
+ *    reports valid = 0 for such a stream.  Other streams are untouched.
+ *  - Queue, errors: as the tones object's.  One launch serves all streams, one wave per stream; a row longer than HD_TONE_SEARCH_CHUNK samples is cut into
+ *    several launches in order, which changes nothing.  Every push returns when its kernels are done.  A push of more than max_push samples for a stream
+ *    is HD_ERR_CAPACITY and adds nothing to any stream. */
+#define HD_TONE_SEARCH_BINS 4096
+#define HD_TONE_SEARCH_HOP 2048
+#define HD_TONE_SEARCH_CHUNK 65536   /* samples per stream and launch: at most 32 segments per wave */
+typedef struct hd_tone_search hd_tone_search;
+typedef struct hd_tone_search_params {
+    uint32_t max_push;         /* most samples per stream and push; default (0): the engine's largest decimated chunk per call, at least 4096 */
+    uint32_t _pad;
+} hd_tone_search_params;
+typedef struct hd_tone_search_info {
+    uint64_t samples;          /* i: samples pushed since the last reset */
+    uint64_t segments;         /* segments completed since the last reset */
+    uint32_t carry;            /* samples kept for the next segment: samples - 2048 segments, at most 4095 */
+    uint32_t _pad;
+} hd_tone_search_info;
+typedef struct hd_tone_search_detect_params {
+    double baud;               /* the stream's baud rate; required, > 0 */
+    double shift_lo_hz;        /* least tone spacing searched; default 170 */
+    double shift_hi_hz;        /* greatest tone spacing searched; default 1000 */
+    double min_quality;        /* least quality for valid = 1; default 0.5 */
+} hd_tone_search_detect_params;
+typedef struct hd_tone_search_result {
+    double   f_hi_hz, f_lo_hz; /* the upper and the lower tone at the decimated rate: what hd_tones_set_modem takes */
+    double   quality;          /* the weaker tone's power above the floor over the floor's power in as many bins */
+    double   floor;            /* the spectrum's median */
+    uint64_t segments;
+    uint32_t bin_lo;           /* the coarse search's lower bin */
+    uint32_t shift_bins;       /* ... and its spacing in bins */
+    uint32_t w;                /* bins per tone window, odd */
+    uint32_t valid;            /* 1: both tones stand clear of the noise (habdec_amd_host.h has the rule) */
+} hd_tone_search_result;
+void hd_tone_search_params_default(hd_tone_search_params* p);
+void hd_tone_search_detect_params_default(hd_tone_search_detect_params* p);            /* baud = 0: to be filled in */
+int  hd_tone_search_create(hd_engine* e, const hd_tone_search_params* p /* null: the defaults */, hd_tone_search** out);
+void hd_tone_search_destroy(hd_tone_search* ts);
+int  hd_tone_search_reset(hd_tone_search* ts, uint32_t stream /* UINT32_MAX: all */);   /* accumulator, segments, sample index and carry = 0 */
+/* Takes every stream's tuned decimated IQ of the call delivered last, read where the call left it, behind a drain of the pipeline (not from inside a
+ * callback).  A call that was pushed already adds nothing: HD_OK.  The rules of hd_tones_push_engine. */
+int  hd_tone_search_push_engine(hd_tone_search* ts);
+/* Rows of cf32 as for hd_tones_push_*: stream s takes n_per_stream[s] (null: n) complex samples at d_iq + 2 * s * stride floats, from device memory on the
+ * engine's GPU (8-byte aligned) or from host memory.  The buffer is the caller's again on return. */
+int  hd_tone_search_push_device(hd_tone_search* ts, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_tone_search_push_host(hd_tone_search* ts, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* p[k] = acc[k] / (segments * sum w^2), as hd_survey_power; zeros with no segment.  *segments (may be null) is always written; returns 4096, or 0 and
+ * writes no power when cap < 4096.  Negative: HD_ERR_*. */
+int  hd_tone_search_power(hd_tone_search* ts, uint32_t stream, double* p, size_t cap, uint64_t* segments);
+int  hd_tone_search_stats(hd_tone_search* ts, uint32_t stream, hd_tone_search_info* out);
+/* hd_tone_search_power followed by hd_host_tone_search_detect (habdec_amd_host.h has the algorithm and its errors). */
+int  hd_tone_search_detect(hd_tone_search* ts, uint32_t stream, const hd_tone_search_detect_params* p, hd_tone_search_result* out);
 
 #ifdef __cplusplus
 }

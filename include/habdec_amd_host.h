@@ -225,6 +225,34 @@ int    hd_host_tones_set_modem(hd_host_tones*, double baud, double f_hi_hz, doub
 size_t hd_host_tones_push(hd_host_tones*, const float* iq, size_t n, float* out);
 int    hd_host_tones_stats(const hd_host_tones*, hd_tones_info* out);
 
+/* ---- tone search (hd_tone_search_*, include/habdec_amd.h has the spectrum's definition): the detector, and one stream of the spectrum ----
+ * hd_host_tone_search_detect: a pure function of a 4096-bin averaged power spectrum P (P[k] at (k - 2048) fsd / 4096) of `segments` segments.  All
+ * arithmetic in double, every sum sequential in ascending index.  In order:
+ *  1. Null arguments, baud <= 0, fsd <= 0, shift_lo_hz <= 0, shift_hi_hz < shift_lo_hz, min_quality < 0, a NaN or an Inf among them: HD_ERR_INVALID.
+ *     Fewer than 8 segments: HD_ERR_UNSUPPORTED.
+ *  2. bin = fsd / 4096.  w = max(1, nearbyint(0.5 baud / bin)) | 1 (odd), h = w / 2: the bins one tone's window holds.  The spacings searched are
+ *     d = ceil(shift_lo_hz / bin) .. min(floor(shift_hi_hz / bin), 4096 - w); no such d, or w >= 4096: HD_ERR_INVALID.
+ *  3. A non-finite P: HD_OK with valid = 0; w and segments are set, every other field is 0.
+ *  4. floor = the median of the 4096 values (the mean of the two middle ones).
+ *  5. B[k] = sum over k - h <= m <= k + h of (P[m] - floor), for h <= k < 4096 - h.
+ *  6. Coarse search: d ascending, then lo from h to 4096 - h - d - 1 ascending; score = min(B[lo], B[lo + d]); the first strictly greatest score
+ *     wins (bin_lo, shift_bins).  The minimum is deliberate: both tones must be there, a lone carrier scores like noise.
+ *  7. Refinement of each of the two bins c = bin_lo, bin_lo + shift_bins, three rounds: r = max(1, nearbyint(0.3 baud / bin)); weights
+ *     max(P[m] - floor, 0) over c - r <= m <= c + r clamped to the array; cf = the weighted centroid (c itself when the weights sum to 0);
+ *     c = nearbyint(cf), ties to even.  The tone is (cf - 2048) bin of the last round: f_lo_hz from bin_lo, f_hi_hz from the other.
+ *  8. quality = score / (w floor), 0 when floor <= 0.  valid = 1 when floor > 0 and quality >= max(min_quality, 10 / sqrt(w segments)); noise alone
+ *     stayed below 6.1 / sqrt(w segments) where it was measured (NOTES.md).
+ * hd_host_tone_search_create / _push / _power / _reset / _destroy: one stream of the spectrum in plain C++ -- the same segmentation over the absolute
+ * sample index and the same float window products, then a double-precision transform and |X|^2 in double; hd_host_tone_search_push takes n cf32 samples
+ * (2 n floats); hd_host_tone_search_power as hd_tone_search_power.  The GPU's accumulators agree with it to the float transform's error, not byte for byte. */
+typedef struct hd_host_tone_search hd_host_tone_search;
+int    hd_host_tone_search_detect(const double* p, uint64_t segments, double fsd, const hd_tone_search_detect_params* params, hd_tone_search_result* out);
+hd_host_tone_search* hd_host_tone_search_create(void);
+void   hd_host_tone_search_destroy(hd_host_tone_search*);
+void   hd_host_tone_search_reset(hd_host_tone_search*);
+void   hd_host_tone_search_push(hd_host_tone_search*, const float* iq, size_t n);
+int    hd_host_tone_search_power(const hd_host_tone_search*, double* p, size_t cap, uint64_t* segments);
+
 #ifdef __cplusplus
 }
 #endif
