@@ -4,7 +4,10 @@
 // host/tone_search.hpp), which reads the decimated IQ too and keeps a long-averaged spectrum per stream.  All take one row per stream through the same
 // three doors -- the engine's last call, rows in device memory, rows in host memory -- describe them to their kernel in a pinned array of per-stream
 // descriptors, launch on the engine's first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc, TonesSrc;
-// tone_search.h: ToneSearchSrc), in the rows' element (float, or float2 for cf32) and in what they launch; the rest is the helpers below.
+// tone_search.h: ToneSearchSrc), in the rows' element (float, or float2 for cf32) and in what they launch; the rest is the helpers below: the doors'
+// checks (check_object), the three push doors and the timed one (push_engine, push_rows, push_timed), the launches of a push (launch_chunks; the probe's is
+// a single one, probe_launch), the refusal of a row above max_push (check_max_push), reset and destroy, and the test hooks' guard counter.  Where an
+// object does something of its own, it says so at its own *_launch or door.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -53,14 +56,24 @@ uint32_t src_from_engine_iq(hd_engine* e, uint32_t s, Src& d)
 uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::TonesSrc& d) { return src_from_engine_iq(e, s, d); }
 uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::ToneSearchSrc& d) { return src_from_engine_iq(e, s, d); }
 
-// The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names.
+// The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names, and
+// kNull, the doors' message for a null object.
 
-// hd_*_push_engine.  null_msg: the error for a null object; fn: the door's name for the message.  launch(max_n): the descriptors are written and
-// the longest row has max_n samples.
-template <typename Obj, typename Launch>
-int push_engine(Obj* o, const char* null_msg, const char* fn, Launch launch)
+// What every door that names a stream tests first, in this order: the object, then the stream's range (all: UINT32_MAX, every stream, passes too).
+// Null outputs and capacities come behind it, then the lock and enter().
+template <typename Obj>
+int check_object(Obj* o, uint32_t stream, bool all = false)
 {
-    if (!o) return fail(HD_ERR_INVALID, null_msg);
+    if (!o) return fail(HD_ERR_INVALID, Obj::kNull);
+    if (!(all && stream == UINT32_MAX) && stream >= o->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    return HD_OK;
+}
+
+// hd_*_push_engine.  fn: the door's name for the message.  launch(o, max_n): the descriptors are written and the longest row has max_n samples.
+template <typename Obj, typename Launch>
+int push_engine(Obj* o, const char* fn, Launch launch)
+{
+    if (!o) return fail(HD_ERR_INVALID, Obj::kNull);
     hd_engine* e = o->e;
     std::lock_guard<std::recursive_mutex> lock(e->mtx);
     if (const int rc = enter(e)) return rc;
@@ -71,15 +84,15 @@ int push_engine(Obj* o, const char* null_msg, const char* fn, Launch launch)
     o->pushed_calls = e->calls;
     uint32_t max_n = 0;
     for (uint32_t s = 0; s < e->S; ++s) max_n = std::max(max_n, src_from_engine(e, s, o->src.p[s]));
-    return launch(max_n);
+    return launch(o, max_n);
 }
 
 // hd_*_push_device (device = true: row s is read in place at rows + s * stride) and hd_*_push_host (the rows are packed end to end into the slab,
 // grown on demand, one copy per row on the engine's first queue).  T: a row's element, float or float2.
 template <typename Obj, typename T, typename Launch>
-int push_rows(Obj* o, const char* null_msg, const T* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, bool device, Launch launch)
+int push_rows(Obj* o, const T* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, bool device, Launch launch)
 {
-    if (!o) return fail(HD_ERR_INVALID, null_msg);
+    if (!o) return fail(HD_ERR_INVALID, Obj::kNull);
     if (!rows) return fail(HD_ERR_INVALID, "null rows");
     if (reinterpret_cast<uintptr_t>(rows) & (alignof(T) - 1)) return fail(HD_ERR_INVALID, "rows must be " + std::to_string(alignof(T)) + "-byte aligned");
     uint32_t max_n = 0; size_t total = 0;
@@ -105,10 +118,53 @@ int push_rows(Obj* o, const char* null_msg, const T* rows, size_t stride, const 
         if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab + at, rows + (size_t)s * stride, (size_t)ns * sizeof(T), hipMemcpyHostToDevice, o->e->qa));
         at += ns;
     }
-    return launch(max_n);
+    return launch(o, max_n);
 }
 
-// The measurement hooks (tools/micro/probe_rate.py, clocked_rate.py; not part of the ABI): the kernels of push() -- the object's hd_*_push_engine, whose
+// The launches behind a push of the clocked decoder, the tones and the tone search: src[s].p and n_total are written and the longest row has max_n samples;
+// one launch per `chunk` samples of it, each waited for before the next one's descriptors are written.  Chunk by chunk: every descriptor's off and n are
+// cut from its n_total, and prepare(s, d) adds, in the same pass over the streams (a second pass is host time a push of 1024 streams shows), what the
+// object's kernel wants beside them; launch() issues the kernel -- false: it does not fit, the push fails with `unfit` -- and starts the object's
+// per-chunk maxima afresh; after() follows the wait.  t1 is recorded behind the last chunk's launch.  (The probe's kernel takes a row whole: probe_launch.)
+template <typename Obj, typename Prepare, typename Launch, typename After>
+int launch_chunks(Obj* o, uint32_t max_n, uint32_t chunk, const char* unfit, Prepare prepare, Launch launch, After after)
+{
+    hipStream_t q = o->e->qa;
+    if (o->t0) HD_HIP(hipEventRecord(o->t0, q));
+    for (uint32_t off = 0; off < max_n; off += chunk) {
+        for (uint32_t s = 0; s < o->S; ++s) {
+            auto& d = o->src.p[s];
+            d.off = off;
+            d.n = d.n_total > off ? std::min<uint32_t>(chunk, d.n_total - off) : 0u;
+            prepare(s, d);
+        }
+        std::atomic_thread_fence(std::memory_order_release);
+        if (!launch()) return fail(HD_ERR_DEVICE, unfit);
+        HD_HIP(hipGetLastError());
+        if (o->t1 && off + chunk >= max_n) HD_HIP(hipEventRecord(o->t1, q));
+        HD_HIP(hipStreamSynchronize(q));
+        after();
+    }
+    return HD_OK;
+}
+
+// Tones and tone search: a row above max_push refuses the whole push, before t0 is recorded and anything is launched.  first(s) goes in front of
+// stream s's test, in the same pass: the tones pass a stream without a modem by there.  max_n: the longest row, counted again behind that.
+template <typename Obj, typename First>
+int check_max_push(Obj* o, const char* who, uint32_t* max_n, First first)
+{
+    *max_n = 0;
+    for (uint32_t s = 0; s < o->S; ++s) {
+        first(s);
+        const uint32_t n = o->src.p[s].n_total;
+        if (n > o->prm.max_push)
+            return fail(HD_ERR_CAPACITY, std::string(who) + ": a push of " + std::to_string(n) + " samples, max_push is " + std::to_string(o->prm.max_push));
+        *max_n = std::max(*max_n, n);
+    }
+    return HD_OK;
+}
+
+// The measurement hooks (tools/micro/*_rate.py; not part of the ABI): the kernels of push() -- the object's hd_*_push_engine, whose
 // launch records t0 and t1 where they are set -- between two HIP events, and the host time of the whole call in microseconds.
 template <typename Obj, typename Push>
 int push_timed(Obj* o, float* kernel_ms, double* host_us, Push push)
@@ -132,6 +188,30 @@ int push_timed(Obj* o, float* kernel_ms, double* host_us, Push push)
     return rc;
 }
 
+// hd_*_reset.  clear(o, s0, ns): the object's own, streams s0 .. s0 + ns - 1 go back to their modem's first state.
+template <typename Obj, typename Clear>
+int reset(Obj* o, uint32_t stream, Clear clear)
+{
+    if (const int rc = check_object(o, stream, true)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(o->e->mtx);
+    if (const int rc = enter(o->e)) return rc;
+    return stream == UINT32_MAX ? clear(o, 0, o->S) : clear(o, stream, 1);
+}
+
+// The test hooks hd_debug_*_guards (not part of the ABI): how many of the `words` guard words at each of the addresses no longer hold `pattern`.  Which
+// addresses an object guards is its own list; the patterns and widths are the kernels' (launch.h, tone_search.h).
+template <size_t N>
+int damaged_guards(const uint32_t* const (&at)[N], uint32_t words, uint32_t pattern)
+{
+    std::vector<uint32_t> g(words);
+    int bad = 0;
+    for (const uint32_t* p : at) {
+        HD_HIP(hipMemcpy(g.data(), p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t w : g) bad += w != pattern;
+    }
+    return bad;
+}
+
 // hd_*_destroy.  (No queue to wait for: every push has waited for its launches.)
 template <typename Obj>
 void destroy(Obj* o)
@@ -148,6 +228,7 @@ void destroy(Obj* o)
 /* ---------------------------------------------------------------- baud-rate probe (kernels/baud_probe.hip) ----------------------------- */
 
 struct hd_baud_probe {
+    static constexpr const char* kNull = "null probe";
     hd_engine* e = nullptr;
     hd_baud_probe_params prm{};
     hd::BaudProbeTables t;
@@ -170,11 +251,11 @@ struct hd_baud_probe {
 
 namespace {
 
-const char kNullProbe[] = "null probe";
-
-// The descriptors are written: one launch for all streams on the engine's first queue, and the wait for it.
-int probe_launch(hd_baud_probe* p)
+// The descriptors are written: one launch for all streams on the engine's first queue, and the wait for it.  Its own: the kernel takes a row whole, so
+// there is no chunk loop, and nothing is launched when every stream's row is empty (hd_baud_probe_push_engine; the other doors return before that).
+int probe_launch(hd_baud_probe* p, uint32_t max_n)
 {
+    if (!max_n) return HD_OK;
     std::atomic_thread_fence(std::memory_order_release);
     if (p->t0) HD_HIP(hipEventRecord(p->t0, p->e->qa));
     hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr, p->acc64, p->acc32, p->F, p->scale, p->ctab);
@@ -233,35 +314,23 @@ int hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* params, hd_ba
 
 void hd_baud_probe_destroy(hd_baud_probe* p) { destroy(p); }
 
-int hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream)
-{
-    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
-    if (stream != UINT32_MAX && stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
-    if (const int rc = enter(p->e)) return rc;
-    return stream == UINT32_MAX ? probe_clear(p, 0, p->S) : probe_clear(p, stream, 1);
-}
+int hd_baud_probe_reset(hd_baud_probe* p, uint32_t stream) { return reset(p, stream, probe_clear); }
 
-int hd_baud_probe_push_engine(hd_baud_probe* p)
-{
-    // The probe launches nothing when every stream's row is empty.  (The clocked decoder's chunk loop simply runs zero times.)
-    return push_engine(p, kNullProbe, "hd_baud_probe_push_engine", [p](uint32_t max_n) { return max_n ? probe_launch(p) : HD_OK; });
-}
+int hd_baud_probe_push_engine(hd_baud_probe* p) { return push_engine(p, "hd_baud_probe_push_engine", probe_launch); }
 
 int hd_baud_probe_push_device(hd_baud_probe* p, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(p, kNullProbe, d_rows, stride, n_per_stream, n, true, [p](uint32_t) { return probe_launch(p); });
+    return push_rows(p, d_rows, stride, n_per_stream, n, true, probe_launch);
 }
 
 int hd_baud_probe_push_host(hd_baud_probe* p, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(p, kNullProbe, rows, stride, n_per_stream, n, false, [p](uint32_t) { return probe_launch(p); });
+    return push_rows(p, rows, stride, n_per_stream, n, false, probe_launch);
 }
 
 int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_state* hdr, hd_baud_probe_candidate* cand, size_t cap)
 {
-    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
-    if (stream >= p->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (const int rc = check_object(p, stream)) return rc;
     if (cap < hd::kProbeCand) return (int)hd::kProbeCand;              // nothing is written
     std::lock_guard<std::recursive_mutex> lock(p->e->mtx);
     if (const int rc = enter(p->e)) return rc;
@@ -284,8 +353,8 @@ int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_
 
 int hd_baud_probe_estimate(hd_baud_probe* p, uint32_t stream, hd_baud_estimate* out)
 {
-    if (!p) return fail(HD_ERR_INVALID, kNullProbe);
-    if (!out) return fail(HD_ERR_INVALID, "null output");
+    if (!p) return fail(HD_ERR_INVALID, hd_baud_probe::kNull);
+    if (!out) return fail(HD_ERR_INVALID, "null output");                // (in front of the stream's range here: hd_baud_probe_state tests that)
     hd_baud_probe_stream_state h;
     std::vector<hd_baud_probe_candidate> c(hd::kProbeCand);
     const int n = hd_baud_probe_state(p, stream, &h, c.data(), c.size());
@@ -301,6 +370,7 @@ int hd_debug_baud_probe_push_timed(hd_baud_probe* p, float* kernel_ms, double* h
 /* ---------------------------------------------------------------- clocked decoder (kernels/clocked.hip) -------------------------------- */
 
 struct hd_clocked {
+    static constexpr const char* kNull = "null clocked decoder";
     hd_engine* e = nullptr;
     hd_clocked_params prm{};
     uint32_t S = 0;
@@ -323,29 +393,21 @@ struct hd_clocked {
 
 namespace {
 
-const char kNullClocked[] = "null clocked decoder";
-
-// src[s].p, sym, ring_mask and n_total are written: one launch per HD_CLOCKED_CHUNK samples of the longest row, each waited for.
+// Its own per chunk: the LDS window of the launch, the widest any stream with a modem needs for its part of the row.
 int clocked_launch(hd_clocked* c, uint32_t max_n)
 {
-    hipStream_t q = c->e->qa;
-    if (c->t0) HD_HIP(hipEventRecord(c->t0, q));
-    for (uint32_t off = 0; off < max_n; off += HD_CLOCKED_CHUNK) {
-        uint32_t lds_words = 64;
-        for (uint32_t s = 0; s < c->S; ++s) {
-            hd::ClockedSrc& d = c->src.p[s];
-            d.off = off;
-            d.n = d.n_total > off ? std::min<uint32_t>(HD_CLOCKED_CHUNK, d.n_total - off) : 0u;
+    uint32_t lds_words = 64;
+    return launch_chunks(
+        c, max_n, HD_CLOCKED_CHUNK, "clocked decoder: the launch's window does not fit the LDS",
+        [&](uint32_t s, const hd::ClockedSrc& d) {
             if (c->modem[s].F) lds_words = std::max(lds_words, hd::clocked_window_words(c->modem[s], d.n));
-        }
-        std::atomic_thread_fence(std::memory_order_release);
-        if (!hd::launch_clocked(q, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, lds_words))
-            return fail(HD_ERR_DEVICE, "clocked decoder: the launch's window does not fit the LDS");
-        HD_HIP(hipGetLastError());
-        if (c->t1 && off + HD_CLOCKED_CHUNK >= max_n) HD_HIP(hipEventRecord(c->t1, q));
-        HD_HIP(hipStreamSynchronize(q));
-    }
-    return HD_OK;
+        },
+        [&] {
+            const uint32_t words = lds_words;
+            lds_words = 64;
+            return hd::launch_clocked(c->e->qa, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, words);
+        },
+        [] {});
 }
 
 int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
@@ -424,19 +486,11 @@ int hd_clocked_create(hd_engine* e, const hd_clocked_params* params, hd_clocked*
 
 void hd_clocked_destroy(hd_clocked* c) { destroy(c); }
 
-int hd_clocked_reset(hd_clocked* c, uint32_t stream)
-{
-    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
-    if (stream != UINT32_MAX && stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = enter(c->e)) return rc;
-    return stream == UINT32_MAX ? clocked_clear(c, 0, c->S) : clocked_clear(c, stream, 1);
-}
+int hd_clocked_reset(hd_clocked* c, uint32_t stream) { return reset(c, stream, clocked_clear); }
 
 int hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t nbits, uint32_t nstops, int invert)
 {
-    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (const int rc = check_object(c, stream)) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     const uint32_t F = hd::clocked_modem_F(c->e->fsd, baud, nbits, (double)nstops);
     if (!F) return fail(HD_ERR_UNSUPPORTED, "clocked decoder: 3.5 <= decimated rate / baud <= " + std::to_string(HD_CLOCKED_MAX_SPB) + ", 7 or 8 data bits, 1 or 2 stop bits");
@@ -445,25 +499,21 @@ int hd_clocked_set_modem(hd_clocked* c, uint32_t stream, double baud, uint32_t n
     return clocked_clear(c, stream, 1);
 }
 
-int hd_clocked_push_engine(hd_clocked* c)
-{
-    return push_engine(c, kNullClocked, "hd_clocked_push_engine", [c](uint32_t max_n) { return clocked_launch(c, max_n); });
-}
+int hd_clocked_push_engine(hd_clocked* c) { return push_engine(c, "hd_clocked_push_engine", clocked_launch); }
 
 int hd_clocked_push_device(hd_clocked* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(c, kNullClocked, d_rows, stride, n_per_stream, n, true, [c](uint32_t max_n) { return clocked_launch(c, max_n); });
+    return push_rows(c, d_rows, stride, n_per_stream, n, true, clocked_launch);
 }
 
 int hd_clocked_push_host(hd_clocked* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(c, kNullClocked, rows, stride, n_per_stream, n, false, [c](uint32_t max_n) { return clocked_launch(c, max_n); });
+    return push_rows(c, rows, stride, n_per_stream, n, false, clocked_launch);
 }
 
 int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, size_t cap)
 {
-    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (const int rc = check_object(c, stream)) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
     if (!out) {
@@ -478,8 +528,7 @@ int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, s
 
 int hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentence* out, size_t cap)
 {
-    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (const int rc = check_object(c, stream)) return rc;
     if (cap && !out) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
@@ -490,8 +539,7 @@ int hd_clocked_take_sentences(hd_clocked* c, uint32_t stream, hd_clocked_sentenc
 
 int hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out)
 {
-    if (!c) return fail(HD_ERR_INVALID, kNullClocked);
-    if (stream >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+    if (const int rc = check_object(c, stream)) return rc;
     if (!out) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
@@ -510,15 +558,9 @@ int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
     if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
-    uint32_t g[4][hd::kClockedGuard];
     const uint32_t* at[4] = {c->ring + (size_t)stream * c->ring_stride, c->ring + (size_t)(stream + 1) * c->ring_stride - hd::kClockedGuard,
                              c->rec + (size_t)stream * c->rec_stride, c->rec + (size_t)(stream + 1) * c->rec_stride - hd::kClockedGuard};
-    int bad = 0;
-    for (int i = 0; i < 4; ++i) {
-        HD_HIP(hipMemcpy(g[i], at[i], sizeof g[i], hipMemcpyDeviceToHost));
-        for (uint32_t w : g[i]) bad += w != hd::kClockedGuardWord;
-    }
-    return bad;
+    return damaged_guards(at, hd::kClockedGuard, hd::kClockedGuardWord);
 }
 
 }  // extern "C"
@@ -526,6 +568,7 @@ int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
 /* ---------------------------------------------------------------- tone-filter demodulator (kernels/tones.hip) -------------------------- */
 
 struct hd_tones {
+    static constexpr const char* kNull = "null tones object";
     hd_engine* e = nullptr;
     hd_tones_params prm{};
     uint32_t S = 0;
@@ -551,39 +594,23 @@ struct hd_tones {
 
 namespace {
 
-const char kNullTones[] = "null tones object";
-
-// src[s].p and n_total are written: a stream without a modem is passed by; one launch per HD_TONES_CHUNK samples of the longest row, each waited for.
+// Its own: a stream without a modem is passed by, in front of the max_push test; the rows' lengths are kept for hd_tones_rows; per chunk, `cap`, the
+// longest part of a row in the launch, which sizes its LDS.
 int tones_launch(hd_tones* t, uint32_t max_n)
 {
-    hipStream_t q = t->e->qa;
-    max_n = 0;
-    for (uint32_t s = 0; s < t->S; ++s) {
-        hd::TonesSrc& d = t->src.p[s];
-        if (!t->modem[s].F) d.n_total = 0;
-        if (d.n_total > t->prm.max_push)
-            return fail(HD_ERR_CAPACITY, "hd_tones: a push of " + std::to_string(d.n_total) + " samples, max_push is " + std::to_string(t->prm.max_push));
-        max_n = std::max(max_n, d.n_total);
-    }
+    if (const int rc = check_max_push(t, "hd_tones", &max_n, [t](uint32_t s) { if (!t->modem[s].F) t->src.p[s].n_total = 0; })) return rc;
     for (uint32_t s = 0; s < t->S; ++s) t->row_n[s] = t->src.p[s].n_total;
-    if (t->t0) HD_HIP(hipEventRecord(t->t0, q));
-    for (uint32_t off = 0; off < max_n; off += HD_TONES_CHUNK) {
-        uint32_t cap = 0;
-        for (uint32_t s = 0; s < t->S; ++s) {
-            hd::TonesSrc& d = t->src.p[s];
-            d.off = off;
-            d.n = d.n_total > off ? std::min<uint32_t>(HD_TONES_CHUNK, d.n_total - off) : 0u;
-            cap = std::max(cap, d.n);
-        }
-        std::atomic_thread_fence(std::memory_order_release);
-        if (!hd::launch_tones(q, t->S, cap, t->src.dev, t->st, t->ring32, t->ring32_stride, t->ring64, t->ring64_stride, t->ctab, t->rows, t->row_stride,
-                              t->prm.max_push))
-            return fail(HD_ERR_DEVICE, "tones: the launch's chunk does not fit the LDS");
-        HD_HIP(hipGetLastError());
-        if (t->t1 && off + HD_TONES_CHUNK >= max_n) HD_HIP(hipEventRecord(t->t1, q));
-        HD_HIP(hipStreamSynchronize(q));
-    }
-    return HD_OK;
+    uint32_t cap = 0;
+    return launch_chunks(
+        t, max_n, HD_TONES_CHUNK, "tones: the launch's chunk does not fit the LDS",
+        [&](uint32_t, const hd::TonesSrc& d) { cap = std::max(cap, d.n); },
+        [&] {
+            const uint32_t longest = cap;
+            cap = 0;
+            return hd::launch_tones(t->e->qa, t->S, longest, t->src.dev, t->st, t->ring32, t->ring32_stride, t->ring64, t->ring64_stride, t->ctab, t->rows,
+                                    t->row_stride, t->prm.max_push);
+        },
+        [] {});
 }
 
 // (The rings need no clearing: nothing in front of a stream's index 0 is read.)
@@ -593,13 +620,6 @@ int tones_clear(hd_tones* t, uint32_t s0, uint32_t ns)
     HD_HIP(hipMemcpyAsync(t->st + s0, t->modem.data() + s0, (size_t)ns * sizeof(hd::TonesState), hipMemcpyHostToDevice, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t s = s0; s < s0 + ns; ++s) t->row_n[s] = 0;
-    return HD_OK;
-}
-
-int tones_check(hd_tones* t, uint32_t stream)
-{
-    if (!t) return fail(HD_ERR_INVALID, kNullTones);
-    if (stream >= t->S) return fail(HD_ERR_INVALID, "stream index out of range");
     return HD_OK;
 }
 
@@ -651,18 +671,11 @@ int hd_tones_create(hd_engine* e, const hd_tones_params* params, hd_tones** out)
 
 void hd_tones_destroy(hd_tones* t) { destroy(t); }
 
-int hd_tones_reset(hd_tones* t, uint32_t stream)
-{
-    if (!t) return fail(HD_ERR_INVALID, kNullTones);
-    if (stream != UINT32_MAX && stream >= t->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
-    if (const int rc = enter(t->e)) return rc;
-    return stream == UINT32_MAX ? tones_clear(t, 0, t->S) : tones_clear(t, stream, 1);
-}
+int hd_tones_reset(hd_tones* t, uint32_t stream) { return reset(t, stream, tones_clear); }
 
 int hd_tones_set_modem(hd_tones* t, uint32_t stream, double baud, double f_hi_hz, double f_lo_hz)
 {
-    if (const int rc = tones_check(t, stream)) return rc;
+    if (const int rc = check_object(t, stream)) return rc;
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     hd::TonesState m;
     const int rc = hd::tones_modem(m, t->e->fsd, baud == 0 ? t->baud[stream] : baud, f_hi_hz, f_lo_hz, t->prm.window_q8);
@@ -675,7 +688,7 @@ int hd_tones_set_modem(hd_tones* t, uint32_t stream, double baud, double f_hi_hz
 
 int hd_tones_set_modem_from_afc(hd_tones* t, uint32_t stream, double baud)
 {
-    if (const int rc = tones_check(t, stream)) return rc;
+    if (const int rc = check_object(t, stream)) return rc;
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     hd_afc_info a;
     if (const int rc = hd_stream_afc(t->e, stream, &a)) return rc;
@@ -684,24 +697,21 @@ int hd_tones_set_modem_from_afc(hd_tones* t, uint32_t stream, double baud)
     return hd_tones_set_modem(t, stream, baud, (a.peak_right - 2048) * bin, (a.peak_left - 2048) * bin);
 }
 
-int hd_tones_push_engine(hd_tones* t)
-{
-    return push_engine(t, kNullTones, "hd_tones_push_engine", [t](uint32_t max_n) { return tones_launch(t, max_n); });
-}
+int hd_tones_push_engine(hd_tones* t) { return push_engine(t, "hd_tones_push_engine", tones_launch); }
 
 int hd_tones_push_device(hd_tones* t, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(t, kNullTones, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, [t](uint32_t max_n) { return tones_launch(t, max_n); });
+    return push_rows(t, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, tones_launch);
 }
 
 int hd_tones_push_host(hd_tones* t, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(t, kNullTones, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, [t](uint32_t max_n) { return tones_launch(t, max_n); });
+    return push_rows(t, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, tones_launch);
 }
 
 int hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
 {
-    if (!t) return fail(HD_ERR_INVALID, kNullTones);
+    if (!t) return fail(HD_ERR_INVALID, hd_tones::kNull);
     if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     *d_rows = t->rows + hd::kTonesGuard;
@@ -712,7 +722,7 @@ int hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n
 
 int hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap)
 {
-    if (const int rc = tones_check(t, stream)) return rc;
+    if (const int rc = check_object(t, stream)) return rc;
     if (cap && !out) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     if (const int rc = enter(t->e)) return rc;
@@ -723,7 +733,7 @@ int hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap)
 
 int hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out)
 {
-    if (const int rc = tones_check(t, stream)) return rc;
+    if (const int rc = check_object(t, stream)) return rc;
     if (!out) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     if (const int rc = enter(t->e)) return rc;
@@ -750,13 +760,7 @@ int hd_debug_tones_guards(hd_tones* t, uint32_t stream)
     }
     at[8] = r64 + (size_t)stream * t->ring64_stride * 2; at[9] = at[8] + t->ring64_stride * 2 - hd::kTonesGuard;
     at[10] = row + (size_t)stream * t->row_stride; at[11] = at[10] + t->row_stride - hd::kTonesGuard;
-    int bad = 0;
-    for (const uint32_t* p : at) {
-        uint32_t g[hd::kTonesGuard];
-        HD_HIP(hipMemcpy(g, p, sizeof g, hipMemcpyDeviceToHost));
-        for (uint32_t w : g) bad += w != hd::kTonesGuardWord;
-    }
-    return bad;
+    return damaged_guards(at, hd::kTonesGuard, hd::kTonesGuardWord);
 }
 
 }  // extern "C"
@@ -764,6 +768,7 @@ int hd_debug_tones_guards(hd_tones* t, uint32_t stream)
 /* ---------------------------------------------------------------- tone search (kernels/tone_search.hip) -------------------------------- */
 
 struct hd_tone_search {
+    static constexpr const char* kNull = "null tone search";
     hd_engine* e = nullptr;
     hd_tone_search_params prm{};
     uint32_t S = 0;
@@ -789,44 +794,31 @@ struct hd_tone_search {
 
 namespace {
 
-const char kNullToneSearch[] = "null tone search";
-
-// src[s].p and n_total are written: one launch per HD_TONE_SEARCH_CHUNK samples of the longest row, each waited for; the streams' counts move on behind
-// every launch.  A row above max_push refuses the whole push before anything is launched.
+// Its own per chunk: the stream's carry, the segments the chunk completes and which carry buffer is read go into the descriptor, and the streams' counts
+// move on behind every launch's wait.  (The kernel's LDS is static: its launch always fits.)
 int tone_search_launch(hd_tone_search* ts, uint32_t max_n)
 {
-    hipStream_t q = ts->e->qa;
-    max_n = 0;
-    for (uint32_t s = 0; s < ts->S; ++s) {
-        const uint32_t n = ts->src.p[s].n_total;
-        if (n > ts->prm.max_push)
-            return fail(HD_ERR_CAPACITY, "hd_tone_search: a push of " + std::to_string(n) + " samples, max_push is " + std::to_string(ts->prm.max_push));
-        max_n = std::max(max_n, n);
-    }
-    if (ts->t0) HD_HIP(hipEventRecord(ts->t0, q));
-    for (uint32_t off = 0; off < max_n; off += HD_TONE_SEARCH_CHUNK) {
-        for (uint32_t s = 0; s < ts->S; ++s) {
-            hd::ToneSearchSrc& d = ts->src.p[s];
-            d.off = off;
-            d.n = d.n_total > off ? std::min<uint32_t>(HD_TONE_SEARCH_CHUNK, d.n_total - off) : 0u;
+    if (const int rc = check_max_push(ts, "hd_tone_search", &max_n, [](uint32_t) {})) return rc;
+    return launch_chunks(
+        ts, max_n, HD_TONE_SEARCH_CHUNK, "",
+        [&](uint32_t s, hd::ToneSearchSrc& d) {
             d.carry = ts->carry_n[s];
             d.segs = hd::tone_search_segments(d.carry, d.n);
             d.flip = ts->flip[s];
-        }
-        std::atomic_thread_fence(std::memory_order_release);
-        hd::launch_tone_search(q, ts->S, ts->src.dev, ts->win, ts->tw, ts->acc, ts->acc_stride, ts->carry, ts->carry_stride);
-        HD_HIP(hipGetLastError());
-        if (ts->t1 && off + HD_TONE_SEARCH_CHUNK >= max_n) HD_HIP(hipEventRecord(ts->t1, q));
-        HD_HIP(hipStreamSynchronize(q));
-        for (uint32_t s = 0; s < ts->S; ++s) {
-            const hd::ToneSearchSrc& d = ts->src.p[s];
-            ts->samples[s] += d.n;
-            ts->segments[s] += d.segs;
-            ts->carry_n[s] = d.carry + d.n - d.segs * hd::kToneSearchStep;
-            if (d.segs) ts->flip[s] ^= 1u;
-        }
-    }
-    return HD_OK;
+        },
+        [&] {
+            hd::launch_tone_search(ts->e->qa, ts->S, ts->src.dev, ts->win, ts->tw, ts->acc, ts->acc_stride, ts->carry, ts->carry_stride);
+            return true;
+        },
+        [&] {
+            for (uint32_t s = 0; s < ts->S; ++s) {
+                const hd::ToneSearchSrc& d = ts->src.p[s];
+                ts->samples[s] += d.n;
+                ts->segments[s] += d.segs;
+                ts->carry_n[s] = d.carry + d.n - d.segs * hd::kToneSearchStep;
+                if (d.segs) ts->flip[s] ^= 1u;
+            }
+        });
 }
 
 // (The carry buffers need no clearing: nothing behind a stream's carry length is read.)
@@ -837,13 +829,6 @@ int tone_search_clear(hd_tone_search* ts, uint32_t s0, uint32_t ns)
                             (size_t)hd::kToneSearchSeg * sizeof(double), ns, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t s = s0; s < s0 + ns; ++s) { ts->samples[s] = ts->segments[s] = 0; ts->carry_n[s] = ts->flip[s] = 0; }
-    return HD_OK;
-}
-
-int tone_search_check(hd_tone_search* ts, uint32_t stream)
-{
-    if (!ts) return fail(HD_ERR_INVALID, kNullToneSearch);
-    if (stream >= ts->S) return fail(HD_ERR_INVALID, "stream index out of range");
     return HD_OK;
 }
 
@@ -895,35 +880,23 @@ int hd_tone_search_create(hd_engine* e, const hd_tone_search_params* params, hd_
 
 void hd_tone_search_destroy(hd_tone_search* ts) { destroy(ts); }
 
-int hd_tone_search_reset(hd_tone_search* ts, uint32_t stream)
-{
-    if (!ts) return fail(HD_ERR_INVALID, kNullToneSearch);
-    if (stream != UINT32_MAX && stream >= ts->S) return fail(HD_ERR_INVALID, "stream index out of range");
-    std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
-    if (const int rc = enter(ts->e)) return rc;
-    return stream == UINT32_MAX ? tone_search_clear(ts, 0, ts->S) : tone_search_clear(ts, stream, 1);
-}
+int hd_tone_search_reset(hd_tone_search* ts, uint32_t stream) { return reset(ts, stream, tone_search_clear); }
 
-int hd_tone_search_push_engine(hd_tone_search* ts)
-{
-    return push_engine(ts, kNullToneSearch, "hd_tone_search_push_engine", [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
-}
+int hd_tone_search_push_engine(hd_tone_search* ts) { return push_engine(ts, "hd_tone_search_push_engine", tone_search_launch); }
 
 int hd_tone_search_push_device(hd_tone_search* ts, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(ts, kNullToneSearch, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true,
-                     [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
+    return push_rows(ts, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, tone_search_launch);
 }
 
 int hd_tone_search_push_host(hd_tone_search* ts, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
 {
-    return push_rows(ts, kNullToneSearch, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false,
-                     [ts](uint32_t max_n) { return tone_search_launch(ts, max_n); });
+    return push_rows(ts, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, tone_search_launch);
 }
 
 int hd_tone_search_power(hd_tone_search* ts, uint32_t stream, double* p, size_t cap, uint64_t* segments)
 {
-    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (const int rc = check_object(ts, stream)) return rc;
     if (!p) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
     if (const int rc = enter(ts->e)) return rc;
@@ -939,7 +912,7 @@ int hd_tone_search_power(hd_tone_search* ts, uint32_t stream, double* p, size_t 
 
 int hd_tone_search_stats(hd_tone_search* ts, uint32_t stream, hd_tone_search_info* out)
 {
-    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (const int rc = check_object(ts, stream)) return rc;
     if (!out) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
     *out = hd_tone_search_info{ts->samples[stream], ts->segments[stream], ts->carry_n[stream], 0u};
@@ -948,7 +921,7 @@ int hd_tone_search_stats(hd_tone_search* ts, uint32_t stream, hd_tone_search_inf
 
 int hd_tone_search_detect(hd_tone_search* ts, uint32_t stream, const hd_tone_search_detect_params* p, hd_tone_search_result* out)
 {
-    if (const int rc = tone_search_check(ts, stream)) return rc;
+    if (const int rc = check_object(ts, stream)) return rc;
     if (!p || !out) return fail(HD_ERR_INVALID, "null argument");
     std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
     std::vector<double> pw(hd::kToneSearchSeg);
@@ -978,13 +951,7 @@ int hd_debug_tone_search_guards(hd_tone_search* ts, uint32_t stream)
         at[2 + 2 * k] = c32 + ((size_t)stream * 2 + k) * ts->carry_stride * 2;
         at[3 + 2 * k] = at[2 + 2 * k] + ts->carry_stride * 2 - hd::kToneSearchGuard;
     }
-    int bad = 0;
-    for (const uint32_t* p : at) {
-        uint32_t g[hd::kToneSearchGuard];
-        HD_HIP(hipMemcpy(g, p, sizeof g, hipMemcpyDeviceToHost));
-        for (uint32_t w : g) bad += w != hd::kToneSearchGuardWord;
-    }
-    return bad;
+    return damaged_guards(at, hd::kToneSearchGuard, hd::kToneSearchGuardWord);
 }
 
 }  // extern "C"

@@ -12,17 +12,13 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "wave_util.h"
 
 namespace hd {
 
 namespace {
 
 __device__ __forceinline__ uint64_t low_mask(uint32_t x) { return x >= 64u ? ~0ull : (1ull << x) - 1ull; }      // bits [0, x)
-__device__ __forceinline__ uint64_t uniform64(uint64_t v)
-{
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 // the lanes of a wave exchange data through its own LDS rows: LDS operations of one wave execute in order, the compiler must keep them in order too
 __device__ __forceinline__ void wave_lds_sync()
 {
@@ -68,15 +64,15 @@ __global__ __launch_bounds__(1024) void k_baud_probe(const ProbeSrc* __restrict_
     // c - 8 .. c - 9 + j.
     __shared__ uint64_t hw_all[16][16];
     __shared__ uint32_t cw_all[16][16];
-    const uint32_t s = blockIdx.x, t = threadIdx.x, l = t & 63u, wave = uniform32(t >> 6);
+    const uint32_t s = blockIdx.x, t = threadIdx.x, l = t & 63u, wave = uni32(t >> 6);
     const ProbeSrc d = src[s];
-    const uint32_t n = uniform32(d.n);
+    const uint32_t n = uni32(d.n);
     if (!n) return;                                                  // (the whole workgroup: nothing of this stream changes)
     hd_baud_probe_stream_state* H = hdr + s;
     uint64_t* hw = hw_all[wave];
     uint32_t* cw = cw_all[wave];
     C[t] = ctab[t];
-    const uint64_t i0 = uniform64(H->samples);
+    const uint64_t i0 = uni64(H->samples);
     uint32_t first = 0;
     if (d.ring_mask) first = (d.sym->base + d.sym->held - n) & d.ring_mask;      // the ring's append position is base + held: the call's output ends there
 
@@ -89,16 +85,16 @@ __global__ __launch_bounds__(1024) void k_baud_probe(const ProbeSrc* __restrict_
     c.n = a32[3 * HD_PROBE_CANDIDATES + t]; c.cur = a32[4 * HD_PROBE_CANDIDATES + t];
     const uint32_t F = Ftab[t], my_scale = scale_tab[t];
     // the scales this wave computes: those of its candidates (a run: the table descends), and scale `wave` for the stream's header
-    const uint32_t sc_hi = uniform32(my_scale), sc_lo = (uint32_t)__builtin_amdgcn_readlane((int)my_scale, 63);
+    const uint32_t sc_hi = uni32(my_scale), sc_lo = (uint32_t)__builtin_amdgcn_readlane((int)my_scale, 63);
     uint32_t need = (2u << sc_hi) - (1u << sc_lo);
     if (wave < HD_PROBE_SCALES) need |= 1u << wave;
 
     // ---- the stream's state: words c0 - 8 .. c0 - 1 of the history (the first of them shares its place in the state with word c0 itself)
     const uint32_t c0 = (uint32_t)(i0 >> 6);
     if (l < 8u) hw[(c0 - 8u + l) & 15u] = H->history[(c0 + l) & 7u];
-    const uint64_t seed = uniform64(H->history[c0 & 7u]) & low_mask((uint32_t)i0 & 63u);      // the samples of word c0 that earlier pushes brought
+    const uint64_t seed = uni64(H->history[c0 & 7u]) & low_mask((uint32_t)i0 & 63u);      // the samples of word c0 that earlier pushes brought
     uint32_t m_prev = 0, hdr_edges = 0;       // m_W[i-1] of scale k in bit k; the edges of scale `wave`, which this wave counts for the header
-    for (uint32_t k = 0; k < HD_PROBE_SCALES; ++k) m_prev |= (uniform32(H->majority[k]) & 1u) << k;
+    for (uint32_t k = 0; k < HD_PROBE_SCALES; ++k) m_prev |= (uni32(H->majority[k]) & 1u) << k;
     __syncthreads();                                                 // the table is in LDS, and every wave has read the header that some will write
 
     const uint32_t n_steps = (((uint32_t)i0 & 63u) + n + 63u) >> 6;

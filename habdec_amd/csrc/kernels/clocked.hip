@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "wave_util.h"
 
 namespace hd {
 
@@ -19,9 +20,8 @@ namespace {
 
 constexpr uint32_t kRingMask = HD_CLOCKED_RING - 1u;
 
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
-
+// (Not to be merged with tones.hip's quantise, another range and scale: each is held to its host restatement -- clocked_quantise, tones_quantise --
+// precisely because kernel and restatement are written separately.)
 __device__ __forceinline__ int32_t quantise(float v, uint32_t invert)
 {
     if (v != v) return 0;
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void k_clocked(const ClockedSrc* __restrict__ s
             const uint32_t j = b + l;
             int32_t q = 0;
             if (j < m) q = quantise(d.ring_mask ? d.p[(first + j) & d.ring_mask] : d.p[first + j], invert);
-            uint32_t sum = (uint32_t)q;                              // inclusive scan over the wave
+            uint32_t sum = (uint32_t)q;                              // inclusive scan over the wave (wave_util.h's wave_scan, written out: see there)
             for (uint32_t o = 1; o < 64u; o <<= 1) {
                 const uint32_t up = (uint32_t)__shfl_up((int)sum, o, 64);
                 if (l >= o) sum += up;

@@ -185,6 +185,8 @@ constexpr uint32_t kSpecWaveLds = 64 * 65 * 4;                      // the trans
 // spectrum_wave_body's twiddle schedule (finish4096): rows per group, rows in front of pass 1, groups of look-ahead.  32 rows wait behind pass 1, the
 // other 32 go out in front of the first products: 96 registers of factors at the most beside the 128 of a[] (k_step_cu<174,4,139>: 249 of 256)
 constexpr int kTwG = 16, kTwH = 32, kTwD = 2;
+// One wave per SIMD (k_survey, k_tone_search): nothing else hides a load, the register file has the room.  (Today's numbers match; the reasons do not.)
+constexpr int kTwSoloG = 16, kTwSoloH = 32, kTwSoloD = 2;
 
 // x: the stream's 4096 input samples (wave-uniform pointer) -- its row of the spectrum input collection, or, where one call's chunk alone fills the
 // buffer, the head of that chunk where the last decimation stage left it (StreamCall::fft_run == 2: no second copy of the samples)

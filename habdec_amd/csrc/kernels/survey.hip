@@ -18,9 +18,6 @@ namespace hd {
 
 static_assert(kSurveyBins == (uint32_t)kFftBins, "the survey uses the engine's 4096-point transform and twiddles");
 
-// k_survey's own twiddle schedule (finish4096): with one wave per SIMD nothing else hides a load, and the register file has the room
-constexpr int kSvTwG = 16, kSvTwH = 32, kSvTwD = 2;
-
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_survey(const float2* __restrict__ x, const float* __restrict__ win,
                                                                                           const float2* __restrict__ tw64, float* __restrict__ partial,
                                                                                           const uint64_t seg0, const uint64_t n_seg, const uint32_t run_len)
@@ -52,9 +49,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             for (int u = 0; u < 16; ++u) a[g + u] = (f32x2){a[g + u].x * wv[u], a[g + u].y * wv[u]};
         }
         f32x2 w[64];
-        specwave::load_tw(w, tw64, 0, kSvTwH, l);                    // (the first twiddle rows, in front of pass 1)
+        specwave::load_tw(w, tw64, 0, kTwSoloH, l);                    // (the first twiddle rows, in front of pass 1)
         specwave::fft64(a);
-        specwave::finish4096<kSvTwG, kSvTwH, kSvTwD>(a, w, tw64, plane, l);                // twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
+        specwave::finish4096<kTwSoloG, kTwSoloH, kTwSoloD>(a, w, tw64, plane, l);                // twiddle, transpose, pass 2: a[xpos(k2)] = X[l + 64 k2]
 #pragma unroll
         for (int i = 0; i < 64; ++i) acc[i] = acc[i] + (a[i].x * a[i].x + a[i].y * a[i].y);
     }

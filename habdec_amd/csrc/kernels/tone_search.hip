@@ -16,6 +16,7 @@
 
 #include "spectrum_wave.h"
 #include "tone_search.h"
+#include "wave_util.h"
 
 namespace hd {
 
@@ -23,10 +24,6 @@ static_assert(kToneSearchSeg == (uint32_t)kFftBins, "the tone search uses the en
 
 namespace {
 
-// k_survey's twiddle schedule (finish4096): one wave per SIMD, the register file has the room
-constexpr int kTsTwG = 16, kTsTwH = 32, kTsTwD = 2;
-
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 typedef __attribute__((address_space(1))) double* gdouble_t;
 typedef const __attribute__((address_space(1))) float* gfloat_t;
 
@@ -62,7 +59,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
         const float* winj = win;
         double* accj = acc;
         asm volatile("" : "+s"(winj), "+s"(accj));
-        const gfloat_t win1 = (gfloat_t)winj;                       // (device memory: said so behind the opaque base, or the loads would be flat ones)
+        // (device memory: said so behind the opaque base, or the loads would be flat ones.  k_survey reads the table through its kernel
+        // argument, whose address space the compiler knows: the window loop below is k_survey's but for this pointer type, so the two stay apart.)
+        const gfloat_t win1 = (gfloat_t)winj;
         f32x2 a[64];
         // ---- pass 1 input: lane n2 = l takes x[64 n1 + l] w[64 n1 + l], x from the carry or the row; all 64 loads go out before the first product
         // (eight at a time: the scheduler would otherwise form all 64 compare masks first, more scalar registers than a wave has)
@@ -84,9 +83,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
             for (int u = 0; u < 16; ++u) a[g + u] = (f32x2){a[g + u].x * wv[u], a[g + u].y * wv[u]};
         }
         f32x2 w[64];
-        specwave::load_tw(w, tw64, 0, kTsTwH, l);
+        specwave::load_tw(w, tw64, 0, kTwSoloH, l);
         specwave::fft64(a);
-        specwave::finish4096<kTsTwG, kTsTwH, kTsTwD>(a, w, tw64, plane, l);                // a[xpos(k2)] = X[l + 64 k2]
+        specwave::finish4096<kTwSoloG, kTwSoloH, kTwSoloD>(a, w, tw64, plane, l);                // a[xpos(k2)] = X[l + 64 k2]
         // ---- half swap and accumulation: bin k = l + 64 k2 lands at i = (k + 2048) & 4095 = l + 64 jj, jj = (k2 + 32) & 63.  Every lane owns its 64 sums:
         // the next segment's loads of them follow this one's stores in the same lane.
 #pragma unroll

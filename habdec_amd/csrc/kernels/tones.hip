@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "launch.h"
+#include "wave_util.h"
 
 namespace hd {
 
@@ -22,31 +23,11 @@ constexpr uint32_t kThreads = 256, kWaves = kThreads / 64;
 __host__ __device__ __forceinline__ uint32_t lds_cap1(uint32_t cap) { return (cap + 1u + 3u) & ~3u; }
 __host__ __device__ __forceinline__ uint32_t lds_bytes(uint32_t cap) { return lds_cap1(cap) * 24u + 1024u * 4u + 4u * kWaves * 4u + kWaves * 8u; }
 
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
-
+// (its own range and scale, restated by the host's tones_quantise: not to be merged with clocked.hip's, see there)
 __device__ __forceinline__ int32_t quantise(float v)
 {
     if (v != v) return 0;
     return (int32_t)(fminf(fmaxf(v, -8.0f), 8.0f) * 256.0f);
-}
-
-// inclusive scans over the wave
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane)
-{
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_scan(uint64_t v, uint32_t lane)
-{
-    for (uint32_t o = 1; o < 64u; o <<= 1) {
-        const uint64_t up = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(v >> 32), o, 64) << 32) | (uint32_t)__shfl_up((int)(uint32_t)v, o, 64);
-        if (lane >= o) v += up;
-    }
-    return v;
 }
 
 // floor(sqrt(x)), x < 2^48: the float estimate is a few units off at most, integer comparisons settle it

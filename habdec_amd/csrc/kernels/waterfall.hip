@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kWfThreads) void k_waterfall_detect(const float* __
 #pragma unroll
                 for (int u = 0; u < 4; ++u) c[u] = hist[0][4 * l + u] + hist[1][4 * l + u] + hist[2][4 * l + u] + hist[3][4 * l + u];
                 const uint32_t s = c[0] + c[1] + c[2] + c[3];
-                uint32_t incl = s;
+                uint32_t incl = s;              // (wave_util.h's wave_scan, written out: see there)
 #pragma unroll
                 for (int d = 1; d < 64; d <<= 1) {
                     const uint32_t up = __shfl_up(incl, d, 64);

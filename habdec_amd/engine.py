@@ -31,8 +31,64 @@ class EngineConfig:
     device: int = 0
 
 
-class Engine:
+class _Handle:
+    """An object of the library behind a handle: L the library, h the handle, _destroy the name of the symbol that frees it."""
+    L = h = _destroy = None
+
+    def close(self):
+        if self.h:
+            getattr(self.L, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _create(self, eng: "Engine", symbol: str, *args):
+        """A side object of an engine: symbol(engine, *args, &handle)."""
+        self.L, self.eng = eng.L, eng
+        h = C.c_void_p()
+        check(getattr(self.L, symbol)(eng.h, *args, C.byref(h)))
+        self.h = h
+
+
+def _params(L, struct, default: str, kw: dict, ints=()):
+    """A parameter struct: the library's defaults (the symbol `default`), then every keyword -- as an int where `ints` names it (True: all), else a float."""
+    p = struct()
+    getattr(L, default)(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, int(v) if ints is True or k in ints else float(v))
+    return p
+
+
+def _with_cap(call, cap: int, struct, convert):
+    """call(out, cap, byref(found)) fills at most cap of `struct` and reports how many there are: again with that capacity where it was more."""
+    while True:
+        out, found = (struct * max(cap, 1))(), C.c_uint32(0)
+        call(out, cap, C.byref(found))
+        if found.value <= cap:
+            return convert(out, found.value)
+        cap = found.value
+
+
+def _power(fn, *h, host: str | None = None):
+    """(float64[4096], segments) from one of the power getters; any other answer than 4096 bins raises (host: the name of a function that sets no message)."""
+    p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
+    n = fn(*h, p.ctypes.data, p.size, C.byref(seg))
+    if n != 4096 and host:
+        raise HabdecError(f"habdec_amd error {n}: {host}")
+    if n != 4096:
+        check(n if n < 0 else -1)
+    return p, int(seg.value)
+
+
+class Engine(_Handle):
+    _destroy = "hd_engine_destroy"
+
     def __init__(self, cfg: EngineConfig | None = None, **kw):
+        self._cbs, self._owned, self._pinned = [], [], []
         cfg = cfg or EngineConfig(**kw)
         self.cfg = cfg
         L = lib()
@@ -48,24 +104,20 @@ class Engine:
         check(L.hd_engine_create(C.byref(c), C.byref(h)))
         self.h, self.L = h, L
         self.S = cfg.n_streams
-        self._cbs = []
 
     def close(self):
-        for sv in getattr(self, "_surveys", []) + getattr(self, "_probes", []):       # (a survey or a probe uses its engine's device and mutex: it goes first)
-            sv.close()
-        self._surveys, self._probes = [], []
-        if getattr(self, "h", None):
-            self.L.hd_engine_destroy(self.h)
-            self.h = None
-        for p in getattr(self, "_pinned", []):
+        for o in self._owned:       # (a side object uses its engine's device and mutex: it goes first)
+            o.close()
+        self._owned = []
+        super().close()
+        for p in self._pinned:
             self.L.hd_pinned_free(p)
         self._pinned = []
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _own(self, obj):
+        """A side object made by one of the factories below: closed with the engine, in front of it."""
+        self._owned.append(obj)
+        return obj
 
     # ---- data path
     def process_host(self, iq: np.ndarray, n: int | None = None, fmt=None):
@@ -100,7 +152,7 @@ class Engine:
             raise HabdecError("hd_pinned_alloc failed")
         buf = (C.c_char * n).from_address(p)
         arr = np.frombuffer(buf, dtype=dtype).reshape(shape)
-        self._pinned = getattr(self, "_pinned", []) + [p]
+        self._pinned.append(p)
         return arr
 
     def process_device(self, dev_ptr: int, stride: int, n: int, fmt=None):
@@ -112,7 +164,6 @@ class Engine:
 
     def ingest(self, files: "IqFiles", max_rounds: int = 1 << 62) -> int:
         """Pump a batch of IQ files (one per stream; cf32, or packed when opened with fmt=) through the engine (hd_ingest_run); returns the samples consumed."""
-        import ctypes as C
         done = C.c_uint64(0)
         check(self.L.hd_ingest_run(self.h, files.h, max_rounds, C.byref(done)))
         return int(done.value)
@@ -229,39 +280,27 @@ class Engine:
 
     def survey(self) -> "Survey":
         """A wideband survey on this engine's GPU and sampling rate (hd_survey_*): close it before the engine."""
-        sv = Survey(self)
-        self._surveys = getattr(self, "_surveys", []) + [sv]
-        return sv
+        return self._own(Survey(self))
 
     def waterfall(self, **params) -> "Waterfall":
         """A waterfall on this engine's GPU and sampling rate (hd_waterfall_*; params as hd_waterfall_params): close it before the engine."""
-        wf = Waterfall(self, **params)
-        self._surveys = getattr(self, "_surveys", []) + [wf]
-        return wf
+        return self._own(Waterfall(self, **params))
 
     def baud_probe(self, **params) -> "BaudProbe":
         """A baud-rate probe on this engine's streams (hd_baud_probe_*; params as hd_baud_probe_params): close it before the engine."""
-        p = BaudProbe(self, **params)
-        self._probes = getattr(self, "_probes", []) + [p]
-        return p
+        return self._own(BaudProbe(self, **params))
 
     def clocked(self, **params) -> "Clocked":
         """A clocked decoder on this engine's streams (hd_clocked_*; params as hd_clocked_params): close it before the engine."""
-        c = Clocked(self, **params)
-        self._probes = getattr(self, "_probes", []) + [c]
-        return c
+        return self._own(Clocked(self, **params))
 
     def tones(self, **params) -> "Tones":
         """A tone-filter demodulator on this engine's streams (hd_tones_*; params as hd_tones_params): close it before the engine."""
-        t = Tones(self, **params)
-        self._probes = getattr(self, "_probes", []) + [t]
-        return t
+        return self._own(Tones(self, **params))
 
     def tone_search(self, **params) -> "ToneSearch":
         """A tone search on this engine's streams (hd_tone_search_*; params as hd_tone_search_params): close it before the engine."""
-        t = ToneSearch(self, **params)
-        self._probes = getattr(self, "_probes", []) + [t]
-        return t
+        return self._own(ToneSearch(self, **params))
 
     def set_format_trial(self, s, on=True):
         """Tee the bits delivered for stream s into a framing trial (hd_stream_set_format_trial); turning it on resets it."""
@@ -291,57 +330,65 @@ def _probe_state(h, cand) -> dict:
     return out
 
 
-class _ProbeRows:
-    """rows: float32 [S, stride] (or [n] for one stream); n_per_stream: None = every row whole."""
-
-    @staticmethod
-    def args(rows, S, n_per_stream):
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
-        if rows.ndim == 1:
-            rows = rows[None, :]
-        assert rows.shape[0] == S, rows.shape
-        n = np.full(S, rows.shape[1], np.uint32) if n_per_stream is None else np.ascontiguousarray(n_per_stream, dtype=np.uint32)
-        assert n.shape == (S,) and (S == 1 or int(n.max(initial=0)) <= rows.shape[1])
-        return rows, n
+def _rows(rows, S, n_per_stream, dtype):
+    """rows: dtype [S, stride] (or [n] for one stream); n_per_stream: None = every row whole."""
+    rows = np.ascontiguousarray(rows, dtype=dtype)
+    if rows.ndim == 1:
+        rows = rows[None, :]
+    assert rows.shape[0] == S, rows.shape
+    n = np.full(S, rows.shape[1], np.uint32) if n_per_stream is None else np.ascontiguousarray(n_per_stream, dtype=np.uint32)
+    assert n.shape == (S,) and (S == 1 or int(n.max(initial=0)) <= rows.shape[1])
+    return rows, n
 
 
-class BaudProbe:
-    """Baud-rate probe of an engine's streams (hd_baud_probe_*, include/habdec_amd.h): push discriminator output, read an estimate."""
+class _RowObject(_Handle):
+    """What BaudProbe, Clocked, Tones and ToneSearch share: made from an engine and a parameter struct, one row per stream through three doors, reset.
+    _prefix names the symbols (hd_clocked -> hd_clocked_create, hd_clocked_params, ...); _ints: the parameters that are integers (_params).  The rows
+    are float32 discriminator output here and complex64 decimated IQ in _IqRowObject."""
+    _prefix, _ints, _dtype = None, (), np.float32
+    _destroy = property(lambda self: self._prefix + "_destroy")
 
     def __init__(self, eng: Engine, **params):
-        self.L, self.eng, self.S = eng.L, eng, eng.S
-        p = capi.hd_baud_probe_params()
-        self.L.hd_baud_probe_params_default(C.byref(p))
-        for k, v in params.items():
-            setattr(p, k, float(v))
-        h = C.c_void_p()
-        check(self.L.hd_baud_probe_create(eng.h, C.byref(p), C.byref(h)))
-        self.h = h
+        self.S = eng.S
+        p = _params(eng.L, getattr(capi, self._prefix + "_params"), self._prefix + "_params_default", params, self._ints)
+        self._create(eng, self._prefix + "_create", C.byref(p))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_baud_probe_destroy(self.h)
-            self.h = None
+    def _fn(self, name):
+        return getattr(self.L, self._prefix + "_" + name)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def reset(self, s=None):
+        check(self._fn("reset")(self.h, 0xFFFFFFFF if s is None else s))
 
     def push_engine(self):
         """Add every stream's discriminator output of the call delivered last (drains the pipeline first, like the data getters)."""
-        check(self.L.hd_baud_probe_push_engine(self.h))
+        check(self._fn("push_engine")(self.h))
 
     def push_host(self, rows, n_per_stream=None):
-        rows, n = _ProbeRows.args(rows, self.S, n_per_stream)
-        check(self.L.hd_baud_probe_push_host(self.h, rows.ctypes.data, rows.shape[1], n.ctypes.data, 0))
+        rows, n = _rows(rows, self.S, n_per_stream, self._dtype)
+        check(self._fn("push_host")(self.h, rows.ctypes.data, rows.shape[1], n.ctypes.data, 0))
 
     def push_device(self, dev_ptr: int, stride: int, n_per_stream):
         """float32 rows at a device address, row s at dev_ptr + 4 * s * stride."""
         n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
         assert n.shape == (self.S,)
-        check(self.L.hd_baud_probe_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+        check(self._fn("push_device")(self.h, dev_ptr, stride, n.ctypes.data, 0))
+
+
+class _IqRowObject(_RowObject):
+    """The cf32 objects: the same doors under the names and docstrings their public surface has (Tones and ToneSearch add their own push_engine text)."""
+    _ints, _dtype = True, np.complex64
+
+    def push_host(self, iq, n_per_stream=None):
+        super().push_host(iq, n_per_stream)
+
+    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
+        """cf32 rows at a device address, row s at dev_ptr + 8 * s * stride."""
+        super().push_device(dev_ptr, stride, n_per_stream)
+
+
+class BaudProbe(_RowObject):
+    """Baud-rate probe of an engine's streams (hd_baud_probe_*, include/habdec_amd.h): push discriminator output, read an estimate."""
+    _prefix = "hd_baud_probe"
 
     def estimate(self, s=0) -> dict:
         e = capi.hd_baud_estimate()
@@ -355,33 +402,17 @@ class BaudProbe:
             check(n if n < 0 else -1)
         return _probe_state(h, cand)
 
-    def reset(self, s=None):
-        check(self.L.hd_baud_probe_reset(self.h, 0xFFFFFFFF if s is None else s))
 
-
-class HostBaudProbe:
+class HostBaudProbe(_Handle):
     """One stream of the probe in plain C++ on the host (hd_host_baud_probe_*): the restatement the kernel is held to, no GPU."""
+    _destroy = "hd_host_baud_probe_free"
 
     def __init__(self, decimated_rate: float, **params):
         self.L = lib()
-        p = capi.hd_baud_probe_params()
-        self.L.hd_baud_probe_params_default(C.byref(p))
-        for k, v in params.items():
-            setattr(p, k, float(v))
+        p = _params(self.L, capi.hd_baud_probe_params, "hd_baud_probe_params_default", params)
         self.h = self.L.hd_host_baud_probe_new(float(decimated_rate), C.byref(p))
         if not self.h:
             raise HabdecError("hd_host_baud_probe_new: 0 < baud_lo < baud_hi <= decimated_rate / 3.5 and min_coherence >= 0")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_baud_probe_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def push(self, d):
         d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
@@ -402,14 +433,6 @@ class HostBaudProbe:
         return _probe_state(h, cand)
 
 
-def _clocked_params(L, params):
-    p = capi.hd_clocked_params()
-    L.hd_clocked_params_default(C.byref(p))
-    for k, v in params.items():
-        setattr(p, k, int(v))
-    return p
-
-
 def _clocked_counters(c) -> dict:
     return {k: int(getattr(c, k)) for k, _ in capi.hd_clocked_counters._fields_}
 
@@ -419,52 +442,17 @@ def _clocked_sentences(a) -> list:
     return [(int(r["pos"]), int(r["flips"]), r["text"].decode("latin-1")) for r in a]
 
 
-class Clocked:
+class Clocked(_RowObject):
     """Clocked soft-decision decoder of an engine's streams (hd_clocked_*, include/habdec_amd.h): push discriminator output, take records and sentences."""
-
-    def __init__(self, eng: Engine, **params):
-        self.L, self.eng, self.S = eng.L, eng, eng.S
-        p = _clocked_params(self.L, params)
-        h = C.c_void_p()
-        check(self.L.hd_clocked_create(eng.h, C.byref(p), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_clocked_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, _ints = "hd_clocked", True
 
     def set_modem(self, s, baud, bits, stops, invert=False):
         """Give stream s its modem (resets the stream)."""
         check(self.L.hd_clocked_set_modem(self.h, s, float(baud), int(bits), int(stops), int(invert)))
 
-    def reset(self, s=None):
-        check(self.L.hd_clocked_reset(self.h, 0xFFFFFFFF if s is None else s))
-
-    def push_engine(self):
-        """Add every stream's discriminator output of the call delivered last (drains the pipeline first, like the data getters)."""
-        check(self.L.hd_clocked_push_engine(self.h))
-
-    def push_host(self, rows, n_per_stream=None):
-        rows, n = _ProbeRows.args(rows, self.S, n_per_stream)
-        check(self.L.hd_clocked_push_host(self.h, rows.ctypes.data, rows.shape[1], n.ctypes.data, 0))
-
-    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
-        """float32 rows at a device address, row s at dev_ptr + 4 * s * stride."""
-        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
-        assert n.shape == (self.S,)
-        check(self.L.hd_clocked_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
-
     def push_tones(self, tones: "Tones"):
         """Add the rows of the tone-filter demodulator's last push (hd_tones_rows), read in place in device memory."""
-        ptr, stride, n = tones.rows()
-        check(self.L.hd_clocked_push_device(self.h, ptr, stride, n.ctypes.data, 0))
+        self.push_device(*tones.rows())
 
     def waiting(self, s=0) -> int:
         n = self.L.hd_clocked_records(self.h, s, None, 0)
@@ -490,28 +478,18 @@ class Clocked:
         return _clocked_counters(c)
 
 
-class HostClocked:
+class HostClocked(_Handle):
     """One stream of the clocked decoder in plain C++ on the host (hd_host_clocked_*): the restatement the kernel is held to, no GPU."""
+    _destroy = "hd_host_clocked_free"
 
     def __init__(self, decimated_rate: float, baud=None, bits=8, stops=2, invert=False, **params):
         self.L = lib()
-        p = _clocked_params(self.L, params)
+        p = _params(self.L, capi.hd_clocked_params, "hd_clocked_params_default", params, True)
         self.h = self.L.hd_host_clocked_new(float(decimated_rate), C.byref(p))
         if not self.h:
             raise HabdecError("hd_host_clocked_new: 16 <= record_cap <= 2^20, repair_bits <= 16, repair_flips <= 4, decimated_rate > 0")
         if baud is not None:
             self.set_modem(baud, bits, stops, invert)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_clocked_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_modem(self, baud, bits, stops, invert=False):
         rc = self.L.hd_host_clocked_set_modem(self.h, float(baud), int(bits), int(stops), int(invert))
@@ -544,50 +522,14 @@ class HostClocked:
         return _clocked_counters(c)
 
 
-def _tones_params(L, params):
-    p = capi.hd_tones_params()
-    L.hd_tones_params_default(C.byref(p))
-    for k, v in params.items():
-        setattr(p, k, int(v))
-    return p
-
-
 def _tones_info(i) -> dict:
     return {k: int(getattr(i, k)) for k, _ in capi.hd_tones_info._fields_}
 
 
-def _iq_rows(iq, S, n_per_stream):
-    """iq: complex64 [S, stride] (or [n] for one stream); n_per_stream: None = every row whole."""
-    iq = np.ascontiguousarray(iq, dtype=np.complex64)
-    if iq.ndim == 1:
-        iq = iq[None, :]
-    assert iq.shape[0] == S, iq.shape
-    n = np.full(S, iq.shape[1], np.uint32) if n_per_stream is None else np.ascontiguousarray(n_per_stream, dtype=np.uint32)
-    assert n.shape == (S,) and (S == 1 or int(n.max(initial=0)) <= iq.shape[1])
-    return iq, n
-
-
-class Tones:
+class Tones(_IqRowObject):
     """Tone-filter demodulator of an engine's streams (hd_tones_*, include/habdec_amd.h): push decimated IQ, get one float row per stream in device memory
     for Clocked.push_tones or BaudProbe.push_device."""
-
-    def __init__(self, eng: Engine, **params):
-        self.L, self.eng, self.S = eng.L, eng, eng.S
-        p = _tones_params(self.L, params)
-        h = C.c_void_p()
-        check(self.L.hd_tones_create(eng.h, C.byref(p), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_tones_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix = "hd_tones"
 
     def set_modem(self, s, baud, f_hi, f_lo):
         """Give stream s its modem (resets the stream); baud 0: the engine stream's."""
@@ -596,22 +538,9 @@ class Tones:
     def set_modem_from_afc(self, s, baud=0.0):
         check(self.L.hd_tones_set_modem_from_afc(self.h, s, float(baud)))
 
-    def reset(self, s=None):
-        check(self.L.hd_tones_reset(self.h, 0xFFFFFFFF if s is None else s))
-
     def push_engine(self):
         """Demodulate every stream's decimated IQ of the call delivered last (drains the pipeline first, like the data getters)."""
-        check(self.L.hd_tones_push_engine(self.h))
-
-    def push_host(self, iq, n_per_stream=None):
-        iq, n = _iq_rows(iq, self.S, n_per_stream)
-        check(self.L.hd_tones_push_host(self.h, iq.ctypes.data, iq.shape[1], n.ctypes.data, 0))
-
-    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
-        """cf32 rows at a device address, row s at dev_ptr + 8 * s * stride."""
-        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
-        assert n.shape == (self.S,)
-        check(self.L.hd_tones_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+        super().push_engine()
 
     def rows(self):
         """(device address of row 0, stride in floats, the rows' lengths) of the last push: valid until the next push or reset."""
@@ -634,28 +563,18 @@ class Tones:
         return _tones_info(i)
 
 
-class HostTones:
+class HostTones(_Handle):
     """One stream of the tone-filter demodulator in plain C++ on the host (hd_host_tones_*): the restatement the kernel is held to, no GPU."""
+    _destroy = "hd_host_tones_free"
 
     def __init__(self, decimated_rate: float, baud=None, f_hi=None, f_lo=None, **params):
         self.L = lib()
-        p = _tones_params(self.L, params)
+        p = _params(self.L, capi.hd_tones_params, "hd_tones_params_default", params, True)
         self.h = self.L.hd_host_tones_new(float(decimated_rate), C.byref(p))
         if not self.h:
             raise HabdecError("hd_host_tones_new: decimated_rate > 0")
         if baud is not None:
             self.set_modem(baud, f_hi, f_lo)
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_tones_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_modem(self, baud, f_hi, f_lo):
         rc = self.L.hd_host_tones_set_modem(self.h, float(baud), float(f_hi), float(f_lo))
@@ -678,11 +597,7 @@ class HostTones:
 
 
 def _tone_search_detect_params(L, params):
-    p = capi.hd_tone_search_detect_params()
-    L.hd_tone_search_detect_params_default(C.byref(p))
-    for k, v in params.items():
-        setattr(p, k, float(v))
-    return p
+    return _params(L, capi.hd_tone_search_detect_params, "hd_tone_search_detect_params_default", params)
 
 
 def _tone_search_result(r) -> dict:
@@ -702,54 +617,17 @@ def tone_search_detect(power: np.ndarray, segments: int, fsd: float, **params) -
     return _tone_search_result(r)
 
 
-class ToneSearch:
+class ToneSearch(_IqRowObject):
     """Long-averaged power spectrum of every stream's decimated IQ and the two-tone detector on top of it (hd_tone_search_*, include/habdec_amd.h)."""
-
-    def __init__(self, eng: Engine, **params):
-        self.L, self.eng, self.S = eng.L, eng, eng.S
-        p = capi.hd_tone_search_params()
-        self.L.hd_tone_search_params_default(C.byref(p))
-        for k, v in params.items():
-            setattr(p, k, int(v))
-        h = C.c_void_p()
-        check(self.L.hd_tone_search_create(eng.h, C.byref(p), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_tone_search_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self, s=None):
-        check(self.L.hd_tone_search_reset(self.h, 0xFFFFFFFF if s is None else s))
+    _prefix = "hd_tone_search"
 
     def push_engine(self):
         """Take every stream's decimated IQ of the call delivered last (drains the pipeline first, like the data getters)."""
-        check(self.L.hd_tone_search_push_engine(self.h))
-
-    def push_host(self, iq, n_per_stream=None):
-        iq, n = _iq_rows(iq, self.S, n_per_stream)
-        check(self.L.hd_tone_search_push_host(self.h, iq.ctypes.data, iq.shape[1], n.ctypes.data, 0))
-
-    def push_device(self, dev_ptr: int, stride: int, n_per_stream):
-        """cf32 rows at a device address, row s at dev_ptr + 8 * s * stride."""
-        n = np.ascontiguousarray(n_per_stream, dtype=np.uint32)
-        assert n.shape == (self.S,)
-        check(self.L.hd_tone_search_push_device(self.h, dev_ptr, stride, n.ctypes.data, 0))
+        super().push_engine()
 
     def power(self, s=0):
         """(float64[4096], segments) of stream s: p[k] belongs to (k - 2048) * decimated rate / 4096."""
-        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
-        n = self.L.hd_tone_search_power(self.h, s, p.ctypes.data, p.size, C.byref(seg))
-        if n != 4096:
-            check(n if n < 0 else -1)
-        return p, int(seg.value)
+        return _power(self.L.hd_tone_search_power, self.h, s)
 
     def stats(self, s=0) -> dict:
         i = capi.hd_tone_search_info()
@@ -763,23 +641,13 @@ class ToneSearch:
         return _tone_search_result(r)
 
 
-class HostToneSearch:
+class HostToneSearch(_Handle):
     """One stream of the tone search's spectrum in plain C++ on the host (hd_host_tone_search_*): double-precision transform, no GPU."""
+    _destroy = "hd_host_tone_search_destroy"
 
     def __init__(self):
         self.L = lib()
         self.h = self.L.hd_host_tone_search_create()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_tone_search_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         self.L.hd_host_tone_search_reset(self.h)
@@ -790,11 +658,7 @@ class HostToneSearch:
             self.L.hd_host_tone_search_push(self.h, iq.ctypes.data, iq.size)
 
     def power(self):
-        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
-        n = self.L.hd_host_tone_search_power(self.h, p.ctypes.data, p.size, C.byref(seg))
-        if n != 4096:
-            raise HabdecError(f"habdec_amd error {n}: hd_host_tone_search_power")
-        return p, int(seg.value)
+        return _power(self.L.hd_host_tone_search_power, self.h, host="hd_host_tone_search_power")
 
     def detect(self, fsd, **params) -> dict:
         p, seg = self.power()
@@ -813,23 +677,13 @@ def chase_repair(span: str, data, nbits=8, repair_bits=8, repair_flips=3):
     return (out.raw[:len(b)].decode("latin-1"), flips.value) if rc == 1 else None
 
 
-class HostFormatTrial:
+class HostFormatTrial(_Handle):
     """Four text stages (7N1, 7N2, 8N1, 8N2) over the same bits on the host (hd_host_format_trial_*)."""
+    _destroy = "hd_host_format_trial_free"
 
     def __init__(self):
         self.L = lib()
         self.h = self.L.hd_host_format_trial_new()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_format_trial_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def push_bits(self, bits):
         bits = np.ascontiguousarray(bits, dtype=np.uint8).reshape(-1)
@@ -848,81 +702,65 @@ def _candidates(out, n) -> list:
 def survey_detect(power: np.ndarray, segments: int, sampling_rate: float, cap: int = 64, **params) -> list:
     """hd_host_survey_detect on a 4096-bin averaged power spectrum (no GPU): candidates as dicts, strongest first; params as hd_survey_params."""
     L = lib()
-    p = capi.hd_survey_params()
-    L.hd_survey_params_default(C.byref(p))
-    for k, v in params.items():
-        setattr(p, k, float(v))
-    out, found = (capi.hd_survey_candidate * max(cap, 1))(), C.c_uint32(0)
-    rc = L.hd_host_survey_detect(np.ascontiguousarray(power, np.float64), int(segments), float(sampling_rate), C.byref(p), out, cap, C.byref(found))
-    if rc:
-        raise HabdecError(f"habdec_amd error {rc}: hd_host_survey_detect")
-    if found.value > cap:
-        return survey_detect(power, segments, sampling_rate, found.value, **params)
-    return _candidates(out, found.value)
+    p, power = _params(L, capi.hd_survey_params, "hd_survey_params_default", params), np.ascontiguousarray(power, np.float64)
+
+    def call(out, cap, found):
+        rc = L.hd_host_survey_detect(power, int(segments), float(sampling_rate), C.byref(p), out, cap, found)
+        if rc:
+            raise HabdecError(f"habdec_amd error {rc}: hd_host_survey_detect")
+    return _with_cap(call, cap, capi.hd_survey_candidate, _candidates)
 
 
-class Survey:
-    """Welch-averaged power spectrum of full-rate IQ and the payload detector on top of it (hd_survey_*, include/habdec_amd.h)."""
+class _WidebandObject(_Handle):
+    """What Survey and Waterfall share: full-rate IQ through two doors (hd_<_prefix>_push_device / _push_host and their _fmt forms), reset."""
+    _prefix = None
+    _destroy = property(lambda self: self._prefix + "_destroy")
 
-    def __init__(self, eng: Engine):
-        self.L, self.eng = eng.L, eng
-        h = C.c_void_p()
-        check(self.L.hd_survey_create(eng.h, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_survey_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def push_device(self, dev_ptr: int, n: int, fmt=None):
-        """n cf32 samples at a device address; the buffer must stay valid until power() / detect() / reset() has returned.
-        fmt: n packed samples (hd_survey_push_device_fmt); the buffer is the caller's again on return."""
+    def _push_device(self, dev_ptr, n, fmt):
         if fmt is not None:
-            check(self.L.hd_survey_push_device_fmt(self.h, capi.iq_fmt(fmt), dev_ptr, n))
+            check(getattr(self.L, self._prefix + "_push_device_fmt")(self.h, capi.iq_fmt(fmt), dev_ptr, n))
             return
-        check(self.L.hd_survey_push_device(self.h, dev_ptr, n))
+        check(getattr(self.L, self._prefix + "_push_device")(self.h, dev_ptr, n))
 
-    def push_host(self, iq: np.ndarray, fmt=None):
-        """fmt: iq is packed, an integer array [n, 2] (or flat, I then Q) of the format's dtype (hd_survey_push_host_fmt)."""
+    def _push_host(self, iq, fmt):
         if fmt is not None and capi.iq_fmt(fmt) != capi.IQ_CF32:
             fmt = capi.iq_fmt(fmt)
             iq = np.ascontiguousarray(iq).reshape(-1)
             if fmt in capi.IQ_DTYPES and iq.dtype != capi.IQ_DTYPES[fmt]:
                 raise HabdecError(f"IQ format {fmt} wants dtype {capi.IQ_DTYPES[fmt]}, not {iq.dtype}")
-            check(self.L.hd_survey_push_host_fmt(self.h, fmt, iq.ctypes.data, iq.size // 2))
+            check(getattr(self.L, self._prefix + "_push_host_fmt")(self.h, fmt, iq.ctypes.data, iq.size // 2))
             return
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
-        check(self.L.hd_survey_push_host(self.h, iq.ctypes.data, iq.size))
+        check(getattr(self.L, self._prefix + "_push_host")(self.h, iq.ctypes.data, iq.size))
+
+    def reset(self):
+        check(getattr(self.L, self._prefix + "_reset")(self.h))
+
+
+class Survey(_WidebandObject):
+    """Welch-averaged power spectrum of full-rate IQ and the payload detector on top of it (hd_survey_*, include/habdec_amd.h)."""
+    _prefix = "hd_survey"
+
+    def __init__(self, eng: Engine):
+        self._create(eng, "hd_survey_create")
+
+    def push_device(self, dev_ptr: int, n: int, fmt=None):
+        """n cf32 samples at a device address; the buffer must stay valid until power() / detect() / reset() has returned.
+        fmt: n packed samples (hd_survey_push_device_fmt); the buffer is the caller's again on return."""
+        self._push_device(dev_ptr, n, fmt)
+
+    def push_host(self, iq: np.ndarray, fmt=None):
+        """fmt: iq is packed, an integer array [n, 2] (or flat, I then Q) of the format's dtype (hd_survey_push_host_fmt)."""
+        self._push_host(iq, fmt)
 
     def power(self):
         """(float64[4096], segments): p[i] belongs to (i - 2048) * sampling_rate / 4096."""
-        p, seg = np.zeros(4096, np.float64), C.c_uint64(0)
-        n = self.L.hd_survey_power(self.h, p.ctypes.data, p.size, C.byref(seg))
-        if n != 4096:
-            check(n if n < 0 else -1)
-        return p, int(seg.value)
+        return _power(self.L.hd_survey_power, self.h)
 
     def detect(self, cap: int = 64, **params) -> list:
         """Candidates as dicts (offset_hz is what Engine.set_front_tune takes), strongest first; params as hd_survey_params."""
-        p = capi.hd_survey_params()
-        self.L.hd_survey_params_default(C.byref(p))
-        for k, v in params.items():
-            setattr(p, k, float(v))
-        out, found = (capi.hd_survey_candidate * max(cap, 1))(), C.c_uint32(0)
-        check(self.L.hd_survey_detect(self.h, C.byref(p), out, cap, C.byref(found)))
-        if found.value > cap:
-            return self.detect(found.value, **params)
-        return _candidates(out, found.value)
-
-    def reset(self):
-        check(self.L.hd_survey_reset(self.h))
+        p = _params(self.L, capi.hd_survey_params, "hd_survey_params_default", params)
+        return _with_cap(lambda out, cap, found: check(self.L.hd_survey_detect(self.h, C.byref(p), out, cap, found)), cap, capi.hd_survey_candidate, _candidates)
 
 
 def _tracks(out, n) -> list:
@@ -931,11 +769,7 @@ def _tracks(out, n) -> list:
 
 
 def _track_params(L, params):
-    p = capi.hd_waterfall_track_params()
-    L.hd_waterfall_track_params_default(C.byref(p))
-    for k, v in params.items():
-        setattr(p, k, int(v) if k in ("gap_rows", "min_rows") else float(v))
-    return p
+    return _params(L, capi.hd_waterfall_track_params, "hd_waterfall_track_params_default", params, ("gap_rows", "min_rows"))
 
 
 def waterfall_tracks(headers: np.ndarray, marks: np.ndarray, sampling_rate: float, cap: int = 64, **params) -> list:
@@ -945,57 +779,29 @@ def waterfall_tracks(headers: np.ndarray, marks: np.ndarray, sampling_rate: floa
     p = _track_params(L, params)
     headers = np.ascontiguousarray(headers, capi.WATERFALL_ROW_DTYPE)
     marks = np.ascontiguousarray(marks, np.uint32).reshape(len(headers), capi.WATERFALL_WORDS)
-    out, found = (capi.hd_waterfall_track * max(cap, 1))(), C.c_uint32(0)
-    rc = L.hd_host_waterfall_tracks(headers.ctypes.data, marks.ctypes.data, len(headers), float(sampling_rate), C.byref(p), out, cap, C.byref(found))
-    if rc:
-        raise HabdecError(f"habdec_amd error {rc}: hd_host_waterfall_tracks")
-    if found.value > cap:
-        return waterfall_tracks(headers, marks, sampling_rate, found.value, **params)
-    return _tracks(out, found.value)
+
+    def call(out, cap, found):
+        rc = L.hd_host_waterfall_tracks(headers.ctypes.data, marks.ctypes.data, len(headers), float(sampling_rate), C.byref(p), out, cap, found)
+        if rc:
+            raise HabdecError(f"habdec_amd error {rc}: hd_host_waterfall_tracks")
+    return _with_cap(call, cap, capi.hd_waterfall_track, _tracks)
 
 
-class Waterfall:
+class Waterfall(_WidebandObject):
     """The survey's rows over time, the per-row detector on the GPU and the tracks on top of its marks (hd_waterfall_*, include/habdec_amd.h)."""
+    _prefix = "hd_waterfall"
 
     def __init__(self, eng: Engine, **params):
-        self.L, self.eng = eng.L, eng
-        p = capi.hd_waterfall_params()
-        self.L.hd_waterfall_params_default(C.byref(p))
-        for k, v in params.items():
-            setattr(p, k, int(v) if k in ("slot_segments", "rows_cap") else float(v))
-        h = C.c_void_p()
-        check(self.L.hd_waterfall_create(eng.h, C.byref(p), C.byref(h)))
-        self.h, self.params = h, p
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_waterfall_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.params = _params(eng.L, capi.hd_waterfall_params, "hd_waterfall_params_default", params, ("slot_segments", "rows_cap"))
+        self._create(eng, "hd_waterfall_create", C.byref(self.params))
 
     def push_device(self, dev_ptr: int, n: int, fmt=None):
         """n cf32 samples at a device address, or with fmt n packed ones; returns when the new rows' headers and marks are on the host."""
-        if fmt is not None:
-            check(self.L.hd_waterfall_push_device_fmt(self.h, capi.iq_fmt(fmt), dev_ptr, n))
-            return
-        check(self.L.hd_waterfall_push_device(self.h, dev_ptr, n))
+        self._push_device(dev_ptr, n, fmt)
 
     def push_host(self, iq: np.ndarray, fmt=None):
         """fmt: iq is packed, an integer array [n, 2] (or flat, I then Q) of the format's dtype (hd_waterfall_push_host_fmt)."""
-        if fmt is not None and capi.iq_fmt(fmt) != capi.IQ_CF32:
-            fmt = capi.iq_fmt(fmt)
-            iq = np.ascontiguousarray(iq).reshape(-1)
-            if fmt in capi.IQ_DTYPES and iq.dtype != capi.IQ_DTYPES[fmt]:
-                raise HabdecError(f"IQ format {fmt} wants dtype {capi.IQ_DTYPES[fmt]}, not {iq.dtype}")
-            check(self.L.hd_waterfall_push_host_fmt(self.h, fmt, iq.ctypes.data, iq.size // 2))
-            return
-        iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)
-        check(self.L.hd_waterfall_push_host(self.h, iq.ctypes.data, iq.size))
+        self._push_host(iq, fmt)
 
     def push_rows(self, rows, segments, n_rows: int | None = None):
         """Rows of float sums made elsewhere: a float32 array [n, 4096] with segments [n], or a device address with n_rows (hd_waterfall_push_rows)."""
@@ -1051,21 +857,14 @@ class Waterfall:
     def tracks(self, cap: int = 64, **params) -> list:
         """Tracks as dicts (offset_hz is what Engine.set_front_tune takes); params as hd_waterfall_track_params."""
         p = _track_params(self.L, params)
-        out, found = (capi.hd_waterfall_track * max(cap, 1))(), C.c_uint32(0)
-        check(self.L.hd_waterfall_tracks(self.h, C.byref(p), out, cap, C.byref(found)))
-        if found.value > cap:
-            return self.tracks(found.value, **params)
-        return _tracks(out, found.value)
-
-    def reset(self):
-        check(self.L.hd_waterfall_reset(self.h))
+        return _with_cap(lambda out, cap, found: check(self.L.hd_waterfall_tracks(self.h, C.byref(p), out, cap, found)), cap, capi.hd_waterfall_track, _tracks)
 
 
-class IqFiles:
+class IqFiles(_Handle):
     """Batched IQ file source (hd_host_iqfiles_*): one IQSource_File-like reader per stream, read in lock step; cf32 files, or packed ones with fmt=."""
+    _destroy = "hd_host_iqfiles_close"
 
     def __init__(self, paths, chunk: int, granule: int, loop: bool = False, realtime_rate: float = 0.0, fmt=None):
-        import ctypes as C
         self.L = lib()
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
         self.fmt = capi.IQ_CF32 if fmt is None else capi.iq_fmt(fmt)
@@ -1074,23 +873,11 @@ class IqFiles:
             raise HabdecError("hd_host_iqfiles_open failed (missing file, chunk < granule, unknown format, ...)")
         self.S, self.chunk = len(paths), chunk
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.hd_host_iqfiles_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def count(self, s: int) -> int: return int(self.L.hd_host_iqfiles_count(self.h, s))
     def rewinds(self, s: int) -> int: return int(self.L.hd_host_iqfiles_rewinds(self.h, s))
 
     def next(self, stride: int | None = None):
         """One round: returns (slab complex64 [S, stride], n_per_stream uint32 [S], streams that read anything)."""
-        import ctypes as C
         stride = stride or self.chunk
         slab = np.zeros((self.S, stride), np.complex64)
         n = np.zeros(self.S, np.uint32)
@@ -1099,7 +886,6 @@ class IqFiles:
 
     def next_raw(self, stride: int | None = None):
         """One round in the files' own bytes: (slab [S, stride, 2] of the format's dtype, n_per_stream, streams that read anything)."""
-        import ctypes as C
         stride = stride or self.chunk
         slab = np.zeros((self.S, stride, 2), capi.IQ_DTYPES[self.fmt])
         n = np.zeros(self.S, np.uint32)
