@@ -149,6 +149,23 @@ class hd_tone_search_result(C.Structure):
 TONE_SEARCH_BINS, TONE_SEARCH_HOP, TONE_SEARCH_CHUNK = 4096, 2048, 65536
 
 
+class hd_combine_params(C.Structure):
+    _fields_ = [("max_push", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class hd_combine_lag_params(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("window", "max_lag", "guard", "min_peak_q8", "min_margin_q8")]
+
+
+class hd_combine_info(C.Structure):
+    _fields_ = [("samples", C.c_uint64)] + [(k, C.c_uint32) for k in ("group", "delay", "weight", "members")]
+
+
+# one hd_combine_lag
+COMBINE_LAG_DTYPE = np.dtype([("stream", "<u4"), ("lag", "<i4"), ("peak", "<i4"), ("second", "<i4"), ("valid", "<u4")])
+COMBINE_MAX_MEMBERS, COMBINE_MAX_DELAY, COMBINE_RING, COMBINE_CHUNK, COMBINE_MAX_LAG, COMBINE_NO_GROUP = 8, 8192, 32768, 4096, 4096, 0xFFFFFFFF
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -293,6 +310,22 @@ ENGINE_API = {
     "hd_tone_search_power": (_int, [_vp, _u32, _vp, _sz, C.POINTER(C.c_uint64)]),
     "hd_tone_search_stats": (_int, [_vp, _u32, C.POINTER(hd_tone_search_info)]),
     "hd_tone_search_detect": (_int, [_vp, _u32, C.POINTER(hd_tone_search_detect_params), C.POINTER(hd_tone_search_result)]),
+    "hd_combine_params_default": (None, [C.POINTER(hd_combine_params)]),
+    "hd_combine_lag_params_default": (None, [C.POINTER(hd_combine_lag_params)]),
+    "hd_combine_create": (_int, [_vp, C.POINTER(hd_combine_params), C.POINTER(_vp)]),
+    "hd_combine_destroy": (None, [_vp]),
+    "hd_combine_reset": (_int, [_vp, _u32]),
+    "hd_combine_set_group": (_int, [_vp, _vp, _u32]),
+    "hd_combine_set_delay": (_int, [_vp, _u32, _u32]),
+    "hd_combine_set_weight": (_int, [_vp, _u32, _u32]),
+    "hd_combine_push_engine": (_int, [_vp]),
+    "hd_combine_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_combine_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_combine_rows": (_int, [_vp, C.POINTER(_vp), C.POINTER(_sz), _vp]),
+    "hd_combine_output": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_combine_stats": (_int, [_vp, _u32, C.POINTER(hd_combine_info)]),
+    "hd_combine_lags": (_int, [_vp, _u32, C.POINTER(hd_combine_lag_params), _vp, _sz]),
+    "hd_combine_align": (_int, [_vp, _u32, C.POINTER(hd_combine_lag_params), _vp, _sz]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -378,6 +411,16 @@ HOST_API = {
     "hd_host_tone_search_reset": (None, [_vp]),
     "hd_host_tone_search_push": (None, [_vp, _vp, _sz]),
     "hd_host_tone_search_power": (_int, [_vp, _vp, _sz, C.POINTER(C.c_uint64)]),
+    "hd_host_combine_create": (_vp, [_vp, _u32]),
+    "hd_host_combine_destroy": (None, [_vp]),
+    "hd_host_combine_reset": (None, [_vp]),
+    "hd_host_combine_set_delay": (_int, [_vp, _u32, _u32]),
+    "hd_host_combine_set_weight": (_int, [_vp, _u32, _u32]),
+    "hd_host_combine_push": (_int, [_vp, _vp, _sz, _vp, _u32, _vp]),
+    "hd_host_combine_lags": (_int, [_vp, C.POINTER(hd_combine_lag_params), _vp, _sz]),
+    "hd_host_combine_align": (_int, [_vp, C.POINTER(hd_combine_lag_params), _vp, _sz]),
+    "hd_host_combine_scores": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_host_combine_stats": (_int, [_vp, _u32, C.POINTER(hd_combine_info)]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

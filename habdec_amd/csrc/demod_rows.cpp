@@ -7,7 +7,8 @@
 // tone_search.h: ToneSearchSrc), in the rows' element (float, or float2 for cf32) and in what they launch; the rest is the helpers below: the doors'
 // checks (check_object), the three push doors and the timed one (push_engine, push_rows, push_timed), the launches of a push (launch_chunks; the probe's is
 // a single one, probe_launch), the refusal of a row above max_push (check_max_push), reset and destroy, and the test hooks' guard counter.  Where an
-// object does something of its own, it says so at its own *_launch or door.
+// object does something of its own, it says so at its own *_launch or door.  The diversity combiner (kernels/combine.hip, host/combine.hpp) is the fifth: it
+// reads float rows as the clocked decoder does (CombineSrc has ClockedSrc's fields), sums the rows of a group of streams and writes rows as the tones do.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -15,8 +16,10 @@
 #include "engine_state.h"
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
+#include "host/combine.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
+#include "kernels/combine.h"
 #include "kernels/spectrum_math.h"
 #include "kernels/tone_search.h"
 
@@ -28,6 +31,7 @@ namespace {
 // A row's length in its descriptor.  (The clocked decoder's n is the part of the row one launch takes: clocked_launch.)
 uint32_t& src_len(hd::ProbeSrc& d) { return d.n; }
 uint32_t& src_len(hd::ClockedSrc& d) { return d.n_total; }
+uint32_t& src_len(hd::CombineSrc& d) { return d.n_total; }
 
 // A descriptor for n elements in linear memory at p.
 template <typename Src>
@@ -952,6 +956,341 @@ int hd_debug_tone_search_guards(hd_tone_search* ts, uint32_t stream)
         at[3 + 2 * k] = at[2 + 2 * k] + ts->carry_stride * 2 - hd::kToneSearchGuard;
     }
     return damaged_guards(at, hd::kToneSearchGuard, hd::kToneSearchGuardWord);
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- diversity combiner (kernels/combine.hip) ----------------------------- */
+
+struct hd_combine {
+    static constexpr const char* kNull = "null combiner";
+    hd_engine* e = nullptr;
+    hd_combine_params prm{};
+    uint32_t S = 0;
+    int16_t* ring = nullptr;                     // [S][ring_stride]: guard | HD_COMBINE_RING samples | guard
+    float* rows = nullptr;                       // [S][row_stride]: guard | max_push floats | guard
+    int32_t* scores = nullptr;                   // [7][2 * HD_COMBINE_MAX_LAG + 1]: the last search's, allocated by the first search
+    size_t ring_stride = 0, row_stride = 0;
+    float* slab = nullptr;                       // hd_combine_push_host: the rows packed end to end, grown on demand
+    size_t slab_n = 0;
+    PinBuf<hd::CombineSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    PinBuf<hd::CombineGroup> grp;                // [S]: a push's groups, in the order of `refs`
+    PinBuf<hd_combine_lag> res;                  // [7]: the last search's results, written by the kernel in place
+    std::vector<uint32_t> group_of, delay, weight, row_n;       // [S]: the stream's reference (HD_COMBINE_NO_GROUP: in no group), its delay and weight, its row's length
+    std::vector<std::vector<uint32_t>> members;  // [S]: by reference, the group's streams, the reference first
+    std::vector<uint64_t> count;                 // [S]: by reference, the group's samples since its last reset
+    std::vector<uint32_t> refs;                  // the references, ascending
+    std::vector<uint32_t> searched;              // the members of the last search, the reference first
+    uint32_t searched_L = 0;
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
+    ~hd_combine()
+    {
+        for (void* p : {(void*)ring, (void*)rows, (void*)scores, (void*)slab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+void combine_list_refs(hd_combine* c)
+{
+    c->refs.clear();
+    for (uint32_t s = 0; s < c->S; ++s) if (c->group_of[s] == s) c->refs.push_back(s);
+}
+
+// Stream s leaves its group; a group that loses its reference is dissolved.
+void combine_leave(hd_combine* c, uint32_t s)
+{
+    const uint32_t r = c->group_of[s];
+    if (r == HD_COMBINE_NO_GROUP) return;
+    auto& mem = c->members[r];
+    if (r == s) {
+        for (uint32_t m : mem) { c->group_of[m] = HD_COMBINE_NO_GROUP; c->row_n[m] = 0; }
+        mem.clear();
+        c->count[r] = 0;
+    } else {
+        mem.erase(std::find(mem.begin(), mem.end(), s));
+        c->group_of[s] = HD_COMBINE_NO_GROUP;
+    }
+}
+
+hd::CombineGroup combine_group(const hd_combine* c, uint32_t r)
+{
+    hd::CombineGroup g{};
+    const auto& mem = c->members[r];
+    g.base = c->count[r];
+    g.count = (uint32_t)mem.size();
+    for (uint32_t m = 0; m < g.count; ++m) { g.stream[m] = mem[m]; g.delay[m] = c->delay[mem[m]]; g.weight[m] = c->weight[mem[m]]; g.wt += g.weight[m]; }
+    g.wt = std::max(g.wt, 1u);
+    return g;
+}
+
+// Its own: a stream in no group is passed by and the members of a group must bring the same length, both in front of the max_push test; the groups'
+// descriptors hold for every chunk of the push (a sample's absolute index is base + off + j); the groups' counts move on behind the last chunk.
+int combine_launch(hd_combine* c, uint32_t max_n)
+{
+    for (uint32_t s = 0; s < c->S; ++s) if (c->group_of[s] == HD_COMBINE_NO_GROUP) c->src.p[s].n_total = 0;
+    for (uint32_t r : c->refs)
+        for (uint32_t m : c->members[r])
+            if (c->src.p[m].n_total != c->src.p[r].n_total)
+                return fail(HD_ERR_INVALID, "hd_combine: stream " + std::to_string(m) + " brings " + std::to_string(c->src.p[m].n_total) + " samples, its group's reference " +
+                                                std::to_string(r) + " brings " + std::to_string(c->src.p[r].n_total));
+    if (const int rc = check_max_push(c, "hd_combine", &max_n, [](uint32_t) {})) return rc;
+    for (uint32_t s = 0; s < c->S; ++s) c->row_n[s] = c->group_of[s] == s ? c->src.p[s].n_total : 0u;
+    const uint32_t ng = (uint32_t)c->refs.size();
+    for (uint32_t k = 0; k < ng; ++k) c->grp.p[k] = combine_group(c, c->refs[k]);
+    uint32_t cap = 0;
+    const int rc = launch_chunks(
+        c, max_n, HD_COMBINE_CHUNK, "",
+        [&](uint32_t, const hd::CombineSrc& d) { cap = std::max(cap, d.n); },
+        [&] {
+            hd::launch_combine(c->e->qa, ng, cap, c->src.dev, c->grp.dev, c->ring, c->ring_stride, c->rows, c->row_stride, c->prm.max_push);
+            cap = 0;
+            return true;
+        },
+        [] {});
+    if (rc) return rc;
+    for (uint32_t r : c->refs) c->count[r] += c->src.p[r].n_total;
+    return HD_OK;
+}
+
+// (The rings need no clearing: nothing in front of a group's index 0 is read.)  One stream: it must be a reference.
+int combine_clear(hd_combine* c, uint32_t s0, uint32_t ns)
+{
+    if (ns == 1 && c->group_of[s0] != s0) return fail(HD_ERR_INVALID, "hd_combine_reset: stream " + std::to_string(s0) + " is no group's reference");
+    for (uint32_t s = s0; s < s0 + ns; ++s) {
+        if (c->group_of[s] != s) continue;
+        c->count[s] = 0;
+        for (uint32_t m : c->members[s]) c->row_n[m] = 0;
+    }
+    return HD_OK;
+}
+
+// hd_combine_lags behind the lock and enter(): the search's two kernels on the engine's first queue and the wait for them.
+int combine_search(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap)
+{
+    if (c->group_of[ref] != ref) return fail(HD_ERR_INVALID, "hd_combine_lags: stream " + std::to_string(ref) + " is no group's reference");
+    if (!hd::combine_lag_params_ok(p))
+        return fail(HD_ERR_INVALID, "hd_combine_lags: window a multiple of 64 in 1024 .. 16384, max_lag a multiple of 64 in 64 .. 4096, guard >= 1");
+    const hd::CombineGroup g = combine_group(c, ref);
+    if (cap < g.count) return fail(HD_ERR_INVALID, "hd_combine_lags: room for " + std::to_string(cap) + " results, the group has " + std::to_string(g.count) + " members");
+    const uint64_t n = c->count[ref], need = (uint64_t)p->window + 2u * (uint64_t)p->max_lag;
+    if (n < need) return fail(HD_ERR_UNSUPPORTED, "hd_combine_lags needs " + std::to_string(need) + " samples (" + std::to_string(n) + " so far)");
+    if (!c->scores) HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->scores), (size_t)(HD_COMBINE_MAX_MEMBERS - 1) * (2 * HD_COMBINE_MAX_LAG + 1) * sizeof(int32_t)));
+    hd::launch_combine_lags(c->e->qa, &g, n, p->window, p->max_lag, p->guard, p->min_peak_q8, p->min_margin_q8, c->ring, c->ring_stride, c->scores, c->res.dev);
+    HD_HIP(hipGetLastError());
+    HD_HIP(hipStreamSynchronize(c->e->qa));
+    std::atomic_thread_fence(std::memory_order_acquire);
+    out[0] = hd_combine_lag{ref, 0, (int32_t)p->window, 0, 1u};
+    for (uint32_t m = 1; m < g.count; ++m) out[m] = c->res.p[m - 1];
+    c->searched.assign(g.stream, g.stream + g.count);
+    c->searched_L = p->max_lag;
+    return HD_OK;
+}
+
+// (the engine's mutex is held)
+int combine_member(hd_combine* c, uint32_t stream, const char* fn)
+{
+    if (c->group_of[stream] == HD_COMBINE_NO_GROUP) return fail(HD_ERR_INVALID, std::string(fn) + ": stream " + std::to_string(stream) + " is in no group");
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_combine_params_default(hd_combine_params* p) { if (p) *p = hd_combine_params{0u, 0u}; }
+void hd_combine_lag_params_default(hd_combine_lag_params* p) { if (p) hd::combine_lag_params_default(p); }
+
+int hd_combine_create(hd_engine* e, const hd_combine_params* params, hd_combine** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_combine> c(new hd_combine);
+    c->e = e; c->S = e->S;
+    if (params) c->prm = *params;
+    if (!c->prm.max_push) c->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
+    if (c->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "combiner parameters: max_push <= 2^28");
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = c->S;
+    c->group_of.assign(S, HD_COMBINE_NO_GROUP); c->delay.assign(S, 0u); c->weight.assign(S, 256u); c->row_n.assign(S, 0u);
+    c->members.assign(S, {}); c->count.assign(S, 0);
+    c->ring_stride = (size_t)HD_COMBINE_RING + 4 * hd::kCombineGuard;             // (2 kCombineGuard int16 samples on either side)
+    c->row_stride = (size_t)c->prm.max_push + 2 * hd::kCombineGuard;
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)S * c->ring_stride * sizeof(int16_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rows), (size_t)S * c->row_stride * sizeof(float)));
+    HD_HIP(c->src.alloc(S));
+    HD_HIP(c->grp.alloc(S));
+    HD_HIP(c->res.alloc(HD_COMBINE_MAX_MEMBERS - 1));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kCombineGuardWord, (size_t)S * c->ring_stride / 2, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rows), (int)hd::kCombineGuardWord, (size_t)S * c->row_stride, e->qa));
+    HD_HIP(hipStreamSynchronize(e->qa));
+    *out = c.release();
+    return HD_OK;
+}
+
+void hd_combine_destroy(hd_combine* c) { destroy(c); }
+
+int hd_combine_reset(hd_combine* c, uint32_t ref) { return reset(c, ref, combine_clear); }
+
+int hd_combine_set_group(hd_combine* c, const uint32_t* streams, uint32_t count)
+{
+    if (!c) return fail(HD_ERR_INVALID, hd_combine::kNull);
+    if (!streams) return fail(HD_ERR_INVALID, "null streams");
+    if (count > HD_COMBINE_MAX_MEMBERS) return fail(HD_ERR_INVALID, "hd_combine_set_group: at most " + std::to_string(HD_COMBINE_MAX_MEMBERS) + " members");
+    for (uint32_t a = 0; a < std::max(count, 1u); ++a) {
+        if (streams[a] >= c->S) return fail(HD_ERR_INVALID, "stream index out of range");
+        for (uint32_t b = 0; b < a; ++b) if (streams[a] == streams[b]) return fail(HD_ERR_INVALID, "hd_combine_set_group: stream " + std::to_string(streams[a]) + " is named twice");
+    }
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (!count) {
+        if (c->group_of[streams[0]] != streams[0]) return fail(HD_ERR_INVALID, "hd_combine_set_group: stream " + std::to_string(streams[0]) + " is no group's reference");
+        combine_leave(c, streams[0]);
+        combine_list_refs(c);
+        return HD_OK;
+    }
+    for (uint32_t a = 0; a < count; ++a) combine_leave(c, streams[a]);
+    const uint32_t r = streams[0];
+    c->members[r].assign(streams, streams + count);
+    c->count[r] = 0;
+    for (uint32_t a = 0; a < count; ++a) { const uint32_t s = streams[a]; c->group_of[s] = r; c->delay[s] = 0; c->weight[s] = 256; c->row_n[s] = 0; }
+    combine_list_refs(c);
+    return HD_OK;
+}
+
+int hd_combine_set_delay(hd_combine* c, uint32_t stream, uint32_t delay)
+{
+    if (const int rc = check_object(c, stream)) return rc;
+    if (delay > HD_COMBINE_MAX_DELAY) return fail(HD_ERR_INVALID, "hd_combine_set_delay: at most " + std::to_string(HD_COMBINE_MAX_DELAY) + " samples");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = combine_member(c, stream, "hd_combine_set_delay")) return rc;
+    c->delay[stream] = delay;
+    return HD_OK;
+}
+
+int hd_combine_set_weight(hd_combine* c, uint32_t stream, uint32_t weight)
+{
+    if (const int rc = check_object(c, stream)) return rc;
+    if (weight > 256u) return fail(HD_ERR_INVALID, "hd_combine_set_weight: at most 256");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = combine_member(c, stream, "hd_combine_set_weight")) return rc;
+    c->weight[stream] = weight;
+    return HD_OK;
+}
+
+int hd_combine_push_engine(hd_combine* c) { return push_engine(c, "hd_combine_push_engine", combine_launch); }
+
+int hd_combine_push_device(hd_combine* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(c, d_rows, stride, n_per_stream, n, true, combine_launch);
+}
+
+int hd_combine_push_host(hd_combine* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(c, rows, stride, n_per_stream, n, false, combine_launch);
+}
+
+int hd_combine_rows(hd_combine* c, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
+{
+    if (!c) return fail(HD_ERR_INVALID, hd_combine::kNull);
+    if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    *d_rows = c->rows + hd::kCombineGuard;
+    *stride = c->row_stride;
+    std::memcpy(n_per_stream, c->row_n.data(), (size_t)c->S * sizeof(uint32_t));
+    return HD_OK;
+}
+
+int hd_combine_output(hd_combine* c, uint32_t stream, float* out, size_t cap)
+{
+    if (const int rc = check_object(c, stream)) return rc;
+    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    const size_t k = std::min<size_t>(c->row_n[stream], cap);
+    if (k) HD_HIP(hipMemcpy(out, c->rows + (size_t)stream * c->row_stride + hd::kCombineGuard, k * sizeof(float), hipMemcpyDeviceToHost));
+    return (int)c->row_n[stream];
+}
+
+int hd_combine_stats(hd_combine* c, uint32_t stream, hd_combine_info* out)
+{
+    if (const int rc = check_object(c, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    const uint32_t r = c->group_of[stream];
+    if (r == HD_COMBINE_NO_GROUP) *out = hd_combine_info{0u, HD_COMBINE_NO_GROUP, 0u, 0u, 0u};
+    else *out = hd_combine_info{c->count[r], r, c->delay[stream], c->weight[stream], (uint32_t)c->members[r].size()};
+    return HD_OK;
+}
+
+int hd_combine_lags(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap)
+{
+    if (const int rc = check_object(c, ref)) return rc;
+    if (!p || !out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    return combine_search(c, ref, p, out, cap);
+}
+
+int hd_combine_align(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap)
+{
+    if (const int rc = check_object(c, ref)) return rc;
+    if (!p || !out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    if (const int rc = combine_search(c, ref, p, out, cap)) return rc;
+    const auto& mem = c->members[ref];
+    uint32_t d[HD_COMBINE_MAX_MEMBERS], w[HD_COMBINE_MAX_MEMBERS];
+    for (size_t m = 0; m < mem.size(); ++m) { d[m] = c->delay[mem[m]]; w[m] = c->weight[mem[m]]; }
+    const int valid = hd::combine_align(out, (uint32_t)mem.size(), d, w);
+    for (size_t m = 0; m < mem.size(); ++m) { c->delay[mem[m]] = d[m]; c->weight[mem[m]] = w[m]; }
+    return valid;
+}
+
+// The measurement hook (tools/micro/combine_rate.py; not part of the ABI): hd_combine_push_device of the rows, its kernels between two HIP events.
+int hd_debug_combine_push_timed(hd_combine* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n, float* kernel_ms, double* host_us)
+{
+    if (!c) return fail(HD_ERR_INVALID, hd_combine::kNull);
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    const uint64_t keep = c->pushed_calls;                           // (push_timed reads the events where the push moved this count: moved here, put back below)
+    const int rc = push_timed(c, kernel_ms, host_us, [&](hd_combine* o) {
+        const int r = hd_combine_push_device(o, d_rows, stride, n_per_stream, n);
+        if (r == HD_OK) o->pushed_calls = keep + 1;
+        return r;
+    });
+    c->pushed_calls = keep;
+    return rc;
+}
+
+// Test hook (tests/test_gpu_combine.py; not part of the ABI): the 2 L + 1 scores of `stream` in the last search; returns their number, 0 where the stream
+// was no member of it beside the reference; nothing is written where cap is below it.
+int hd_debug_combine_scores(hd_combine* c, uint32_t stream, int32_t* out, size_t cap)
+{
+    if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    const size_t k = 2 * (size_t)c->searched_L + 1;
+    for (size_t m = 1; m < c->searched.size(); ++m) {
+        if (c->searched[m] != stream) continue;
+        if (out && cap >= k) HD_HIP(hipMemcpy(out, c->scores + (m - 1) * k, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        return (int)k;
+    }
+    return 0;
+}
+
+// Test hook (tests/test_gpu_combine.py; not part of the ABI): how many of the guard words around the stream's ring and its row no longer hold their pattern.
+int hd_debug_combine_guards(hd_combine* c, uint32_t stream)
+{
+    if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
+    if (const int rc = enter(c->e)) return rc;
+    const uint32_t* r32 = reinterpret_cast<const uint32_t*>(c->ring);         // (its guards as 32-bit words: kCombineGuard on either side)
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(c->rows);
+    const uint32_t* at[4];
+    at[0] = r32 + (size_t)stream * c->ring_stride / 2; at[1] = at[0] + c->ring_stride / 2 - hd::kCombineGuard;
+    at[2] = row + (size_t)stream * c->row_stride; at[3] = at[2] + c->row_stride - hd::kCombineGuard;
+    return damaged_guards(at, hd::kCombineGuard, hd::kCombineGuardWord);
 }
 
 }  // extern "C"

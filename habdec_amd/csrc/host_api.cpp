@@ -7,6 +7,7 @@
 #include "host/afc_tracker.hpp"
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
+#include "host/combine.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
 #include "host/decim_plan.hpp"
@@ -421,6 +422,65 @@ int hd_host_tone_search_power(const hd_host_tone_search* h, double* p, size_t ca
     if (cap < hd::kToneSearchBins) return 0;
     h->st.power(p);
     return (int)hd::kToneSearchBins;
+}
+
+/* ---- diversity combiner (kernels/combine.hip; see host/combine.hpp) ---- */
+struct hd_host_combine {
+    hd::CombineHostGroup g;
+};
+hd_host_combine* hd_host_combine_create(const uint32_t* streams, uint32_t count)
+{
+    auto* h = new hd_host_combine;
+    if (!h->g.make(streams, count)) { delete h; return nullptr; }
+    return h;
+}
+void hd_host_combine_destroy(hd_host_combine* h) { delete h; }
+void hd_host_combine_reset(hd_host_combine* h) { if (h) h->g.reset(); }
+int hd_host_combine_set_delay(hd_host_combine* h, uint32_t m, uint32_t delay)
+{
+    if (!h || m >= h->g.count || delay > HD_COMBINE_MAX_DELAY) return HD_ERR_INVALID;
+    h->g.delay[m] = delay;
+    return HD_OK;
+}
+int hd_host_combine_set_weight(hd_host_combine* h, uint32_t m, uint32_t weight)
+{
+    if (!h || m >= h->g.count || weight > 256u) return HD_ERR_INVALID;
+    h->g.weight[m] = weight;
+    return HD_OK;
+}
+int hd_host_combine_push(hd_host_combine* h, const float* rows, size_t stride, const uint32_t* n_per_member, uint32_t n, float* out)
+{
+    if (!h) return HD_ERR_INVALID;
+    const uint32_t len = n_per_member ? n_per_member[0] : n;
+    for (uint32_t m = 1; n_per_member && m < h->g.count; ++m) if (n_per_member[m] != len) return HD_ERR_INVALID;
+    if (!len) return HD_OK;
+    if (!rows || !out || (h->g.count > 1 && len > stride)) return HD_ERR_INVALID;
+    h->g.push(rows, stride, len, out);
+    return HD_OK;
+}
+int hd_host_combine_lags(hd_host_combine* h, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap)
+{
+    if (!h || !p || !out || cap < h->g.count) return HD_ERR_INVALID;
+    return h->g.lags(p, out);
+}
+int hd_host_combine_align(hd_host_combine* h, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap)
+{
+    if (const int rc = hd_host_combine_lags(h, p, out, cap)) return rc;
+    return hd::combine_align(out, h->g.count, h->g.delay, h->g.weight);
+}
+int hd_host_combine_scores(const hd_host_combine* h, uint32_t m, int32_t* out, size_t cap)
+{
+    if (!h || m < 1 || m >= h->g.count) return HD_ERR_INVALID;
+    if (h->g.scores.empty()) return 0;
+    const size_t k = 2 * (size_t)h->g.scores_L + 1;
+    if (out && cap >= k) std::memcpy(out, h->g.scores.data() + (size_t)(m - 1) * k, k * sizeof(int32_t));
+    return (int)k;
+}
+int hd_host_combine_stats(const hd_host_combine* h, uint32_t m, hd_combine_info* out)
+{
+    if (!h || !out || m >= h->g.count) return HD_ERR_INVALID;
+    *out = hd_combine_info{h->g.n, h->g.stream[0], h->g.delay[m], h->g.weight[m], h->g.count};
+    return HD_OK;
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

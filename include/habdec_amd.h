@@ -747,6 +747,95 @@ int  hd_tone_search_stats(hd_tone_search* ts, uint32_t stream, hd_tone_search_in
 /* hd_tone_search_power followed by hd_host_tone_search_detect (habdec_amd_host.h has the algorithm and its errors). */
 int  hd_tone_search_detect(hd_tone_search* ts, uint32_t stream, const hd_tone_search_detect_params* p, hd_tone_search_result* out);
 
+/* ---- diversity combiner: several receivers of one payload, aligned and summed into one row for the clocked decoder (not in the reference) ----
+ * tones -> COMBINE -> hd_clocked_push_device.  Several engine streams may be receivers of the same payload; decoded alone each fails where their sum
+ * still decodes (NOTES.md has the ladder).  A combiner is attached to an engine like a tones object (its device, mutex and first queue; destroy it before
+ * the engine).  Its input is one float row per engine stream -- any row hd_clocked_push_device takes: above all what hd_tones_rows hands out, but also the
+ * discriminator's row -- and its output is float rows in device memory that hd_clocked_push_device takes unchanged.  Integer arithmetic behind the
+ * quantisation: kernel, host restatement (hd_host_combine_*) and a numpy model agree byte for byte.
+ *  - Groups: a group is 1 to HD_COMBINE_MAX_MEMBERS (8) distinct engine streams; the first is the reference r and the group is known by r.
+ *    hd_combine_set_group defines a group and resets its members: every sample count 0, every delay 0, every weight 256.  A stream that was in another
+ *    group leaves it; a group that loses its reference is dissolved.  count = 0 with streams[0] naming a reference dissolves that group.  A stream in no
+ *    group is passed by: its samples are not counted and its row has length 0.
+ *  - Per member m: a delay d_m in 0 .. HD_COMBINE_MAX_DELAY (8192) and a weight w_m in 0 .. 256.  Neither setter resets anything: the new values hold from
+ *    the next push on.
+ *  - Quantisation, the clocked decoder's: q = 0 for NaN, else (int32)(clamp(v, -4, 4) * 1024) truncated toward zero.  q_m(i) is member m's sample at the
+ *    absolute index i since the group's last reset, 0 for i < 0.  Each member keeps its newest HD_COMBINE_RING (32768) samples on the GPU as int16.
+ *  - Push: all members of a group must bring the same number of samples n in one push, else the call is HD_ERR_INVALID before anything is launched or
+ *    counted (in any group).  A row above max_push: HD_ERR_CAPACITY, likewise.  One launch per HD_COMBINE_CHUNK (4096) samples of the longest row.
+ *  - Output, for the group's indices j of the push: sum(j) = the sum over m of w_m q_m(j - d_m) (|sum| <= 2^23); Wt = the sum of the w_m;
+ *    o = sum / max(1, Wt), truncated toward zero; the float written is o / 1024.0f, exact, and the clocked decoder's quantisation gives o back.  Row r has
+ *    length n, the rows of the other members length 0.
+ *  - Lag search (hd_combine_lags), over the rings -- delays and weights play no part: window N (a multiple of 64 in 1024 .. 16384), max_lag L (a multiple
+ *    of 64 in 64 .. 4096), guard >= 1 in samples (the caller's bit length).  HD_ERR_UNSUPPORTED until the group has n >= N + 2 L samples.
+ *    b_m(i) = 1 iff q_m(i) > 0.  For every member m != r and every l in -L .. L: A_m(l) = #{ i in [n-L-N, n-L) : b_r(i) == b_m(i + l) }, the score
+ *    c_m(l) = 2 A_m(l) - N.  lag = the l of the largest score, ties to the smaller |l|, then to the negative l; peak = that score; second = the largest
+ *    score over |l - lag| > guard (-N where no l is that far away); valid iff 256 peak >= min_peak_q8 N and 256 (peak - second) >= min_margin_q8 N.
+ *    Meaning: the reference's sample i is the member's sample i + lag.  The reference's own entry is {lag 0, peak N, second 0, valid 1}.  RTTY's start
+ *    and stop bits repeat every character, so `second` sits at a character period and is large; an unmodulated carrier scores N at every lag and has
+ *    margin 0.  NOTES.md has where the defaults come from.
+ *  - Align (hd_combine_align): the search, then with top = the largest lag among the valid members and 0, every valid member (the reference too) gets
+ *    d_m = top - lag_m (at most 2 L <= 8192); every invalid member gets weight 0 and keeps its delay.  THE OUTPUT'S TIME AXIS MOVES WHEN DELAYS CHANGE:
+ *    reset the clocked decoder behind the combiner (hd_clocked_reset of the reference's stream) after an align that changed a delay.
+ *  - Queue, errors: as the tones object's; every push returns when its kernels are done. */
+#define HD_COMBINE_MAX_MEMBERS 8
+#define HD_COMBINE_MAX_DELAY 8192
+#define HD_COMBINE_RING 32768      /* per-stream sample history on the GPU, int16 */
+#define HD_COMBINE_CHUNK 4096      /* samples per stream and launch */
+#define HD_COMBINE_MIN_WINDOW 1024
+#define HD_COMBINE_MAX_WINDOW 16384
+#define HD_COMBINE_MAX_LAG 4096
+#define HD_COMBINE_NO_GROUP 0xFFFFFFFFu
+typedef struct hd_combine hd_combine;
+typedef struct hd_combine_params {
+    uint32_t max_push;         /* samples per stream and push the rows hold; default (0): the engine's largest decimated chunk per call, at least 4096 */
+    uint32_t _pad;
+} hd_combine_params;
+typedef struct hd_combine_lag_params {
+    uint32_t window;           /* N; default 8192 */
+    uint32_t max_lag;          /* L; default 2048 */
+    uint32_t guard;            /* samples; required, >= 1: the bit length */
+    uint32_t min_peak_q8;      /* default 76: peak / N >= 0.297, three times what noise alone reaches */
+    uint32_t min_margin_q8;    /* default 16: (peak - second) / N >= 0.0625, a third of the weakest signal's margin */
+} hd_combine_lag_params;
+typedef struct hd_combine_lag {
+    uint32_t stream;
+    int32_t  lag, peak, second;
+    uint32_t valid;
+} hd_combine_lag;
+typedef struct hd_combine_info {
+    uint64_t samples;          /* n of the stream's group since its last reset; 0 in no group */
+    uint32_t group;            /* the group's reference, HD_COMBINE_NO_GROUP in no group */
+    uint32_t delay, weight;
+    uint32_t members;          /* of the stream's group */
+} hd_combine_info;
+void hd_combine_params_default(hd_combine_params* p);
+void hd_combine_lag_params_default(hd_combine_lag_params* p);               /* guard = 0: to be filled in */
+int  hd_combine_create(hd_engine* e, const hd_combine_params* p /* null: the defaults */, hd_combine** out);   /* no stream is in a group */
+void hd_combine_destroy(hd_combine* c);
+/* Counts and rings of a group (by its reference; a stream that is no reference: HD_ERR_INVALID) or of all (UINT32_MAX) start again; groups, delays and
+ * weights stay; the rows have length 0. */
+int  hd_combine_reset(hd_combine* c, uint32_t ref /* UINT32_MAX: all */);
+int  hd_combine_set_group(hd_combine* c, const uint32_t* streams, uint32_t count);
+int  hd_combine_set_delay(hd_combine* c, uint32_t stream, uint32_t delay);     /* HD_ERR_INVALID: above HD_COMBINE_MAX_DELAY, or a stream in no group */
+int  hd_combine_set_weight(hd_combine* c, uint32_t stream, uint32_t weight);   /* HD_ERR_INVALID: above 256, or a stream in no group */
+/* The discriminator rows of the call delivered last (what hd_stream_demodulated returns), with the rules of hd_clocked_push_engine: a call that was
+ * pushed already adds nothing and leaves the rows as they are. */
+int  hd_combine_push_engine(hd_combine* c);
+/* Rows of float as for hd_clocked_push_*: stream s takes n_per_stream[s] (null: n) floats at rows + s * stride. */
+int  hd_combine_push_device(hd_combine* c, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_combine_push_host(hd_combine* c, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* The device rows of the last push, exactly as hd_tones_rows: the triple goes straight into hd_clocked_push_device. */
+int  hd_combine_rows(hd_combine* c, const float** d_rows, size_t* stride, uint32_t* n_per_stream);
+/* A host copy of one row of the last push: returns its length and writes min(length, cap) floats.  Negative: HD_ERR_*. */
+int  hd_combine_output(hd_combine* c, uint32_t stream, float* out, size_t cap);
+int  hd_combine_stats(hd_combine* c, uint32_t stream, hd_combine_info* out);
+/* The lag search of the group with reference ref: writes one entry per member, the reference's first, in the group's order; HD_ERR_INVALID where cap is
+ * below the group's member count.  HD_OK, or HD_ERR_*. */
+int  hd_combine_lags(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap);
+/* hd_combine_lags, then the align step.  Returns the number of valid entries (the reference's among them), or HD_ERR_*. */
+int  hd_combine_align(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -253,6 +253,25 @@ void   hd_host_tone_search_reset(hd_host_tone_search*);
 void   hd_host_tone_search_push(hd_host_tone_search*, const float* iq, size_t n);
 int    hd_host_tone_search_power(const hd_host_tone_search*, double* p, size_t cap, uint64_t* segments);
 
+/* ---- diversity combiner (hd_combine_*, include/habdec_amd.h has the definition): one group of it in plain C++, sample by sample and lag by lag ----
+ * The same integers as the kernels: rows, scores and results of the same pushes equal the device's byte for byte.  hd_host_combine_create: a group of
+ * `count` members named by `streams` (the reference first; the names only label the results), NULL unless 1 <= count <= 8 and the names are distinct;
+ * every delay 0, every weight 256.  Members are addressed by their position m in the group.  hd_host_combine_push: member m brings n_per_member[m]
+ * (null: n) floats at rows + m * stride; unequal lengths are HD_ERR_INVALID and nothing is counted; n floats are written to out.  hd_host_combine_lags /
+ * _align as hd_combine_lags / hd_combine_align; hd_host_combine_scores copies member m's (m >= 1) 2 L + 1 scores of the last search and returns their
+ * number (0 before a search; nothing is written where cap is below it).  hd_host_combine_stats as hd_combine_stats. */
+typedef struct hd_host_combine hd_host_combine;
+hd_host_combine* hd_host_combine_create(const uint32_t* streams, uint32_t count);
+void   hd_host_combine_destroy(hd_host_combine*);
+void   hd_host_combine_reset(hd_host_combine*);
+int    hd_host_combine_set_delay(hd_host_combine*, uint32_t m, uint32_t delay);
+int    hd_host_combine_set_weight(hd_host_combine*, uint32_t m, uint32_t weight);
+int    hd_host_combine_push(hd_host_combine*, const float* rows, size_t stride, const uint32_t* n_per_member, uint32_t n, float* out);
+int    hd_host_combine_lags(hd_host_combine*, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap);
+int    hd_host_combine_align(hd_host_combine*, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap);
+int    hd_host_combine_scores(const hd_host_combine*, uint32_t m, int32_t* out, size_t cap);
+int    hd_host_combine_stats(const hd_host_combine*, uint32_t m, hd_combine_info* out);
+
 #ifdef __cplusplus
 }
 #endif
