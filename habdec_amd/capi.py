@@ -166,6 +166,20 @@ COMBINE_LAG_DTYPE = np.dtype([("stream", "<u4"), ("lag", "<i4"), ("peak", "<i4")
 COMBINE_MAX_MEMBERS, COMBINE_MAX_DELAY, COMBINE_RING, COMBINE_CHUNK, COMBINE_MAX_LAG, COMBINE_NO_GROUP = 8, 8192, 32768, 4096, 4096, 0xFFFFFFFF
 
 
+class hd_ssdv_params(C.Structure):
+    _fields_ = [("max_fill", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class hd_ssdv_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("bytes", "decided", "fillers", "crc_bad", "overlaps")] + [("packets", C.c_uint64 * 5)]
+
+
+# one hd_ssdv_packet
+SSDV_PACKET_DTYPE = np.dtype([("pos", "<u8")] + [(k, "<u4") for k in ("trial", "errors", "erasures", "erasures_changed", "type", "image_id", "packet_id", "width",
+                                                                      "height", "flags", "mcu_offset", "mcu_index")] + [("callsign", "S8"), ("data", "u1", (256,))])
+SSDV_NOFEC, SSDV_TYPE_NOFEC, SSDV_RING, SSDV_LAUNCH = 255, 0x67, 4096, 16384
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -326,6 +340,16 @@ ENGINE_API = {
     "hd_combine_stats": (_int, [_vp, _u32, C.POINTER(hd_combine_info)]),
     "hd_combine_lags": (_int, [_vp, _u32, C.POINTER(hd_combine_lag_params), _vp, _sz]),
     "hd_combine_align": (_int, [_vp, _u32, C.POINTER(hd_combine_lag_params), _vp, _sz]),
+    "hd_ssdv_params_default": (None, [C.POINTER(hd_ssdv_params)]),
+    "hd_ssdv_create": (_int, [_vp, C.POINTER(hd_ssdv_params), C.POINTER(_vp)]),
+    "hd_ssdv_destroy": (None, [_vp]),
+    "hd_ssdv_reset": (_int, [_vp, _u32]),
+    "hd_ssdv_push_bytes": (_int, [_vp, _u32, _vp, _vp, _sz]),
+    "hd_ssdv_push_records": (_int, [_vp, _u32, _vp, _sz, _u32]),
+    "hd_ssdv_push_clocked": (_int, [_vp, _vp]),
+    "hd_ssdv_scan": (_int, [_vp]),
+    "hd_ssdv_take_packets": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_ssdv_stats": (_int, [_vp, _u32, C.POINTER(hd_ssdv_counters)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -421,6 +445,15 @@ HOST_API = {
     "hd_host_combine_align": (_int, [_vp, C.POINTER(hd_combine_lag_params), _vp, _sz]),
     "hd_host_combine_scores": (_int, [_vp, _u32, _vp, _sz]),
     "hd_host_combine_stats": (_int, [_vp, _u32, C.POINTER(hd_combine_info)]),
+    "hd_host_ssdv_create": (_vp, [C.POINTER(hd_ssdv_params)]),
+    "hd_host_ssdv_destroy": (None, [_vp]),
+    "hd_host_ssdv_reset": (None, [_vp]),
+    "hd_host_ssdv_push_bytes": (_int, [_vp, _vp, _vp, _sz]),
+    "hd_host_ssdv_push_records": (_int, [_vp, _vp, _sz, _u32]),
+    "hd_host_ssdv_take_packets": (_int, [_vp, _vp, _sz]),
+    "hd_host_ssdv_stats": (_int, [_vp, C.POINTER(hd_ssdv_counters)]),
+    "hd_host_ssdv_encode": (None, [_vp, _vp]),
+    "hd_host_ssdv_make_packet": (None, [C.c_uint8, C.c_char_p, C.c_uint8, C.c_uint16, C.c_uint16, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint16, _vp, _vp]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

@@ -9,6 +9,8 @@
 // a single one, probe_launch), the refusal of a row above max_push (check_max_push), reset and destroy, and the test hooks' guard counter.  Where an
 // object does something of its own, it says so at its own *_launch or door.  The diversity combiner (kernels/combine.hip, host/combine.hpp) is the fifth: it
 // reads float rows as the clocked decoder does (CombineSrc has ClockedSrc's fields), sums the rows of a group of streams and writes rows as the tones do.
+// The SSDV object (kernels/ssdv.hip, host/ssdv.hpp) is the sixth: it takes bytes, not rows -- its doors append on the host -- and shares the doors' checks,
+// the chunked launches (its descriptors' n_total counts candidates), reset, destroy and the guard counter.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -17,9 +19,11 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
+#include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
 #include "kernels/combine.h"
+#include "kernels/ssdv.h"
 #include "kernels/spectrum_math.h"
 #include "kernels/tone_search.h"
 
@@ -1291,6 +1295,274 @@ int hd_debug_combine_guards(hd_combine* c, uint32_t stream)
     at[0] = r32 + (size_t)stream * c->ring_stride / 2; at[1] = at[0] + c->ring_stride / 2 - hd::kCombineGuard;
     at[2] = row + (size_t)stream * c->row_stride; at[3] = at[2] + c->row_stride - hd::kCombineGuard;
     return damaged_guards(at, hd::kCombineGuard, hd::kCombineGuardWord);
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- SSDV packets (kernels/ssdv.hip) -------------------------------------- */
+
+struct hd_ssdv {
+    static constexpr const char* kNull = "null SSDV object";
+    static constexpr uint32_t kStage = 1u << 18;  // words of one scan round's upload
+    hd_engine* e = nullptr;
+    hd_ssdv_params prm{};
+    uint32_t S = 0;
+    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_SSDV_RING words | guard
+    uint32_t* cnt = nullptr;                     // guard | the launch's accepted candidates, [S] crc_bad | guard
+    uint32_t* out = nullptr;                     // guard | HD_SSDV_LAUNCH results (hd::SsdvOut) | guard
+    hd::SsdvTables* tab = nullptr;
+    size_t ring_stride = 0;
+    PinBuf<hd::SsdvSrc> src;                     // [S]: a launch's descriptors, read by the kernels in place (a launch is waited for before the next is written)
+    PinBuf<uint32_t> stage;                      // [kStage]: a round's new words, stream behind stream, read by k_ssdv_append in place
+    std::vector<hd::SsdvStream> st;              // [S]: the doors, the delivery and the counters; `words` holds what is not uploaded yet
+    std::vector<uint64_t> up;                    // [S]: words uploaded since the stream's last reset
+    std::vector<uint32_t> h_cnt;
+    std::vector<hd::SsdvOut> h_out, found;       // a launch's results; a scan's
+    bool launched = false;                       // the last scan launched k_ssdv_scan (the measurement hook's question)
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a scan's last round
+    ~hd_ssdv()
+    {
+        for (void* p : {(void*)ring, (void*)cnt, (void*)out, (void*)tab}) if (p) (void)hipFree(p);
+    }
+};
+
+namespace {
+
+constexpr size_t kSsdvOutWords = sizeof(hd::SsdvOut) / sizeof(uint32_t);
+
+// One round: up to HD_SSDV_RING - 256 new words per stream go up (a ring then holds every word of every candidate the round decides, and the append
+// writes no slot a candidate of an earlier round still needs: those are decided), then every position that is decided now is launched, at most
+// HD_SSDV_LAUNCH candidates over all streams per launch, so that the results of a launch always fit.  Rounds until nothing is left; then the results
+// are sorted by (stream, pos) and delivered -- which packets a scan delivers cannot depend on the order in which waves finished.
+int ssdv_scan(hd_ssdv* v)
+{
+    hipStream_t q = v->e->qa;
+    v->found.clear();
+    v->launched = false;
+    for (;;) {
+        uint32_t used = 0, max_new = 0, max_cand = 0, active = 0;
+        for (uint32_t s = 0; s < v->S; ++s) {
+            hd::SsdvStream& st = v->st[s];
+            hd::SsdvSrc& d = v->src.p[s];
+            const uint32_t take = (uint32_t)std::min<uint64_t>({st.n - v->up[s], (uint64_t)HD_SSDV_RING - 256u, (uint64_t)hd_ssdv::kStage - used});
+            if (take) std::memcpy(v->stage.p + used, st.words.data() + (size_t)(v->up[s] - st.first), (size_t)take * sizeof(uint32_t));
+            d.append_pos = v->up[s]; d.stage_at = used; d.stage_n = take;
+            used += take; v->up[s] += take;
+            st.drop(v->up[s]);
+            d.base = st.decided;
+            d.n_total = v->up[s] >= 256u ? (uint32_t)(v->up[s] - 255u - st.decided) : 0u;
+            d.off = 0; d.n = 0;
+            max_new = std::max(max_new, take); max_cand = std::max(max_cand, d.n_total);
+            active += d.n_total != 0;
+        }
+        if (!max_new && !max_cand) break;
+        std::atomic_thread_fence(std::memory_order_release);
+        hd::launch_ssdv_append(q, v->S, max_new, v->src.dev, v->stage.dev, v->ring, v->ring_stride);
+        HD_HIP(hipGetLastError());
+        if (!max_cand) { HD_HIP(hipStreamSynchronize(q)); continue; }
+        uint32_t cap = 0;
+        hipError_t fetch = hipSuccess;
+        const int rc = launch_chunks(
+            v, max_cand, std::max(1u, (uint32_t)HD_SSDV_LAUNCH / active), "",
+            [&](uint32_t, const hd::SsdvSrc& d) { cap = std::max(cap, d.n); },
+            [&] {
+                if (hipMemsetAsync(v->cnt + hd::kSsdvGuard, 0, (size_t)(1 + v->S) * sizeof(uint32_t), q) != hipSuccess) return false;
+                hd::launch_ssdv_scan(q, v->S, cap, v->src.dev, v->tab, v->ring, v->ring_stride, v->cnt + hd::kSsdvGuard,
+                                     reinterpret_cast<hd::SsdvOut*>(v->out + hd::kSsdvGuard), HD_SSDV_LAUNCH);
+                cap = 0;
+                return true;
+            },
+            [&] {                                // the launch is done: its counters, and its results if it has any
+                if (fetch != hipSuccess) return;
+                fetch = hipMemcpy(v->h_cnt.data(), v->cnt + hd::kSsdvGuard, v->h_cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+                if (fetch != hipSuccess) return;
+                for (uint32_t s = 0; s < v->S; ++s) v->st[s].crc_bad += v->h_cnt[1 + s];
+                const size_t k = std::min<size_t>(v->h_cnt[0], HD_SSDV_LAUNCH);
+                if (!k) return;
+                fetch = hipMemcpy(v->h_out.data(), v->out + hd::kSsdvGuard, k * sizeof(hd::SsdvOut), hipMemcpyDeviceToHost);
+                if (fetch == hipSuccess) v->found.insert(v->found.end(), v->h_out.begin(), v->h_out.begin() + k);
+            });
+        if (rc) return rc;
+        HD_HIP(fetch);
+        v->launched = true;
+        for (uint32_t s = 0; s < v->S; ++s) v->st[s].decided += v->src.p[s].n_total;
+    }
+    std::sort(v->found.begin(), v->found.end(), [](const hd::SsdvOut& a, const hd::SsdvOut& b) { return a.stream != b.stream ? a.stream < b.stream : a.pos < b.pos; });
+    for (const hd::SsdvOut& r : v->found) {
+        if (r.stream >= v->S) continue;
+        hd_ssdv_packet p;
+        std::memset(&p, 0, sizeof p);
+        p.pos = r.pos; p.trial = r.trial; p.errors = r.errors; p.erasures = r.erasures; p.erasures_changed = r.changed;
+        std::memcpy(p.data, r.data, sizeof p.data);
+        hd::ssdv_header(&p);
+        v->st[r.stream].deliver(p);
+    }
+    return HD_OK;
+}
+
+int ssdv_clear(hd_ssdv* v, uint32_t s0, uint32_t ns)
+{
+    for (uint32_t s = s0; s < s0 + ns; ++s) { v->st[s].reset(); v->up[s] = 0; }
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_ssdv_params_default(hd_ssdv_params* p) { if (p) hd::ssdv_params_default(p); }
+
+int hd_ssdv_create(hd_engine* e, const hd_ssdv_params* params, hd_ssdv** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_ssdv> v(new hd_ssdv);
+    v->e = e; v->S = e->S;
+    hd::ssdv_params_default(&v->prm);
+    if (params) v->prm = *params;
+    if (!hd::ssdv_params_ok(&v->prm)) return fail(HD_ERR_INVALID, "SSDV parameters: max_fill <= 64");
+    // (a launch takes at least one candidate of every active stream and its results must fit HD_SSDV_LAUNCH slots)
+    if (e->S > HD_SSDV_LAUNCH) return fail(HD_ERR_UNSUPPORTED, "hd_ssdv_create: at most " + std::to_string(HD_SSDV_LAUNCH) + " streams");
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = v->S;
+    v->st.resize(S); v->up.assign(S, 0);
+    for (auto& st : v->st) st.max_fill = v->prm.max_fill;
+    v->h_cnt.assign(1 + (size_t)S, 0u); v->h_out.resize(HD_SSDV_LAUNCH);
+    v->ring_stride = (size_t)HD_SSDV_RING + 2 * hd::kSsdvGuard;
+    const size_t cnt_words = 1 + (size_t)S + 2 * hd::kSsdvGuard, out_words = (size_t)HD_SSDV_LAUNCH * kSsdvOutWords + 2 * hd::kSsdvGuard;
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->ring), (size_t)S * v->ring_stride * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->cnt), cnt_words * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->out), out_words * sizeof(uint32_t)));
+    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->tab), sizeof(hd::SsdvTables)));
+    HD_HIP(v->src.alloc(S));
+    HD_HIP(v->stage.alloc(hd_ssdv::kStage));
+    std::unique_ptr<hd::SsdvTables> t(new hd::SsdvTables);
+    const hd::SsdvField& F = hd::ssdv_field();
+    for (uint32_t l = 0; l < 64; ++l) {
+        uint8_t pw[4] = {1, 1, 1, 1};
+        for (uint32_t k = 0; k <= 32; ++k) {
+            t->chien[k][l] = (uint32_t)pw[0] | (uint32_t)pw[1] << 8 | (uint32_t)pw[2] << 16 | (uint32_t)pw[3] << 24;
+            for (uint32_t b = 0; b < 4; ++b) pw[b] = F.mul(pw[b], F.loc[255u - (l + 64u * b)]);
+        }
+    }
+    std::memcpy(t->loc, F.loc, sizeof t->loc);
+    for (uint32_t m = 0; m < 32; ++m) {
+        for (uint32_t k = 0; k < 8; ++k) t->rootmul[m][k] = F.mul(F.root[m], F.exp[k]);
+        t->root127[m] = F.exp[((uint32_t)F.log[F.root[m]] * 127u) % 255u];
+    }
+    HD_HIP(hipMemcpyAsync(v->tab, t.get(), sizeof(hd::SsdvTables), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->ring), (int)hd::kSsdvGuardWord, (size_t)S * v->ring_stride, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->cnt), (int)hd::kSsdvGuardWord, cnt_words, e->qa));
+    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->out), (int)hd::kSsdvGuardWord, out_words, e->qa));
+    HD_HIP(hipStreamSynchronize(e->qa));         // (`t` is a local)
+    *out = v.release();
+    return HD_OK;
+}
+
+void hd_ssdv_destroy(hd_ssdv* v) { destroy(v); }
+
+int hd_ssdv_reset(hd_ssdv* v, uint32_t stream) { return reset(v, stream, ssdv_clear); }
+
+int hd_ssdv_push_bytes(hd_ssdv* v, uint32_t stream, const uint8_t* bytes, const uint32_t* conf, size_t n)
+{
+    if (const int rc = check_object(v, stream)) return rc;
+    if (n && !bytes) return fail(HD_ERR_INVALID, "null bytes");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    v->st[stream].push_bytes(bytes, conf, n);
+    return HD_OK;
+}
+
+int hd_ssdv_push_records(hd_ssdv* v, uint32_t stream, const hd_clocked_record* records, size_t n, uint32_t char_len)
+{
+    if (const int rc = check_object(v, stream)) return rc;
+    if (n && !records) return fail(HD_ERR_INVALID, "null records");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    v->st[stream].push_records(records, n, char_len);
+    return HD_OK;
+}
+
+int hd_ssdv_scan(hd_ssdv* v)
+{
+    if (!v) return fail(HD_ERR_INVALID, hd_ssdv::kNull);
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    return ssdv_scan(v);
+}
+
+int hd_ssdv_push_clocked(hd_ssdv* v, hd_clocked* c)
+{
+    if (!v) return fail(HD_ERR_INVALID, hd_ssdv::kNull);
+    if (!c) return fail(HD_ERR_INVALID, hd_clocked::kNull);
+    if (v->e != c->e) return fail(HD_ERR_INVALID, "hd_ssdv_push_clocked: the two objects belong to different engines");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    std::vector<hd::ClockedState> hs(c->S);      // one copy says which streams have records waiting
+    HD_HIP(hipMemcpy(hs.data(), c->st, hs.size() * sizeof(hd::ClockedState), hipMemcpyDeviceToHost));
+    std::vector<hd_clocked_record> buf;
+    for (uint32_t s = 0; s < v->S; ++s) {
+        const hd::ClockedState& m = c->modem[s];
+        if (!m.F || m.nbits != 8u || hs[s].written == hs[s].taken) continue;
+        buf.resize((size_t)(hs[s].written - hs[s].taken));
+        size_t n = 0;
+        if (const int rc = clocked_drain(c, s, buf.data(), buf.size(), &n)) return rc;
+        const uint32_t char_len = (uint32_t)(((uint64_t)(1u + m.nbits + m.nstops) * m.F + 32768u) >> 16);
+        v->st[s].push_records(buf.data(), n, char_len);
+    }
+    return ssdv_scan(v);
+}
+
+int hd_ssdv_take_packets(hd_ssdv* v, uint32_t stream, hd_ssdv_packet* out, size_t cap)
+{
+    if (const int rc = check_object(v, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    return (int)v->st[stream].take(out, cap);
+}
+
+int hd_ssdv_stats(hd_ssdv* v, uint32_t stream, hd_ssdv_counters* out)
+{
+    if (const int rc = check_object(v, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    v->st[stream].stats(out);
+    return HD_OK;
+}
+
+// The measurement hook (tools/micro/ssdv_rate.py; not part of the ABI): hd_ssdv_push_clocked (c null: hd_ssdv_scan), the host time of the whole call
+// in microseconds and the launches of its last round between two HIP events (0 where k_ssdv_scan was not launched).
+int hd_debug_ssdv_scan_timed(hd_ssdv* v, hd_clocked* c, float* kernel_ms, double* host_us)
+{
+    if (!v || !kernel_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    HD_HIP(hipEventCreate(&v->t0));
+    HD_HIP(hipEventCreate(&v->t1));
+    const auto w0 = std::chrono::steady_clock::now();
+    const int rc = c ? hd_ssdv_push_clocked(v, c) : hd_ssdv_scan(v);
+    *host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+    *kernel_ms = 0;
+    if (rc == HD_OK && v->launched && hipEventQuery(v->t1) == hipSuccess) (void)hipEventElapsedTime(kernel_ms, v->t0, v->t1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(v->t0); (void)hipEventDestroy(v->t1);
+    v->t0 = v->t1 = nullptr;
+    return rc;
+}
+
+// Test hook (tests/test_gpu_ssdv.py; not part of the ABI): how many of the guard words around the stream's ring, the counters and the results no longer
+// hold their pattern.
+int hd_debug_ssdv_guards(hd_ssdv* v, uint32_t stream)
+{
+    if (!v || stream >= v->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
+    if (const int rc = enter(v->e)) return rc;
+    const uint32_t* at[6] = {v->ring + (size_t)stream * v->ring_stride, v->ring + (size_t)(stream + 1) * v->ring_stride - hd::kSsdvGuard,
+                             v->cnt, v->cnt + hd::kSsdvGuard + 1 + v->S,
+                             v->out, v->out + hd::kSsdvGuard + (size_t)HD_SSDV_LAUNCH * kSsdvOutWords};
+    return damaged_guards(at, hd::kSsdvGuard, hd::kSsdvGuardWord);
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
+#include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
 #include "host/decim_plan.hpp"
@@ -481,6 +482,54 @@ int hd_host_combine_stats(const hd_host_combine* h, uint32_t m, hd_combine_info*
     if (!h || !out || m >= h->g.count) return HD_ERR_INVALID;
     *out = hd_combine_info{h->g.n, h->g.stream[0], h->g.delay[m], h->g.weight[m], h->g.count};
     return HD_OK;
+}
+
+/* ---- SSDV packets (kernels/ssdv.hip; see host/ssdv.hpp) ---- */
+struct hd_host_ssdv {
+    hd::SsdvStream s;
+};
+hd_host_ssdv* hd_host_ssdv_create(const hd_ssdv_params* params)
+{
+    hd_ssdv_params p;
+    hd::ssdv_params_default(&p);
+    if (params) p = *params;
+    if (!hd::ssdv_params_ok(&p)) return nullptr;
+    auto* h = new hd_host_ssdv;
+    h->s.max_fill = p.max_fill;
+    return h;
+}
+void hd_host_ssdv_destroy(hd_host_ssdv* h) { delete h; }
+void hd_host_ssdv_reset(hd_host_ssdv* h) { if (h) h->s.reset(); }
+int hd_host_ssdv_push_bytes(hd_host_ssdv* h, const uint8_t* bytes, const uint32_t* conf, size_t n)
+{
+    if (!h || (n && !bytes)) return HD_ERR_INVALID;
+    h->s.push_bytes(bytes, conf, n);
+    h->s.scan();
+    return HD_OK;
+}
+int hd_host_ssdv_push_records(hd_host_ssdv* h, const hd_clocked_record* records, size_t n, uint32_t char_len)
+{
+    if (!h || (n && !records)) return HD_ERR_INVALID;
+    h->s.push_records(records, n, char_len);
+    h->s.scan();
+    return HD_OK;
+}
+int hd_host_ssdv_take_packets(hd_host_ssdv* h, hd_ssdv_packet* out, size_t cap)
+{
+    if (!h) return HD_ERR_INVALID;
+    return (int)h->s.take(out, cap);
+}
+int hd_host_ssdv_stats(const hd_host_ssdv* h, hd_ssdv_counters* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    h->s.stats(out);
+    return HD_OK;
+}
+void hd_host_ssdv_encode(const uint8_t* data223, uint8_t* parity32) { if (data223 && parity32) hd::ssdv_encode(data223, parity32); }
+void hd_host_ssdv_make_packet(uint8_t type, const char* callsign, uint8_t image_id, uint16_t packet_id, uint16_t width, uint16_t height, uint8_t flags,
+                              uint8_t mcu_offset, uint16_t mcu_index, const uint8_t* payload205, uint8_t* out256)
+{
+    if (payload205 && out256) hd::ssdv_make_packet(type, callsign, image_id, packet_id, width, height, flags, mcu_offset, mcu_index, payload205, out256);
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

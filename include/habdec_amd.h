@@ -836,6 +836,82 @@ int  hd_combine_lags(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p
 /* hd_combine_lags, then the align step.  Returns the number of valid entries (the reference's among them), or HD_ERR_*. */
 int  hd_combine_align(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, hd_combine_lag* out, size_t cap);
 
+/* ---- SSDV packets: Reed-Solomon decoding with soft erasures (the reference's ssdv_callback_ side channel; built from the published format) ----
+ * tones -> combine -> clocked -> SSDV.  Picture payloads send the same RTTY bytes as telemetry, but as 256-byte SSDV packets, each an RS(255,223)
+ * codeword behind a sync byte.  An SSDV object is attached to an engine like a clocked decoder (its device, mutex and first queue; destroy it before the
+ * engine).  Its input is bytes with a confidence each -- above all the clocked decoder's records, whose soft values say which bytes to erase and whose
+ * positions say where a character was lost -- and its output is whole corrected packets, the 256 bytes an SSDV server takes.  JPEG reassembly is not
+ * built, and the facade's ssdv_callback_ still never fires.  No copy of the fsphil/ssdv library is at hand: agreement with it rests on the published
+ * format alone.  Kernel (kernels/ssdv.hip), host restatement (hd_host_ssdv_*) and a numpy model agree byte for byte on all of the following.
+ *  - Stream: per engine stream a sequence of pairs (b_i, c_i); i is the absolute byte index since the stream's last reset (uint64), b_i a byte, c_i a
+ *    confidence in 0 .. 0xFFFFFF (the push doors saturate it).  How a stream is cut into pushes and scans cannot matter.
+ *  - Code: GF(2^8) modulo x^8 + x^7 + x^2 + x + 1 (0x187), alpha = 0x02.  The received word of candidate i is r_j = b_{i+j}, j = 1 .. 255; as a
+ *    polynomial r_1 is the coefficient of x^254 and r_255 that of x^0.  A codeword is a word whose polynomial vanishes at alpha^(11 (112 + m)),
+ *    m = 0 .. 31: the CCSDS (255,223) code in the conventional basis.  Bytes 1 .. 223 are data, 224 .. 255 parity.  CRC: CRC-32 (reflected, polynomial
+ *    0xEDB88320, initial value and final xor 0xFFFFFFFF) over bytes 1 .. 219, stored big-endian in bytes 220 .. 223.  Byte 0 is the sync byte 0x55; no
+ *    code covers it.  (The generator polynomial is palindromic, 1, 91, 127, 86, 16, 30, ...; an encoded packet has 32 zero syndromes.)
+ *  - Candidates: position i is decided once i + 256 <= n, n = bytes pushed.  Every position is a candidate: a sync gate would throw away packets the
+ *    code can repair.
+ *  - Trials, in this order, the first that succeeds wins.  No-FEC: if b_i == 0x55 and b_{i+1} == 0x67 and the CRC of bytes 1 .. 219 as received
+ *    matches: trial = HD_SSDV_NOFEC (255), nothing corrected.  Then t = 0, 1, 2, 3 with f_t = 0, 8, 16, 24 erasures: E_t is the set of the f_t positions
+ *    j in 1 .. 255 with the smallest key (c_{i+j} << 8) | j.  The trial succeeds iff there is a codeword w with e = |{ j not in E_t : w_j != r_j }| and
+ *    2 e + f_t <= 32 (such a w is unique) and w's CRC matches.  A codeword whose CRC is wrong: crc_bad += 1 and the next trial runs.  (A decoder may
+ *    skip work whose outcome it knows -- 32 zero syndromes, say; the outcomes are what is defined.)
+ *  - Packet: pos = i, trial, errors = e, erasures = f_t, erasures_changed = the erased positions whose byte changed, type = w_1, data[256] = 0x55
+ *    followed by w (even where b_i was something else), and the header: callsign from bytes 2 .. 5, a big-endian uint32 in base 40, digits taken least
+ *    significant first while the value is not 0 (0 '-', 1 .. 10 '0' .. '9', 11 .. 13 '-', 14 .. 39 'A' .. 'Z'); image id byte 6; packet id bytes 7 .. 8
+ *    big-endian; width byte 9 * 16; height byte 10 * 16; flags byte 11; MCU offset byte 12; MCU index bytes 13 .. 14 big-endian.  After the CRC no field
+ *    is tested for plausibility.
+ *  - Delivery: per stream, results are taken in increasing pos; a result with pos < (pos of the last delivered packet) + 256 is dropped, overlaps += 1.
+ *    Which packets a scan delivers does not depend on the order in which waves finish.  Packets wait on the host until hd_ssdv_take_packets.
+ *  - Counters per stream: bytes (n, fillers among them), decided, fillers, crc_bad, overlaps, packets[5] (delivered, by trial 0 .. 3, then no-FEC).
+ *  - False accepts: a random word decodes to some codeword with probability 2.6e-14, 9.9e-10, 1.2e-5 and 2.6e-2 at f = 0, 8, 16, 24 (NOTES.md derives
+ *    it: below 1e-4 up to f = 16, not at 24), and the CRC-32 then passes with probability 2^-32: 6e-12 per candidate over the four trials, beside the
+ *    clocked decoder's 0.14 % per failed match.
+ *  - Doors: the push doors append on the host; a scan uploads what is new, launches once for all streams (in chunks of at most HD_SSDV_LAUNCH
+ *    candidates), waits and collects.  hd_ssdv_push_records: b = ch & 0xFF, c = min(0xFFFFFF, min over k < 8 of |data_k|).  Gap rule: the door remembers
+ *    the pos of the stream's last record across pushes; for a record at pos after one at prev, k = (pos - prev + char_len / 2) / char_len in integer
+ *    division; if 2 <= k <= 1 + max_fill, k - 1 fillers (b = 0, c = 0) go in front of the record and fillers += k - 1; a larger k is a pause in
+ *    transmission and inserts nothing; char_len = 0 switches the rule off.  hd_ssdv_push_clocked: for every stream whose clocked modem has 8 data bits
+ *    it takes all waiting records exactly as hd_clocked_records does (they pass through the clocked text stage, so sentences are unaffected), pushes
+ *    them with char_len = (K F + 32768) >> 16 of that stream's clock, then scans; streams with 7 data bits are passed by.
+ *  - Queue, errors: as the clocked decoder's; a scan returns when its kernels are done. */
+#define HD_SSDV_NOFEC 255u         /* hd_ssdv_packet.trial of a packet accepted without the code */
+#define HD_SSDV_TYPE_NOFEC 0x67u
+#define HD_SSDV_RING 4096          /* per-stream bytes on the GPU */
+#define HD_SSDV_LAUNCH 16384       /* candidates per launch over all streams */
+typedef struct hd_ssdv hd_ssdv;
+typedef struct hd_ssdv_params {
+    uint32_t max_fill;         /* the gap rule's longest run of fillers; default 7, at most 64, 0: none */
+    uint32_t _pad;
+} hd_ssdv_params;
+typedef struct hd_ssdv_packet {
+    uint64_t pos;
+    uint32_t trial;            /* 0 .. 3, or HD_SSDV_NOFEC */
+    uint32_t errors, erasures, erasures_changed;
+    uint32_t type;
+    uint32_t image_id, packet_id, width, height, flags, mcu_offset, mcu_index;
+    char     callsign[8];      /* NUL-terminated */
+    uint8_t  data[256];
+} hd_ssdv_packet;
+typedef struct hd_ssdv_counters {
+    uint64_t bytes, decided, fillers, crc_bad, overlaps;
+    uint64_t packets[5];
+} hd_ssdv_counters;
+void hd_ssdv_params_default(hd_ssdv_params* p);
+int  hd_ssdv_create(hd_engine* e, const hd_ssdv_params* p /* null: the defaults */, hd_ssdv** out);   /* HD_ERR_UNSUPPORTED: more than HD_SSDV_LAUNCH streams */
+void hd_ssdv_destroy(hd_ssdv* v);
+/* Bytes, counters, the gap rule's memory and the delivery's last pos of the stream start again; packets not yet taken stay. */
+int  hd_ssdv_reset(hd_ssdv* v, uint32_t stream /* UINT32_MAX: all */);
+int  hd_ssdv_push_bytes(hd_ssdv* v, uint32_t stream, const uint8_t* bytes, const uint32_t* conf /* null: every c = 0xFFFFFF */, size_t n);
+int  hd_ssdv_push_records(hd_ssdv* v, uint32_t stream, const hd_clocked_record* records, size_t n, uint32_t char_len);
+/* HD_ERR_INVALID unless both objects belong to one engine. */
+int  hd_ssdv_push_clocked(hd_ssdv* v, hd_clocked* c);
+int  hd_ssdv_scan(hd_ssdv* v);
+/* Hands out up to cap of the stream's waiting packets, oldest first, and returns how many were written; out null: how many wait.  Negative: HD_ERR_*. */
+int  hd_ssdv_take_packets(hd_ssdv* v, uint32_t stream, hd_ssdv_packet* out, size_t cap);
+int  hd_ssdv_stats(hd_ssdv* v, uint32_t stream, hd_ssdv_counters* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,6 +272,25 @@ int    hd_host_combine_align(hd_host_combine*, const hd_combine_lag_params* p, h
 int    hd_host_combine_scores(const hd_host_combine*, uint32_t m, int32_t* out, size_t cap);
 int    hd_host_combine_stats(const hd_host_combine*, uint32_t m, hd_combine_info* out);
 
+/* ---- SSDV packets (hd_ssdv_*, include/habdec_amd.h has the definition): one stream of it in plain C++, candidate by candidate ----
+ * The doors, the gap rule, the delivery and the counters are the code the engine's object runs; the decoder restates the kernel by another route (log
+ * tables, Berlekamp-Massey with an inverse) and the same pushes give the same packets and counters byte for byte.  hd_host_ssdv_create: NULL for
+ * parameters hd_ssdv_create refuses.  Every push door scans.  hd_host_ssdv_encode: the 32 parity bytes (bytes 224 .. 255) of 223 data bytes.
+ * hd_host_ssdv_make_packet: sync byte, type, the header fields, 205 payload bytes, CRC-32 and parity; a packet of type 0x67 (no-FEC) carries zeros where
+ * the parity would be.  The callsign: its first 6 characters count, letters in either case and digits; any other character is stored as digit 0 and
+ * reads back as '-'. */
+typedef struct hd_host_ssdv hd_host_ssdv;
+hd_host_ssdv* hd_host_ssdv_create(const hd_ssdv_params* params);
+void   hd_host_ssdv_destroy(hd_host_ssdv*);
+void   hd_host_ssdv_reset(hd_host_ssdv*);
+int    hd_host_ssdv_push_bytes(hd_host_ssdv*, const uint8_t* bytes, const uint32_t* conf, size_t n);
+int    hd_host_ssdv_push_records(hd_host_ssdv*, const hd_clocked_record* records, size_t n, uint32_t char_len);
+int    hd_host_ssdv_take_packets(hd_host_ssdv*, hd_ssdv_packet* out, size_t cap);
+int    hd_host_ssdv_stats(const hd_host_ssdv*, hd_ssdv_counters* out);
+void   hd_host_ssdv_encode(const uint8_t* data223, uint8_t* parity32);
+void   hd_host_ssdv_make_packet(uint8_t type, const char* callsign, uint8_t image_id, uint16_t packet_id, uint16_t width, uint16_t height, uint8_t flags,
+                                uint8_t mcu_offset, uint16_t mcu_index, const uint8_t* payload205, uint8_t* out256);
+
 #ifdef __cplusplus
 }
 #endif
