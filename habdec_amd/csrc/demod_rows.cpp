@@ -6,7 +6,8 @@
 // descriptors, launch on the engine's first queue and wait for it.  They differ in the descriptor (launch.h: ProbeSrc, ClockedSrc, TonesSrc;
 // tone_search.h: ToneSearchSrc), in the rows' element (float, or float2 for cf32) and in what they launch; the rest is the helpers below: the doors'
 // checks (check_object), the three push doors and the timed one (push_engine, push_rows, push_timed), the launches of a push (launch_chunks; the probe's is
-// a single one, probe_launch), the refusal of a row above max_push (check_max_push), reset and destroy, and the test hooks' guard counter.  Where an
+// a single one, probe_launch), the refusal of a row above max_push (check_max_push), reset and destroy, and the test hooks' guard counter.  Device memory
+// is held in DevBuf and, where the kernels' rows lie between guard words, Guarded (engine_state.h): no object frees anything by hand.  Where an
 // object does something of its own, it says so at its own *_launch or door.  The diversity combiner (kernels/combine.hip, host/combine.hpp) is the fifth: it
 // reads float rows as the clocked decoder does (CombineSrc has ClockedSrc's fields), sums the rows of a group of streams and writes rows as the tones do.
 // The SSDV object (kernels/ssdv.hip, host/ssdv.hpp) is the sixth: it takes bytes, not rows -- its doors append on the host -- and shares the doors' checks,
@@ -24,7 +25,6 @@
 #include "host/tone_search.hpp"
 #include "kernels/combine.h"
 #include "kernels/ssdv.h"
-#include "kernels/spectrum_math.h"
 #include "kernels/tone_search.h"
 
 using hd::eng::enter;
@@ -64,7 +64,7 @@ uint32_t src_from_engine_iq(hd_engine* e, uint32_t s, Src& d)
 uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::TonesSrc& d) { return src_from_engine_iq(e, s, d); }
 uint32_t src_from_engine(hd_engine* e, uint32_t s, hd::ToneSearchSrc& d) { return src_from_engine_iq(e, s, d); }
 
-// The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab / slab_n, pushed_calls and t0 / t1 under these names, and
+// The helpers take any of the objects: all carry e, S, src (PinBuf of the descriptors), slab (DevBuf), pushed_calls and t0 / t1 under these names, and
 // kNull, the doors' message for a null object.
 
 // What every door that names a stream tests first, in this order: the object, then the stream's range (all: UINT32_MAX, every stream, passes too).
@@ -113,17 +113,13 @@ int push_rows(Obj* o, const T* rows, size_t stride, const uint32_t* n_per_stream
     if (const int rc = enter(o->e)) return rc;
     if (!total) return HD_OK;                  // nothing to read: before the device-pointer check
     if (device && !is_device_pointer(rows)) return fail(HD_ERR_INVALID, "rows are not device memory (the _host call takes host memory)");
-    if (!device && total > o->slab_n) {
-        if (o->slab) { (void)hipFree(o->slab); o->slab = nullptr; o->slab_n = 0; }
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&o->slab), total * sizeof(T)));
-        o->slab_n = total;
-    }
+    if (!device) HD_HIP(o->slab.grow(total));
     size_t at = 0;
     for (uint32_t s = 0; s < o->S; ++s) {
         auto& d = o->src.p[s];
         const uint32_t ns = n_per_stream ? n_per_stream[s] : n;
-        src_set(d, device ? rows + (size_t)s * stride : o->slab + at, ns);
-        if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab + at, rows + (size_t)s * stride, (size_t)ns * sizeof(T), hipMemcpyHostToDevice, o->e->qa));
+        src_set(d, device ? rows + (size_t)s * stride : o->slab.p + at, ns);
+        if (!device && ns) HD_HIP(hipMemcpyAsync(o->slab.p + at, rows + (size_t)s * stride, (size_t)ns * sizeof(T), hipMemcpyHostToDevice, o->e->qa));
         at += ns;
     }
     return launch(o, max_n);
@@ -206,18 +202,54 @@ int reset(Obj* o, uint32_t stream, Clear clear)
     return stream == UINT32_MAX ? clear(o, 0, o->S) : clear(o, stream, 1);
 }
 
-// The test hooks hd_debug_*_guards (not part of the ABI): how many of the `words` guard words at each of the addresses no longer hold `pattern`.  Which
-// addresses an object guards is its own list; the patterns and widths are the kernels' (launch.h, tone_search.h).
-template <size_t N>
-int damaged_guards(const uint32_t* const (&at)[N], uint32_t words, uint32_t pattern)
+// The test hooks hd_debug_*_guards (not part of the ABI): how many guard words in front of and behind each of the rows no longer hold their array's
+// pattern.  Which rows an object guards is its own list; where a row's guards lie, how wide they are and what they hold is its array's (Guarded).
+int damaged_guards(std::initializer_list<GuardedRow> rows)
 {
-    std::vector<uint32_t> g(words);
+    std::vector<uint32_t> g;
     int bad = 0;
-    for (const uint32_t* p : at) {
-        HD_HIP(hipMemcpy(g.data(), p, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (uint32_t w : g) bad += w != pattern;
-    }
+    for (const GuardedRow& r : rows)
+        for (const uint32_t* p : {r.front, r.back}) {
+            g.resize(r.G);
+            HD_HIP(hipMemcpy(g.data(), p, r.G * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (uint32_t w : g) bad += w != r.pattern;
+        }
     return bad;
+}
+
+// hd_*_create of the objects that write or refuse by max_push: 0 is the default, what the engine's longest call leaves or 4096; above 2^28 it is refused.
+// who: the object in the message.
+int default_max_push(const hd_engine* e, uint32_t* max_push, const char* who)
+{
+    if (!*max_push) *max_push = std::max<uint32_t>(e->n2_cap, 4096u);
+    if (*max_push > (1u << 28)) return fail(HD_ERR_INVALID, std::string(who) + " parameters: max_push <= 2^28");
+    return HD_OK;
+}
+
+// hd_tones_rows / hd_combine_rows: the rows the object's last push wrote, in place.  Both objects carry them as rows (Guarded<float>) and row_n.
+template <typename Obj>
+int output_rows(Obj* o, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
+{
+    if (!o) return fail(HD_ERR_INVALID, Obj::kNull);
+    if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(o->e->mtx);
+    *d_rows = o->rows.row(0);
+    *stride = o->rows.stride;
+    std::memcpy(n_per_stream, o->row_n.data(), (size_t)o->S * sizeof(uint32_t));
+    return HD_OK;
+}
+
+// hd_tones_output / hd_combine_output: one of those rows to the host; returns its length, whatever cap let through.
+template <typename Obj>
+int output_row(Obj* o, uint32_t stream, float* out, size_t cap)
+{
+    if (const int rc = check_object(o, stream)) return rc;
+    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(o->e->mtx);
+    if (const int rc = enter(o->e)) return rc;
+    const size_t k = std::min<size_t>(o->row_n[stream], cap);
+    if (k) HD_HIP(hipMemcpy(out, o->rows.row(stream), k * sizeof(float), hipMemcpyDeviceToHost));
+    return (int)o->row_n[stream];
 }
 
 // hd_*_destroy.  (No queue to wait for: every push has waited for its launches.)
@@ -241,20 +273,15 @@ struct hd_baud_probe {
     hd_baud_probe_params prm{};
     hd::BaudProbeTables t;
     uint32_t S = 0;
-    hd_baud_probe_stream_state* hdr = nullptr;   // [S]
-    unsigned long long* acc64 = nullptr;         // [S][2][1024]: P, Q
-    uint32_t* acc32 = nullptr;                   // [S][5][1024]: NB, re, im, n, cur_block
-    uint32_t *F = nullptr, *scale = nullptr;
-    int32_t* ctab = nullptr;
-    float* slab = nullptr;                       // hd_baud_probe_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
+    DevBuf<hd_baud_probe_stream_state> hdr;      // [S]
+    DevBuf<unsigned long long> acc64;            // [S][2][1024]: P, Q
+    DevBuf<uint32_t> acc32;                      // [S][5][1024]: NB, re, im, n, cur_block
+    DevBuf<uint32_t> F, scale;
+    DevBuf<int32_t> ctab;
+    DevBuf<float> slab;                          // hd_baud_probe_push_host: the rows packed end to end, grown on demand
     PinBuf<hd::ProbeSrc> src;                    // [S]: the push's descriptors, read by the kernel in place (a push returns when its kernel is done)
     uint64_t pushed_calls = 0;                   // hd_baud_probe_push_engine: e->calls at the last push (the call delivered last is calls - 1)
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launch
-    ~hd_baud_probe()
-    {
-        for (void* p : {(void*)hdr, (void*)acc64, (void*)acc32, (void*)F, (void*)scale, (void*)ctab, (void*)slab}) if (p) (void)hipFree(p);
-    }
 };
 
 namespace {
@@ -266,7 +293,7 @@ int probe_launch(hd_baud_probe* p, uint32_t max_n)
     if (!max_n) return HD_OK;
     std::atomic_thread_fence(std::memory_order_release);
     if (p->t0) HD_HIP(hipEventRecord(p->t0, p->e->qa));
-    hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr, p->acc64, p->acc32, p->F, p->scale, p->ctab);
+    hd::launch_baud_probe(p->e->qa, p->S, p->src.dev, p->hdr.p, p->acc64.p, p->acc32.p, p->F.p, p->scale.p, p->ctab.p);
     if (p->t1) HD_HIP(hipEventRecord(p->t1, p->e->qa));
     HD_HIP(hipGetLastError());
     HD_HIP(hipStreamSynchronize(p->e->qa));
@@ -276,9 +303,9 @@ int probe_launch(hd_baud_probe* p, uint32_t max_n)
 int probe_clear(hd_baud_probe* p, uint32_t s0, uint32_t ns)
 {
     hipStream_t q = p->e->qa;
-    HD_HIP(hipMemsetAsync(p->hdr + s0, 0, (size_t)ns * sizeof(hd_baud_probe_stream_state), q));
-    HD_HIP(hipMemsetAsync(p->acc64 + (size_t)s0 * 2 * hd::kProbeCand, 0, (size_t)ns * 2 * hd::kProbeCand * sizeof(unsigned long long), q));
-    HD_HIP(hipMemsetAsync(p->acc32 + (size_t)s0 * 5 * hd::kProbeCand, 0, (size_t)ns * 5 * hd::kProbeCand * sizeof(uint32_t), q));
+    HD_HIP(hipMemsetAsync(p->hdr.p + s0, 0, (size_t)ns * sizeof(hd_baud_probe_stream_state), q));
+    HD_HIP(hipMemsetAsync(p->acc64.p + (size_t)s0 * 2 * hd::kProbeCand, 0, (size_t)ns * 2 * hd::kProbeCand * sizeof(unsigned long long), q));
+    HD_HIP(hipMemsetAsync(p->acc32.p + (size_t)s0 * 5 * hd::kProbeCand, 0, (size_t)ns * 5 * hd::kProbeCand * sizeof(uint32_t), q));
     HD_HIP(hipStreamSynchronize(q));
     return HD_OK;
 }
@@ -304,16 +331,16 @@ int hd_baud_probe_create(hd_engine* e, const hd_baud_probe_params* params, hd_ba
     p->t.make(e->fsd, p->prm);
     std::vector<uint32_t> sc(hd::kProbeCand);
     for (uint32_t k = 0; k < hd::kProbeCand; ++k) sc[k] = p->t.scale[k];
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->hdr), (size_t)p->S * sizeof(hd_baud_probe_stream_state)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc64), (size_t)p->S * 2 * hd::kProbeCand * sizeof(unsigned long long)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->acc32), (size_t)p->S * 5 * hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->F), hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->scale), hd::kProbeCand * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&p->ctab), 1024 * sizeof(int32_t)));
+    HD_HIP(p->hdr.alloc_unfilled(p->S));
+    HD_HIP(p->acc64.alloc_unfilled((size_t)p->S * 2 * hd::kProbeCand));
+    HD_HIP(p->acc32.alloc_unfilled((size_t)p->S * 5 * hd::kProbeCand));
+    HD_HIP(p->F.alloc_unfilled(hd::kProbeCand));
+    HD_HIP(p->scale.alloc_unfilled(hd::kProbeCand));
+    HD_HIP(p->ctab.alloc_unfilled(1024));
     HD_HIP(p->src.alloc(p->S));
-    HD_HIP(hipMemcpyAsync(p->F, p->t.F, hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemcpyAsync(p->scale, sc.data(), hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemcpyAsync(p->ctab, p->t.C, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->F.p, p->t.F, hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->scale.p, sc.data(), hd::kProbeCand * sizeof(uint32_t), hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(p->ctab.p, p->t.C, 1024 * sizeof(int32_t), hipMemcpyHostToDevice, e->qa));
     if (const int rc = probe_clear(p.get(), 0, p->S)) return rc;       // (waits for the queue: `sc` is a local)
     p->pushed_calls = 0;
     *out = p.release();
@@ -345,9 +372,9 @@ int hd_baud_probe_state(hd_baud_probe* p, uint32_t stream, hd_baud_probe_stream_
     hd_baud_probe_stream_state h;
     std::vector<unsigned long long> a64(2 * hd::kProbeCand);
     std::vector<uint32_t> a32(5 * hd::kProbeCand);
-    HD_HIP(hipMemcpy(&h, p->hdr + stream, sizeof h, hipMemcpyDeviceToHost));
-    HD_HIP(hipMemcpy(a64.data(), p->acc64 + (size_t)stream * a64.size(), a64.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HD_HIP(hipMemcpy(a32.data(), p->acc32 + (size_t)stream * a32.size(), a32.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(&h, p->hdr.p + stream, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a64.data(), p->acc64.p + (size_t)stream * a64.size(), a64.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(a32.data(), p->acc32.p + (size_t)stream * a32.size(), a32.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     h.n_candidates = hd::kProbeCand;
     if (hdr) *hdr = h;
     for (uint32_t k = 0; cand && k < hd::kProbeCand; ++k) {
@@ -382,22 +409,19 @@ struct hd_clocked {
     hd_engine* e = nullptr;
     hd_clocked_params prm{};
     uint32_t S = 0;
-    hd::ClockedState* st = nullptr;              // [S]
-    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_CLOCKED_RING running sums | guard
-    uint32_t* rec = nullptr;                     // [S][rec_stride]: guard | record_cap records | guard
-    size_t ring_stride = 0, rec_stride = 0;
-    float* slab = nullptr;                       // hd_clocked_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
+    DevBuf<hd::ClockedState> st;                 // [S]
+    Guarded<uint32_t> ring;                      // [S]: guard | HD_CLOCKED_RING running sums | guard
+    Guarded<uint32_t> rec;                       // [S]: guard | record_cap records | guard
+    DevBuf<float> slab;                          // hd_clocked_push_host: the rows packed end to end, grown on demand
     PinBuf<hd::ClockedSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
     std::vector<hd::ClockedState> modem;         // [S]: the state a reset gives the stream (F = 0: off)
     std::vector<hd::ClockedText> tx;             // [S]
     uint64_t pushed_calls = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
-    ~hd_clocked()
-    {
-        for (void* p : {(void*)st, (void*)ring, (void*)rec, (void*)slab}) if (p) (void)hipFree(p);
-    }
 };
+// (the strides the kernel was written against, launch.h)
+static_assert(Guarded<uint32_t>::stride_of(HD_CLOCKED_RING, hd::kClockedGuard) == HD_CLOCKED_RING + 2 * hd::kClockedGuard, "clocked ring stride");
+static_assert(Guarded<uint32_t>::stride_of(1024 * hd::kClockedRecWords, hd::kClockedGuard) == 1024 * hd::kClockedRecWords + 2 * hd::kClockedGuard, "clocked record stride");
 
 namespace {
 
@@ -413,7 +437,7 @@ int clocked_launch(hd_clocked* c, uint32_t max_n)
         [&] {
             const uint32_t words = lds_words;
             lds_words = 64;
-            return hd::launch_clocked(c->e->qa, c->S, c->src.dev, c->st, c->ring, c->ring_stride, c->rec, c->rec_stride, c->prm.record_cap, words);
+            return hd::launch_clocked(c->e->qa, c->S, c->src.dev, c->st.p, c->ring.base(), c->ring.stride, c->rec.base(), c->rec.stride, c->prm.record_cap, words);
         },
         [] {});
 }
@@ -421,8 +445,8 @@ int clocked_launch(hd_clocked* c, uint32_t max_n)
 int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
 {
     hipStream_t q = c->e->qa;
-    HD_HIP(hipMemcpyAsync(c->st + s0, c->modem.data() + s0, (size_t)ns * sizeof(hd::ClockedState), hipMemcpyHostToDevice, q));
-    HD_HIP(hipMemset2DAsync(c->ring + (size_t)s0 * c->ring_stride + hd::kClockedGuard, c->ring_stride * sizeof(uint32_t), 0,
+    HD_HIP(hipMemcpyAsync(c->st.p + s0, c->modem.data() + s0, (size_t)ns * sizeof(hd::ClockedState), hipMemcpyHostToDevice, q));
+    HD_HIP(hipMemset2DAsync(c->ring.row(s0), c->ring.stride * sizeof(uint32_t), 0,
                             (size_t)HD_CLOCKED_RING * sizeof(uint32_t), ns, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t s = s0; s < s0 + ns; ++s) { c->tx[s].reset(); c->tx[s].nbits = c->modem[s].nbits; }
@@ -433,13 +457,13 @@ int clocked_clear(hd_clocked* c, uint32_t s0, uint32_t ns)
 int clocked_drain(hd_clocked* c, uint32_t s, hd_clocked_record* out, size_t cap, size_t* n_out)
 {
     hd::ClockedState h;
-    HD_HIP(hipMemcpy(&h, c->st + s, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(&h, c->st.p + s, sizeof h, hipMemcpyDeviceToHost));
     const uint64_t have = h.written - h.taken, rc = c->prm.record_cap;
     const size_t k = out ? (size_t)std::min<uint64_t>(have, cap) : (size_t)have;
     *n_out = k;
     if (!k) return HD_OK;
     std::vector<hd_clocked_record> tmp(k);
-    const uint32_t* base = c->rec + (size_t)s * c->rec_stride + hd::kClockedGuard;
+    const uint32_t* base = c->rec.row(s);
     for (size_t i = 0; i < k;) {             // at most two pieces: the ring wraps once inside record_cap records
         const uint64_t slot = (h.taken + i) % rc;
         const size_t m = (size_t)std::min<uint64_t>(k - i, rc - slot);
@@ -447,7 +471,7 @@ int clocked_drain(hd_clocked* c, uint32_t s, hd_clocked_record* out, size_t cap,
         i += m;
     }
     h.taken += k;
-    HD_HIP(hipMemcpy(reinterpret_cast<char*>(c->st + s) + offsetof(hd::ClockedState, taken), &h.taken, sizeof h.taken, hipMemcpyHostToDevice));
+    HD_HIP(hipMemcpy(reinterpret_cast<char*>(c->st.p + s) + offsetof(hd::ClockedState, taken), &h.taken, sizeof h.taken, hipMemcpyHostToDevice));
     c->tx[s].feed(tmp.data(), k);
     if (out) std::memcpy(out, tmp.data(), k * sizeof(hd_clocked_record));
     return HD_OK;
@@ -479,14 +503,10 @@ int hd_clocked_create(hd_engine* e, const hd_clocked_params* params, hd_clocked*
         hd::clocked_state_reset(c->modem[s], F, F ? nbits : 0u, F ? (uint32_t)nstops : 0u, 0u);
         c->tx[s].repair_bits = c->prm.repair_bits; c->tx[s].repair_flips = c->prm.repair_flips;
     }
-    c->ring_stride = (size_t)HD_CLOCKED_RING + 2 * hd::kClockedGuard;
-    c->rec_stride = (size_t)c->prm.record_cap * hd::kClockedRecWords + 2 * hd::kClockedGuard;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->st), (size_t)c->S * sizeof(hd::ClockedState)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)c->S * c->ring_stride * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rec), (size_t)c->S * c->rec_stride * sizeof(uint32_t)));
+    HD_HIP(c->st.alloc_unfilled(c->S));
+    HD_HIP(c->ring.alloc(c->S, HD_CLOCKED_RING, hd::kClockedGuard, hd::kClockedGuardWord, e->qa));
+    HD_HIP(c->rec.alloc(c->S, (size_t)c->prm.record_cap * hd::kClockedRecWords, hd::kClockedGuard, hd::kClockedGuardWord, e->qa));
     HD_HIP(c->src.alloc(c->S));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kClockedGuardWord, (size_t)c->S * c->ring_stride, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rec), (int)hd::kClockedGuardWord, (size_t)c->S * c->rec_stride, e->qa));
     if (const int rc = clocked_clear(c.get(), 0, c->S)) return rc;
     *out = c.release();
     return HD_OK;
@@ -526,7 +546,7 @@ int hd_clocked_records(hd_clocked* c, uint32_t stream, hd_clocked_record* out, s
     if (const int rc = enter(c->e)) return rc;
     if (!out) {
         hd::ClockedState h;
-        HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+        HD_HIP(hipMemcpy(&h, c->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
         return (int)(h.written - h.taken);
     }
     size_t n = 0;
@@ -552,7 +572,7 @@ int hd_clocked_stats(hd_clocked* c, uint32_t stream, hd_clocked_counters* out)
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
     hd::ClockedState h;
-    HD_HIP(hipMemcpy(&h, c->st + stream, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(&h, c->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
     const hd::ClockedText& t = c->tx[stream];
     *out = hd_clocked_counters{h.n, h.p, h.chars, h.rejects, h.dropped, t.matches_failed, t.plain, t.repaired};
     return HD_OK;
@@ -566,9 +586,7 @@ int hd_debug_clocked_guards(hd_clocked* c, uint32_t stream)
     if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
-    const uint32_t* at[4] = {c->ring + (size_t)stream * c->ring_stride, c->ring + (size_t)(stream + 1) * c->ring_stride - hd::kClockedGuard,
-                             c->rec + (size_t)stream * c->rec_stride, c->rec + (size_t)(stream + 1) * c->rec_stride - hd::kClockedGuard};
-    return damaged_guards(at, hd::kClockedGuard, hd::kClockedGuardWord);
+    return damaged_guards({{c->ring, stream}, {c->rec, stream}});
 }
 
 }  // extern "C"
@@ -580,25 +598,23 @@ struct hd_tones {
     hd_engine* e = nullptr;
     hd_tones_params prm{};
     uint32_t S = 0;
-    hd::TonesState* st = nullptr;                // [S]
-    uint32_t* ring32 = nullptr;                  // [S][4][ring32_stride]: guard | kTonesRing32 running sums | guard
-    unsigned long long* ring64 = nullptr;        // [S][ring64_stride]: guard | kTonesRing64 running sums | guard
-    int32_t* ctab = nullptr;                     // [1024]
-    float* rows = nullptr;                       // [S][row_stride]: guard | max_push floats | guard
-    size_t ring32_stride = 0, ring64_stride = 0, row_stride = 0;
-    float2* slab = nullptr;                      // hd_tones_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
+    DevBuf<hd::TonesState> st;                   // [S]
+    Guarded<uint32_t> ring32;                    // [S * 4]: guard | kTonesRing32 running sums | guard
+    Guarded<unsigned long long> ring64;          // [S]: guard | kTonesRing64 running sums | guard
+    DevBuf<int32_t> ctab;                        // [1024]
+    Guarded<float> rows;                         // [S]: guard | max_push floats | guard
+    DevBuf<float2> slab;                         // hd_tones_push_host: the rows packed end to end, grown on demand
     PinBuf<hd::TonesSrc> src;                    // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
     std::vector<hd::TonesState> modem;           // [S]: the state a reset gives the stream (F = 0: no modem)
     std::vector<double> baud;                    // [S]: the engine stream's baud rate when the object was made
     std::vector<uint32_t> row_n;                 // [S]: the rows' lengths after the last push
     uint64_t pushed_calls = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
-    ~hd_tones()
-    {
-        for (void* p : {(void*)st, (void*)ring32, (void*)ring64, (void*)ctab, (void*)rows, (void*)slab}) if (p) (void)hipFree(p);
-    }
 };
+// (the strides the kernel was written against, launch.h; the 64-bit ring's guards are kTonesGuard / 2 of its words each)
+static_assert(Guarded<uint32_t>::stride_of(hd::kTonesRing32, hd::kTonesGuard) == hd::kTonesRing32 + 2 * hd::kTonesGuard, "tones 32-bit ring stride");
+static_assert(Guarded<unsigned long long>::stride_of(hd::kTonesRing64, hd::kTonesGuard) == hd::kTonesRing64 + hd::kTonesGuard, "tones 64-bit ring stride");
+static_assert(Guarded<float>::stride_of(4096, hd::kTonesGuard) == 4096 + 2 * hd::kTonesGuard, "tones row stride");
 
 namespace {
 
@@ -615,8 +631,8 @@ int tones_launch(hd_tones* t, uint32_t max_n)
         [&] {
             const uint32_t longest = cap;
             cap = 0;
-            return hd::launch_tones(t->e->qa, t->S, longest, t->src.dev, t->st, t->ring32, t->ring32_stride, t->ring64, t->ring64_stride, t->ctab, t->rows,
-                                    t->row_stride, t->prm.max_push);
+            return hd::launch_tones(t->e->qa, t->S, longest, t->src.dev, t->st.p, t->ring32.base(), t->ring32.stride, t->ring64.base(), t->ring64.stride, t->ctab.p,
+                                    t->rows.base(), t->rows.stride, t->prm.max_push);
         },
         [] {});
 }
@@ -625,7 +641,7 @@ int tones_launch(hd_tones* t, uint32_t max_n)
 int tones_clear(hd_tones* t, uint32_t s0, uint32_t ns)
 {
     hipStream_t q = t->e->qa;
-    HD_HIP(hipMemcpyAsync(t->st + s0, t->modem.data() + s0, (size_t)ns * sizeof(hd::TonesState), hipMemcpyHostToDevice, q));
+    HD_HIP(hipMemcpyAsync(t->st.p + s0, t->modem.data() + s0, (size_t)ns * sizeof(hd::TonesState), hipMemcpyHostToDevice, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t s = s0; s < s0 + ns; ++s) t->row_n[s] = 0;
     return HD_OK;
@@ -647,8 +663,7 @@ int hd_tones_create(hd_engine* e, const hd_tones_params* params, hd_tones** out)
     hd::tones_params_default(&t->prm);
     if (params) t->prm = *params;
     if (!hd::tones_window_ok(t->prm.window_q8)) return fail(HD_ERR_UNSUPPORTED, "tones parameters: 32 <= window_q8 <= 256");
-    if (!t->prm.max_push) t->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
-    if (t->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "tones parameters: max_push <= 2^28");
+    if (const int rc = default_max_push(e, &t->prm.max_push, "tones")) return rc;
     if (const int rc = enter(e)) return rc;
     t->modem.resize(t->S);
     t->baud.resize(t->S);
@@ -657,21 +672,15 @@ int hd_tones_create(hd_engine* e, const hd_tones_params* params, hd_tones** out)
         hd::tones_state_reset(t->modem[s], 0, 0, 0, 0);
         t->baud[s] = e->st[s].baud;
     }
-    t->ring32_stride = (size_t)hd::kTonesRing32 + 2 * hd::kTonesGuard;
-    t->ring64_stride = (size_t)hd::kTonesRing64 + hd::kTonesGuard;             // (its guards are kTonesGuard / 2 64-bit words each)
-    t->row_stride = (size_t)t->prm.max_push + 2 * hd::kTonesGuard;
     int32_t C[1024];
     hd::tones_table(C);
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->st), (size_t)t->S * sizeof(hd::TonesState)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ring32), (size_t)t->S * 4 * t->ring32_stride * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ring64), (size_t)t->S * t->ring64_stride * sizeof(unsigned long long)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->rows), (size_t)t->S * t->row_stride * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&t->ctab), sizeof C));
+    HD_HIP(t->st.alloc_unfilled(t->S));
+    HD_HIP(t->ring32.alloc((size_t)t->S * 4, hd::kTonesRing32, hd::kTonesGuard, hd::kTonesGuardWord, e->qa));
+    HD_HIP(t->ring64.alloc(t->S, hd::kTonesRing64, hd::kTonesGuard, hd::kTonesGuardWord, e->qa));
+    HD_HIP(t->rows.alloc(t->S, t->prm.max_push, hd::kTonesGuard, hd::kTonesGuardWord, e->qa));
+    HD_HIP(t->ctab.alloc_unfilled(1024));
     HD_HIP(t->src.alloc(t->S));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->ring32), (int)hd::kTonesGuardWord, (size_t)t->S * 4 * t->ring32_stride, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->ring64), (int)hd::kTonesGuardWord, (size_t)t->S * t->ring64_stride * 2, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(t->rows), (int)hd::kTonesGuardWord, (size_t)t->S * t->row_stride, e->qa));
-    HD_HIP(hipMemcpyAsync(t->ctab, C, sizeof C, hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(t->ctab.p, C, sizeof C, hipMemcpyHostToDevice, e->qa));
     if (const int rc = tones_clear(t.get(), 0, t->S)) return rc;       // (waits for the queue: `C` is a local)
     *out = t.release();
     return HD_OK;
@@ -717,27 +726,9 @@ int hd_tones_push_host(hd_tones* t, const float* iq, size_t stride, const uint32
     return push_rows(t, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, tones_launch);
 }
 
-int hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
-{
-    if (!t) return fail(HD_ERR_INVALID, hd_tones::kNull);
-    if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
-    *d_rows = t->rows + hd::kTonesGuard;
-    *stride = t->row_stride;
-    std::memcpy(n_per_stream, t->row_n.data(), (size_t)t->S * sizeof(uint32_t));
-    return HD_OK;
-}
+int hd_tones_rows(hd_tones* t, const float** d_rows, size_t* stride, uint32_t* n_per_stream) { return output_rows(t, d_rows, stride, n_per_stream); }
 
-int hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap)
-{
-    if (const int rc = check_object(t, stream)) return rc;
-    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
-    if (const int rc = enter(t->e)) return rc;
-    const size_t k = std::min<size_t>(t->row_n[stream], cap);
-    if (k) HD_HIP(hipMemcpy(out, t->rows + (size_t)stream * t->row_stride + hd::kTonesGuard, k * sizeof(float), hipMemcpyDeviceToHost));
-    return (int)t->row_n[stream];
-}
+int hd_tones_output(hd_tones* t, uint32_t stream, float* out, size_t cap) { return output_row(t, stream, out, cap); }
 
 int hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out)
 {
@@ -746,7 +737,7 @@ int hd_tones_stats(hd_tones* t, uint32_t stream, hd_tones_info* out)
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     if (const int rc = enter(t->e)) return rc;
     hd::TonesState h;
-    HD_HIP(hipMemcpy(&h, t->st + stream, sizeof h, hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(&h, t->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
     *out = hd_tones_info{h.n, h.F, h.full, h.W, h.L, h.phi[0], h.phi[1]};
     return HD_OK;
 }
@@ -759,16 +750,8 @@ int hd_debug_tones_guards(hd_tones* t, uint32_t stream)
     if (!t || stream >= t->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(t->e->mtx);
     if (const int rc = enter(t->e)) return rc;
-    const uint32_t* r64 = reinterpret_cast<const uint32_t*>(t->ring64);       // (its guards as 32-bit words: kTonesGuard on either side)
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(t->rows);
-    const uint32_t* at[12];
-    for (uint32_t k = 0; k < 4; ++k) {
-        at[2 * k] = t->ring32 + ((size_t)stream * 4 + k) * t->ring32_stride;
-        at[2 * k + 1] = at[2 * k] + t->ring32_stride - hd::kTonesGuard;
-    }
-    at[8] = r64 + (size_t)stream * t->ring64_stride * 2; at[9] = at[8] + t->ring64_stride * 2 - hd::kTonesGuard;
-    at[10] = row + (size_t)stream * t->row_stride; at[11] = at[10] + t->row_stride - hd::kTonesGuard;
-    return damaged_guards(at, hd::kTonesGuard, hd::kTonesGuardWord);
+    const size_t r = (size_t)stream * 4;
+    return damaged_guards({{t->ring32, r}, {t->ring32, r + 1}, {t->ring32, r + 2}, {t->ring32, r + 3}, {t->ring64, stream}, {t->rows, stream}});
 }
 
 }  // extern "C"
@@ -780,25 +763,22 @@ struct hd_tone_search {
     hd_engine* e = nullptr;
     hd_tone_search_params prm{};
     uint32_t S = 0;
-    double* acc = nullptr;                       // [S][acc_stride]: guard | 4096 fftshifted sums | guard
-    float2* carry = nullptr;                     // [S][2][carry_stride]: guard | 4096 samples | guard -- the stream's two carry buffers (kernels/tone_search.hip)
-    float* win = nullptr;                        // [4096] the survey's window table
-    float2* own_tw = nullptr;                    // the twiddles where the engine computes no spectra and holds none
+    Guarded<double> acc;                         // [S]: guard | 4096 fftshifted sums | guard
+    Guarded<float2> carry;                       // [S * 2]: guard | 4096 samples | guard -- the stream's two carry buffers (kernels/tone_search.hip)
+    DevBuf<float> win;                           // [4096] the survey's window table
+    DevBuf<float2> own_tw;                       // the twiddles where the engine computes no spectra and holds none
     const float2* tw = nullptr;
-    size_t acc_stride = 0, carry_stride = 0;
     double sum_w2 = 0;                           // sum of w^2, in double over the float table
-    float2* slab = nullptr;                      // hd_tone_search_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
+    DevBuf<float2> slab;                         // hd_tone_search_push_host: the rows packed end to end, grown on demand
     PinBuf<hd::ToneSearchSrc> src;               // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
     std::vector<uint64_t> samples, segments;     // [S]: since the stream's last reset
     std::vector<uint32_t> carry_n, flip;         // [S]: the carry's length, and which of the two buffers holds it
     uint64_t pushed_calls = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
-    ~hd_tone_search()
-    {
-        for (void* p : {(void*)acc, (void*)carry, (void*)win, (void*)own_tw, (void*)slab}) if (p) (void)hipFree(p);
-    }
 };
+// (the stride the kernel was written against, tone_search.h: kToneSearchGuard / 2 doubles, or samples, on either side)
+static_assert(Guarded<double>::stride_of(hd::kToneSearchSeg, hd::kToneSearchGuard) == hd::kToneSearchSeg + hd::kToneSearchGuard, "tone search accumulator stride");
+static_assert(Guarded<float2>::stride_of(hd::kToneSearchSeg, hd::kToneSearchGuard) == hd::kToneSearchSeg + hd::kToneSearchGuard, "tone search carry stride");
 
 namespace {
 
@@ -815,7 +795,7 @@ int tone_search_launch(hd_tone_search* ts, uint32_t max_n)
             d.flip = ts->flip[s];
         },
         [&] {
-            hd::launch_tone_search(ts->e->qa, ts->S, ts->src.dev, ts->win, ts->tw, ts->acc, ts->acc_stride, ts->carry, ts->carry_stride);
+            hd::launch_tone_search(ts->e->qa, ts->S, ts->src.dev, ts->win.p, ts->tw, ts->acc.base(), ts->acc.stride, ts->carry.base(), ts->carry.stride);
             return true;
         },
         [&] {
@@ -833,7 +813,7 @@ int tone_search_launch(hd_tone_search* ts, uint32_t max_n)
 int tone_search_clear(hd_tone_search* ts, uint32_t s0, uint32_t ns)
 {
     hipStream_t q = ts->e->qa;
-    HD_HIP(hipMemset2DAsync(ts->acc + (size_t)s0 * ts->acc_stride + hd::kToneSearchGuard / 2, ts->acc_stride * sizeof(double), 0,
+    HD_HIP(hipMemset2DAsync(ts->acc.row(s0), ts->acc.stride * sizeof(double), 0,
                             (size_t)hd::kToneSearchSeg * sizeof(double), ns, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t s = s0; s < s0 + ns; ++s) { ts->samples[s] = ts->segments[s] = 0; ts->carry_n[s] = ts->flip[s] = 0; }
@@ -855,32 +835,20 @@ int hd_tone_search_create(hd_engine* e, const hd_tone_search_params* params, hd_
     std::unique_ptr<hd_tone_search> ts(new hd_tone_search);
     ts->e = e; ts->S = e->S;
     if (params) ts->prm = *params;
-    if (!ts->prm.max_push) ts->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
-    if (ts->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "tone search parameters: max_push <= 2^28");
+    if (const int rc = default_max_push(e, &ts->prm.max_push, "tone search")) return rc;
     if (const int rc = enter(e)) return rc;
     const uint32_t S = ts->S;
     ts->samples.assign(S, 0); ts->segments.assign(S, 0); ts->carry_n.assign(S, 0u); ts->flip.assign(S, 0u);
-    ts->acc_stride = (size_t)hd::kToneSearchSeg + hd::kToneSearchGuard;          // (kToneSearchGuard / 2 doubles, or samples, on either side)
-    ts->carry_stride = (size_t)hd::kToneSearchSeg + hd::kToneSearchGuard;
     std::vector<float> w(hd::kToneSearchSeg);
     hd::survey_window(w.data());
     for (float v : w) ts->sum_w2 += (double)v * (double)v;
     std::vector<float2> tw_host;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->acc), (size_t)S * ts->acc_stride * sizeof(double)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->carry), (size_t)S * 2 * ts->carry_stride * sizeof(float2)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->win), w.size() * sizeof(float)));
+    HD_HIP(ts->acc.alloc(S, hd::kToneSearchSeg, hd::kToneSearchGuard, hd::kToneSearchGuardWord, e->qa));
+    HD_HIP(ts->carry.alloc((size_t)S * 2, hd::kToneSearchSeg, hd::kToneSearchGuard, hd::kToneSearchGuardWord, e->qa));
+    HD_HIP(ts->win.alloc_unfilled(w.size()));
     HD_HIP(ts->src.alloc(S));
-    ts->tw = e->fft_tw.p;
-    if (!ts->tw) {   // an engine without spectra holds no twiddles: the same table, the object's own
-        tw_host.resize(hd::kFftBins);
-        hd::specwave::fft_twiddles(tw_host.data());
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&ts->own_tw), tw_host.size() * sizeof(float2)));
-        HD_HIP(hipMemcpyAsync(ts->own_tw, tw_host.data(), tw_host.size() * sizeof(float2), hipMemcpyHostToDevice, e->qa));
-        ts->tw = ts->own_tw;
-    }
-    HD_HIP(hipMemcpyAsync(ts->win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ts->acc), (int)hd::kToneSearchGuardWord, (size_t)S * ts->acc_stride * 2, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ts->carry), (int)hd::kToneSearchGuardWord, (size_t)S * 2 * ts->carry_stride * 2, e->qa));
+    if (const int rc = hd::eng::engine_or_own_twiddles(e, ts->own_tw, tw_host, e->qa, &ts->tw)) return rc;
+    HD_HIP(hipMemcpyAsync(ts->win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, e->qa));
     if (const int rc = tone_search_clear(ts.get(), 0, S)) return rc;   // (waits for the queue: the tables are locals)
     *out = ts.release();
     return HD_OK;
@@ -912,7 +880,7 @@ int hd_tone_search_power(hd_tone_search* ts, uint32_t stream, double* p, size_t 
     if (segments) *segments = segs;
     if (cap < hd::kToneSearchSeg) return 0;
     // (no queue to wait for: every push has waited for its launches)
-    HD_HIP(hipMemcpy(p, ts->acc + (size_t)stream * ts->acc_stride + hd::kToneSearchGuard / 2, hd::kToneSearchSeg * sizeof(double), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(p, ts->acc.row(stream), hd::kToneSearchSeg * sizeof(double), hipMemcpyDeviceToHost));
     const double norm = (double)segs * ts->sum_w2;
     for (uint32_t i = 0; i < hd::kToneSearchSeg; ++i) p[i] = segs ? p[i] / norm : 0.0;
     return (int)hd::kToneSearchSeg;
@@ -951,15 +919,7 @@ int hd_debug_tone_search_guards(hd_tone_search* ts, uint32_t stream)
     if (!ts || stream >= ts->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(ts->e->mtx);
     if (const int rc = enter(ts->e)) return rc;
-    const uint32_t* a32 = reinterpret_cast<const uint32_t*>(ts->acc);
-    const uint32_t* c32 = reinterpret_cast<const uint32_t*>(ts->carry);
-    const uint32_t* at[6];
-    at[0] = a32 + (size_t)stream * ts->acc_stride * 2; at[1] = at[0] + ts->acc_stride * 2 - hd::kToneSearchGuard;
-    for (uint32_t k = 0; k < 2; ++k) {
-        at[2 + 2 * k] = c32 + ((size_t)stream * 2 + k) * ts->carry_stride * 2;
-        at[3 + 2 * k] = at[2 + 2 * k] + ts->carry_stride * 2 - hd::kToneSearchGuard;
-    }
-    return damaged_guards(at, hd::kToneSearchGuard, hd::kToneSearchGuardWord);
+    return damaged_guards({{ts->acc, stream}, {ts->carry, (size_t)stream * 2}, {ts->carry, (size_t)stream * 2 + 1}});
 }
 
 }  // extern "C"
@@ -971,12 +931,10 @@ struct hd_combine {
     hd_engine* e = nullptr;
     hd_combine_params prm{};
     uint32_t S = 0;
-    int16_t* ring = nullptr;                     // [S][ring_stride]: guard | HD_COMBINE_RING samples | guard
-    float* rows = nullptr;                       // [S][row_stride]: guard | max_push floats | guard
-    int32_t* scores = nullptr;                   // [7][2 * HD_COMBINE_MAX_LAG + 1]: the last search's, allocated by the first search
-    size_t ring_stride = 0, row_stride = 0;
-    float* slab = nullptr;                       // hd_combine_push_host: the rows packed end to end, grown on demand
-    size_t slab_n = 0;
+    Guarded<int16_t> ring;                       // [S]: guard | HD_COMBINE_RING samples | guard
+    Guarded<float> rows;                         // [S]: guard | max_push floats | guard
+    DevBuf<int32_t> scores;                      // [7][2 * HD_COMBINE_MAX_LAG + 1]: the last search's, allocated by the first search
+    DevBuf<float> slab;                          // hd_combine_push_host: the rows packed end to end, grown on demand
     PinBuf<hd::CombineSrc> src;                  // [S]: a launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
     PinBuf<hd::CombineGroup> grp;                // [S]: a push's groups, in the order of `refs`
     PinBuf<hd_combine_lag> res;                  // [7]: the last search's results, written by the kernel in place
@@ -988,11 +946,10 @@ struct hd_combine {
     uint32_t searched_L = 0;
     uint64_t pushed_calls = 0;
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push
-    ~hd_combine()
-    {
-        for (void* p : {(void*)ring, (void*)rows, (void*)scores, (void*)slab}) if (p) (void)hipFree(p);
-    }
 };
+// (the strides the kernel was written against, combine.h: 2 kCombineGuard int16 samples on either side of the ring)
+static_assert(Guarded<int16_t>::stride_of(HD_COMBINE_RING, hd::kCombineGuard) == HD_COMBINE_RING + 4 * hd::kCombineGuard, "combiner ring stride");
+static_assert(Guarded<float>::stride_of(4096, hd::kCombineGuard) == 4096 + 2 * hd::kCombineGuard, "combiner row stride");
 
 namespace {
 
@@ -1048,7 +1005,7 @@ int combine_launch(hd_combine* c, uint32_t max_n)
         c, max_n, HD_COMBINE_CHUNK, "",
         [&](uint32_t, const hd::CombineSrc& d) { cap = std::max(cap, d.n); },
         [&] {
-            hd::launch_combine(c->e->qa, ng, cap, c->src.dev, c->grp.dev, c->ring, c->ring_stride, c->rows, c->row_stride, c->prm.max_push);
+            hd::launch_combine(c->e->qa, ng, cap, c->src.dev, c->grp.dev, c->ring.base(), c->ring.stride, c->rows.base(), c->rows.stride, c->prm.max_push);
             cap = 0;
             return true;
         },
@@ -1080,8 +1037,8 @@ int combine_search(hd_combine* c, uint32_t ref, const hd_combine_lag_params* p, 
     if (cap < g.count) return fail(HD_ERR_INVALID, "hd_combine_lags: room for " + std::to_string(cap) + " results, the group has " + std::to_string(g.count) + " members");
     const uint64_t n = c->count[ref], need = (uint64_t)p->window + 2u * (uint64_t)p->max_lag;
     if (n < need) return fail(HD_ERR_UNSUPPORTED, "hd_combine_lags needs " + std::to_string(need) + " samples (" + std::to_string(n) + " so far)");
-    if (!c->scores) HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->scores), (size_t)(HD_COMBINE_MAX_MEMBERS - 1) * (2 * HD_COMBINE_MAX_LAG + 1) * sizeof(int32_t)));
-    hd::launch_combine_lags(c->e->qa, &g, n, p->window, p->max_lag, p->guard, p->min_peak_q8, p->min_margin_q8, c->ring, c->ring_stride, c->scores, c->res.dev);
+    if (!c->scores.p) HD_HIP(c->scores.alloc_unfilled((size_t)(HD_COMBINE_MAX_MEMBERS - 1) * (2 * HD_COMBINE_MAX_LAG + 1)));
+    hd::launch_combine_lags(c->e->qa, &g, n, p->window, p->max_lag, p->guard, p->min_peak_q8, p->min_margin_q8, c->ring.base(), c->ring.stride, c->scores.p, c->res.dev);
     HD_HIP(hipGetLastError());
     HD_HIP(hipStreamSynchronize(c->e->qa));
     std::atomic_thread_fence(std::memory_order_acquire);
@@ -1114,21 +1071,16 @@ int hd_combine_create(hd_engine* e, const hd_combine_params* params, hd_combine*
     std::unique_ptr<hd_combine> c(new hd_combine);
     c->e = e; c->S = e->S;
     if (params) c->prm = *params;
-    if (!c->prm.max_push) c->prm.max_push = std::max<uint32_t>(e->n2_cap, 4096u);
-    if (c->prm.max_push > (1u << 28)) return fail(HD_ERR_INVALID, "combiner parameters: max_push <= 2^28");
+    if (const int rc = default_max_push(e, &c->prm.max_push, "combiner")) return rc;
     if (const int rc = enter(e)) return rc;
     const uint32_t S = c->S;
     c->group_of.assign(S, HD_COMBINE_NO_GROUP); c->delay.assign(S, 0u); c->weight.assign(S, 256u); c->row_n.assign(S, 0u);
     c->members.assign(S, {}); c->count.assign(S, 0);
-    c->ring_stride = (size_t)HD_COMBINE_RING + 4 * hd::kCombineGuard;             // (2 kCombineGuard int16 samples on either side)
-    c->row_stride = (size_t)c->prm.max_push + 2 * hd::kCombineGuard;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->ring), (size_t)S * c->ring_stride * sizeof(int16_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&c->rows), (size_t)S * c->row_stride * sizeof(float)));
+    HD_HIP(c->ring.alloc(S, HD_COMBINE_RING, hd::kCombineGuard, hd::kCombineGuardWord, e->qa));
+    HD_HIP(c->rows.alloc(S, c->prm.max_push, hd::kCombineGuard, hd::kCombineGuardWord, e->qa));
     HD_HIP(c->src.alloc(S));
     HD_HIP(c->grp.alloc(S));
     HD_HIP(c->res.alloc(HD_COMBINE_MAX_MEMBERS - 1));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->ring), (int)hd::kCombineGuardWord, (size_t)S * c->ring_stride / 2, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->rows), (int)hd::kCombineGuardWord, (size_t)S * c->row_stride, e->qa));
     HD_HIP(hipStreamSynchronize(e->qa));
     *out = c.release();
     return HD_OK;
@@ -1195,27 +1147,9 @@ int hd_combine_push_host(hd_combine* c, const float* rows, size_t stride, const 
     return push_rows(c, rows, stride, n_per_stream, n, false, combine_launch);
 }
 
-int hd_combine_rows(hd_combine* c, const float** d_rows, size_t* stride, uint32_t* n_per_stream)
-{
-    if (!c) return fail(HD_ERR_INVALID, hd_combine::kNull);
-    if (!d_rows || !stride || !n_per_stream) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    *d_rows = c->rows + hd::kCombineGuard;
-    *stride = c->row_stride;
-    std::memcpy(n_per_stream, c->row_n.data(), (size_t)c->S * sizeof(uint32_t));
-    return HD_OK;
-}
+int hd_combine_rows(hd_combine* c, const float** d_rows, size_t* stride, uint32_t* n_per_stream) { return output_rows(c, d_rows, stride, n_per_stream); }
 
-int hd_combine_output(hd_combine* c, uint32_t stream, float* out, size_t cap)
-{
-    if (const int rc = check_object(c, stream)) return rc;
-    if (cap && !out) return fail(HD_ERR_INVALID, "null output");
-    std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
-    if (const int rc = enter(c->e)) return rc;
-    const size_t k = std::min<size_t>(c->row_n[stream], cap);
-    if (k) HD_HIP(hipMemcpy(out, c->rows + (size_t)stream * c->row_stride + hd::kCombineGuard, k * sizeof(float), hipMemcpyDeviceToHost));
-    return (int)c->row_n[stream];
-}
+int hd_combine_output(hd_combine* c, uint32_t stream, float* out, size_t cap) { return output_row(c, stream, out, cap); }
 
 int hd_combine_stats(hd_combine* c, uint32_t stream, hd_combine_info* out)
 {
@@ -1277,7 +1211,7 @@ int hd_debug_combine_scores(hd_combine* c, uint32_t stream, int32_t* out, size_t
     const size_t k = 2 * (size_t)c->searched_L + 1;
     for (size_t m = 1; m < c->searched.size(); ++m) {
         if (c->searched[m] != stream) continue;
-        if (out && cap >= k) HD_HIP(hipMemcpy(out, c->scores + (m - 1) * k, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (out && cap >= k) HD_HIP(hipMemcpy(out, c->scores.p + (m - 1) * k, k * sizeof(int32_t), hipMemcpyDeviceToHost));
         return (int)k;
     }
     return 0;
@@ -1289,12 +1223,7 @@ int hd_debug_combine_guards(hd_combine* c, uint32_t stream)
     if (!c || stream >= c->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(c->e->mtx);
     if (const int rc = enter(c->e)) return rc;
-    const uint32_t* r32 = reinterpret_cast<const uint32_t*>(c->ring);         // (its guards as 32-bit words: kCombineGuard on either side)
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(c->rows);
-    const uint32_t* at[4];
-    at[0] = r32 + (size_t)stream * c->ring_stride / 2; at[1] = at[0] + c->ring_stride / 2 - hd::kCombineGuard;
-    at[2] = row + (size_t)stream * c->row_stride; at[3] = at[2] + c->row_stride - hd::kCombineGuard;
-    return damaged_guards(at, hd::kCombineGuard, hd::kCombineGuardWord);
+    return damaged_guards({{c->ring, stream}, {c->rows, stream}});
 }
 
 }  // extern "C"
@@ -1307,11 +1236,10 @@ struct hd_ssdv {
     hd_engine* e = nullptr;
     hd_ssdv_params prm{};
     uint32_t S = 0;
-    uint32_t* ring = nullptr;                    // [S][ring_stride]: guard | HD_SSDV_RING words | guard
-    uint32_t* cnt = nullptr;                     // guard | the launch's accepted candidates, [S] crc_bad | guard
-    uint32_t* out = nullptr;                     // guard | HD_SSDV_LAUNCH results (hd::SsdvOut) | guard
-    hd::SsdvTables* tab = nullptr;
-    size_t ring_stride = 0;
+    Guarded<uint32_t> ring;                      // [S]: guard | HD_SSDV_RING words | guard
+    Guarded<uint32_t> cnt;                       // one row: guard | the launch's accepted candidates, [S] crc_bad | guard
+    Guarded<uint32_t> out;                       // one row: guard | HD_SSDV_LAUNCH results (hd::SsdvOut) | guard
+    DevBuf<hd::SsdvTables> tab;
     PinBuf<hd::SsdvSrc> src;                     // [S]: a launch's descriptors, read by the kernels in place (a launch is waited for before the next is written)
     PinBuf<uint32_t> stage;                      // [kStage]: a round's new words, stream behind stream, read by k_ssdv_append in place
     std::vector<hd::SsdvStream> st;              // [S]: the doors, the delivery and the counters; `words` holds what is not uploaded yet
@@ -1320,11 +1248,9 @@ struct hd_ssdv {
     std::vector<hd::SsdvOut> h_out, found;       // a launch's results; a scan's
     bool launched = false;                       // the last scan launched k_ssdv_scan (the measurement hook's question)
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a scan's last round
-    ~hd_ssdv()
-    {
-        for (void* p : {(void*)ring, (void*)cnt, (void*)out, (void*)tab}) if (p) (void)hipFree(p);
-    }
 };
+// (the stride the kernels were written against, ssdv.h)
+static_assert(Guarded<uint32_t>::stride_of(HD_SSDV_RING, hd::kSsdvGuard) == HD_SSDV_RING + 2 * hd::kSsdvGuard, "SSDV ring stride");
 
 namespace {
 
@@ -1357,7 +1283,7 @@ int ssdv_scan(hd_ssdv* v)
         }
         if (!max_new && !max_cand) break;
         std::atomic_thread_fence(std::memory_order_release);
-        hd::launch_ssdv_append(q, v->S, max_new, v->src.dev, v->stage.dev, v->ring, v->ring_stride);
+        hd::launch_ssdv_append(q, v->S, max_new, v->src.dev, v->stage.dev, v->ring.base(), v->ring.stride);
         HD_HIP(hipGetLastError());
         if (!max_cand) { HD_HIP(hipStreamSynchronize(q)); continue; }
         uint32_t cap = 0;
@@ -1366,20 +1292,20 @@ int ssdv_scan(hd_ssdv* v)
             v, max_cand, std::max(1u, (uint32_t)HD_SSDV_LAUNCH / active), "",
             [&](uint32_t, const hd::SsdvSrc& d) { cap = std::max(cap, d.n); },
             [&] {
-                if (hipMemsetAsync(v->cnt + hd::kSsdvGuard, 0, (size_t)(1 + v->S) * sizeof(uint32_t), q) != hipSuccess) return false;
-                hd::launch_ssdv_scan(q, v->S, cap, v->src.dev, v->tab, v->ring, v->ring_stride, v->cnt + hd::kSsdvGuard,
-                                     reinterpret_cast<hd::SsdvOut*>(v->out + hd::kSsdvGuard), HD_SSDV_LAUNCH);
+                if (hipMemsetAsync(v->cnt.row(0), 0, (size_t)(1 + v->S) * sizeof(uint32_t), q) != hipSuccess) return false;
+                hd::launch_ssdv_scan(q, v->S, cap, v->src.dev, v->tab.p, v->ring.base(), v->ring.stride, v->cnt.row(0),
+                                     reinterpret_cast<hd::SsdvOut*>(v->out.row(0)), HD_SSDV_LAUNCH);
                 cap = 0;
                 return true;
             },
             [&] {                                // the launch is done: its counters, and its results if it has any
                 if (fetch != hipSuccess) return;
-                fetch = hipMemcpy(v->h_cnt.data(), v->cnt + hd::kSsdvGuard, v->h_cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+                fetch = hipMemcpy(v->h_cnt.data(), v->cnt.row(0), v->h_cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
                 if (fetch != hipSuccess) return;
                 for (uint32_t s = 0; s < v->S; ++s) v->st[s].crc_bad += v->h_cnt[1 + s];
                 const size_t k = std::min<size_t>(v->h_cnt[0], HD_SSDV_LAUNCH);
                 if (!k) return;
-                fetch = hipMemcpy(v->h_out.data(), v->out + hd::kSsdvGuard, k * sizeof(hd::SsdvOut), hipMemcpyDeviceToHost);
+                fetch = hipMemcpy(v->h_out.data(), v->out.row(0), k * sizeof(hd::SsdvOut), hipMemcpyDeviceToHost);
                 if (fetch == hipSuccess) v->found.insert(v->found.end(), v->h_out.begin(), v->h_out.begin() + k);
             });
         if (rc) return rc;
@@ -1429,12 +1355,10 @@ int hd_ssdv_create(hd_engine* e, const hd_ssdv_params* params, hd_ssdv** out)
     v->st.resize(S); v->up.assign(S, 0);
     for (auto& st : v->st) st.max_fill = v->prm.max_fill;
     v->h_cnt.assign(1 + (size_t)S, 0u); v->h_out.resize(HD_SSDV_LAUNCH);
-    v->ring_stride = (size_t)HD_SSDV_RING + 2 * hd::kSsdvGuard;
-    const size_t cnt_words = 1 + (size_t)S + 2 * hd::kSsdvGuard, out_words = (size_t)HD_SSDV_LAUNCH * kSsdvOutWords + 2 * hd::kSsdvGuard;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->ring), (size_t)S * v->ring_stride * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->cnt), cnt_words * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->out), out_words * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&v->tab), sizeof(hd::SsdvTables)));
+    HD_HIP(v->ring.alloc(S, HD_SSDV_RING, hd::kSsdvGuard, hd::kSsdvGuardWord, e->qa));
+    HD_HIP(v->cnt.alloc(1, 1 + (size_t)S, hd::kSsdvGuard, hd::kSsdvGuardWord, e->qa));
+    HD_HIP(v->out.alloc(1, (size_t)HD_SSDV_LAUNCH * kSsdvOutWords, hd::kSsdvGuard, hd::kSsdvGuardWord, e->qa));
+    HD_HIP(v->tab.alloc_unfilled(1));
     HD_HIP(v->src.alloc(S));
     HD_HIP(v->stage.alloc(hd_ssdv::kStage));
     std::unique_ptr<hd::SsdvTables> t(new hd::SsdvTables);
@@ -1451,10 +1375,7 @@ int hd_ssdv_create(hd_engine* e, const hd_ssdv_params* params, hd_ssdv** out)
         for (uint32_t k = 0; k < 8; ++k) t->rootmul[m][k] = F.mul(F.root[m], F.exp[k]);
         t->root127[m] = F.exp[((uint32_t)F.log[F.root[m]] * 127u) % 255u];
     }
-    HD_HIP(hipMemcpyAsync(v->tab, t.get(), sizeof(hd::SsdvTables), hipMemcpyHostToDevice, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->ring), (int)hd::kSsdvGuardWord, (size_t)S * v->ring_stride, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->cnt), (int)hd::kSsdvGuardWord, cnt_words, e->qa));
-    HD_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v->out), (int)hd::kSsdvGuardWord, out_words, e->qa));
+    HD_HIP(hipMemcpyAsync(v->tab.p, t.get(), sizeof(hd::SsdvTables), hipMemcpyHostToDevice, e->qa));
     HD_HIP(hipStreamSynchronize(e->qa));         // (`t` is a local)
     *out = v.release();
     return HD_OK;
@@ -1500,7 +1421,7 @@ int hd_ssdv_push_clocked(hd_ssdv* v, hd_clocked* c)
     std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
     if (const int rc = enter(v->e)) return rc;
     std::vector<hd::ClockedState> hs(c->S);      // one copy says which streams have records waiting
-    HD_HIP(hipMemcpy(hs.data(), c->st, hs.size() * sizeof(hd::ClockedState), hipMemcpyDeviceToHost));
+    HD_HIP(hipMemcpy(hs.data(), c->st.p, hs.size() * sizeof(hd::ClockedState), hipMemcpyDeviceToHost));
     std::vector<hd_clocked_record> buf;
     for (uint32_t s = 0; s < v->S; ++s) {
         const hd::ClockedState& m = c->modem[s];
@@ -1559,10 +1480,7 @@ int hd_debug_ssdv_guards(hd_ssdv* v, uint32_t stream)
     if (!v || stream >= v->S) return fail(HD_ERR_INVALID, "bad argument");
     std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
     if (const int rc = enter(v->e)) return rc;
-    const uint32_t* at[6] = {v->ring + (size_t)stream * v->ring_stride, v->ring + (size_t)(stream + 1) * v->ring_stride - hd::kSsdvGuard,
-                             v->cnt, v->cnt + hd::kSsdvGuard + 1 + v->S,
-                             v->out, v->out + hd::kSsdvGuard + (size_t)HD_SSDV_LAUNCH * kSsdvOutWords};
-    return damaged_guards(at, hd::kSsdvGuard, hd::kSsdvGuardWord);
+    return damaged_guards({{v->ring, stream}, {v->cnt, 0}, {v->out, 0}});
 }
 
 }  // extern "C"

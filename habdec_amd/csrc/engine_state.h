@@ -20,6 +20,7 @@
 #include "host/format_trial.hpp"
 #include "host/text_stage.hpp"
 #include "kernels/launch.h"
+#include "kernels/spectrum_math.h"
 
 struct hd_engine;
 
@@ -42,13 +43,58 @@ struct DevBuf {
     size_t n = 0;
     hipError_t alloc(size_t count)
     {
-        n = count;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
+        hipError_t e = alloc_unfilled(count);
         if (e == hipSuccess) e = hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
         return e;
     }
+    // For what its owner fills itself, by a clear or a copy on its own queue: nothing is written here, and nothing runs on the null stream.
+    hipError_t alloc_unfilled(size_t count)
+    {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
+        n = e == hipSuccess ? count : 0;
+        return e;
+    }
+    // At least `count` elements.  Where it grows, the old memory is freed first and the contents are not kept.
+    hipError_t grow(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; }
+        return alloc_unfilled(count);
+    }
     ~DevBuf() { if (p) (void)hipFree(p); }
 };
+
+// `rows` rows of guard | payload | guard in device memory, the one layout every kernel with guarded arrays assumes: G 32-bit words of `pattern` on either
+// side of each row's payload, so a row is payload + 2 G 4 / sizeof(T) elements of T.  (A payload is a whole number of 32-bit words.)
+template <typename T>
+struct Guarded {
+    static constexpr size_t stride_of(size_t payload, uint32_t G) { return payload + 2 * (size_t)G * sizeof(uint32_t) / sizeof(T); }
+    DevBuf<T> buf;
+    size_t stride = 0;                     // a row, guards included, in elements: what the kernels take beside base()
+    uint32_t G = 0, pattern = 0;
+    // The allocation, and one fill of the whole array with the pattern on `queue` (not waited for): the payloads are the owner's to clear.
+    hipError_t alloc(size_t rows, size_t payload, uint32_t guard_words, uint32_t guard_pattern, hipStream_t queue)
+    {
+        G = guard_words; pattern = guard_pattern;
+        stride = stride_of(payload, G);
+        hipError_t e = buf.alloc_unfilled(rows * stride);
+        if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(buf.p), (int)pattern, rows * stride * sizeof(T) / sizeof(uint32_t), queue);
+        return e;
+    }
+    T* base() const { return buf.p; }
+    T* row(size_t r) const { return buf.p + r * stride + G * sizeof(uint32_t) / sizeof(T); }     // row r's payload
+    const uint32_t* guard_front(size_t r) const { return reinterpret_cast<const uint32_t*>(buf.p + r * stride); }
+    const uint32_t* guard_back(size_t r) const { return reinterpret_cast<const uint32_t*>(buf.p + (r + 1) * stride) - G; }
+};
+
+// The guards of one row of a guarded array of any element, for the test hooks' counter (demod_rows.cpp: damaged_guards).
+struct GuardedRow {
+    const uint32_t *front, *back;
+    uint32_t G, pattern;
+    template <typename T>
+    GuardedRow(const Guarded<T>& a, size_t r) : front(a.guard_front(r)), back(a.guard_back(r)), G(a.G), pattern(a.pattern) {}
+};
+
 template <typename T>
 struct PinBuf {
     T* p = nullptr;
@@ -134,6 +180,8 @@ using hd::eng::check_stream;
 using hd::eng::flush_locked;
 using hd::eng::DevBuf;
 using hd::eng::PinBuf;
+using hd::eng::Guarded;
+using hd::eng::GuardedRow;
 using hd::eng::SizeState;
 using hd::eng::StreamHost;
 
@@ -299,6 +347,20 @@ inline bool is_device_pointer(const void* p)
         return false;
     }
     return true;
+}
+
+// The transform's twiddles for an object beside the pipeline: the engine's, or, where the engine computes no spectra and holds none, the same table
+// uploaded into `own` on q.  host: where that table is made, the creator's local -- the upload is enqueued, not waited for.
+inline int engine_or_own_twiddles(const hd_engine* e, DevBuf<float2>& own, std::vector<float2>& host, hipStream_t q, const float2** tw)
+{
+    *tw = e->fft_tw.p;
+    if (*tw) return HD_OK;
+    host.resize(hd::kFftBins);
+    hd::specwave::fft_twiddles(host.data());
+    HD_HIP(own.alloc_unfilled(host.size()));
+    HD_HIP(hipMemcpyAsync(own.p, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice, q));
+    *tw = own.p;
+    return HD_OK;
 }
 
 } }  // namespace hd::eng

@@ -7,7 +7,6 @@
 #include "host/iq_convert.hpp"
 #include "host/survey.hpp"
 #include "host/waterfall.hpp"
-#include "kernels/spectrum_math.h"
 #include "kernels/survey.h"
 #include "kernels/waterfall.h"
 
@@ -21,10 +20,10 @@ struct WideFeed {
     hd_engine* e = nullptr;
     hipStream_t q = nullptr;               // the object's own queue: launches, staging copies and the read-backs
     const float2* tw = nullptr;            // the engine's twiddles, or own_tw where the engine computes no spectra
-    float2* own_tw = nullptr;
-    float* win = nullptr;                  // [4096] the window table
-    float2* slab = nullptr;                // host and packed pushes: staging for kSlabSegs segments, allocated by the first push that needs it
-    unsigned char* pslab = nullptr;        // packed HOST pushes: the same segments packed (sized for cs16), allocated by the first of them
+    DevBuf<float2> own_tw;
+    DevBuf<float> win;                     // [4096] the window table
+    DevBuf<float2> slab;                   // host and packed pushes: staging for kSlabSegs segments, allocated by the first push that needs it
+    DevBuf<unsigned char> pslab;           // packed HOST pushes: the same segments packed (sized for cs16), allocated by the first of them
     static constexpr uint32_t kSlabSegs = 256;   // whole segments one staging copy carries ((256 + 1) hops = 4 MiB + 16 KiB)
 
     // The queue and the two tables.  w, tw_host: the tables on the host, the creator's locals -- their uploads are enqueued, not waited for: the
@@ -35,23 +34,12 @@ struct WideFeed {
         HD_HIP(hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
         w.resize(hd::kSurveyBins);
         hd::survey_window(w.data());
-        HD_HIP(hipMalloc(reinterpret_cast<void**>(&win), w.size() * sizeof(float)));
-        tw = e->fft_tw.p;
-        if (!tw) {   // an engine without spectra holds no twiddles: the same table, the object's own
-            tw_host.resize(hd::kFftBins);
-            hd::specwave::fft_twiddles(tw_host.data());
-            HD_HIP(hipMalloc(reinterpret_cast<void**>(&own_tw), tw_host.size() * sizeof(float2)));
-            HD_HIP(hipMemcpyAsync(own_tw, tw_host.data(), tw_host.size() * sizeof(float2), hipMemcpyHostToDevice, q));
-            tw = own_tw;
-        }
-        HD_HIP(hipMemcpyAsync(win, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, q));
+        HD_HIP(win.alloc_unfilled(w.size()));
+        if (const int rc = hd::eng::engine_or_own_twiddles(e, own_tw, tw_host, q, &tw)) return rc;
+        HD_HIP(hipMemcpyAsync(win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, q));
         return HD_OK;
     }
-    ~WideFeed()
-    {
-        for (void* p : {(void*)own_tw, (void*)win, (void*)slab, (void*)pslab}) if (p) (void)hipFree(p);
-        if (q) (void)hipStreamDestroy(q);
-    }
+    ~WideFeed() { if (q) (void)hipStreamDestroy(q); }     // (the object's destroy has waited for q: the buffers, destroyed behind this, are idle)
 };
 
 // The argument checks of a push, in the order process_packed (engine.cpp) uses: format, null, alignment -- then the caller takes the lock.
@@ -80,8 +68,8 @@ int feed_push(WideFeed& f, int fmt, const void* iq, bool device, uint64_t n_seg,
     if (device && !packed) return enqueue(static_cast<const float2*>(iq), 0, 0, n_seg);
     const size_t bps = hd::iq_bytes(fmt);
     const size_t slab_samples = (size_t)(WideFeed::kSlabSegs + 1) * hd::kSurveyHop;
-    if (!f.slab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&f.slab), slab_samples * sizeof(float2)));
-    if (packed && !device && !f.pslab) HD_HIP(hipMalloc(reinterpret_cast<void**>(&f.pslab), slab_samples * 4u));
+    if (!f.slab.p) HD_HIP(f.slab.alloc_unfilled(slab_samples));
+    if (packed && !device && !f.pslab.p) HD_HIP(f.pslab.alloc_unfilled(slab_samples * 4u));
     const uint64_t per_slab = (uint64_t)(WideFeed::kSlabSegs / unit) * unit;      // at least one unit: unit <= 64 segments
     const unsigned char* p = static_cast<const unsigned char*>(iq);
     for (uint64_t s = 0; s < n_seg; s += per_slab) {
@@ -89,15 +77,15 @@ int feed_push(WideFeed& f, int fmt, const void* iq, bool device, uint64_t n_seg,
         const size_t samples = (size_t)(s1 - s + 1) * hd::kSurveyHop;
         const unsigned char* from = p + (size_t)s * hd::kSurveyHop * bps;
         if (!packed) {
-            HD_HIP(hipMemcpyAsync(f.slab, from, samples * sizeof(float2), hipMemcpyHostToDevice, f.q));
+            HD_HIP(hipMemcpyAsync(f.slab.p, from, samples * sizeof(float2), hipMemcpyHostToDevice, f.q));
         } else {
             if (!device) {
-                HD_HIP(hipMemcpyAsync(f.pslab, from, samples * bps, hipMemcpyHostToDevice, f.q));
-                from = f.pslab;
+                HD_HIP(hipMemcpyAsync(f.pslab.p, from, samples * bps, hipMemcpyHostToDevice, f.q));
+                from = f.pslab.p;
             }
-            if (!hd::launch_iq_unpack(f.q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, f.slab, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
+            if (!hd::launch_iq_unpack(f.q, fmt, 1, (uint32_t)samples, from, 0, nullptr, (uint32_t)samples, f.slab.p, 0)) return fail(HD_ERR_INVALID, "no unpack kernel for this IQ format");
         }
-        if (const int rc = enqueue(f.slab, s, s, s1)) return rc;
+        if (const int rc = enqueue(f.slab.p, s, s, s1)) return rc;
     }
     return HD_OK;
 }
@@ -121,16 +109,12 @@ void destroy(Obj* o)
 struct hd_survey {
     WideFeed feed;
     uint32_t runs_per_launch = 1024;       // HD_SURVEY_RUNS, read at creation
-    float* partial = nullptr;              // [runs_per_launch][4096] float rows of the launch in flight (launches of one queue run in order)
-    double* acc = nullptr;                 // [4096], for the life of the survey
+    DevBuf<float> partial;                 // [runs_per_launch][4096] float rows of the launch in flight (launches of one queue run in order)
+    DevBuf<double> acc;                    // [4096], for the life of the survey
     double* h_acc = nullptr;               // page-locked landing place of the read-back
     double sum_w2 = 0;                     // sum of w^2, in double over the float table
     uint64_t segments = 0;
-    ~hd_survey()
-    {
-        for (void* p : {(void*)partial, (void*)acc}) if (p) (void)hipFree(p);
-        if (h_acc) (void)hipHostFree(h_acc);
-    }
+    ~hd_survey() { if (h_acc) (void)hipHostFree(h_acc); }
 };
 
 namespace {
@@ -141,8 +125,8 @@ int survey_enqueue(hd_survey* sv, const float2* x, uint64_t base_seg, uint64_t s
     for (uint64_t s = seg0; s < seg1;) {
         const uint64_t runs_left = (seg1 - s + r - 1) / r;
         const uint32_t runs = (uint32_t)std::min<uint64_t>(runs_left, sv->runs_per_launch);
-        hd::launch_survey(sv->feed.q, runs, x, sv->feed.win, sv->feed.tw, sv->partial, s - base_seg, seg1 - base_seg, r);
-        hd::launch_survey_reduce(sv->feed.q, sv->partial, runs, sv->acc);
+        hd::launch_survey(sv->feed.q, runs, x, sv->feed.win.p, sv->feed.tw, sv->partial.p, s - base_seg, seg1 - base_seg, r);
+        hd::launch_survey_reduce(sv->feed.q, sv->partial.p, runs, sv->acc.p);
         HD_HIP(hipGetLastError());
         s += (uint64_t)runs * r;
     }
@@ -184,10 +168,10 @@ int hd_survey_create(hd_engine* e, hd_survey** out)
     std::vector<float2> tw;
     if (const int rc = sv->feed.create(e, w, tw)) return rc;
     for (float v : w) sv->sum_w2 += (double)v * (double)v;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->partial), (size_t)sv->runs_per_launch * hd::kSurveyBins * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&sv->acc), hd::kSurveyBins * sizeof(double)));
+    HD_HIP(sv->partial.alloc_unfilled((size_t)sv->runs_per_launch * hd::kSurveyBins));
+    HD_HIP(sv->acc.alloc_unfilled(hd::kSurveyBins));
     HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&sv->h_acc), hd::kSurveyBins * sizeof(double), hipHostMallocDefault));
-    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->feed.q));
+    HD_HIP(hipMemsetAsync(sv->acc.p, 0, hd::kSurveyBins * sizeof(double), sv->feed.q));
     HD_HIP(hipStreamSynchronize(sv->feed.q));   // (the tables above are locals)
     *out = sv.release();
     return HD_OK;
@@ -200,7 +184,7 @@ int hd_survey_reset(hd_survey* sv)
     if (!sv) return fail(HD_ERR_INVALID, "null survey");
     std::lock_guard<std::recursive_mutex> lock(sv->feed.e->mtx);
     if (const int rc = enter(sv->feed.e)) return rc;
-    HD_HIP(hipMemsetAsync(sv->acc, 0, hd::kSurveyBins * sizeof(double), sv->feed.q));
+    HD_HIP(hipMemsetAsync(sv->acc.p, 0, hd::kSurveyBins * sizeof(double), sv->feed.q));
     HD_HIP(hipStreamSynchronize(sv->feed.q));   // (what was pushed before is done with its buffers)
     sv->segments = 0;
     return HD_OK;
@@ -219,7 +203,7 @@ int hd_survey_power(hd_survey* sv, double* p, size_t cap, uint64_t* segments)
     if (const int rc = enter(sv->feed.e)) return rc;
     if (segments) *segments = sv->segments;
     if (cap < hd::kSurveyBins) return 0;
-    HD_HIP(hipMemcpyAsync(sv->h_acc, sv->acc, hd::kSurveyBins * sizeof(double), hipMemcpyDeviceToHost, sv->feed.q));
+    HD_HIP(hipMemcpyAsync(sv->h_acc, sv->acc.p, hd::kSurveyBins * sizeof(double), hipMemcpyDeviceToHost, sv->feed.q));
     HD_HIP(hipStreamSynchronize(sv->feed.q));
     const double norm = (double)sv->segments * sv->sum_w2;
     for (uint32_t i = 0; i < hd::kSurveyBins; ++i) p[i] = sv->segments ? sv->h_acc[i] / norm : 0.0;
@@ -270,12 +254,12 @@ struct hd_waterfall {
     WideFeed feed;
     hd_waterfall_params par{};
     uint32_t guard_lo = 0, guard_hi = 0;   // the bins dc_guard_hz takes out
-    float* factor = nullptr;               // [65] F[s]
-    float* ring = nullptr;                 // [rows_cap][4096]: row r lives at slot r % rows_cap
-    uint32_t* hits = nullptr;              // [4096]
-    hd::WaterfallRec* rec = nullptr;       // [kChunkRows] the detector's records of the chunk in flight
+    DevBuf<float> factor;                  // [65] F[s]
+    DevBuf<float> ring;                    // [rows_cap][4096]: row r lives at slot r % rows_cap
+    DevBuf<uint32_t> hits;                 // [4096]
+    DevBuf<hd::WaterfallRec> rec;          // [kChunkRows] the detector's records of the chunk in flight
     hd::WaterfallRec* h_rec = nullptr;     // their page-locked landing place
-    uint32_t* d_seg = nullptr;             // [kChunkRows] hd_waterfall_push_rows: the chunk's segment counts
+    DevBuf<uint32_t> d_seg;                // [kChunkRows] hd_waterfall_push_rows: the chunk's segment counts
     uint32_t* h_hits = nullptr;            // page-locked landing place of hd_waterfall_hits
     uint64_t samples = 0;                  // pushed since creation or reset
     uint64_t rows_counted = 0;             // unflagged rows
@@ -285,7 +269,6 @@ struct hd_waterfall {
     uint32_t chunk_rows = kChunkRows;             // HD_WATERFALL_CHUNK, read at creation: fewer, so that short pushes reach the several-launch shapes
     ~hd_waterfall()
     {
-        for (void* p : {(void*)factor, (void*)ring, (void*)hits, (void*)rec, (void*)d_seg}) if (p) (void)hipFree(p);
         if (h_rec) (void)hipHostFree(h_rec);
         if (h_hits) (void)hipHostFree(h_hits);
     }
@@ -300,10 +283,10 @@ int waterfall_detect_chunk(hd_waterfall* wf, uint32_t slot, uint32_t n, const ui
                            const uint32_t* seg)
 {
     hipStream_t q = wf->feed.q;
-    hd::launch_waterfall_detect(q, n, wf->ring + (size_t)slot * hd::kWaterfallBins, d_seg, seg_full, seg_last, wf->guard_lo, wf->guard_hi, wf->factor, wf->rec);
-    hd::launch_waterfall_hits(q, wf->rec, n, wf->hits);
+    hd::launch_waterfall_detect(q, n, wf->ring.p + (size_t)slot * hd::kWaterfallBins, d_seg, seg_full, seg_last, wf->guard_lo, wf->guard_hi, wf->factor.p, wf->rec.p);
+    hd::launch_waterfall_hits(q, wf->rec.p, n, wf->hits.p);
     HD_HIP(hipGetLastError());
-    HD_HIP(hipMemcpyAsync(wf->h_rec, wf->rec, (size_t)n * sizeof(hd::WaterfallRec), hipMemcpyDeviceToHost, q));
+    HD_HIP(hipMemcpyAsync(wf->h_rec, wf->rec.p, (size_t)n * sizeof(hd::WaterfallRec), hipMemcpyDeviceToHost, q));
     HD_HIP(hipStreamSynchronize(q));
     for (uint32_t b = 0; b < n; ++b) {
         const hd::WaterfallRec& r = wf->h_rec[b];
@@ -327,7 +310,7 @@ int waterfall_enqueue(hd_waterfall* wf, const float2* x, uint64_t base_seg, uint
         const uint64_t rows_left = (seg1 - s + L - 1) / L;
         const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
         const uint32_t n = (uint32_t)std::min<uint64_t>(rows_left, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
-        hd::launch_survey(wf->feed.q, n, x, wf->feed.win, wf->feed.tw, wf->ring + (size_t)slot * hd::kWaterfallBins, s - base_seg, seg1 - base_seg, L);
+        hd::launch_survey(wf->feed.q, n, x, wf->feed.win.p, wf->feed.tw, wf->ring.p + (size_t)slot * hd::kWaterfallBins, s - base_seg, seg1 - base_seg, L);
         const uint64_t s_end = std::min<uint64_t>(seg1, s + (uint64_t)n * L);
         const uint32_t seg_last = (uint32_t)(s_end - (s + (uint64_t)(n - 1) * L));
         for (uint32_t b = 0; b < n; ++b) { first[b] = wf->samples + (s + (uint64_t)b * L) * hd::kSurveyHop; seg[b] = b + 1 == n ? seg_last : L; }
@@ -374,15 +357,15 @@ int hd_waterfall_create(hd_engine* e, const hd_waterfall_params* p, hd_waterfall
     if (const int rc = wf->feed.create(e, w, tw)) return rc;
     for (uint32_t s = 1; s <= hd::kWaterfallMaxSeg; ++s) f[s] = hd::waterfall_factor(wf->par.threshold_db, s);
     hipStream_t q = wf->feed.q;
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->factor), f.size() * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->ring), (size_t)wf->par.rows_cap * hd::kWaterfallBins * sizeof(float)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->hits), hd::kWaterfallBins * sizeof(uint32_t)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec)));
-    HD_HIP(hipMalloc(reinterpret_cast<void**>(&wf->d_seg), hd_waterfall::kChunkRows * sizeof(uint32_t)));
+    HD_HIP(wf->factor.alloc_unfilled(f.size()));
+    HD_HIP(wf->ring.alloc_unfilled((size_t)wf->par.rows_cap * hd::kWaterfallBins));
+    HD_HIP(wf->hits.alloc_unfilled(hd::kWaterfallBins));
+    HD_HIP(wf->rec.alloc_unfilled(hd_waterfall::kChunkRows));
+    HD_HIP(wf->d_seg.alloc_unfilled(hd_waterfall::kChunkRows));
     HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_rec), hd_waterfall::kChunkRows * sizeof(hd::WaterfallRec), hipHostMallocDefault));
     HD_HIP(hipHostMalloc(reinterpret_cast<void**>(&wf->h_hits), hd::kWaterfallBins * sizeof(uint32_t), hipHostMallocDefault));
-    HD_HIP(hipMemcpyAsync(wf->factor, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, q));
-    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), q));
+    HD_HIP(hipMemcpyAsync(wf->factor.p, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, q));
+    HD_HIP(hipMemsetAsync(wf->hits.p, 0, hd::kWaterfallBins * sizeof(uint32_t), q));
     HD_HIP(hipStreamSynchronize(q));   // (the tables above are locals)
     *out = wf.release();
     return HD_OK;
@@ -395,7 +378,7 @@ int hd_waterfall_reset(hd_waterfall* wf)
     if (!wf) return fail(HD_ERR_INVALID, "null waterfall");
     std::lock_guard<std::recursive_mutex> lock(wf->feed.e->mtx);
     if (const int rc = enter(wf->feed.e)) return rc;
-    HD_HIP(hipMemsetAsync(wf->hits, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->feed.q));
+    HD_HIP(hipMemsetAsync(wf->hits.p, 0, hd::kWaterfallBins * sizeof(uint32_t), wf->feed.q));
     HD_HIP(hipStreamSynchronize(wf->feed.q));
     wf->headers.clear();
     wf->marks.clear();
@@ -425,12 +408,12 @@ int hd_waterfall_push_rows(hd_waterfall* wf, const float* rows, const uint32_t* 
     for (uint32_t r = 0; r < n_rows;) {
         const uint32_t slot = (uint32_t)(wf->headers.size() % wf->par.rows_cap);
         const uint32_t n = std::min(n_rows - r, std::min<uint32_t>(wf->chunk_rows, wf->par.rows_cap - slot));
-        HD_HIP(hipMemcpyAsync(wf->ring + (size_t)slot * hd::kWaterfallBins, rows + (size_t)r * hd::kWaterfallBins, (size_t)n * hd::kWaterfallBins * sizeof(float),
+        HD_HIP(hipMemcpyAsync(wf->ring.p + (size_t)slot * hd::kWaterfallBins, rows + (size_t)r * hd::kWaterfallBins, (size_t)n * hd::kWaterfallBins * sizeof(float),
                               device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, q));
-        HD_HIP(hipMemcpyAsync(wf->d_seg, segments + r, n * sizeof(uint32_t), hipMemcpyHostToDevice, q));
+        HD_HIP(hipMemcpyAsync(wf->d_seg.p, segments + r, n * sizeof(uint32_t), hipMemcpyHostToDevice, q));
         uint64_t at = wf->samples;
         for (uint32_t b = 0; b < n; ++b) { first[b] = at; at += (uint64_t)segments[r + b] * hd::kSurveyHop; }
-        if (const int rc = waterfall_detect_chunk(wf, slot, n, wf->d_seg, 0, 0, first, segments + r)) return rc;
+        if (const int rc = waterfall_detect_chunk(wf, slot, n, wf->d_seg.p, 0, 0, first, segments + r)) return rc;
         wf->samples = at;
         r += n;
     }
@@ -476,7 +459,7 @@ int hd_waterfall_rows(hd_waterfall* wf, uint64_t first_row, uint32_t n, float* o
     for (uint32_t r = 0; r < n;) {           // at most two pieces: the ring wraps once inside rows_cap rows
         const uint32_t slot = (uint32_t)((first_row + r) % cap);
         const uint32_t k = (uint32_t)std::min<uint64_t>(n - r, cap - slot);
-        HD_HIP(hipMemcpyAsync(out + (size_t)r * hd::kWaterfallBins, wf->ring + (size_t)slot * hd::kWaterfallBins, (size_t)k * hd::kWaterfallBins * sizeof(float),
+        HD_HIP(hipMemcpyAsync(out + (size_t)r * hd::kWaterfallBins, wf->ring.p + (size_t)slot * hd::kWaterfallBins, (size_t)k * hd::kWaterfallBins * sizeof(float),
                               hipMemcpyDeviceToHost, wf->feed.q));
         r += k;
     }
@@ -490,7 +473,7 @@ int hd_waterfall_hits(hd_waterfall* wf, uint32_t hits[4096], uint64_t* rows_coun
     if (!hits) return fail(HD_ERR_INVALID, "null output");
     std::lock_guard<std::recursive_mutex> lock(wf->feed.e->mtx);
     if (const int rc = enter(wf->feed.e)) return rc;
-    HD_HIP(hipMemcpyAsync(wf->h_hits, wf->hits, hd::kWaterfallBins * sizeof(uint32_t), hipMemcpyDeviceToHost, wf->feed.q));
+    HD_HIP(hipMemcpyAsync(wf->h_hits, wf->hits.p, hd::kWaterfallBins * sizeof(uint32_t), hipMemcpyDeviceToHost, wf->feed.q));
     HD_HIP(hipStreamSynchronize(wf->feed.q));
     std::memcpy(hits, wf->h_hits, hd::kWaterfallBins * sizeof(uint32_t));
     if (rows_counted) *rows_counted = wf->rows_counted;

@@ -1,8 +1,6 @@
 """The first stage with the rotation at the input rate in its staging loop (k_decimate_tuned, kernels/decimate.hip), from the compiler's own metadata:
 all eight first-stage shapes compile for gfx950 in both arithmetic modes without spills or scratch, and the single-wave shapes keep the occupancy of the
 untuned kernel they stand in for.  No GPU needed: hipcc cross-compiles a device-only listing, read the way tests/test_kernel_resources.py reads it."""
-import re
-
 import pytest
 
 from test_kernel_resources import CSRC, kernel_table
@@ -11,16 +9,9 @@ SHAPES = ["2,69,256", "4,139,256", "8,280,256", "8,54,256", "16,107,128", "32,21
 CU_LDS = 160 * 1024
 
 
-def lds_bytes(listing: str):
+def lds_bytes(table: dict):
     """kernel name as kernel_table spells it -> static LDS of a workgroup"""
-    import subprocess
-    out = {}
-    meta = listing[listing.index("amdhsa.kernels:"):]
-    for blk in re.split(r"\n  - \.agpr_count", meta)[1:]:
-        name = subprocess.run(["c++filt", re.search(r"\.name:\s+(\S+)", blk).group(1)], capture_output=True, text=True).stdout.strip()
-        name = re.sub(r"\(.*", "", name).replace("void hd::", "").replace("hd::", "").replace("exact::", "").replace("fast::", "").replace(" ", "")
-        out[name] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk).group(1))
-    return out
+    return {name: k["lds"] for name, k in table.items()}
 
 
 def workgroups_per_cu(vgpr: int, lds: int, lanes: int) -> int:
@@ -34,7 +25,7 @@ def workgroups_per_cu(vgpr: int, lds: int, lanes: int) -> int:
 def test_tuned_first_stages_do_not_spill_and_keep_their_occupancy(tmp_path, fast):
     t = kernel_table(CSRC / "kernels" / "decimate.hip", tmp_path, fast)
     listing = (tmp_path / "decimate.s").read_text()
-    lds = lds_bytes(listing)
+    lds = lds_bytes(t)
     for shape in SHAPES:
         k, u = f"k_decimate_tuned<{shape}>", f"k_decimate<{shape}>"
         assert k in t, (k, sorted(x for x in t if x.startswith("k_decimate")))

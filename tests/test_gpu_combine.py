@@ -319,3 +319,15 @@ def test_four_receivers_of_two_payloads_end_to_end(hd, receivers):
     assert n_combined >= max(single) + 3
     assert all(comb.debug_guards(s) == 0 for s in range(8))
     eng.close()
+
+
+# ---------------------------------------------------------------- the guard hook itself
+
+def test_the_guard_hook_counts_damaged_words(hd):
+    from test_gpu_tones import damage_the_row_guards
+    eng = hd.Engine(n_streams=3, max_chunk=TM.WEAK["n"], sampling_rate=TM.WEAK["fs"], decimation=TM.WEAK["D"])
+    comb = hd.combine.Combiner(eng, max_push=64)
+    d_rows, stride, _ = comb.rows()
+    damaged, restored = damage_the_row_guards(comb.debug_guards, d_rows, stride, 64)
+    assert damaged == [1, 2, 1] and restored == [0, 0, 0]
+    eng.close()

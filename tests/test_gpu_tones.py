@@ -285,3 +285,42 @@ def test_bad_parameters_and_null_arguments(hd):
     assert t.stats(0)["samples"] == 100
     assert L.hd_debug_tones_guards(t.h, 0) == 0 and L.hd_debug_tones_guards(t.h, 1) == 0
     eng.close()
+
+
+# ---------------------------------------------------------------- the guard hook itself
+
+def damage_the_row_guards(hook, d_rows, stride, max_push):
+    """What an hd_debug_*_guards hook says of three streams' output rows while four guard words are overwritten in device memory, and after they are put
+    back.  d_rows, stride: as hd_*_rows gives them (the address of row 0's payload, a row's stride in floats); G words guard a row on either side."""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes, hip.hipMemcpy.restype = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int], ctypes.c_int
+    to_device, to_host = 1, 2
+    G = (stride - max_push) // 2
+    assert G >= 1 and stride == max_push + 2 * G
+    words = [-G,                                  # the first word of the allocation
+             stride - 1,                          # the last word of stream 1's front guard
+             stride + max_push,                   # the first word of stream 1's back guard
+             2 * stride + max_push + G - 1]       # the last word of the allocation
+    saved = []
+    for w in words:
+        v = ctypes.c_uint32(0)
+        assert hip.hipMemcpy(ctypes.byref(v), d_rows + 4 * w, 4, to_host) == 0
+        saved.append(v.value)
+        bad = ctypes.c_uint32(v.value ^ 0xFFFFFFFF)
+        assert hip.hipMemcpy(d_rows + 4 * w, ctypes.byref(bad), 4, to_device) == 0
+    assert len(set(saved)) == 1, saved            # all four held the one pattern
+    damaged = [hook(s) for s in range(3)]
+    for w, v in zip(words, saved):
+        assert hip.hipMemcpy(d_rows + 4 * w, ctypes.byref(ctypes.c_uint32(v)), 4, to_device) == 0
+    return damaged, [hook(s) for s in range(3)]
+
+
+def test_the_guard_hook_counts_damaged_words(hd):
+    """The hook looks at the words that guard the rows: the outermost words of the array and the two guards between streams 1's neighbours."""
+    eng = hd.Engine(n_streams=3, max_chunk=TM.WEAK["n"], sampling_rate=TM.WEAK["fs"], decimation=TM.WEAK["D"])
+    t = eng.tones(max_push=64)
+    d_rows, stride, _ = t.rows()
+    damaged, restored = damage_the_row_guards(lambda s: eng.L.hd_debug_tones_guards(t.h, s), d_rows, stride, 64)
+    assert damaged == [1, 2, 1] and restored == [0, 0, 0]
+    eng.close()

@@ -33,7 +33,8 @@ def kernel_table(src: Path, tmp: Path, fast: bool = False):
         g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
         name = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip()
         name = re.sub(r"\(.*", "", name).replace("void hd::", "").replace("hd::", "").replace("exact::", "").replace("fast::", "").replace(" ", "")
-        table[name] = dict(vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")), scratch=int(g("private_segment_fixed_size")))
+        table[name] = dict(vgpr=int(g("vgpr_count")), spill=int(g("vgpr_spill_count")), scratch=int(g("private_segment_fixed_size")),
+                           sgpr=int(g("sgpr_count")), sgpr_spill=int(g("sgpr_spill_count")), lds=int(g("group_segment_fixed_size")))
     return table
 
 

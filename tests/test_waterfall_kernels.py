@@ -30,8 +30,5 @@ def test_waterfall_kernels(tmp_path):
     assert "ds_add_u32" in txt                                               # ... and they are there
     assert "v_fma_f32" not in txt and "v_pk_fma_f32" not in txt              # floor and level: each product and sum rounded once
     # LDS per workgroup: the row (16 KiB), four histograms (4 KiB), a few words -- two workgroups and more fit a CU's 160 KiB
-    meta = txt[txt.index("amdhsa.kernels:"):]
-    blk = [b for b in re.split(r"\n  - \.agpr_count", meta)[1:] if "k_waterfall_detect" in b]
-    assert len(blk) == 1
-    lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk[0]).group(1))
+    lds = t["k_waterfall_detect"]["lds"]
     assert 20 * 1024 <= lds <= 21 * 1024 and 2 * lds <= 160 * 1024, lds

@@ -6,57 +6,40 @@ Per repetition: batch calls (pipeline = 2), hd_flush, the tone-filter demodulato
 rows (cfg4: 1024 streams in 256 groups of 4, 1024 samples each), both through the library's measurement hooks (host time of the whole call; the kernel
 alone between two HIP events).  Prints the medians and the spreads (min .. max) over the repetitions behind the warm-up, k_combine against the yardstick
 -- k_tones' median plus its max - min for the same calls -- and the wall time of hd_combine_lags over every group at the default window and lag range."""
-import argparse, ctypes as C, statistics, sys, time
-from pathlib import Path
-ROOT = Path(__file__).resolve().parents[2]
-sys.path.insert(0, str(ROOT))
-import numpy as np, torch, bench, habdec_amd
+import ctypes as C, time
+import numpy as np
+from _rate import Rig, fmt, med, parser
 from habdec_amd import capi
 from habdec_amd.combine import Combiner, _lag_params
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="cfg4"); ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=7)
+    ap = parser()
     ap.add_argument("--members", type=int, default=4); ap.add_argument("--shift", type=float, default=500.0)
     a = ap.parse_args()
-    w = dict(bench.WORKLOADS[a.workload]); S, Cn = w["S"], w["C"]
-    dev = torch.device("cuda", 0)
-    ring, rc, _ = bench.generate_ring(torch, dev, w, S, 0, 1234)
-    base = ring.data_ptr()
-    eng = habdec_amd.Engine(n_streams=S, max_chunk=Cn, sampling_rate=w["fs"], decimation=w["D"], baud=w["baud"], rtty_bits=w["bits"], rtty_stops=w["stops"],
-                            lowpass_bw_hz=w["lp_bw"], lowpass_trans=w["lp_trans"], ungated=w["ungated"], pipeline=2)
+    rig = Rig(a.workload); eng, w, S, Cn = rig.eng, rig.w, rig.S, rig.Cn
     tones, comb = eng.tones(), Combiner(eng)
     for s in range(S):
         tones.set_modem(s, 0, a.shift / 2, -a.shift / 2)
     groups = [list(range(g, min(g + a.members, S))) for g in range(0, S, a.members)]
     for g in groups:
         comb.set_group(g)
-    t_tones = eng.L.hd_debug_tones_push_timed
-    t_tones.restype, t_tones.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-    t_comb = eng.L.hd_debug_combine_push_timed
-    t_comb.restype, t_comb.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    t_tones = rig.timed("hd_debug_tones_push_timed")
+    t_comb = rig.timed("hd_debug_combine_push_timed", C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32)
     host_us, kern_us = {"tones": [], "combine": []}, {"tones": [], "combine": []}
-    i = 0
 
     def one(keep):
-        nonlocal i
-        for _ in range(4):
-            eng.process_device(base + (i % rc) * S * Cn * 8, Cn, Cn); i += 1
-        eng.flush()
-        ms, us = C.c_float(0), C.c_double(0)
-        capi.check(t_tones(tones.h, C.byref(ms), C.byref(us)))
+        rig.feed(4)
+        kern, host = t_tones(tones.h)
         if keep:
-            host_us["tones"].append(us.value); kern_us["tones"].append(ms.value * 1e3)
+            host_us["tones"].append(host); kern_us["tones"].append(kern)
         ptr, stride, n = tones.rows()
-        capi.check(t_comb(comb.h, ptr, stride, n.ctypes.data, 0, C.byref(ms), C.byref(us)))
+        kern, host = t_comb(comb.h, ptr, stride, n.ctypes.data, 0)
         if keep:
-            host_us["combine"].append(us.value); kern_us["combine"].append(ms.value * 1e3)
+            host_us["combine"].append(host); kern_us["combine"].append(kern)
 
     for r in range(a.warmup + a.reps):
         one(r >= a.warmup)
-    med = statistics.median
-    fmt = lambda v: f"median {med(v):.1f} us (min {min(v):.1f} .. max {max(v):.1f})"
     print(f"workload {a.workload} S={S} in {len(groups)} groups of {a.members}, {Cn // w['D']} decimated samples per stream and call: median of {a.reps} behind {a.warmup}")
     print("hd_tones_push_engine, host time of the call:                   ", fmt(host_us["tones"]))
     print("k_tones alone (HIP events):                                    ", fmt(kern_us["tones"]))

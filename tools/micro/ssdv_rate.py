@@ -8,56 +8,40 @@ random bytes.  Per repetition: one batch call, hd_flush, hd_clocked_push_engine,
 warm-up, the yardstick (k_clocked's median plus its max - min: HELD or MISSED, not a gate).  cfg4's rows turn out to give that modem too few characters
 for any stream to reach a packet's length, so the tool then times hd_ssdv_scan under a stated load of random bytes (--per-stream per stream and scan),
 where every candidate fails all four trials, and the restatement on one core for the same number of candidates."""
-import argparse, ctypes as C, statistics, sys, time
-from pathlib import Path
-ROOT = Path(__file__).resolve().parents[2]
-sys.path.insert(0, str(ROOT))
-import numpy as np, torch, bench, habdec_amd
+import ctypes as C, time
+import numpy as np
+from _rate import Rig, fmt, med, parser
 from habdec_amd.ssdv import HostSsdv, Ssdv
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="cfg4"); ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=7)
+    ap = parser()
     ap.add_argument("--calls", type=int, default=1, help="batch calls and clocked pushes per hd_ssdv_push_clocked (1: after each clocked push)")
     ap.add_argument("--lead", type=int, default=100, help="unmeasured calls in front, until every stream holds a packet's length of bytes")
     ap.add_argument("--per-stream", type=int, default=4, help="bytes per stream and scan of the stated load")
     a = ap.parse_args()
-    w = dict(bench.WORKLOADS[a.workload]); S, Cn = w["S"], w["C"]
-    dev = torch.device("cuda", 0)
-    ring, rc, _ = bench.generate_ring(torch, dev, w, S, 0, 1234)
-    base = ring.data_ptr()
-    eng = habdec_amd.Engine(n_streams=S, max_chunk=Cn, sampling_rate=w["fs"], decimation=w["D"], baud=w["baud"], rtty_bits=w["bits"], rtty_stops=w["stops"],
-                            lowpass_bw_hz=w["lp_bw"], lowpass_trans=w["lp_trans"], ungated=w["ungated"], pipeline=2)
+    rig = Rig(a.workload); eng, w, S, Cn = rig.eng, rig.w, rig.S, rig.Cn
     clk, v = eng.clocked(), Ssdv(eng)
     for s in range(S):
         clk.set_modem(s, 300.0, 8, 2)
-    f_clk, f_v = eng.L.hd_debug_clocked_push_timed, eng.L.hd_debug_ssdv_scan_timed
-    f_clk.restype, f_clk.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-    f_v.restype, f_v.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    f_clk, f_v = rig.timed("hd_debug_clocked_push_timed"), rig.timed("hd_debug_ssdv_scan_timed", C.c_void_p)
     host_us, kern_us = {"clocked": [], "ssdv": []}, {"clocked": [], "ssdv": []}
-    new_bytes, i = [], 0
+    new_bytes = []
     for _ in range(a.lead):                                          # a stream decides nothing before it holds 256 bytes: about 75 calls' characters
-        eng.process_device(base + (i % rc) * S * Cn * 8, Cn, Cn); i += 1
-        eng.flush()
+        rig.feed()
         clk.push_engine()
     v.push_clocked(clk)
     for r in range(a.warmup + a.reps):
-        ms, us = C.c_float(0), C.c_double(0)
         kc = hc = 0.0
         for _ in range(a.calls):                                     # (one clocked push per batch call: a push takes the call delivered last)
-            eng.process_device(base + (i % rc) * S * Cn * 8, Cn, Cn); i += 1
-            eng.flush()
-            habdec_amd.capi.check(f_clk(clk.h, C.byref(ms), C.byref(us)))
-            kc, hc = ms.value * 1e3, us.value
+            rig.feed()
+            kc, hc = f_clk(clk.h)
         before = sum(v.stats(s)["bytes"] for s in range(S))
-        habdec_amd.capi.check(f_v(v.h, clk.h, C.byref(ms), C.byref(us)))
+        kv, hv = f_v(v.h, clk.h)
         if r >= a.warmup:
             host_us["clocked"].append(hc); kern_us["clocked"].append(kc)
-            host_us["ssdv"].append(us.value); kern_us["ssdv"].append(ms.value * 1e3)
+            host_us["ssdv"].append(hv); kern_us["ssdv"].append(kv)
             new_bytes.append(sum(v.stats(s)["bytes"] for s in range(S)) - before)
-    med = statistics.median
-    fmt = lambda x: f"median {med(x):.1f} us (min {min(x):.1f} .. max {max(x):.1f})"
     print(f"workload {a.workload} S={S}, {a.calls} calls of {Cn // w['D']} decimated samples per repetition: median of {a.reps} behind {a.warmup}")
     print("hd_ssdv_push_clocked, host time of the call:  ", fmt(host_us["ssdv"]))
     print("k_ssdv_scan alone (HIP events):                ", fmt(kern_us["ssdv"]))
@@ -81,10 +65,9 @@ def main():
     for r in range(a.warmup + a.reps):
         for s in range(S):
             w2.push_bytes(s, rng.integers(0, 256, a.per_stream, dtype=np.uint8), rng.integers(0, 1 << 24, a.per_stream, dtype=np.uint32))
-        ms, us = C.c_float(0), C.c_double(0)
-        habdec_amd.capi.check(f_v(w2.h, None, C.byref(ms), C.byref(us)))
+        kv, hv = f_v(w2.h, None)
         if r >= a.warmup:
-            syn_host.append(us.value); syn_kern.append(ms.value * 1e3)
+            syn_host.append(hv); syn_kern.append(kv)
     st2 = [w2.stats(s) for s in range(S)]
     print(f"stated load, {S * a.per_stream} candidates of random bytes per scan ({a.per_stream} per stream): hd_ssdv_scan host time", fmt(syn_host))
     print("k_ssdv_scan alone under that load (HIP events):", fmt(syn_kern), "; crc_bad", sum(x["crc_bad"] for x in st2), "of", sum(x["decided"] for x in st2), "decided")

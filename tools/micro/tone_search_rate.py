@@ -7,51 +7,35 @@ Per repetition: one batch call (pipeline = 2), hd_flush, then the tone search's 
 push completes one segment per stream -- 1024 transforms, one wave per SIMD -- and the pushes between only append to the carries: the two kinds are
 reported separately, each as the median and the spread (min .. max) over the repetitions behind the warm-up.  The yardstick is hd_survey_push_device of
 S segments (2048 (S - 1) + 4096 samples, one segment per wave) between HIP events on the survey's queue."""
-import argparse, ctypes as C, statistics, sys
-from pathlib import Path
-ROOT = Path(__file__).resolve().parents[2]
-sys.path.insert(0, str(ROOT))
-import torch, bench, habdec_amd
+import ctypes as C
+from _rate import Rig, fmt, habdec_amd, med, parser, torch
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="cfg4"); ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=7)
-    a = ap.parse_args()
-    w = dict(bench.WORKLOADS[a.workload]); S, Cn = w["S"], w["C"]
-    dev = torch.device("cuda", 0)
-    ring, rc, _ = bench.generate_ring(torch, dev, w, S, 0, 1234)
-    base = ring.data_ptr()
-    eng = habdec_amd.Engine(n_streams=S, max_chunk=Cn, sampling_rate=w["fs"], decimation=w["D"], baud=w["baud"], rtty_bits=w["bits"], rtty_stops=w["stops"],
-                            lowpass_bw_hz=w["lp_bw"], lowpass_trans=w["lp_trans"], ungated=w["ungated"], pipeline=2)
+    a = parser().parse_args()
+    rig = Rig(a.workload); eng, w, S, Cn = rig.eng, rig.w, rig.S, rig.Cn
     ts, sv = eng.tone_search(), eng.survey()
-    timed = eng.L.hd_debug_tone_search_push_timed
-    timed.restype, timed.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
+    timed = rig.timed("hd_debug_tone_search_push_timed")
     sv_timed = eng.L.hd_debug_survey_push_timed
     sv_timed.restype, sv_timed.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_float)]
     n_sv = 2048 * (S - 1) + 4096
-    wide = torch.randn(2 * n_sv, device=dev, dtype=torch.float32)
+    wide = torch.randn(2 * n_sv, device=rig.dev, dtype=torch.float32)
     torch.cuda.synchronize()
     host_us, kern_us, survey_us = {"light": [], "transform": []}, {"light": [], "transform": []}, []
     seen = {"light": 0, "transform": 0}
-    i = 0
     while min(seen.values()) < a.warmup + a.reps:
-        eng.process_device(base + (i % rc) * S * Cn * 8, Cn, Cn); i += 1
-        eng.flush()
+        rig.feed()
         before = ts.stats(0)["segments"]
-        ms, us = C.c_float(0), C.c_double(0)
-        habdec_amd.capi.check(timed(ts.h, C.byref(ms), C.byref(us)))
+        kern, host = timed(ts.h)
         kind = "transform" if ts.stats(0)["segments"] > before else "light"
         seen[kind] += 1
         if seen[kind] > a.warmup and len(host_us[kind]) < a.reps:
-            host_us[kind].append(us.value); kern_us[kind].append(ms.value * 1e3)
+            host_us[kind].append(host); kern_us[kind].append(kern)
     for r in range(a.warmup + a.reps):
         ms = C.c_float(0)
         habdec_amd.capi.check(sv_timed(sv.h, wide.data_ptr(), n_sv, C.byref(ms)))
         if r >= a.warmup:
             survey_us.append(ms.value * 1e3)
-    med = statistics.median
-    fmt = lambda v: f"median {med(v):.1f} us (min {min(v):.1f} .. max {max(v):.1f})"
     print(f"workload {a.workload} S={S}, {Cn // w['D']} decimated samples per stream and call: median of {a.reps} behind {a.warmup}; stream 0: {ts.stats(0)}")
     print("hd_tone_search_push_engine, a push that completes no segment, host time:  ", fmt(host_us["light"]))
     print("k_tone_search of such a push (HIP events):                                ", fmt(kern_us["light"]))

@@ -6,46 +6,28 @@ Per repetition: batch calls (pipeline = 2), hd_flush, then the tone-filter demod
 call's discriminator output (cfg4: 1024 streams, 1024 decimated samples each), both through the library's measurement hooks (host time of the whole call;
 the kernel alone between two HIP events); which of the two goes first alternates.  Prints the medians and the spreads (min .. max) over the repetitions
 behind the warm-up."""
-import argparse, ctypes as C, statistics, sys
-from pathlib import Path
-ROOT = Path(__file__).resolve().parents[2]
-sys.path.insert(0, str(ROOT))
-import torch, bench, habdec_amd
+from _rate import Rig, fmt, med, parser
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="cfg4"); ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--reps", type=int, default=7)
+    ap = parser()
     ap.add_argument("--shift", type=float, default=500.0, help="the tones are set shift / 2 above and below the centre")
     a = ap.parse_args()
-    w = dict(bench.WORKLOADS[a.workload]); S, Cn = w["S"], w["C"]
-    dev = torch.device("cuda", 0)
-    ring, rc, _ = bench.generate_ring(torch, dev, w, S, 0, 1234)
-    base = ring.data_ptr()
-    eng = habdec_amd.Engine(n_streams=S, max_chunk=Cn, sampling_rate=w["fs"], decimation=w["D"], baud=w["baud"], rtty_bits=w["bits"], rtty_stops=w["stops"],
-                            lowpass_bw_hz=w["lp_bw"], lowpass_trans=w["lp_trans"], ungated=w["ungated"], pipeline=2)
+    rig = Rig(a.workload); eng, w, S, Cn = rig.eng, rig.w, rig.S, rig.Cn
     probe, tones = eng.baud_probe(), eng.tones()
     for s in range(S):
         tones.set_modem(s, 0, a.shift / 2, -a.shift / 2)
     hooks = {}
     for name, obj in (("probe", probe), ("tones", tones)):
-        f = getattr(eng.L, "hd_debug_baud_probe_push_timed" if name == "probe" else "hd_debug_tones_push_timed")
-        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]
-        hooks[name] = (f, obj)
+        hooks[name] = (rig.timed("hd_debug_baud_probe_push_timed" if name == "probe" else "hd_debug_tones_push_timed"), obj)
     host_us, kern_us = {k: [] for k in hooks}, {k: [] for k in hooks}
-    i = 0
     for r in range(a.warmup + a.reps):
-        for _ in range(4):
-            eng.process_device(base + (i % rc) * S * Cn * 8, Cn, Cn); i += 1
-        eng.flush()
+        rig.feed(4)
         for name in (("probe", "tones") if r % 2 else ("tones", "probe")):
             f, obj = hooks[name]
-            ms, us = C.c_float(0), C.c_double(0)
-            habdec_amd.capi.check(f(obj.h, C.byref(ms), C.byref(us)))
+            kern, host = f(obj.h)
             if r >= a.warmup:
-                host_us[name].append(us.value); kern_us[name].append(ms.value * 1e3)
-    med = statistics.median
-    fmt = lambda v: f"median {med(v):.1f} us (min {min(v):.1f} .. max {max(v):.1f})"
+                host_us[name].append(host); kern_us[name].append(kern)
     st = tones.stats(0)
     print(f"workload {a.workload} S={S}, {Cn // w['D']} decimated samples per stream and call: median of {a.reps} behind {a.warmup}; modem of stream 0: {st}")
     print("hd_tones_push_engine, host time of the call:     ", fmt(host_us["tones"]))
