@@ -7,7 +7,7 @@ synthetic IQ generator.  There is no Python or CPU implementation of the data pa
 `lib()` raises.
 """
 from .capi import lib, LIB_PATH, HabdecError  # noqa: F401
-from .engine import BaudProbe, Clocked, Engine, EngineConfig, HostBaudProbe, HostClocked, HostFormatTrial, HostToneSearch, HostTones, IqFiles, Survey, ToneSearch, Tones, Waterfall, chase_repair, survey_detect, tone_search_detect, waterfall_tracks  # noqa: F401
+from .engine import BaudProbe, Clocked, Engine, EngineConfig, HostBaudProbe, HostClocked, HostFormatTrial, HostToneSearch, HostTones, IqFiles, Survey, ToneSearch, Tones, Waterfall, chase_repair, fir_demod_lds_bytes, fir_demod_max_taps, survey_detect, tone_search_detect, waterfall_tracks  # noqa: F401
 
 __all__ = ["lib", "LIB_PATH", "HabdecError", "BaudProbe", "Clocked", "Engine", "EngineConfig", "HostBaudProbe", "HostClocked", "HostFormatTrial", "HostToneSearch", "HostTones", "IqFiles", "Survey", "ToneSearch", "Tones",
-           "Waterfall", "chase_repair", "survey_detect", "tone_search_detect", "waterfall_tracks"]
+           "Waterfall", "chase_repair", "fir_demod_lds_bytes", "fir_demod_max_taps", "survey_detect", "tone_search_detect", "waterfall_tracks"]

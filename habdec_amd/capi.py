@@ -212,6 +212,7 @@ ENGINE_API = {
     "hd_engine_streams": (_u32, [_vp]),
     "hd_engine_decimation": (_u32, [_vp]),
     "hd_engine_decimated_rate": (_dbl, [_vp]),
+    "hd_engine_lowpass_taps_max": (_u32, [_vp]),
     "hd_stream_set_baud": (_int, [_vp, _u32, _dbl]),
     "hd_stream_set_rtty": (_int, [_vp, _u32, _u32, _f]),
     "hd_stream_set_lowpass_bw": (_int, [_vp, _u32, _f]),
@@ -358,6 +359,8 @@ HOST_API = {
     "hd_host_decim_plan": (_int, [C.c_uint, C.POINTER(_int), C.POINTER(C.c_uint)]),
     "hd_host_decim_taps": (_sz, [C.c_uint, _int, _f32p, _sz]),
     "hd_host_lowpass_design": (_sz, [_f, _f, _sz, _sz, _int, _f32p, _sz]),
+    "hd_host_fir_demod_lds_bytes": (_sz, [_u32, C.POINTER(C.c_size_t)]),
+    "hd_host_fir_demod_max_taps": (_u32, [_sz]),
     "hd_host_rtty_new": (_vp, [_sz, _f]),
     "hd_host_rtty_free": (None, [_vp]),
     "hd_host_rtty_pending": (_sz, [_vp]),

@@ -51,12 +51,16 @@ __host__ __device__ inline uint32_t sc_pack_fft_run(uint32_t run, uint32_t buf) 
 // buffers take turns).  So no run writes a head any more (33 MB per step at /16, 67 at /4, 8.4 in the headline launch, for a change that may never come):
 //   head_prev = 1: the stream's previous run was the PREVIOUS call -- a consumer reads head[j] = prev_buf[fir_hist_cap + j], j < head_n;
 //   head_prev = 0: it was earlier -- the head was copied aside (head_save = 1) by the first call in which the stream did not run, and sits in the side buffer.
-__host__ __device__ inline uint32_t sc_taps_prev(const StreamCall& c) { return c.fir_taps_prev & 0xFFFFu; }
+// (The tap count has sixteen bits here.  No run has more: the engine refuses a design above min(taps_cap, what k_fir_demod's LDS image admits, kTapsPrevMax)
+// while it plans the call -- hd_engine_lowpass_taps_max, host/fir_lds.hpp, where a static assertion holds the LDS limit of a 160 KB CU against this field.
+// That closes ADVICE r06's finding: a count of 65537 or more used to be cut to its low bits, so that every run took itself for the first after a change.)
+constexpr uint32_t kTapsPrevMax = 0xFFFFu;
+__host__ __device__ inline uint32_t sc_taps_prev(const StreamCall& c) { return c.fir_taps_prev & kTapsPrevMax; }
 __host__ __device__ inline uint32_t sc_head_n(const StreamCall& c) { return (c.fir_taps_prev >> 16) & 0x3FFFu; }
 __host__ __device__ inline bool sc_head_prev(const StreamCall& c) { return (c.fir_taps_prev >> 30) & 1u; }
 __host__ __device__ inline bool sc_head_save(const StreamCall& c) { return (c.fir_taps_prev >> 31) & 1u; }
 __host__ __device__ inline uint32_t sc_pack_taps_prev(uint32_t taps_prev, uint32_t head_n, bool head_prev, bool head_save)
-{ return (taps_prev & 0xFFFFu) | ((head_n & 0x3FFFu) << 16) | ((head_prev ? 1u : 0u) << 30) | ((head_save ? 1u : 0u) << 31); }
+{ return (taps_prev & kTapsPrevMax) | ((head_n & 0x3FFFu) << 16) | ((head_prev ? 1u : 0u) << 30) | ((head_save ? 1u : 0u) << 31); }
 
 // Low-pass history across a change of the tap count.  The reference keeps ONE buffer [history (T-1) | input (m)] per filter
 // (FirFilter.h:141-167): after a run its first T-1 slots hold the last T-1 inputs, the slots behind still hold the run's

@@ -137,6 +137,15 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         hipDeviceProp_t prop;
         HD_HIP(hipGetDeviceProperties(&prop, cfg->device));
         e->n_cus = (uint32_t)prop.multiProcessorCount;
+        // The longest low-pass the engine runs: k_fir_demod keeps a tile's inputs for ALL taps in LDS, and a workgroup gets what the device grants one (with
+        // the opt-in launch_fir_demod asks for above 64 KB) -- 18899 taps inside a gfx950 CU's 160 KB.  The exact mode takes that kernel for every run, the
+        // fast mode for every run that starts a filter from zeros, so the one limit holds for both; plan_call refuses a longer design.
+        int lds_block = 0, lds_optin = 0;
+        HD_HIP(hipDeviceGetAttribute(&lds_block, hipDeviceAttributeMaxSharedMemoryPerBlock, cfg->device));
+        if (hipDeviceGetAttribute(&lds_optin, hipDeviceAttributeSharedMemPerBlockOptin, cfg->device) != hipSuccess) { (void)hipGetLastError(); lds_optin = 0; }
+        e->lds_per_wg = (size_t)std::max(std::max(lds_block, lds_optin), 0);
+        e->lp_taps_max = std::min<uint32_t>(hd::fir_demod_max_taps(e->lds_per_wg), hd::kTapsPrevMax);
+        if (e->lp_taps_max < 161u) return fail(HD_ERR_DEVICE, "the device grants a workgroup " + std::to_string(e->lds_per_wg) + " bytes of LDS: too little for the low-pass kernel");
         // Stage 1 of equally sized pushes runs as a linear split over k workgroups per CU.  Synchronous mode: all eight LDS slots of a
         // CU (measured against the classic per-stream grid on the same box: 125 vs 137 us per launch; 12, 16, 24, 32, 64 per CU: 150,
         // 135, 141, 135, 132 us).  Batch mode when the step kernel does not apply: six, so that the previous call's back half, on the
@@ -313,9 +322,9 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
             HDK(launch_fft_feed, q, S, e->fbuf[0].p, e->fbuf_stride, e->fft_in.p, sl.d_call.p, e->fir_hist_cap);
             hd::launch_spectrum_wave(q, S, e->fft_in.p, e->fft_tw.p, e->spec.p, e->power.p, sl.h_stats.dev, sl.d_call.p, e->fsd, e->bins_sep, 0u);   // (fft_run = 0 everywhere: every wave returns at once)
         }
-        HDK(launch_fir_demod, q, S, 0, 0, e->fbuf[0].p, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S, nullptr, e->carry[0].p,
+        if (!HDK(launch_fir_demod, q, S, 0, 0, e->lds_per_wg, e->fbuf[0].p, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S, nullptr, e->carry[0].p,
                              e->carry[1].p, sl.d_call.p, e->fir_hist_cap, e->tail.p, e->tail_cap, e->d_symstate.p, e->fbuf[1].p,
-                             e->fir_head.p, e->head_cap, e->fbuf[2].p);
+                             e->fir_head.p, e->head_cap, e->fbuf[2].p)) return fail(HD_ERR_DEVICE, "low-pass kernel refused its smallest launch");
         HDK(launch_symbols, q, S, 1, 1, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p, sl.d_call.p,
                            sl.h_slots.dev, e->slot_words, nullptr, 0, e->min_R, 0u);
         HD_HIP(hipStreamSynchronize(q));
@@ -350,6 +359,7 @@ void hd_engine_destroy(hd_engine* e)
 uint32_t hd_engine_streams(const hd_engine* e) { return e ? e->S : 0; }
 uint32_t hd_engine_decimation(const hd_engine* e) { return e ? e->D : 0; }
 double hd_engine_decimated_rate(const hd_engine* e) { return e ? e->fsd : 0; }
+uint32_t hd_engine_lowpass_taps_max(const hd_engine* e) { return e ? std::min(e->taps_cap, e->lp_taps_max) : 0; }
 uint64_t hd_engine_sentences_ok(const hd_engine* e) { return e ? e->sentences_ok : 0; }
 void hd_engine_set_timing(hd_engine* e, int on) { if (e) e->timing_every = on < 0 ? 0u : (uint32_t)on; }
 int hd_engine_timing(hd_engine* e, hd_timing* out)
@@ -774,6 +784,9 @@ int plan_call(hd_engine* e, hd_engine::CallSlot& sl, const uint32_t* n_per_strea
             const uint32_t T = (uint32_t)st.lp.taps.size();
             if (!T) return fail(HD_ERR_UNSUPPORTED, "low-pass transition width leaves no taps (reference filters nothing then)");
             if (T > e->taps_cap) return fail(HD_ERR_CAPACITY, "low-pass tap count exceeds engine capacity");
+            // (the LDS image of k_fir_demod and the sixteen bits of fir_taps_prev: refused here, before anything is queued -- the launch could not happen)
+            if (T > e->lp_taps_max)
+                return fail(HD_ERR_CAPACITY, "low-pass design of " + std::to_string(T) + " taps on stream " + std::to_string(s) + " exceeds hd_engine_lowpass_taps_max = " + std::to_string(e->lp_taps_max));
             if (nx.fir_buf < (size_t)m + T) { nx.fir_buf = (size_t)m + T; c.fir_zero_hist = 1; }   // FirFilter.h:141-147
             c.fir_m = m; c.fir_taps = T;
             // (tap count of the previous run, and where the first samples of that run's input are: in the previous call's buffer if that is where it ran, else aside)
@@ -1199,10 +1212,11 @@ int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
     } else {
         uint32_t lpN = 0;
         if (const int rc = lowpass_transforms(e, p, r, b, &lpN)) return rc;
-        HDK(launch_fir_demod, qb, S, p.max_m, lpN ? 0u : p.max_taps, b.fcur, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S,
+        if (!HDK(launch_fir_demod, qb, S, p.max_m, lpN ? 0u : p.max_taps, e->lds_per_wg, b.fcur, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S,
                              e->cfg.keep_filtered ? e->filtered.p : nullptr, e->carry[b.cin].p, e->carry[b.cout].p, r.dcall, e->fir_hist_cap,
                              e->tail.p, e->tail_cap, e->d_symstate.p, b.fnext, e->fir_head.p, e->head_cap, b.fprev, e->demod_ck_acc.p,
-                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f);
+                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f))
+            return fail(HD_ERR_DEVICE, "low-pass kernel could not be launched with " + std::to_string(p.max_taps) + " taps");    // (plan_call admits no such call)
         HDK(launch_symbols, qb, S, p.max_m, p.max_new, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p,
                            r.dcall, sl.h_slots.dev, e->slot_words, e->flips_cap ? e->flips_dbg.p : nullptr, e->flips_cap, e->min_R, sl.seq, ev_ride ? sl.ev_done : nullptr,
                            e->demod_ck_acc.p);

@@ -17,6 +17,7 @@
 #include "host/afc_tracker.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
+#include "host/fir_lds.hpp"
 #include "host/format_trial.hpp"
 #include "host/text_stage.hpp"
 #include "kernels/launch.h"
@@ -192,6 +193,8 @@ struct hd_engine {
     uint32_t S = 0, D = 1;
     uint32_t n1_cap = 0, n2_cap = 0;        // per-call capacities after stage 1 / last stage
     uint32_t taps_cap = 0, fir_hist_cap = 0; // low-pass tap capacity, history slots in front of the pending samples
+    size_t lds_per_wg = 0;                   // LDS the device grants one workgroup (queried at creation)
+    uint32_t lp_taps_max = 0;                // longest low-pass a call may run: k_fir_demod's LDS image inside lds_per_wg (host/fir_lds.hpp), at most kTapsPrevMax
     size_t fbuf_stride = 0;
     uint32_t tail_cap = 0, backlog_cap = 0, slot_words = 0, flips_cap = 0, max_R = 0, min_R = 4;
     int bins_sep = 8;

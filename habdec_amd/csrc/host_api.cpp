@@ -13,6 +13,7 @@
 #include "host/tone_search.hpp"
 #include "host/decim_plan.hpp"
 #include "host/fir_design.hpp"
+#include "host/fir_lds.hpp"
 #include "host/format_trial.hpp"
 #include "host/gui_payload.hpp"
 #include "host/telemetry.hpp"
@@ -63,6 +64,12 @@ size_t hd_host_lowpass_design(float cutoff_rel, float transition, size_t batch, 
     std::memcpy(taps, d.taps.data(), std::min(cap, d.taps.size()) * sizeof(float));
     return d.taps.size();
 }
+size_t hd_host_fir_demod_lds_bytes(uint32_t taps, size_t* static_bytes)
+{
+    if (static_bytes) *static_bytes = hd::kFirStaticLds;
+    return hd::fir_demod_lds_bytes(taps);
+}
+uint32_t hd_host_fir_demod_max_taps(size_t lds_bytes) { return hd::fir_demod_max_taps(lds_bytes); }
 
 hd_host_rtty* hd_host_rtty_new(size_t nbits, float nstops) { auto* r = new hd_host_rtty; r->f.nbits = nbits; r->f.nstops = nstops; return r; }
 void hd_host_rtty_free(hd_host_rtty* r) { delete r; }

@@ -19,6 +19,7 @@
 
 #include "arith.h"
 #include "exact_math.h"
+#include "../host/fir_lds.hpp"
 #include "launch.h"
 
 namespace hd {
@@ -37,16 +38,8 @@ extern "C" void HD_DBG_NAME(hd_debug_fir_stamps)(unsigned long long* host, size_
 #define FSTAMP_WRITE() do { } while (0)
 #endif
 
-constexpr int kFirLanes = 256;
-#ifndef HD_FIR_OUT
-#define HD_FIR_OUT 6
-#endif
-constexpr int kFirOut = HD_FIR_OUT;              // adjacent outputs per lane (even; 6: lanes 48 bytes apart, conflict-free 16-byte LDS reads)
-constexpr int kFirTile = kFirOut * kFirLanes;    // outputs computed per tile
-constexpr int kFirAdvance = kFirTile - kFirOut;  // outputs written per tile (lane 0 only supplies lane 1's predecessor)
-constexpr int kFirWin = (16 + kFirOut) / 2;      // 16-byte pairs a block of sixteen taps touches (samples 0 .. 14 + kFirOut of the lane's window)
-constexpr int kFirSlack = 16 + 2 * kFirWin;      // samples a lane may read past its last tap (the re-read last block of a kFirOut-output window)
-static_assert(kFirOut % 2 == 0 && kFirOut >= 2 && kFirOut <= 8, "outputs per lane: pairs of samples, lane windows 16-byte aligned");
+// (the tile geometry -- kFirLanes, kFirOut, kFirTile, kFirAdvance, kFirWin, kFirSlack -- and the LDS image that follows from it: host/fir_lds.hpp)
+static_assert(sizeof(float2) == kFirSampleBytes, "fir_demod_lds_bytes counts complex samples");
 
 typedef float fd_f32x2 __attribute__((ext_vector_type(2)));
 typedef float fd_f32x4 __attribute__((ext_vector_type(4)));
@@ -298,7 +291,7 @@ void launch_fetch_params(hipStream_t st, const void* host_mapped, void* dst, siz
     hipLaunchKernelGGL(k_fetch_params, dim3((n16 + 255) / 256), dim3(256), 0, st, static_cast<const uint4*>(host_mapped), static_cast<uint4*>(dst), n16);
 }
 
-void launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32_t max_taps, const float2* fbuf, size_t stride,
+bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32_t max_taps, size_t lds_limit, const float2* fbuf, size_t stride,
                       const float* taps, uint32_t taps_stride, float* demod, size_t demod_stride, float2* filtered,
                       const DemodCarry* carry_in, DemodCarry* carry_out, const StreamCall* call, uint32_t fir_hist_cap,
                       float* sym_ring, uint32_t ring_cap, const SymState* sym, float2* fbuf_next,
@@ -306,10 +299,22 @@ void launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32
                       const float2* pre, uint32_t pre_stride, float pre_scale)
 {
     const uint32_t tiles = max_m ? (max_m + kFirAdvance - 1) / kFirAdvance : 1;
-    const size_t lds = (size_t)(kFirTile + (max_taps ? max_taps : 1) + kFirSlack + 4) * sizeof(float2);
+    const size_t lds = fir_demod_lds_bytes(max_taps);
+    // (the engine refuses a longer design while it plans the call, hd_engine_lowpass_taps_max: this is the last line, in front of a launch that could not happen)
+    if (lds + kFirStaticLds > lds_limit) return false;
+    if (lds > 64u * 1024u) {      // beyond the default grant of dynamic LDS: opt in, once per device and size reached
+        static size_t granted[64];
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+        if (granted[dev] < lds) {
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_fir_demod), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+            granted[dev] = lds;
+        }
+    }
     dim3 grid(tiles, n_streams);
     hipLaunchKernelGGL(k_fir_demod, grid, dim3(kFirLanes), lds, st, fbuf, stride, taps, taps_stride, demod, demod_stride, filtered,
                        carry_in, carry_out, call, fir_hist_cap, sym_ring, ring_cap, sym, fbuf_next, head_side, head_cap, fbuf_prev, ck_acc, pre, pre_stride, pre_scale);
+    return true;
 }
 
 // ---- Fast mode, long low-pass filters (configs[4]: 4097 taps over 4096 samples per call = 67 MFLOP per stream and call done directly): the same correlation

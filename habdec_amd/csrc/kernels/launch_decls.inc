@@ -29,7 +29,9 @@ void launch_chunk_post(hipStream_t st, uint32_t n_streams, float2* fbuf, size_t 
                        const uint2* tune, const float* tune_tab);
 void launch_fft_feed(hipStream_t st, uint32_t n_streams, const float2* fbuf, size_t stride, float2* fft_in,
                      const StreamCall* call, uint32_t fir_hist_cap);
-void launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32_t max_taps, const float2* fbuf, size_t stride,
+// (max_taps sizes the tile's LDS image, host/fir_lds.hpp: fir_demod_lds_bytes; false, and nothing launched, when it and the kernel's static LDS exceed lds_limit
+// -- what the device grants a workgroup -- or the opt-in above 64 KB fails)
+bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32_t max_taps, size_t lds_limit, const float2* fbuf, size_t stride,
                       const float* taps, uint32_t taps_stride, float* demod, size_t demod_stride, float2* filtered /*or null*/,
                       const DemodCarry* carry_in, DemodCarry* carry_out, const StreamCall* call, uint32_t fir_hist_cap,
                       float* sym_ring, uint32_t ring_cap, const SymState* sym, float2* fbuf_next,

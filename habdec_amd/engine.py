@@ -252,6 +252,10 @@ class Engine(_Handle):
 
     def symbol_backlog(self, s=0) -> int: return self.L.hd_stream_symbol_backlog(self.h, s)
 
+    def lowpass_taps_max(self) -> int:
+        """The longest low-pass design a call may run (hd_engine_lowpass_taps_max); a call whose design is longer is refused with HD_ERR_CAPACITY."""
+        return int(self.L.hd_engine_lowpass_taps_max(self.h))
+
     def bits_total(self, s=0) -> int: return int(self.L.hd_stream_bits_total(self.h, s))
     def flip_list_full(self, s=0) -> int: return int(self.L.hd_stream_flip_list_full(self.h, s))
 
@@ -594,6 +598,17 @@ class HostTones(_Handle):
         i = capi.hd_tones_info()
         check(self.L.hd_host_tones_stats(self.h, C.byref(i)))
         return _tones_info(i)
+
+
+def fir_demod_lds_bytes(taps: int) -> tuple:
+    """(dynamic, static) LDS bytes of a low-pass launch whose longest filter has `taps` taps (hd_host_fir_demod_lds_bytes; no GPU)."""
+    st = C.c_size_t(0)
+    return int(lib().hd_host_fir_demod_lds_bytes(int(taps), C.byref(st))), int(st.value)
+
+
+def fir_demod_max_taps(lds_bytes: int) -> int:
+    """The largest odd tap count whose low-pass launch fits `lds_bytes` of LDS, 0 if none does (hd_host_fir_demod_max_taps; no GPU)."""
+    return int(lib().hd_host_fir_demod_max_taps(int(lds_bytes)))
 
 
 def _tone_search_detect_params(L, params):

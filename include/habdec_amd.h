@@ -98,6 +98,20 @@ uint32_t hd_engine_streams(const hd_engine* e);
 /* getDecimationFactor / getDecimatedSamplingRate (Decoder.h:716-735) */
 uint32_t hd_engine_decimation(const hd_engine* e);
 double   hd_engine_decimated_rate(const hd_engine* e);
+/* The longest low-pass design a call may run, in taps.  The design follows the reference (FirFilter.h:185-188): size_t(4 / transition) taps, clamped to the
+ * batch length of the call and forced odd -- so a narrow hd_stream_set_lowpass_trans makes the tap count follow the pushes.  The low-pass kernel keeps a
+ * tile's inputs for all taps in LDS, so the limit is the smaller of
+ *  - the engine's tap capacity (from max_chunk / decimation), and
+ *  - the largest odd count whose launch fits the LDS the device grants one workgroup (habdec_amd_host.h: hd_host_fir_demod_max_taps; 18899 taps in the
+ *    160 KB of an MI355X CU), never more than 65535.
+ * One limit for both arithmetic modes.  A call in which some stream's design is longer is refused with HD_ERR_CAPACITY while it is planned: nothing is
+ * queued, every stream stays as it was and the engine stays usable (widen the transition, or push less, and call again).
+ * A change of the tap count between two runs of a stream reproduces the reference's stale-buffer transient exactly for a decrease and for an increase of
+ * up to min(8192, m) taps, m = the batch length of the previous run: the first run with more taps takes, behind the kept history, the first samples of
+ * the previous run's input, of which the engine keeps 8192.  A larger increase that does not restart the filter from zeros (the reference restarts when
+ * its buffer grows) reads zeros where the reference reads older contents of its buffer: the first T - 1 outputs of that run (T = the new count) and what
+ * the discriminator makes of them differ from the reference's; from output T - 1 on the run is the reference's again. */
+uint32_t hd_engine_lowpass_taps_max(const hd_engine* e);
 
 /* ---- per-stream control plane: the reference setters of the same names (Decoder.h:238-257, 655-712) ---- */
 int hd_stream_set_baud(hd_engine* e, uint32_t stream, double baud);
@@ -179,7 +193,7 @@ void hd_set_chars_callback(hd_engine* e, hd_chars_cb cb, void* user);         /*
  * NULL.  Every n must be <= max_chunk and a multiple of the decimation factor (the Decoder facade keeps the
  * remainder queued on the host exactly like Decoder.h:429-435).  Returns after the decoded text of this
  * call has been delivered (callbacks fired, getters updated).  A call the engine refuses (bad sizes, a low-pass design that leaves no taps or exceeds
- * the tap capacity) leaves every stream as it was; a call that fails after its first upload or launch puts the engine into its failed state
+ * hd_engine_lowpass_taps_max) leaves every stream as it was; a call that fails after its first upload or launch puts the engine into its failed state
  * (HD_ERR_DEVICE from then on). */
 int hd_process_host(hd_engine* e, const float* iq, size_t stream_stride, const uint32_t* n_per_stream, uint32_t n);
 /* Page-locked host memory the GPU addresses in place.  An IQ buffer that lives in such memory and is handed to hd_process_host of a SYNCHRONOUS engine

@@ -27,6 +27,13 @@ size_t hd_host_decim_taps(unsigned total_factor, int stage, float* taps, size_t 
 size_t hd_host_lowpass_design(float cutoff_rel, float transition, size_t batch, size_t prev_ntaps, int float_trig,
                               float* taps, size_t cap);
 
+/* The LDS a low-pass launch needs (kernels/fir_demod.hip: a tile's inputs for ALL taps of the longest filter of the call live in LDS), and its inverse.
+ * hd_host_fir_demod_lds_bytes: dynamic LDS bytes of a launch whose longest filter has `taps` taps; *static_bytes (optional) receives the kernel's static LDS,
+ * which the launch needs on top.  hd_host_fir_demod_max_taps: the largest odd tap count whose launch, dynamic and static together, fits `lds_bytes`
+ * (0: none) -- 6611 for 64 KB, 18899 for the 160 KB of a gfx950 CU.  The engine derives hd_engine_lowpass_taps_max from it and the device's LDS per workgroup. */
+size_t hd_host_fir_demod_lds_bytes(uint32_t taps, size_t* static_bytes);
+uint32_t hd_host_fir_demod_max_taps(size_t lds_bytes);
+
 /* RTTY<bool> (RTTY.h:59-137) */
 typedef struct hd_host_rtty hd_host_rtty;
 hd_host_rtty* hd_host_rtty_new(size_t nbits, float nstops);

@@ -96,6 +96,7 @@ SURFACE = {'BaudProbe': ("(eng: 'Engine', **params)",
              'front_tune': ('method', "(self, s=0) -> 'dict'", None),
              'ingest': ('method', '(self, files: "\'IqFiles\'", max_rounds: \'int\' = 4611686018427387904) -> \'int\'', '633b6b2518d4'),
              'last_sentence': ('method', '(self, s=0)', None),
+             'lowpass_taps_max': ('method', "(self) -> 'int'", 'b9b04548f68b'),
              'on_sentence': ('method', '(self, fn)', None),
              'pinned_array': ('method', "(self, shape, dtype=<class 'numpy.complex64'>) -> 'np.ndarray'", '1a28eaa0c557'),
              'power': ('method', '(self, s=0)', None),
@@ -220,6 +221,8 @@ SURFACE = {'BaudProbe': ("(eng: 'Engine', **params)",
                 'rows_total': ('method', "(self) -> 'int'", None),
                 'tracks': ('method', "(self, cap: 'int' = 64, **params) -> 'list'", 'dec8f8a79743')}),
  'chase_repair': ("(span: 'str', data, nbits=8, repair_bits=8, repair_flips=3)", '4a9d073cb332', None),
+ 'fir_demod_lds_bytes': ("(taps: 'int') -> 'tuple'", '928425e41a4a', None),
+ 'fir_demod_max_taps': ("(lds_bytes: 'int') -> 'int'", '2fb0e3faad7a', None),
  'lib': ("() -> 'C.CDLL'", '82fc8db882d9', None),
  'survey_detect': ("(power: 'np.ndarray', segments: 'int', sampling_rate: 'float', cap: 'int' = 64, **params) -> 'list'", '452b7a877851', None),
  'tone_search_detect': ("(power: 'np.ndarray', segments: 'int', fsd: 'float', **params) -> 'dict'", '042d7e59e6ef', None),
