@@ -180,6 +180,29 @@ SSDV_PACKET_DTYPE = np.dtype([("pos", "<u8")] + [(k, "<u4") for k in ("trial", "
 SSDV_NOFEC, SSDV_TYPE_NOFEC, SSDV_RING, SSDV_LAUNCH = 255, 0x67, 4096, 16384
 
 
+class hd_fsk4_frame(C.Structure):
+    _fields_ = [("payload_bytes", C.c_uint32), ("uw", C.c_uint8 * 2), ("_pad", C.c_uint16), ("interleave_mul", C.c_uint32), ("scrambler_seed", C.c_uint32),
+                ("golay_poly", C.c_uint32)]
+
+
+class hd_fsk4_params(C.Structure):
+    _fields_ = [("max_push", C.c_uint32), ("window_q8", C.c_uint32), ("uw_max_errors", C.c_uint32), ("chase_bits", C.c_uint32), ("max_corrected", C.c_int32),
+                ("_pad", C.c_uint32)]
+
+
+class hd_fsk4_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("samples", "slots", "candidates", "gate_passes", "crc_failures", "refused", "overlaps", "frames")] + \
+        [("F", C.c_uint32), ("W", C.c_uint32), ("step", C.c_uint32 * 4), ("symbols", C.c_uint32), ("codewords", C.c_uint32)]
+
+
+# one hd_fsk4_rx, one hd_fsk4_candidate
+FSK4_RX_DTYPE = np.dtype([("slot", "<u8"), ("start_sample", "<u8"), ("metric", "<u8"), ("payload_bytes", "<u4"), ("corrected", "<u4"), ("phase", "<u4"),
+                          ("uw_errors", "<u4"), ("payload", "u1", (32,))])
+FSK4_CANDIDATE_DTYPE = np.dtype([("slot", "<u8"), ("metric", "<u8"), ("crc_ok", "<u4"), ("corrected", "<u4"), ("uw_errors", "<u4"), ("_pad", "<u4"),
+                                 ("payload", "u1", (32,))])
+FSK4_MAX_SPB, FSK4_CHUNK, FSK4_LAUNCH, FSK4_HORUS_V1, FSK4_HORUS_V2 = 2048, 4096, 16384, 1, 2
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -351,6 +374,18 @@ ENGINE_API = {
     "hd_ssdv_scan": (_int, [_vp]),
     "hd_ssdv_take_packets": (_int, [_vp, _u32, _vp, _sz]),
     "hd_ssdv_stats": (_int, [_vp, _u32, C.POINTER(hd_ssdv_counters)]),
+    "hd_fsk4_params_default": (None, [C.POINTER(hd_fsk4_params)]),
+    "hd_fsk4_frame_preset": (_int, [_int, C.POINTER(hd_fsk4_frame)]),
+    "hd_fsk4_create": (_int, [_vp, C.POINTER(hd_fsk4_params), C.POINTER(_vp)]),
+    "hd_fsk4_destroy": (None, [_vp]),
+    "hd_fsk4_reset": (_int, [_vp, _u32]),
+    "hd_fsk4_set_modem": (_int, [_vp, _u32, _dbl, _dbl, _dbl, C.POINTER(hd_fsk4_frame)]),
+    "hd_fsk4_push_engine": (_int, [_vp]),
+    "hd_fsk4_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_fsk4_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_fsk4_scan": (_int, [_vp]),
+    "hd_fsk4_take_frames": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_fsk4_stats": (_int, [_vp, _u32, C.POINTER(hd_fsk4_counters)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -457,6 +492,17 @@ HOST_API = {
     "hd_host_ssdv_stats": (_int, [_vp, C.POINTER(hd_ssdv_counters)]),
     "hd_host_ssdv_encode": (None, [_vp, _vp]),
     "hd_host_ssdv_make_packet": (None, [C.c_uint8, C.c_char_p, C.c_uint8, C.c_uint16, C.c_uint16, C.c_uint16, C.c_uint8, C.c_uint8, C.c_uint16, _vp, _vp]),
+    "hd_host_fsk4_new": (_vp, [_dbl, C.POINTER(hd_fsk4_params)]),
+    "hd_host_fsk4_free": (None, [_vp]),
+    "hd_host_fsk4_reset": (None, [_vp]),
+    "hd_host_fsk4_set_modem": (_int, [_vp, _dbl, _dbl, _dbl, C.POINTER(hd_fsk4_frame)]),
+    "hd_host_fsk4_push": (_sz, [_vp, _vp, _sz]),
+    "hd_host_fsk4_take_frames": (_int, [_vp, _vp, _sz]),
+    "hd_host_fsk4_stats": (_int, [_vp, C.POINTER(hd_fsk4_counters)]),
+    "hd_host_fsk4_slots": (_sz, [_vp, C.c_uint64, _vp, _sz]),
+    "hd_host_fsk4_candidates": (_int, [_vp, _vp, _sz]),
+    "hd_host_fsk4_encode": (_sz, [C.POINTER(hd_fsk4_frame), _vp, _vp]),
+    "hd_host_fsk4_crc16": (_u32, [_vp, _sz]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

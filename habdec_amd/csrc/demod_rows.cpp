@@ -11,7 +11,9 @@
 // object does something of its own, it says so at its own *_launch or door.  The diversity combiner (kernels/combine.hip, host/combine.hpp) is the fifth: it
 // reads float rows as the clocked decoder does (CombineSrc has ClockedSrc's fields), sums the rows of a group of streams and writes rows as the tones do.
 // The SSDV object (kernels/ssdv.hip, host/ssdv.hpp) is the sixth: it takes bytes, not rows -- its doors append on the host -- and shares the doors' checks,
-// the chunked launches (its descriptors' n_total counts candidates), reset, destroy and the guard counter.
+// the chunked launches (its descriptors' n_total counts candidates), reset, destroy and the guard counter.  The 4FSK modem (kernels/fsk4.hip,
+// host/fsk4.hpp) is the seventh: the tones' doors, descriptor and chunked slot launches in front, the SSDV object's chunked candidate launches and host
+// delivery behind.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -20,10 +22,12 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
+#include "host/fsk4.hpp"
 #include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
 #include "kernels/combine.h"
+#include "kernels/fsk4.h"
 #include "kernels/ssdv.h"
 #include "kernels/tone_search.h"
 
@@ -1481,6 +1485,298 @@ int hd_debug_ssdv_guards(hd_ssdv* v, uint32_t stream)
     std::lock_guard<std::recursive_mutex> lock(v->e->mtx);
     if (const int rc = enter(v->e)) return rc;
     return damaged_guards({{v->ring, stream}, {v->cnt, 0}, {v->out, 0}});
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- Horus Binary 4FSK (kernels/fsk4.hip) --------------------------------- */
+
+struct hd_fsk4 {
+    static constexpr const char* kNull = "null fsk4 object";
+    hd_engine* e = nullptr;
+    hd_fsk4_params prm{};
+    uint32_t S = 0, slot_cap = 0;
+    DevBuf<hd::Fsk4State> st;                    // [S]
+    Guarded<uint32_t> ring32;                    // [S * 8]: guard | kFsk4Ring32 running sums | guard
+    Guarded<uint32_t> slots;                     // [S]: guard | slot_cap records of four words | guard
+    Guarded<uint32_t> cnt;                       // one row: guard | the launch's candidates behind the gate (and three words unused) | guard
+    Guarded<uint32_t> out;                       // one row: guard | HD_FSK4_LAUNCH results (hd::Fsk4Out) | guard
+    DevBuf<hd::Fsk4Tab> tab;                     // [S]
+    DevBuf<int32_t> ctab;                        // [1024]
+    DevBuf<float2> slab;                         // hd_fsk4_push_host: the rows packed end to end, grown on demand
+    PinBuf<hd::TonesSrc> src;                    // [S]: a slot launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    PinBuf<hd::Fsk4Cand> cand;                   // [S]: a frame launch's
+    std::vector<hd::Fsk4Stream> stream;          // [S]: the modem (s: the state a reset gives, with n and g as the device has them), the frame's tables,
+                                                 // selection, delivery and counters
+    std::vector<hd::Fsk4Out> h_out, found;       // a launch's results; a scan's
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the slot launches of a push ...
+    hipEvent_t f0 = nullptr, f1 = nullptr;       // ... and around the frame launches of its scan
+    bool frames_launched = false;
+};
+// (the strides the kernels were written against, fsk4.h)
+static_assert(Guarded<uint32_t>::stride_of(hd::kFsk4Ring32, hd::kFsk4Guard) == hd::kFsk4Ring32 + 2 * hd::kFsk4Guard, "fsk4 ring stride");
+static_assert(sizeof(hd::Fsk4Out) == 64 && sizeof(hd::Fsk4Tab) % 16 == 0, "fsk4 result and table layout");
+
+namespace {
+
+constexpr size_t kFsk4OutWords = sizeof(hd::Fsk4Out) / sizeof(uint32_t);
+
+// launch_chunks over the frame launch's descriptors: the object's engine and streams, `cand` under the name the helper knows, the scan's two events.
+struct Fsk4FrameLaunches {
+    hd_engine* e;
+    uint32_t S;
+    PinBuf<hd::Fsk4Cand>& src;
+    hipEvent_t t0, t1;
+};
+
+// Every candidate whose last slot exists and is not decided: at most HD_FSK4_LAUNCH over all streams per launch, so that the results of a launch always
+// fit.  The results are sorted by (stream, slot) before they meet the selection -- what a scan delivers cannot depend on the order in which waves
+// finished.  Every slot a candidate reads is in the ring: fsk4_slot_cap.
+int fsk4_scan(hd_fsk4* f)
+{
+    hipStream_t q = f->e->qa;
+    f->found.clear();
+    f->frames_launched = false;
+    uint32_t max_cand = 0, active = 0;
+    for (uint32_t s = 0; s < f->S; ++s) {
+        const hd::Fsk4Stream& st = f->stream[s];
+        hd::Fsk4Cand& d = f->cand.p[s];
+        d.base = st.decided;
+        d.n_total = (uint32_t)std::min<uint64_t>(st.decidable(st.s.g), f->slot_cap);
+        d.off = 0; d.n = 0;
+        max_cand = std::max(max_cand, d.n_total);
+        active += d.n_total != 0;
+    }
+    if (!max_cand) return HD_OK;
+    uint32_t cap = 0;
+    hipError_t fetch = hipSuccess;
+    Fsk4FrameLaunches view{f->e, f->S, f->cand, f->f0, f->f1};
+    const int rc = launch_chunks(
+        &view, max_cand, std::max(1u, (uint32_t)HD_FSK4_LAUNCH / active), "",
+        [&](uint32_t, const hd::Fsk4Cand& d) { cap = std::max(cap, d.n); },
+        [&] {
+            if (hipMemsetAsync(f->cnt.row(0), 0, 4 * sizeof(uint32_t), q) != hipSuccess) return false;
+            hd::launch_fsk4_frames(q, f->S, cap, f->cand.dev, f->tab.p, f->slots.base(), f->slots.stride, f->slot_cap, f->prm.uw_max_errors, f->prm.chase_bits,
+                                   f->cnt.row(0), reinterpret_cast<hd::Fsk4Out*>(f->out.row(0)), HD_FSK4_LAUNCH);
+            cap = 0;
+            return true;
+        },
+        [&] {                                    // the launch is done: its count, and its results if it has any
+            if (fetch != hipSuccess) return;
+            uint32_t k = 0;
+            fetch = hipMemcpy(&k, f->cnt.row(0), sizeof k, hipMemcpyDeviceToHost);
+            k = std::min<uint32_t>(k, HD_FSK4_LAUNCH);
+            if (fetch != hipSuccess || !k) return;
+            fetch = hipMemcpy(f->h_out.data(), f->out.row(0), k * sizeof(hd::Fsk4Out), hipMemcpyDeviceToHost);
+            if (fetch == hipSuccess) f->found.insert(f->found.end(), f->h_out.begin(), f->h_out.begin() + k);
+        });
+    if (rc) return rc;
+    HD_HIP(fetch);
+    f->frames_launched = true;
+    std::sort(f->found.begin(), f->found.end(), [](const hd::Fsk4Out& a, const hd::Fsk4Out& b) { return a.stream != b.stream ? a.stream < b.stream : a.slot < b.slot; });
+    for (const hd::Fsk4Out& r : f->found)
+        if (r.stream < f->S) f->stream[r.stream].accept(r);
+    for (uint32_t s = 0; s < f->S; ++s) f->stream[s].decided_more(f->cand.p[s].n_total);
+    return HD_OK;
+}
+
+// Its own: a stream without a modem is passed by, in front of the max_push test; per chunk, `cap`, the longest part of a row in the launch, which sizes
+// its LDS; behind the last chunk the host's copy of n and g follows the device's, and the scan runs.
+int fsk4_launch(hd_fsk4* f, uint32_t max_n)
+{
+    if (const int rc = check_max_push(f, "hd_fsk4", &max_n, [f](uint32_t s) { if (!f->stream[s].s.F) f->src.p[s].n_total = 0; })) return rc;
+    uint32_t cap = 0;
+    const int rc = launch_chunks(
+        f, max_n, HD_FSK4_CHUNK, "fsk4: the launch's chunk does not fit the LDS",
+        [&](uint32_t, const hd::TonesSrc& d) { cap = std::max(cap, d.n); },
+        [&] {
+            const uint32_t longest = cap;
+            cap = 0;
+            return hd::launch_fsk4_slots(f->e->qa, f->S, longest, f->src.dev, f->st.p, f->ring32.base(), f->ring32.stride, f->ctab.p, f->slots.base(),
+                                         f->slots.stride, f->slot_cap);
+        },
+        [] {});
+    if (rc) return rc;
+    for (uint32_t s = 0; s < f->S; ++s) {
+        hd::Fsk4State& m = f->stream[s].s;
+        if (!m.F) continue;
+        m.n += f->src.p[s].n_total;
+        m.g = hd::fsk4_slots_before(m.F, m.n);
+    }
+    return fsk4_scan(f);
+}
+
+// (The rings need no clearing: nothing in front of a stream's index 0 is read, and no candidate reads a slot that was not written since.)
+int fsk4_clear(hd_fsk4* f, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = f->e->qa;
+    for (uint32_t s = s0; s < s0 + ns; ++s) {
+        f->stream[s].reset();
+        HD_HIP(hipMemcpyAsync(f->st.p + s, &f->stream[s].s, sizeof(hd::Fsk4State), hipMemcpyHostToDevice, q));
+    }
+    HD_HIP(hipStreamSynchronize(q));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_fsk4_params_default(hd_fsk4_params* p) { if (p) hd::fsk4_params_default(p); }
+
+int hd_fsk4_create(hd_engine* e, const hd_fsk4_params* params, hd_fsk4** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_fsk4> f(new hd_fsk4);
+    f->e = e; f->S = e->S;
+    hd::fsk4_params_default(&f->prm);
+    if (params) f->prm = *params;
+    if (!hd::fsk4_window_ok(f->prm.window_q8)) return fail(HD_ERR_UNSUPPORTED, "fsk4 parameters: 32 <= window_q8 <= 256");
+    if (!hd::fsk4_params_ok(&f->prm)) return fail(HD_ERR_INVALID, "fsk4 parameters: uw_max_errors <= 4, chase_bits <= 6, max_push <= 2^22");
+    // (a launch takes at least one candidate of every active stream and its results must fit HD_FSK4_LAUNCH slots)
+    if (e->S > HD_FSK4_LAUNCH) return fail(HD_ERR_UNSUPPORTED, "hd_fsk4_create: at most " + std::to_string(HD_FSK4_LAUNCH) + " streams");
+    if (const int rc = default_max_push(e, &f->prm.max_push, "fsk4")) return rc;
+    if (f->prm.max_push > (1u << 22)) return fail(HD_ERR_INVALID, "fsk4 parameters: max_push <= 2^22");
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = f->S;
+    f->slot_cap = hd::fsk4_slot_cap(f->prm.max_push);
+    f->stream.resize(S);
+    for (auto& st : f->stream) st.set_params(f->prm);
+    f->h_out.resize(HD_FSK4_LAUNCH);
+    int32_t C[1024];
+    hd::tones_table(C);
+    HD_HIP(f->st.alloc_unfilled(S));
+    HD_HIP(f->ring32.alloc((size_t)S * 8, hd::kFsk4Ring32, hd::kFsk4Guard, hd::kFsk4GuardWord, e->qa));
+    HD_HIP(f->slots.alloc(S, (size_t)f->slot_cap * 4, hd::kFsk4Guard, hd::kFsk4GuardWord, e->qa));
+    HD_HIP(f->cnt.alloc(1, 4, hd::kFsk4Guard, hd::kFsk4GuardWord, e->qa));
+    HD_HIP(f->out.alloc(1, (size_t)HD_FSK4_LAUNCH * kFsk4OutWords, hd::kFsk4Guard, hd::kFsk4GuardWord, e->qa));
+    HD_HIP(f->tab.alloc(S));
+    HD_HIP(f->ctab.alloc_unfilled(1024));
+    HD_HIP(f->src.alloc(S));
+    HD_HIP(f->cand.alloc(S));
+    HD_HIP(hipMemcpyAsync(f->ctab.p, C, sizeof C, hipMemcpyHostToDevice, e->qa));
+    if (const int rc = fsk4_clear(f.get(), 0, S)) return rc;           // (waits for the queue: `C` is a local)
+    *out = f.release();
+    return HD_OK;
+}
+
+void hd_fsk4_destroy(hd_fsk4* f) { destroy(f); }
+
+int hd_fsk4_reset(hd_fsk4* f, uint32_t stream) { return reset(f, stream, fsk4_clear); }
+
+int hd_fsk4_set_modem(hd_fsk4* f, uint32_t stream, double baud, double f0_hz, double spacing_hz, const hd_fsk4_frame* frame)
+{
+    if (const int rc = check_object(f, stream)) return rc;
+    if (!frame) return fail(HD_ERR_INVALID, "null frame");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    std::unique_ptr<hd::Fsk4Tab> tab(new hd::Fsk4Tab);
+    if (!hd::fsk4_tables(*frame, *tab))
+        return fail(HD_ERR_UNSUPPORTED, "fsk4: a frame the decoder cannot take (3 <= payload_bytes <= 32, interleave_mul coprime with the body's bits, a nonzero 15-bit seed, a Golay generator)");
+    hd::Fsk4State m;
+    const int rc = hd::fsk4_modem(m, f->e->fsd, baud, f0_hz, spacing_hz, f->prm.window_q8);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "fsk4: 8 <= decimated rate / baud <= " + std::to_string(HD_FSK4_MAX_SPB));
+    if (rc) return fail(rc, "fsk4: every tone f0 + t spacing, t = 0 .. 3, inside +- decimated rate / 2");
+    if (const int rc2 = enter(f->e)) return rc2;
+    hd::Fsk4Stream& st = f->stream[stream];
+    st.s = m; st.tab = *tab;
+    HD_HIP(hipMemcpyAsync(f->tab.p + stream, &st.tab, sizeof(hd::Fsk4Tab), hipMemcpyHostToDevice, f->e->qa));
+    return fsk4_clear(f, stream, 1);
+}
+
+int hd_fsk4_push_engine(hd_fsk4* f) { return push_engine(f, "hd_fsk4_push_engine", fsk4_launch); }
+
+int hd_fsk4_push_device(hd_fsk4* f, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(f, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, fsk4_launch);
+}
+
+int hd_fsk4_push_host(hd_fsk4* f, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(f, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, fsk4_launch);
+}
+
+int hd_fsk4_scan(hd_fsk4* f)
+{
+    if (!f) return fail(HD_ERR_INVALID, hd_fsk4::kNull);
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    return fsk4_scan(f);
+}
+
+int hd_fsk4_take_frames(hd_fsk4* f, uint32_t stream, hd_fsk4_rx* out, size_t cap)
+{
+    if (const int rc = check_object(f, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    return (int)f->stream[stream].take(out, cap);
+}
+
+// (samples and slots are the device's own: a host copy that had drifted would show here)
+int hd_fsk4_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_counters* out)
+{
+    if (const int rc = check_object(f, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    hd::Fsk4State h;
+    HD_HIP(hipMemcpy(&h, f->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
+    f->stream[stream].stats(out, h.n, h.g);
+    return HD_OK;
+}
+
+// The measurement hook (tools/micro/fsk4_rate.py; not part of the ABI): hd_fsk4_push_engine with the slot launches and the frame launches of its scan
+// each between two HIP events (0 where none was launched), and the host time of the whole call in microseconds.
+int hd_debug_fsk4_push_timed(hd_fsk4* f, float* slots_ms, float* frames_ms, double* host_us)
+{
+    if (!f || !slots_ms || !frames_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    HD_HIP(hipEventCreate(&f->f0));
+    HD_HIP(hipEventCreate(&f->f1));
+    f->frames_launched = false;
+    const int rc = push_timed(f, slots_ms, host_us, hd_fsk4_push_engine);
+    *frames_ms = 0;
+    if (rc == HD_OK && f->frames_launched && hipEventQuery(f->f1) == hipSuccess) (void)hipEventElapsedTime(frames_ms, f->f0, f->f1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(f->f0); (void)hipEventDestroy(f->f1);
+    f->f0 = f->f1 = nullptr;
+    return rc;
+}
+
+// Test hooks (tests/test_gpu_fsk4.py; not part of the ABI).  The records of the slots first .. first + n - 1 as the stream's ring holds them, 4 n words.
+int hd_debug_fsk4_slots(hd_fsk4* f, uint32_t stream, uint64_t first, uint32_t* out, size_t n)
+{
+    if (!f || stream >= f->S || !out || n > f->slot_cap) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    for (size_t k = 0; k < n;) {
+        const size_t at = (size_t)((first + k) & (f->slot_cap - 1u)), run = std::min<size_t>(n - k, f->slot_cap - at);
+        HD_HIP(hipMemcpy(out + 4 * k, f->slots.row(stream) + 4 * at, run * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        k += run;
+    }
+    return (int)n;
+}
+
+// The log of the stream's candidates behind the unique-word gate, as hd_host_fsk4_candidates.
+int hd_debug_fsk4_candidates(hd_fsk4* f, uint32_t stream, hd_fsk4_candidate* out, size_t cap)
+{
+    if (!f || stream >= f->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    return (int)f->stream[stream].take_log(out, cap);
+}
+
+// How many of the guard words around the stream's eight rings and its slots, the count and the results no longer hold their pattern.
+int hd_debug_fsk4_guards(hd_fsk4* f, uint32_t stream)
+{
+    if (!f || stream >= f->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    const size_t r = (size_t)stream * 8;
+    return damaged_guards({{f->ring32, r}, {f->ring32, r + 1}, {f->ring32, r + 2}, {f->ring32, r + 3}, {f->ring32, r + 4}, {f->ring32, r + 5},
+                           {f->ring32, r + 6}, {f->ring32, r + 7}, {f->slots, stream}, {f->cnt, 0}, {f->out, 0}});
 }
 
 }  // extern "C"

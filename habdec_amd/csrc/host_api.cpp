@@ -8,6 +8,7 @@
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
+#include "host/fsk4.hpp"
 #include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
@@ -538,6 +539,68 @@ void hd_host_ssdv_make_packet(uint8_t type, const char* callsign, uint8_t image_
 {
     if (payload205 && out256) hd::ssdv_make_packet(type, callsign, image_id, packet_id, width, height, flags, mcu_offset, mcu_index, payload205, out256);
 }
+
+/* ---- Horus Binary 4FSK (kernels/fsk4.hip; see host/fsk4.hpp) ---- */
+struct hd_host_fsk4 {
+    double fsd;
+    hd_fsk4_params prm;
+    hd::Fsk4Stream st;
+};
+int hd_fsk4_frame_preset(int preset, hd_fsk4_frame* out) { return out && hd::fsk4_preset(preset, out) ? HD_OK : out ? HD_ERR_UNSUPPORTED : HD_ERR_INVALID; }
+hd_host_fsk4* hd_host_fsk4_new(double decimated_rate, const hd_fsk4_params* params)
+{
+    hd_fsk4_params prm;
+    hd::fsk4_params_default(&prm);
+    if (params) prm = *params;
+    if (!(decimated_rate > 0) || !hd::fsk4_window_ok(prm.window_q8) || !hd::fsk4_params_ok(&prm)) return nullptr;
+    if (!prm.max_push) prm.max_push = 4096;
+    auto* h = new hd_host_fsk4;
+    h->fsd = decimated_rate; h->prm = prm;
+    h->st.set_params(prm);
+    h->st.host_rings(prm.max_push);
+    return h;
+}
+void hd_host_fsk4_free(hd_host_fsk4* h) { delete h; }
+void hd_host_fsk4_reset(hd_host_fsk4* h) { if (h) h->st.reset(); }
+int hd_host_fsk4_set_modem(hd_host_fsk4* h, double baud, double f0_hz, double spacing_hz, const hd_fsk4_frame* frame)
+{
+    if (!h || !frame) return HD_ERR_INVALID;
+    hd::Fsk4Tab tab;
+    if (!hd::fsk4_tables(*frame, tab)) return HD_ERR_UNSUPPORTED;
+    hd::Fsk4State m;
+    if (const int rc = hd::fsk4_modem(m, h->fsd, baud, f0_hz, spacing_hz, h->prm.window_q8)) return rc;
+    h->st.s = m; h->st.tab = tab;
+    h->st.reset();
+    return HD_OK;
+}
+// (in pieces of max_push, a scan behind each: the slot ring holds what one piece adds to the candidates that wait)
+size_t hd_host_fsk4_push(hd_host_fsk4* h, const float* iq, size_t n)
+{
+    if (!h || !iq || !h->st.s.F) return 0;
+    for (size_t at = 0; at < n;) {
+        const size_t k = std::min<size_t>(n - at, h->prm.max_push);
+        h->st.push_samples(iq + 2 * at, k);
+        h->st.scan();
+        at += k;
+    }
+    return n;
+}
+int hd_host_fsk4_take_frames(hd_host_fsk4* h, hd_fsk4_rx* out, size_t cap) { return h ? (int)h->st.take(out, cap) : HD_ERR_INVALID; }
+int hd_host_fsk4_stats(const hd_host_fsk4* h, hd_fsk4_counters* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    h->st.stats(out, h->st.s.n, h->st.s.g);
+    return HD_OK;
+}
+size_t hd_host_fsk4_slots(const hd_host_fsk4* h, uint64_t first, uint32_t* out, size_t n)
+{
+    if (!h || !out || first + n > h->st.s.g || h->st.s.g - first > h->st.slot_cap) return 0;
+    for (size_t k = 0; k < n; ++k) std::memcpy(out + 4 * k, &h->st.slots[(size_t)((first + k) & (h->st.slot_cap - 1u)) * 4u], 4 * sizeof(uint32_t));
+    return n;
+}
+int hd_host_fsk4_candidates(hd_host_fsk4* h, hd_fsk4_candidate* out, size_t cap) { return h ? (int)h->st.take_log(out, cap) : HD_ERR_INVALID; }
+size_t hd_host_fsk4_encode(const hd_fsk4_frame* frame, const uint8_t* payload, uint8_t* out) { return frame && payload && out ? hd::fsk4_encode(*frame, payload, out) : 0; }
+uint32_t hd_host_fsk4_crc16(const uint8_t* bytes, size_t n) { return bytes || !n ? hd::fsk4_crc16(bytes, n) : 0xFFFFu; }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */
 struct hd_host_baud_probe {

@@ -926,6 +926,115 @@ int  hd_ssdv_scan(hd_ssdv* v);
 int  hd_ssdv_take_packets(hd_ssdv* v, uint32_t stream, hd_ssdv_packet* out, size_t cap);
 int  hd_ssdv_stats(hd_ssdv* v, uint32_t stream, hd_ssdv_counters* out);
 
+/* ---- Horus Binary 4FSK: tone bank, frame search on a timing grid, soft Golay(23,12) (not in the reference; built from the published format) ----
+ * survey -> front tune -> FSK4.  A second modulation beside RTTY: 4FSK at about 100 baud, a 22- or 32-byte payload, Golay(23,12) parity, interleaved and
+ * scrambled behind the unique word 0x24 0x24.  An fsk4 object is attached to an engine like a tones object (its device, mutex and first queue; destroy
+ * it before the engine) and reads the same input, each stream's tuned decimated cf32 IQ, through the same three doors.  Frames leave through
+ * hd_fsk4_take_frames alone, never through the sentence callbacks.  horusdemodlib is not at hand: agreement with it rests on the format as restated
+ * here alone, and every format constant is a field of hd_fsk4_frame.  Kernels (kernels/fsk4.hip), host restatement (hd_host_fsk4_*) and a numpy model
+ * (tests/fsk4_model.py) agree byte for byte on all of the following.  fsd = hd_engine_decimated_rate(e).
+ *  - On air: bytes go most significant bit first, two bits make a symbol, first bit high; symbol value v is the tone f0 + v spacing (natural binary).
+ *  - Frame: the unique word uw[0] uw[1], then a body of B = P + ceil(11 K / 8) bytes, P = payload_bytes, K = ceil(8 P / 12): 4 (2 + B) symbols.
+ *    HD_FSK4_HORUS_V1: P 22, K 15, B 43, 180 symbols; HD_FSK4_HORUS_V2: P 32, K 22, B 63, 260 symbols.
+ *  - Body before interleaving: the payload, then the parity bit stream.  Codeword k has the 12 data bits 12 k .. 12 k + 11 of the payload, bytes taken
+ *    most significant bit first, zeros past the payload's end; its 11 parity bits are the remainder of data x^11 by golay_poly (0xC75), appended most
+ *    significant first to the parity stream, whose last byte is zero-padded.  As a 23-bit word a codeword is data << 11 | parity.
+ *  - Interleaver: body bits are numbered i <-> byte i / 8, bit i % 8 (least significant first, unlike the on-air order); bit i moves to
+ *    j = interleave_mul i mod 8 B (337 and 503: the largest primes below 344 and 504).
+ *  - Scrambler, after the interleaver, same numbering: a 15-bit state, scrambler_seed (0x4A80) at every frame start; out = bit 1 ^ bit 0, then
+ *    state = state >> 1 | out << 14; body bit i is xored with the i-th output (0,0,0,0,0,0,1,1,1,1,1,1,0,1,1,0, ...).
+ *  - Payload check: the last two payload bytes are CRC16-CCITT (0x1021, initial value 0xFFFF, nothing reflected, no final xor) over the first P - 2,
+ *    low byte first.
+ *  - Modem (hd_fsk4_set_modem): F = floor(fsd / baud * 65536 + 0.5); HD_ERR_UNSUPPORTED unless 8 <= fsd / baud <= HD_FSK4_MAX_SPB and the frame is one the
+ *    decoder can take (3 <= P <= 32, interleave_mul coprime with 8 B, a nonzero 15-bit seed, golay_poly a divisor of x^23 + 1 of degree 11);
+ *    Phi_t = (uint32)(int64)nearbyint((f0 + t spacing) / fsd * 2^32), t = 0 .. 3, HD_ERR_INVALID unless every tone lies inside +-fsd / 2;
+ *    W = max(1, (F window_q8 + 2^23) >> 24): the whole symbol by default, because the timing is recovered.  The tones are the caller's: nothing
+ *    searches for them or tracks them.
+ *  - Per sample i (uint64 since the stream's last reset): the tones object's rules for four tones -- q = 0 for NaN, else (int32)(clamp(v, -8, 8) * 256);
+ *    a = (uint32)(i Phi_t) >> 22; r_re = (q_re C[a] + q_im C[(a + 768) & 1023]) >> 15, r_im = (q_im C[a] - q_re C[(a + 768) & 1023]) >> 15 with the
+ *    probe's table C; running sums mod 2^32; A_t(i) = floor(sqrt(re^2 + im^2)) of the sums over the W samples up to i (fewer in front of sample 0).
+ *  - Slots: a timing grid of eight phases per symbol, slot g = 8 k + p.  Slot g's record is (A_0, A_1, A_2, A_3) at its last sample
+ *    end(g) = ((g + 8) F >> 19) - 1, four uint32; it exists once that sample is pushed.  Records go to a per-stream ring on the GPU.
+ *  - Candidates: every slot g is one, a frame whose symbol m is slot g + 8 m.  It is decided by the first scan after its last slot exists, exactly
+ *    once; every push ends with a scan, and what comes out does not depend on how the samples were cut into pushes.
+ *      1. Hard symbol: argmax_t A_t, the lowest t on ties.
+ *      2. Unique-word gate: the 16 hard bits of the first 8 symbols differ from the unique word in at most uw_max_errors bits, or the candidate ends here.
+ *      3. Soft bits of symbol m: hi = max(A_2, A_3) - max(A_0, A_1), lo = max(A_1, A_3) - max(A_0, A_2); a hard bit is soft > 0, its confidence |soft|.
+ *      4. On-air bit r of the body is body byte r / 8, bit 7 - r % 8; descrambling negates, de-interleaving permutes; K words of 23 soft values are
+ *         gathered; the zero-padded data positions of the last word are hard 0 with confidence 2^24.
+ *      5. Soft Golay, per word: the chase_bits least confident positions (ties: the one nearer the most significant bit first) are position 0, 1, ...
+ *         of a flip pattern; for each of the 2^chase_bits patterns, lowest number first, the hard word with the pattern's positions flipped is decoded to
+ *         the one codeword within distance 3 (syndrome table, made at set_modem); its cost is the sum of the confidences where it differs from the
+ *         unflipped hard word.  The lowest cost wins, the earlier pattern on ties.  corrected = the bits in which the winners differ from the hard words.
+ *      6. crc_ok: the CRC16 of the decoded payload matches.  metric = the sum over the frame's symbols of max_t A_t.
+ *  - Guard against noise: the code is perfect, so step 5 never fails, and gate and CRC alone pass about 3e-8 of noise candidates.
+ *    A frame is refused when corrected > max_corrected (default 2 K: noise corrects about 2.85 bits per word, a frame at 5 % bit errors about 1.2).
+ *  - Selection: only candidates with crc_ok within max_corrected count.  The first of them opens a group; those less than 16 slots (two symbols: the
+ *    neighbouring timing phases of one frame) behind it contest the delivery -- fewest corrected bits, then the largest metric, then the lowest slot
+ *    -- and the best is delivered once every slot of that contest is decided, two symbols behind the frame's end.  A later candidate less than
+ *    8 (symbols - 1) slots behind the delivered one overlaps that frame (the next frame may follow at once, and its early phases with it) and is
+ *    dropped, overlaps += 1; the next one opens the next group.  (A contest as long as the frame would hold every frame back by its own length.)
+ *    Frames wait on the host, per stream in increasing position, until hd_fsk4_take_frames.
+ *  - Counters per stream: samples, slots, candidates (decided), gate_passes, crc_failures, refused (by max_corrected), overlaps, frames.
+ *  - Queue, errors: as the tones object's; a push returns when its kernels are done.  A push longer than max_push: HD_ERR_CAPACITY.  A row longer than
+ *    HD_FSK4_CHUNK samples is cut into launches; a scan's candidates into launches of at most HD_FSK4_LAUNCH over all streams.
+ *  - Not built: finding or tracking the tones, timing finer than a slot, the payload's fields and upload bodies, 2FSK Horus, feeding the combiner. */
+#define HD_FSK4_MAX_SPB 2048
+#define HD_FSK4_CHUNK 4096         /* samples of a row per launch of the slot kernel */
+#define HD_FSK4_LAUNCH 16384       /* candidates per launch of the frame kernel over all streams */
+#define HD_FSK4_MAX_PAYLOAD 32
+#define HD_FSK4_HORUS_V1 1
+#define HD_FSK4_HORUS_V2 2
+typedef struct hd_fsk4 hd_fsk4;
+typedef struct hd_fsk4_frame {
+    uint32_t payload_bytes;    /* P */
+    uint8_t  uw[2];
+    uint16_t _pad;
+    uint32_t interleave_mul, scrambler_seed, golay_poly;
+} hd_fsk4_frame;
+typedef struct hd_fsk4_params {
+    uint32_t max_push;         /* longest push per stream in samples; 0: what the engine's longest call leaves, or 4096; at most 2^22 */
+    uint32_t window_q8;        /* the tone filters' window in 1/256 symbols, 32 .. 256; default 256 */
+    uint32_t uw_max_errors;    /* 0 .. 4; default 2 */
+    uint32_t chase_bits;       /* 0 .. 6; default 4 */
+    int32_t  max_corrected;    /* a frame with more corrected bits is refused; negative (the default): 2 K of the stream's frame */
+    uint32_t _pad;
+} hd_fsk4_params;
+typedef struct hd_fsk4_rx {    /* one delivered frame */
+    uint64_t slot;             /* the frame's first slot, 8 k + phase */
+    uint64_t start_sample;     /* the first sample of its first symbol: slot F >> 19 */
+    uint64_t metric;
+    uint32_t payload_bytes, corrected, phase, uw_errors;
+    uint8_t  payload[HD_FSK4_MAX_PAYLOAD];
+} hd_fsk4_rx;
+typedef struct hd_fsk4_candidate {   /* one candidate behind the unique-word gate, whatever became of it (the restatement's and the test hooks' record) */
+    uint64_t slot, metric;
+    uint32_t crc_ok, corrected, uw_errors, _pad;
+    uint8_t  payload[HD_FSK4_MAX_PAYLOAD];
+} hd_fsk4_candidate;
+typedef struct hd_fsk4_counters {
+    uint64_t samples, slots, candidates, gate_passes, crc_failures, refused, overlaps, frames;
+    uint32_t F, W, step[4];    /* the modem's integers: F = 0, no modem */
+    uint32_t symbols, codewords;
+} hd_fsk4_counters;
+void hd_fsk4_params_default(hd_fsk4_params* p);
+/* The two presets.  HD_ERR_UNSUPPORTED: no such preset. */
+int  hd_fsk4_frame_preset(int preset, hd_fsk4_frame* out);
+int  hd_fsk4_create(hd_engine* e, const hd_fsk4_params* p /* null: the defaults */, hd_fsk4** out);   /* HD_ERR_UNSUPPORTED: window_q8, more than HD_FSK4_LAUNCH streams */
+void hd_fsk4_destroy(hd_fsk4* f);
+/* Samples, slots, candidates, counters and the open group of the stream start again; the modem stays, and so do frames not yet taken. */
+int  hd_fsk4_reset(hd_fsk4* f, uint32_t stream /* UINT32_MAX: all */);
+int  hd_fsk4_set_modem(hd_fsk4* f, uint32_t stream, double baud, double f0_hz, double spacing_hz, const hd_fsk4_frame* frame);   /* resets the stream */
+/* The three doors of the tones object, with its rules; each ends with a scan. */
+int  hd_fsk4_push_engine(hd_fsk4* f);
+int  hd_fsk4_push_device(hd_fsk4* f, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_fsk4_push_host(hd_fsk4* f, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* Decides every candidate whose last slot exists and is not decided yet.  Every push ends with one, so on its own it finds nothing left: HD_OK. */
+int  hd_fsk4_scan(hd_fsk4* f);
+/* Hands out up to cap of the stream's waiting frames, oldest first, and returns how many were written; out null: how many wait.  Negative: HD_ERR_*. */
+int  hd_fsk4_take_frames(hd_fsk4* f, uint32_t stream, hd_fsk4_rx* out, size_t cap);
+int  hd_fsk4_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_counters* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,6 +298,28 @@ void   hd_host_ssdv_encode(const uint8_t* data223, uint8_t* parity32);
 void   hd_host_ssdv_make_packet(uint8_t type, const char* callsign, uint8_t image_id, uint16_t packet_id, uint16_t width, uint16_t height, uint8_t flags,
                                 uint8_t mcu_offset, uint16_t mcu_index, const uint8_t* payload205, uint8_t* out256);
 
+/* ---- Horus Binary 4FSK (hd_fsk4_*, include/habdec_amd.h has the definition): one stream of it in plain C++, sample by sample, candidate by candidate ----
+ * The same integers as the kernels: slot records, candidate records, frames and counters of the same samples equal the device's byte for byte, however
+ * the samples are cut into pushes.  Selection, delivery and counters are the code the engine's object runs.  hd_host_fsk4_new: NULL unless
+ * decimated_rate > 0 and the parameters are ones hd_fsk4_create takes (max_push 0: 4096).  hd_host_fsk4_set_modem: the errors of hd_fsk4_set_modem.
+ * hd_host_fsk4_push: n cf32 samples (2 n floats), then a scan; 0 without a modem.  hd_host_fsk4_slots: the records of the slots first .. first + n - 1
+ * (4 n words) while the ring still holds them; returns how many it wrote.  hd_host_fsk4_candidates: takes the log of the candidates behind the
+ * unique-word gate, oldest first (the log keeps the newest 65536); out null: how many wait.  hd_host_fsk4_encode: payload_bytes bytes at payload (the
+ * caller's CRC included) -> the frame's 2 + B bytes at out, unique word first; returns their number, 0 for a frame the decoder cannot take.
+ * hd_host_fsk4_crc16: the payload check over n bytes. */
+typedef struct hd_host_fsk4 hd_host_fsk4;
+hd_host_fsk4* hd_host_fsk4_new(double decimated_rate, const hd_fsk4_params* params);
+void   hd_host_fsk4_free(hd_host_fsk4*);
+void   hd_host_fsk4_reset(hd_host_fsk4*);
+int    hd_host_fsk4_set_modem(hd_host_fsk4*, double baud, double f0_hz, double spacing_hz, const hd_fsk4_frame* frame);
+size_t hd_host_fsk4_push(hd_host_fsk4*, const float* iq, size_t n);
+int    hd_host_fsk4_take_frames(hd_host_fsk4*, hd_fsk4_rx* out, size_t cap);
+int    hd_host_fsk4_stats(const hd_host_fsk4*, hd_fsk4_counters* out);
+size_t hd_host_fsk4_slots(const hd_host_fsk4*, uint64_t first, uint32_t* out, size_t n);
+int    hd_host_fsk4_candidates(hd_host_fsk4*, hd_fsk4_candidate* out, size_t cap);
+size_t hd_host_fsk4_encode(const hd_fsk4_frame* frame, const uint8_t* payload, uint8_t* out);
+uint32_t hd_host_fsk4_crc16(const uint8_t* bytes, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
