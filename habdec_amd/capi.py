@@ -203,6 +203,29 @@ FSK4_CANDIDATE_DTYPE = np.dtype([("slot", "<u8"), ("metric", "<u8"), ("crc_ok", 
 FSK4_MAX_SPB, FSK4_CHUNK, FSK4_LAUNCH, FSK4_HORUS_V1, FSK4_HORUS_V2 = 2048, 4096, 16384, 1, 2
 
 
+class hd_fsk4_retune_info(C.Structure):
+    _fields_ = [("retunes", C.c_uint64), ("late", C.c_uint64), ("waiting", C.c_uint64), ("psi", C.c_uint32 * 4)]
+
+
+class hd_fsk4_track_params(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("max_push", "epoch_segments", "decay_q8", "min_quality_q8", "min_segments", "deadband")]
+
+
+class hd_fsk4_comb_params(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("baud", "spacing_lo_hz", "spacing_hi_hz", "f_lo_hz", "f_hi_hz")] + [("min_quality_q8", C.c_uint32), ("segments_ok", C.c_uint32)]
+
+
+class hd_fsk4_track_info(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("samples", "segments", "epochs", "valid_epochs", "retunes")]
+
+
+# one hd_fsk4_comb_record, one hd_fsk4_track_est
+FSK4_COMB_RECORD_DTYPE = np.dtype([("f0_q8", "<i4"), ("spacing_q8", "<i4"), ("c0", "<u4"), ("d", "<u4"), ("w", "<u4"), ("floor", "<u4"), ("score", "<u4"),
+                                   ("quality_q8", "<u4"), ("valid", "<u4"), ("centroid_q8", "<i4", (4,)), ("_pad", "<u4", (3,))])
+FSK4_TRACK_EST_DTYPE = np.dtype([("rec", FSK4_COMB_RECORD_DTYPE), ("f0_hz", "<f8"), ("spacing_hz", "<f8"), ("end_sample", "<u8"), ("epoch", "<u8")])
+assert FSK4_COMB_RECORD_DTYPE.itemsize == 64 and FSK4_TRACK_EST_DTYPE.itemsize == 96
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -386,6 +409,19 @@ ENGINE_API = {
     "hd_fsk4_scan": (_int, [_vp]),
     "hd_fsk4_take_frames": (_int, [_vp, _u32, _vp, _sz]),
     "hd_fsk4_stats": (_int, [_vp, _u32, C.POINTER(hd_fsk4_counters)]),
+    "hd_fsk4_retune": (_int, [_vp, _u32, _dbl, _dbl, C.c_uint64]),
+    "hd_fsk4_retune_stats": (_int, [_vp, _u32, C.POINTER(hd_fsk4_retune_info)]),
+    "hd_fsk4_track_params_default": (None, [C.POINTER(hd_fsk4_track_params)]),
+    "hd_fsk4_track_create": (_int, [_vp, C.POINTER(hd_fsk4_track_params), C.POINTER(_vp)]),
+    "hd_fsk4_track_destroy": (None, [_vp]),
+    "hd_fsk4_track_reset": (_int, [_vp, _u32]),
+    "hd_fsk4_track_set_stream": (_int, [_vp, _u32, _dbl, _dbl, _dbl, _dbl, _dbl]),
+    "hd_fsk4_track_attach": (_int, [_vp, _vp]),
+    "hd_fsk4_track_push_engine": (_int, [_vp]),
+    "hd_fsk4_track_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_fsk4_track_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_fsk4_track_estimate": (_int, [_vp, _u32, _vp]),
+    "hd_fsk4_track_stats": (_int, [_vp, _u32, C.POINTER(hd_fsk4_track_info)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -503,6 +539,18 @@ HOST_API = {
     "hd_host_fsk4_candidates": (_int, [_vp, _vp, _sz]),
     "hd_host_fsk4_encode": (_sz, [C.POINTER(hd_fsk4_frame), _vp, _vp]),
     "hd_host_fsk4_crc16": (_u32, [_vp, _sz]),
+    "hd_host_fsk4_retune": (_int, [_vp, _dbl, _dbl, C.c_uint64]),
+    "hd_host_fsk4_retune_stats": (_int, [_vp, C.POINTER(hd_fsk4_retune_info)]),
+    "hd_host_fsk4_comb_detect": (_int, [_vp, _dbl, C.POINTER(hd_fsk4_comb_params), _vp]),
+    "hd_host_fsk4_track_new": (_vp, [_dbl, C.POINTER(hd_fsk4_track_params)]),
+    "hd_host_fsk4_track_free": (None, [_vp]),
+    "hd_host_fsk4_track_reset": (None, [_vp]),
+    "hd_host_fsk4_track_set_stream": (_int, [_vp, _dbl, _dbl, _dbl, _dbl, _dbl]),
+    "hd_host_fsk4_track_attach": (None, [_vp, _vp]),
+    "hd_host_fsk4_track_push": (None, [_vp, _vp, _sz]),
+    "hd_host_fsk4_track_records": (_int, [_vp, _vp, _sz]),
+    "hd_host_fsk4_track_stats": (_int, [_vp, C.POINTER(hd_fsk4_track_info)]),
+    "hd_host_fsk4_track_acc": (_int, [_vp, _vp]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

@@ -13,7 +13,8 @@
 // The SSDV object (kernels/ssdv.hip, host/ssdv.hpp) is the sixth: it takes bytes, not rows -- its doors append on the host -- and shares the doors' checks,
 // the chunked launches (its descriptors' n_total counts candidates), reset, destroy and the guard counter.  The 4FSK modem (kernels/fsk4.hip,
 // host/fsk4.hpp) is the seventh: the tones' doors, descriptor and chunked slot launches in front, the SSDV object's chunked candidate launches and host
-// delivery behind.
+// delivery behind.  The 4FSK tone tracker (kernels/fsk4_track.hip, host/fsk4_track.hpp) is the eighth: the tone search's doors, descriptor and kernel over
+// accumulators of its own, cut into rounds at every stream's epoch end (launch_rounds, which the modem's retunes use too), the comb detector behind them.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
@@ -23,11 +24,13 @@
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
 #include "host/fsk4.hpp"
+#include "host/fsk4_track.hpp"
 #include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
 #include "kernels/combine.h"
 #include "kernels/fsk4.h"
+#include "kernels/fsk4_track.h"
 #include "kernels/ssdv.h"
 #include "kernels/tone_search.h"
 
@@ -152,6 +155,39 @@ int launch_chunks(Obj* o, uint32_t max_n, uint32_t chunk, const char* unfit, Pre
         if (o->t1 && off + chunk >= max_n) HD_HIP(hipEventRecord(o->t1, q));
         HD_HIP(hipStreamSynchronize(q));
         after();
+    }
+    return HD_OK;
+}
+
+// The launches behind a push whose streams are cut each at places of its own -- the tracker's epoch ends, the 4FSK modem's retunes: round by round,
+// take(s, d, left) says how many of the `left` samples stream s still has the next launch takes (at least one; d.off and d.n are written here, the
+// rest of the descriptor by take), launch() issues the kernel (false: it does not fit, the push fails with `unfit`), after() follows the wait and may
+// launch and wait for more.  Without cuts the rounds are launch_chunks' chunks.  o->done [S]: the object's scratch.  A stream with nothing left is
+// not asked: its descriptor gets n = 0 and keeps whatever else an earlier round wrote there, which no kernel reads -- k_tone_search and k_fsk4_slots
+// leave at n = 0 before they look at another field.
+template <typename Obj, typename Take, typename Launch, typename After>
+int launch_rounds(Obj* o, const char* unfit, Take take, Launch launch, After after)
+{
+    hipStream_t q = o->e->qa;
+    if (o->t0) HD_HIP(hipEventRecord(o->t0, q));
+    o->done.assign(o->S, 0u);
+    for (;;) {
+        bool any = false;
+        for (uint32_t s = 0; s < o->S; ++s) {
+            auto& d = o->src.p[s];
+            const uint32_t left = d.n_total - o->done[s];
+            d.off = o->done[s];
+            d.n = left ? take(s, d, left) : 0u;
+            o->done[s] += d.n;
+            any |= d.n != 0;
+        }
+        if (!any) break;
+        std::atomic_thread_fence(std::memory_order_release);
+        if (!launch()) return fail(HD_ERR_DEVICE, unfit);
+        HD_HIP(hipGetLastError());
+        if (o->t1) HD_HIP(hipEventRecord(o->t1, q));                   // (recorded again behind every launch: the last one's stands)
+        HD_HIP(hipStreamSynchronize(q));
+        if (const int rc = after()) return rc;
     }
     return HD_OK;
 }
@@ -1513,6 +1549,7 @@ struct hd_fsk4 {
     hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the slot launches of a push ...
     hipEvent_t f0 = nullptr, f1 = nullptr;       // ... and around the frame launches of its scan
     bool frames_launched = false;
+    std::vector<uint32_t> done;                  // launch_rounds' scratch
 };
 // (the strides the kernels were written against, fsk4.h)
 static_assert(Guarded<uint32_t>::stride_of(hd::kFsk4Ring32, hd::kFsk4Guard) == hd::kFsk4Ring32 + 2 * hd::kFsk4Guard, "fsk4 ring stride");
@@ -1581,29 +1618,47 @@ int fsk4_scan(hd_fsk4* f)
     return HD_OK;
 }
 
-// Its own: a stream without a modem is passed by, in front of the max_push test; per chunk, `cap`, the longest part of a row in the launch, which sizes
-// its LDS; behind the last chunk the host's copy of n and g follows the device's, and the scan runs.
+// The tones a retune put in force go to the device: phi and psi lie together in the state.  On the queue, in front of the next launch.
+hipError_t fsk4_copy_tones(hd_fsk4* f, uint32_t s)
+{
+    return hipMemcpyAsync(reinterpret_cast<char*>(f->st.p + s) + offsetof(hd::Fsk4State, phi), f->stream[s].s.phi, 8 * sizeof(uint32_t), hipMemcpyHostToDevice,
+                          f->e->qa);
+}
+
+// Its own: a stream without a modem is passed by, in front of the max_push test.  Round by round (launch_rounds): a stream's retunes whose sample has come
+// take effect and its new tones are copied on the queue; the launch takes the stream's samples up to the next waiting retune, HD_FSK4_CHUNK at most;
+// `cap`, the longest part of a row in the launch, sizes its LDS; behind the wait the host's copy of n and g follows the device's.  Then the scan.
 int fsk4_launch(hd_fsk4* f, uint32_t max_n)
 {
     if (const int rc = check_max_push(f, "hd_fsk4", &max_n, [f](uint32_t s) { if (!f->stream[s].s.F) f->src.p[s].n_total = 0; })) return rc;
     uint32_t cap = 0;
-    const int rc = launch_chunks(
-        f, max_n, HD_FSK4_CHUNK, "fsk4: the launch's chunk does not fit the LDS",
-        [&](uint32_t, const hd::TonesSrc& d) { cap = std::max(cap, d.n); },
+    hipError_t copy = hipSuccess;                // of a retuned stream's tones; a failure ends the push behind the round's wait, with HIP's own message
+    const int rc = launch_rounds(
+        f, "fsk4: the launch's chunk does not fit the LDS",
+        [&](uint32_t s, hd::TonesSrc&, uint32_t left) {
+            hd::Fsk4Stream& st = f->stream[s];
+            if (!st.pending.empty() && st.apply_retunes() && copy == hipSuccess) copy = fsk4_copy_tones(f, s);
+            const uint32_t n = (uint32_t)st.uncut(std::min<uint32_t>(left, HD_FSK4_CHUNK));
+            cap = std::max(cap, n);
+            return n;
+        },
         [&] {
             const uint32_t longest = cap;
             cap = 0;
             return hd::launch_fsk4_slots(f->e->qa, f->S, longest, f->src.dev, f->st.p, f->ring32.base(), f->ring32.stride, f->ctab.p, f->slots.base(),
                                          f->slots.stride, f->slot_cap);
         },
-        [] {});
+        [&]() -> int {
+            for (uint32_t s = 0; s < f->S; ++s) {
+                hd::Fsk4State& m = f->stream[s].s;
+                if (!m.F || !f->src.p[s].n) continue;
+                m.n += f->src.p[s].n;
+                m.g = hd::fsk4_slots_before(m.F, m.n);
+            }
+            HD_HIP(copy);
+            return HD_OK;
+        });
     if (rc) return rc;
-    for (uint32_t s = 0; s < f->S; ++s) {
-        hd::Fsk4State& m = f->stream[s].s;
-        if (!m.F) continue;
-        m.n += f->src.p[s].n_total;
-        m.g = hd::fsk4_slots_before(m.F, m.n);
-    }
     return fsk4_scan(f);
 }
 
@@ -1727,6 +1782,36 @@ int hd_fsk4_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_counters* out)
     return HD_OK;
 }
 
+int hd_fsk4_retune(hd_fsk4* f, uint32_t stream, double f0_hz, double spacing_hz, uint64_t at_sample)
+{
+    if (const int rc = check_object(f, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    hd::Fsk4Stream& st = f->stream[stream];
+    if (!st.s.F) return fail(HD_ERR_INVALID, "hd_fsk4_retune: the stream has no modem");
+    uint32_t phi[4];
+    if (hd::fsk4_retune_steps(f->e->fsd, f0_hz, spacing_hz, phi)) return fail(HD_ERR_INVALID, "fsk4: every tone f0 + t spacing, t = 0 .. 3, inside +- decimated rate / 2");
+    st.retune(phi, at_sample);
+    if (st.apply_retunes()) {                     // its sample has come already: at once
+        HD_HIP(fsk4_copy_tones(f, stream));
+        HD_HIP(hipStreamSynchronize(f->e->qa));
+    }
+    return HD_OK;
+}
+
+int hd_fsk4_retune_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_retune_info* out)
+{
+    if (const int rc = check_object(f, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(f->e->mtx);
+    if (const int rc = enter(f->e)) return rc;
+    hd::Fsk4State h;
+    HD_HIP(hipMemcpy(&h, f->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
+    const hd::Fsk4Stream& st = f->stream[stream];
+    *out = hd_fsk4_retune_info{st.retunes, st.late, st.pending.size(), {h.psi[0], h.psi[1], h.psi[2], h.psi[3]}};
+    return HD_OK;
+}
+
 // The measurement hook (tools/micro/fsk4_rate.py; not part of the ABI): hd_fsk4_push_engine with the slot launches and the frame launches of its scan
 // each between two HIP events (0 where none was launched), and the host time of the whole call in microseconds.
 int hd_debug_fsk4_push_timed(hd_fsk4* f, float* slots_ms, float* frames_ms, double* host_us)
@@ -1777,6 +1862,283 @@ int hd_debug_fsk4_guards(hd_fsk4* f, uint32_t stream)
     const size_t r = (size_t)stream * 8;
     return damaged_guards({{f->ring32, r}, {f->ring32, r + 1}, {f->ring32, r + 2}, {f->ring32, r + 3}, {f->ring32, r + 4}, {f->ring32, r + 5},
                            {f->ring32, r + 6}, {f->ring32, r + 7}, {f->slots, stream}, {f->cnt, 0}, {f->out, 0}});
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- 4FSK tone tracker (kernels/fsk4_track.hip) --------------------------- */
+
+struct hd_fsk4_track {
+    static constexpr const char* kNull = "null fsk4 tracker";
+    hd_engine* e = nullptr;
+    hd_fsk4_track_params prm{};
+    uint32_t S = 0;
+    Guarded<double> acc;                         // [S]: guard | 4096 fftshifted sums | guard -- the tone search's layout, this object's own sums
+    Guarded<float2> carry;                       // [S * 2]: the tone search's two carry buffers per stream
+    Guarded<uint32_t> rec;                       // [S]: guard | the 16 words of the stream's newest record | guard
+    DevBuf<float> win;                           // [4096] the survey's window table
+    DevBuf<float2> own_tw;                       // the twiddles where the engine computes no spectra and holds none
+    const float2* tw = nullptr;
+    DevBuf<float2> slab;                         // hd_fsk4_track_push_host: the rows packed end to end, grown on demand
+    PinBuf<hd::ToneSearchSrc> src;               // [S]: a spectrum launch's descriptors
+    PinBuf<hd::Fsk4CombSrc> comb;                // [S]: a comb launch's
+    std::vector<hd::Fsk4TrackBook> book;         // [S]: the stream's search, epochs, counts and records
+    std::vector<uint32_t> carry_n, flip;         // [S]: the carry's length, and which of the two buffers holds it
+    std::vector<uint32_t> done;                  // launch_rounds' scratch
+    std::vector<hd_fsk4_comb_record> h_rec;      // [S]: a comb launch's records
+    hd_fsk4* modem = nullptr;                    // attached: retuned at epoch ends
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the launches of a push ...
+    hipEvent_t c0 = nullptr, c1 = nullptr;       // ... and around each comb launch, whose times add up in comb_ms
+    float comb_ms = 0;
+};
+static_assert(sizeof(hd_fsk4_comb_record) == 64, "the comb record is 16 words");
+static_assert(Guarded<double>::stride_of(hd::kFsk4CombBins, hd::kFsk4TrackGuard) == hd::kToneSearchSeg + hd::kToneSearchGuard && hd::kFsk4TrackGuard == hd::kToneSearchGuard,
+              "the tracker's sums and carries have the tone search's layout: its kernel writes them");
+
+namespace {
+
+// One comb launch over the streams whose descriptor says due, waited for; the records of all streams come back (a stream that was not due keeps its last).
+int fsk4_track_comb(hd_fsk4_track* tr)
+{
+    hipStream_t q = tr->e->qa;
+    std::atomic_thread_fence(std::memory_order_release);
+    if (tr->c0) HD_HIP(hipEventRecord(tr->c0, q));
+    hd::launch_fsk4_comb(q, tr->S, tr->comb.dev, tr->acc.base(), tr->acc.stride, tr->rec.base(), tr->rec.stride);
+    HD_HIP(hipGetLastError());
+    if (tr->c1) HD_HIP(hipEventRecord(tr->c1, q));
+    if (tr->t1) HD_HIP(hipEventRecord(tr->t1, q));                     // (the push's last launch so far)
+    HD_HIP(hipStreamSynchronize(q));
+    if (tr->c1) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, tr->c0, tr->c1) == hipSuccess) tr->comb_ms += ms;
+    }
+    HD_HIP(hipMemcpy2D(tr->h_rec.data(), sizeof(hd_fsk4_comb_record), tr->rec.row(0), tr->rec.stride * sizeof(uint32_t), sizeof(hd_fsk4_comb_record), tr->S,
+                       hipMemcpyDeviceToHost));
+    return HD_OK;
+}
+
+// Its own: a stream without a search is passed by, in front of the max_push test.  Round by round (launch_rounds): the spectrum launch -- the tone search's,
+// with its descriptor -- takes a stream's samples up to its epoch's end, HD_TONE_SEARCH_CHUNK at most; behind the wait the counts move on, and where
+// an epoch ended the comb launch follows, its records join the streams' logs and an attached modem is retuned.
+int fsk4_track_launch(hd_fsk4_track* tr, uint32_t max_n)
+{
+    if (const int rc = check_max_push(tr, "hd_fsk4_track", &max_n, [tr](uint32_t s) { if (!tr->book[s].set) tr->src.p[s].n_total = 0; })) return rc;
+    const uint32_t E = tr->prm.epoch_segments;
+    return launch_rounds(
+        tr, "",
+        [&](uint32_t s, hd::ToneSearchSrc& d, uint32_t left) {
+            const uint32_t n = (uint32_t)tr->book[s].uncut(std::min<uint32_t>(left, HD_TONE_SEARCH_CHUNK), E);
+            d.carry = tr->carry_n[s];
+            d.segs = hd::tone_search_segments(d.carry, n);
+            d.flip = tr->flip[s];
+            return n;
+        },
+        [&] {
+            hd::launch_tone_search(tr->e->qa, tr->S, tr->src.dev, tr->win.p, tr->tw, tr->acc.base(), tr->acc.stride, tr->carry.base(), tr->carry.stride);
+            return true;
+        },
+        [&]() -> int {
+            bool any = false;
+            for (uint32_t s = 0; s < tr->S; ++s) {
+                const hd::ToneSearchSrc& d = tr->src.p[s];
+                hd::Fsk4CombSrc& c = tr->comb.p[s];
+                c.due = 0;
+                if (!d.n) continue;
+                hd::Fsk4TrackBook& b = tr->book[s];
+                b.samples += d.n;
+                b.segments += d.segs;
+                tr->carry_n[s] = d.carry + d.n - d.segs * hd::kToneSearchStep;
+                if (d.segs) tr->flip[s] ^= 1u;
+                if (b.samples != b.epoch_end(E)) continue;
+                c.plan = b.plan; c.due = 1; c.min_quality_q8 = tr->prm.min_quality_q8; c.segments_ok = b.segments_ok(tr->prm); c.decay_q8 = tr->prm.decay_q8;
+                any = true;
+            }
+            if (!any) return HD_OK;
+            if (const int rc = fsk4_track_comb(tr)) return rc;
+            for (uint32_t s = 0; s < tr->S; ++s) {
+                if (!tr->comb.p[s].due) continue;
+                hd::Fsk4TrackBook& b = tr->book[s];
+                const hd_fsk4_track_est est = b.close_epoch(tr->h_rec[s], tr->prm, tr->e->fsd);
+                if (!tr->modem || !tr->modem->stream[s].s.F) continue;
+                if (!b.wants_retune(est, hd::fsk4_steps_ahead(tr->modem->stream[s]), tr->e->fsd, tr->prm.deadband)) continue;
+                uint32_t phi[4];
+                if (hd::fsk4_retune_steps(tr->e->fsd, est.f0_hz, est.spacing_hz, phi)) continue;      // a tone out of band: no retune, and no error either
+                if (const int rc = hd_fsk4_retune(tr->modem, s, est.f0_hz, est.spacing_hz, est.end_sample)) return rc;
+                ++b.retunes;
+            }
+            return HD_OK;
+        });
+}
+
+// (The carry buffers need no clearing: nothing behind a stream's carry length is read.)
+int fsk4_track_clear(hd_fsk4_track* tr, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = tr->e->qa;
+    HD_HIP(hipMemset2DAsync(tr->acc.row(s0), tr->acc.stride * sizeof(double), 0, (size_t)hd::kFsk4CombBins * sizeof(double), ns, q));
+    HD_HIP(hipMemset2DAsync(tr->rec.row(s0), tr->rec.stride * sizeof(uint32_t), 0, sizeof(hd_fsk4_comb_record), ns, q));
+    HD_HIP(hipStreamSynchronize(q));
+    for (uint32_t s = s0; s < s0 + ns; ++s) { tr->book[s].reset(); tr->carry_n[s] = tr->flip[s] = 0; }
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_fsk4_track_params_default(hd_fsk4_track_params* p) { if (p) hd::fsk4_track_params_default(p); }
+
+int hd_fsk4_track_create(hd_engine* e, const hd_fsk4_track_params* params, hd_fsk4_track** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_fsk4_track> tr(new hd_fsk4_track);
+    tr->e = e; tr->S = e->S;
+    hd::fsk4_track_params_default(&tr->prm);
+    if (params) tr->prm = *params;
+    if (!hd::fsk4_track_params_ok(&tr->prm)) return fail(HD_ERR_INVALID, "fsk4 tracker parameters: 1 <= epoch_segments <= 4096, decay_q8 <= 256");
+    if (const int rc = default_max_push(e, &tr->prm.max_push, "fsk4 tracker")) return rc;
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = tr->S;
+    tr->book.resize(S); tr->carry_n.assign(S, 0u); tr->flip.assign(S, 0u); tr->h_rec.resize(S);
+    std::vector<float> w(hd::kToneSearchSeg);
+    hd::survey_window(w.data());
+    std::vector<float2> tw_host;
+    HD_HIP(tr->acc.alloc(S, hd::kFsk4CombBins, hd::kFsk4TrackGuard, hd::kFsk4TrackGuardWord, e->qa));
+    HD_HIP(tr->carry.alloc((size_t)S * 2, hd::kToneSearchSeg, hd::kFsk4TrackGuard, hd::kFsk4TrackGuardWord, e->qa));
+    HD_HIP(tr->rec.alloc(S, sizeof(hd_fsk4_comb_record) / sizeof(uint32_t), hd::kFsk4TrackGuard, hd::kFsk4TrackGuardWord, e->qa));
+    HD_HIP(tr->win.alloc_unfilled(w.size()));
+    HD_HIP(tr->src.alloc(S));
+    HD_HIP(tr->comb.alloc(S));
+    if (const int rc = hd::eng::engine_or_own_twiddles(e, tr->own_tw, tw_host, e->qa, &tr->tw)) return rc;
+    HD_HIP(hipMemcpyAsync(tr->win.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, e->qa));
+    if (const int rc = fsk4_track_clear(tr.get(), 0, S)) return rc;    // (waits for the queue: the tables are locals)
+    *out = tr.release();
+    return HD_OK;
+}
+
+void hd_fsk4_track_destroy(hd_fsk4_track* tr) { destroy(tr); }
+
+int hd_fsk4_track_reset(hd_fsk4_track* tr, uint32_t stream) { return reset(tr, stream, fsk4_track_clear); }
+
+int hd_fsk4_track_set_stream(hd_fsk4_track* tr, uint32_t stream, double baud, double spacing_lo_hz, double spacing_hi_hz, double f_lo_hz, double f_hi_hz)
+{
+    if (const int rc = check_object(tr, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    hd::Fsk4CombPlan pl;
+    const int rc = hd::fsk4_comb_plan(tr->e->fsd, baud, spacing_lo_hz, spacing_hi_hz, f_lo_hz, f_hi_hz, pl);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "fsk4 tracker: a tone spacing below 2 baud is not searched");
+    if (rc) return fail(rc, "fsk4 tracker: baud > 0, 0 < spacing_lo_hz <= spacing_hi_hz, f_lo_hz < f_hi_hz, and a band that holds the narrowest comb");
+    if (const int rc2 = enter(tr->e)) return rc2;
+    tr->book[stream].plan = pl; tr->book[stream].baud = baud; tr->book[stream].set = true;
+    return fsk4_track_clear(tr, stream, 1);
+}
+
+int hd_fsk4_track_attach(hd_fsk4_track* tr, hd_fsk4* f)
+{
+    if (!tr) return fail(HD_ERR_INVALID, hd_fsk4_track::kNull);
+    if (f && f->e != tr->e) return fail(HD_ERR_INVALID, "hd_fsk4_track_attach: the fsk4 object belongs to another engine");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    tr->modem = f;
+    return HD_OK;
+}
+
+int hd_fsk4_track_push_engine(hd_fsk4_track* tr) { return push_engine(tr, "hd_fsk4_track_push_engine", fsk4_track_launch); }
+
+int hd_fsk4_track_push_device(hd_fsk4_track* tr, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(tr, reinterpret_cast<const float2*>(d_iq), stride, n_per_stream, n, true, fsk4_track_launch);
+}
+
+int hd_fsk4_track_push_host(hd_fsk4_track* tr, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(tr, reinterpret_cast<const float2*>(iq), stride, n_per_stream, n, false, fsk4_track_launch);
+}
+
+int hd_fsk4_track_estimate(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_est* out)
+{
+    if (const int rc = check_object(tr, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    if (tr->book[stream].log.empty()) return fail(HD_ERR_UNSUPPORTED, "hd_fsk4_track_estimate: no epoch of the stream has ended");
+    *out = tr->book[stream].log.back();
+    return HD_OK;
+}
+
+int hd_fsk4_track_stats(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_info* out)
+{
+    if (const int rc = check_object(tr, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    tr->book[stream].stats(out);
+    return HD_OK;
+}
+
+// The measurement hook (tools/micro/fsk4_track_rate.py; not part of the ABI): hd_fsk4_track_push_engine between two HIP events -- the spectrum launches,
+// the comb launches and the waits between them -- the comb launches alone (0 where no epoch ended), and the host time of the whole call in microseconds.
+int hd_debug_fsk4_track_push_timed(hd_fsk4_track* tr, float* push_ms, float* comb_ms, double* host_us)
+{
+    if (!tr || !push_ms || !comb_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    if (const int rc = enter(tr->e)) return rc;
+    HD_HIP(hipEventCreate(&tr->c0));
+    HD_HIP(hipEventCreate(&tr->c1));
+    tr->comb_ms = 0;
+    const int rc = push_timed(tr, push_ms, host_us, hd_fsk4_track_push_engine);
+    *comb_ms = tr->comb_ms;
+    (void)hipEventDestroy(tr->c0); (void)hipEventDestroy(tr->c1);
+    tr->c0 = tr->c1 = nullptr;
+    return rc;
+}
+
+// Test hooks (tests/test_gpu_fsk4_track.py; not part of the ABI).  All records of the stream since its last reset, oldest first (the log keeps the newest
+// 4096); out null: how many.
+int hd_debug_fsk4_track_records(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_est* out, size_t cap)
+{
+    if (!tr || stream >= tr->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    return (int)tr->book[stream].take_log(out, cap, true);
+}
+
+// The stream's 4096 sums as they lie in device memory.
+int hd_debug_fsk4_track_acc(hd_fsk4_track* tr, uint32_t stream, double* out)
+{
+    if (!tr || stream >= tr->S || !out) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    if (const int rc = enter(tr->e)) return rc;
+    HD_HIP(hipMemcpy(out, tr->acc.row(stream), hd::kFsk4CombBins * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)hd::kFsk4CombBins;
+}
+
+// One comb launch over spectra of the test's making: spectra [S][4096] replace the streams' sums, stream s is searched by its own plan where due[s] is
+// set (with segments_ok[s] and the object's min_quality_q8 and decay_q8), and the records of all streams come back.  The streams want a reset afterwards.
+int hd_debug_fsk4_track_comb(hd_fsk4_track* tr, const double* spectra, const uint32_t* due, const uint32_t* segments_ok, hd_fsk4_comb_record* out)
+{
+    if (!tr || !spectra || !due || !segments_ok || !out) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    if (const int rc = enter(tr->e)) return rc;
+    for (uint32_t s = 0; s < tr->S; ++s)
+        if (due[s] && !tr->book[s].set) return fail(HD_ERR_INVALID, "hd_debug_fsk4_track_comb: a due stream without a search");
+    HD_HIP(hipMemcpy2D(tr->acc.row(0), tr->acc.stride * sizeof(double), spectra, hd::kFsk4CombBins * sizeof(double), hd::kFsk4CombBins * sizeof(double), tr->S,
+                       hipMemcpyHostToDevice));
+    for (uint32_t s = 0; s < tr->S; ++s) {
+        hd::Fsk4CombSrc& c = tr->comb.p[s];
+        c.plan = tr->book[s].plan; c.due = due[s] ? 1u : 0u; c.min_quality_q8 = tr->prm.min_quality_q8; c.segments_ok = segments_ok[s] ? 1u : 0u;
+        c.decay_q8 = tr->prm.decay_q8;
+    }
+    if (const int rc = fsk4_track_comb(tr)) return rc;
+    std::memcpy(out, tr->h_rec.data(), (size_t)tr->S * sizeof(hd_fsk4_comb_record));
+    return HD_OK;
+}
+
+// How many of the guard words around the stream's sums, its two carry buffers and its record no longer hold their pattern.
+int hd_debug_fsk4_track_guards(hd_fsk4_track* tr, uint32_t stream)
+{
+    if (!tr || stream >= tr->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
+    if (const int rc = enter(tr->e)) return rc;
+    return damaged_guards({{tr->acc, stream}, {tr->carry, (size_t)stream * 2}, {tr->carry, (size_t)stream * 2 + 1}, {tr->rec, stream}});
 }
 
 }  // extern "C"

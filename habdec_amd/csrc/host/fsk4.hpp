@@ -176,6 +176,22 @@ inline int fsk4_modem(Fsk4State& s, double fsd, double baud, double f0, double s
     return HD_OK;
 }
 
+// hd_fsk4_retune's checks and the new tones' steps, by set_modem's rule: HD_ERR_INVALID for a tone outside +- fsd / 2 (or a non-finite one).
+inline int fsk4_retune_steps(double fsd, double f0, double spacing, uint32_t* phi)
+{
+    for (uint32_t t = 0; t < 4; ++t) {
+        const double f = f0 + t * spacing;
+        if (!(std::fabs(f) < fsd / 2)) return HD_ERR_INVALID;
+        phi[t] = (uint32_t)(int64_t)std::nearbyint(f / fsd * 4294967296.0);
+    }
+    return HD_OK;
+}
+// A retune that waits for its sample.
+struct Fsk4Retune {
+    uint64_t at;
+    uint32_t phi[4];
+};
+
 // Slots a stream's ring holds, a power of two: the 8 (260 - 1) slots a candidate may wait for its last one, a push's new slots (at most one per sample,
 // at 8 samples per symbol) and the slot in flight.
 inline uint32_t fsk4_slot_cap(uint32_t max_push)
@@ -263,6 +279,8 @@ struct Fsk4Stream {
     std::deque<hd_fsk4_rx> waiting;
     std::deque<hd_fsk4_candidate> log;           // the candidates behind the gate, for hd_host_fsk4_candidates and the test hook
     static constexpr size_t kLog = 65536;
+    std::deque<Fsk4Retune> pending;              // retunes that wait for their sample, in the order of the calls
+    uint64_t retunes = 0, late = 0;              // retunes that took effect; those of them whose sample was behind the stream's index
     // the restatement's own
     std::vector<int32_t> C;
     std::vector<uint32_t> ring[8];
@@ -287,7 +305,36 @@ struct Fsk4Stream {
         decided = candidates = gate_passes = crc_failures = refused = overlaps = frames = 0;
         open = false; blocked_until = 0;
         log.clear();
+        pending.clear();
+        retunes = late = 0;
     }
+    // hd_fsk4_retune.  The retunes take effect in the order of the calls: the one in front waits for its sample, those behind it for the one in front.
+    void retune(const uint32_t* phi, uint64_t at)
+    {
+        Fsk4Retune r;
+        r.at = at;
+        for (uint32_t t = 0; t < 4; ++t) r.phi[t] = phi[t];
+        pending.push_back(r);
+    }
+    // In front of sample s.n: every retune in front of the queue whose sample is s.n or behind it takes effect at s.n, Psi_t += s.n (Phi_old - Phi_new)
+    // mod 2^32 -- the rotator's phase at s.n is what it would have been.  True: the state changed (the engine's object copies phi and psi to the device).
+    bool apply_retunes()
+    {
+        bool any = false;
+        for (; !pending.empty() && pending.front().at <= s.n; pending.pop_front()) {
+            const Fsk4Retune& r = pending.front();
+            for (uint32_t t = 0; t < 4; ++t) {
+                s.psi[t] += (uint32_t)s.n * (s.phi[t] - r.phi[t]);
+                s.phi[t] = r.phi[t];
+            }
+            ++retunes;
+            late += r.at < s.n;
+            any = true;
+        }
+        return any;
+    }
+    // Samples from s.n on that no waiting retune cuts (after apply_retunes()): at most `want`.
+    uint64_t uncut(uint64_t want) const { return pending.empty() ? want : std::min<uint64_t>(want, pending.front().at - s.n); }
     uint32_t limit() const { return max_corrected < 0 ? 2u * tab.K : (uint32_t)max_corrected; }
 
     // The candidates that can be decided once g slots exist, first and count: a candidate's last slot is its first + 8 (nsym - 1).
@@ -368,11 +415,12 @@ struct Fsk4Stream {
         if (!s.F) return;
         for (size_t j = 0; j < n; ++j) {
             const uint64_t i = s.n;
+            if (!pending.empty()) apply_retunes();
             const int32_t q_re = tones_quantise(iq[2 * j]), q_im = tones_quantise(iq[2 * j + 1]);
             const bool slot = fsk4_slot_end(s.F, s.g) == i;
             uint32_t A[4];
             for (uint32_t t = 0; t < 4; ++t) {
-                const uint32_t a = ((uint32_t)i * s.phi[t]) >> 22;
+                const uint32_t a = ((uint32_t)i * s.phi[t] + s.psi[t]) >> 22;
                 const int32_t c = C[a], sn = C[(a + 768u) & 1023u];
                 const int32_t r[2] = {(q_re * c + q_im * sn) >> 15, (q_im * c - q_re * sn) >> 15};
                 int64_t w[2];

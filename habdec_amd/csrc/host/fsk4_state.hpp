@@ -16,9 +16,10 @@ struct Fsk4State {
     uint32_t F;                // 0: the stream has no modem
     uint32_t W;
     uint32_t phi[4];
+    uint32_t psi[4];           // the tones' phase words: 0 after set_modem and reset, moved by every retune so that the rotators' phases are continuous
     uint32_t tot[8];           // sums of r_re, r_im of tone 0, then of tones 1 .. 3, over j < n, mod 2^32
-    uint32_t _pad[2];
 };
+static_assert(sizeof(Fsk4State) == 88, "fsk4 state layout: phi and psi lie together, a retune copies them in one piece");
 // A stream's history, kept as running sums like the tones object's: word (k & (kFsk4Ring32 - 1)) of ring t is tot[t] after k samples, for the newest
 // kFsk4Ring32 values of k <= n.  W <= kFsk4Ring32.
 constexpr uint32_t kFsk4Ring32 = 2048;

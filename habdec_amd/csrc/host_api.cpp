@@ -9,6 +9,7 @@
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
 #include "host/fsk4.hpp"
+#include "host/fsk4_track.hpp"
 #include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
@@ -573,6 +574,21 @@ int hd_host_fsk4_set_modem(hd_host_fsk4* h, double baud, double f0_hz, double sp
     h->st.reset();
     return HD_OK;
 }
+int hd_host_fsk4_retune(hd_host_fsk4* h, double f0_hz, double spacing_hz, uint64_t at_sample)
+{
+    if (!h || !h->st.s.F) return HD_ERR_INVALID;
+    uint32_t phi[4];
+    if (const int rc = hd::fsk4_retune_steps(h->fsd, f0_hz, spacing_hz, phi)) return rc;
+    h->st.retune(phi, at_sample);
+    h->st.apply_retunes();
+    return HD_OK;
+}
+int hd_host_fsk4_retune_stats(const hd_host_fsk4* h, hd_fsk4_retune_info* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    *out = hd_fsk4_retune_info{h->st.retunes, h->st.late, h->st.pending.size(), {h->st.s.psi[0], h->st.s.psi[1], h->st.s.psi[2], h->st.s.psi[3]}};
+    return HD_OK;
+}
 // (in pieces of max_push, a scan behind each: the slot ring holds what one piece adds to the candidates that wait)
 size_t hd_host_fsk4_push(hd_host_fsk4* h, const float* iq, size_t n)
 {
@@ -601,6 +617,54 @@ size_t hd_host_fsk4_slots(const hd_host_fsk4* h, uint64_t first, uint32_t* out, 
 int hd_host_fsk4_candidates(hd_host_fsk4* h, hd_fsk4_candidate* out, size_t cap) { return h ? (int)h->st.take_log(out, cap) : HD_ERR_INVALID; }
 size_t hd_host_fsk4_encode(const hd_fsk4_frame* frame, const uint8_t* payload, uint8_t* out) { return frame && payload && out ? hd::fsk4_encode(*frame, payload, out) : 0; }
 uint32_t hd_host_fsk4_crc16(const uint8_t* bytes, size_t n) { return bytes || !n ? hd::fsk4_crc16(bytes, n) : 0xFFFFu; }
+
+/* ---- 4FSK tone tracker (kernels/fsk4_track.hip; see host/fsk4_track.hpp) ---- */
+int hd_host_fsk4_comb_detect(const double* acc, double decimated_rate, const hd_fsk4_comb_params* p, hd_fsk4_comb_record* out)
+{
+    if (out) std::memset(out, 0, sizeof *out);
+    if (!acc || !p || !out) return HD_ERR_INVALID;
+    hd::Fsk4CombPlan pl;
+    if (const int rc = hd::fsk4_comb_plan(decimated_rate, p->baud, p->spacing_lo_hz, p->spacing_hi_hz, p->f_lo_hz, p->f_hi_hz, pl)) return rc;
+    hd::fsk4_comb_detect(acc, pl, p->min_quality_q8, p->segments_ok != 0, out);
+    return HD_OK;
+}
+struct hd_host_fsk4_track { hd::Fsk4TrackStream t; };
+hd_host_fsk4_track* hd_host_fsk4_track_new(double decimated_rate, const hd_fsk4_track_params* params)
+{
+    hd_fsk4_track_params prm;
+    hd::fsk4_track_params_default(&prm);
+    if (params) prm = *params;
+    if (!(decimated_rate > 0) || !hd::fsk4_track_params_ok(&prm)) return nullptr;
+    auto* h = new hd_host_fsk4_track;
+    h->t.prm = prm; h->t.fsd = decimated_rate;
+    return h;
+}
+void hd_host_fsk4_track_free(hd_host_fsk4_track* h) { delete h; }
+void hd_host_fsk4_track_reset(hd_host_fsk4_track* h) { if (h) h->t.reset(); }
+int hd_host_fsk4_track_set_stream(hd_host_fsk4_track* h, double baud, double spacing_lo_hz, double spacing_hi_hz, double f_lo_hz, double f_hi_hz)
+{
+    if (!h) return HD_ERR_INVALID;
+    hd::Fsk4CombPlan pl;
+    if (const int rc = hd::fsk4_comb_plan(h->t.fsd, baud, spacing_lo_hz, spacing_hi_hz, f_lo_hz, f_hi_hz, pl)) return rc;
+    h->t.book.plan = pl; h->t.book.baud = baud; h->t.book.set = true;
+    h->t.reset();
+    return HD_OK;
+}
+void hd_host_fsk4_track_attach(hd_host_fsk4_track* h, hd_host_fsk4* modem) { if (h) h->t.modem = modem ? &modem->st : nullptr; }
+void hd_host_fsk4_track_push(hd_host_fsk4_track* h, const float* iq, size_t n) { if (h && iq && n) h->t.push(iq, n); }
+int hd_host_fsk4_track_records(hd_host_fsk4_track* h, hd_fsk4_track_est* out, size_t cap) { return h ? (int)h->t.book.take_log(out, cap, true) : HD_ERR_INVALID; }
+int hd_host_fsk4_track_stats(const hd_host_fsk4_track* h, hd_fsk4_track_info* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    h->t.book.stats(out);
+    return HD_OK;
+}
+int hd_host_fsk4_track_acc(const hd_host_fsk4_track* h, double* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    std::memcpy(out, h->t.ts.acc.data(), hd::kFsk4CombBins * sizeof(double));
+    return (int)hd::kFsk4CombBins;
+}
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */
 struct hd_host_baud_probe {

@@ -75,8 +75,8 @@ __global__ __launch_bounds__(256) void k_fsk4_slots(const TonesSrc* __restrict__
     uint32_t* part32 = reinterpret_cast<uint32_t*>(C + 1024);                         // [8][kWaves]
 
     const uint32_t W = uni32(st->W);
-    uint32_t phi[4];
-    for (uint32_t k = 0; k < 4u; ++k) phi[k] = uni32(st->phi[k]);
+    uint32_t phi[4], psi[4];
+    for (uint32_t k = 0; k < 4u; ++k) { phi[k] = uni32(st->phi[k]); psi[k] = uni32(st->psi[k]); }
     const uint64_t n = uni64(st->n), g0 = uni64(st->g);
     uint32_t carry[8];
     for (uint32_t k = 0; k < 8u; ++k) carry[k] = uni32(st->tot[k]);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void k_fsk4_slots(const TonesSrc* __restrict__
         uint32_t sum[8];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
-            const uint32_t a = (i32 * phi[k]) >> 22;
+            const uint32_t a = (i32 * phi[k] + psi[k]) >> 22;
             const int32_t c = C[a], sn = C[(a + 768u) & 1023u];
             sum[2 * k] = (uint32_t)((q_re * c + q_im * sn) >> 15);
             sum[2 * k + 1] = (uint32_t)((q_im * c - q_re * sn) >> 15);

@@ -104,6 +104,10 @@ def _counters(c) -> dict:
     return d
 
 
+def _retune_info(i) -> dict:
+    return {"retunes": int(i.retunes), "late": int(i.late), "waiting": int(i.waiting), "psi": [int(v) for v in i.psi]}
+
+
 class Fsk4(_IqRowObject):
     """4FSK modem of an engine's streams: give a stream its modem, push decimated IQ (every push scans), take frames.  Closed with its engine, in front
     of it."""
@@ -140,6 +144,15 @@ class Fsk4(_IqRowObject):
         c = capi.hd_fsk4_counters()
         check(self.L.hd_fsk4_stats(self.h, s, C.byref(c)))
         return _counters(c)
+
+    def retune(self, s, f0, spacing, at_sample=0):
+        """Move stream s's four tones at sample at_sample (counted from the stream's last reset) without a reset: the frame in flight is kept."""
+        check(self.L.hd_fsk4_retune(self.h, s, float(f0), float(spacing), int(at_sample)))
+
+    def retune_stats(self, s=0) -> dict:
+        i = capi.hd_fsk4_retune_info()
+        check(self.L.hd_fsk4_retune_stats(self.h, s, C.byref(i)))
+        return _retune_info(i)
 
     # ---- the library's test and measurement hooks (not part of the ABI)
 
@@ -195,6 +208,16 @@ class HostFsk4(_Handle):
 
     def reset(self):
         self.L.hd_host_fsk4_reset(self.h)
+
+    def retune(self, f0, spacing, at_sample=0):
+        rc = self.L.hd_host_fsk4_retune(self.h, float(f0), float(spacing), int(at_sample))
+        if rc:
+            raise HabdecError("habdec_amd error %d: hd_host_fsk4_retune (a modem, and every tone inside +- rate / 2)" % rc)
+
+    def retune_stats(self) -> dict:
+        i = capi.hd_fsk4_retune_info()
+        check(self.L.hd_host_fsk4_retune_stats(self.h, C.byref(i)))
+        return _retune_info(i)
 
     def push(self, iq) -> int:
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(-1)

@@ -948,10 +948,15 @@ int  hd_ssdv_stats(hd_ssdv* v, uint32_t stream, hd_ssdv_counters* out);
  *  - Modem (hd_fsk4_set_modem): F = floor(fsd / baud * 65536 + 0.5); HD_ERR_UNSUPPORTED unless 8 <= fsd / baud <= HD_FSK4_MAX_SPB and the frame is one the
  *    decoder can take (3 <= P <= 32, interleave_mul coprime with 8 B, a nonzero 15-bit seed, golay_poly a divisor of x^23 + 1 of degree 11);
  *    Phi_t = (uint32)(int64)nearbyint((f0 + t spacing) / fsd * 2^32), t = 0 .. 3, HD_ERR_INVALID unless every tone lies inside +-fsd / 2;
- *    W = max(1, (F window_q8 + 2^23) >> 24): the whole symbol by default, because the timing is recovered.  The tones are the caller's: nothing
- *    searches for them or tracks them.
+ *    W = max(1, (F window_q8 + 2^23) >> 24): the whole symbol by default, because the timing is recovered.  Psi_t = 0.  The tones
+ *    come from the caller or from the tracker below (hd_fsk4_track_*).
+ *  - Retune (hd_fsk4_retune): new Phi_t by the modem's rule (HD_ERR_INVALID: a tone outside +-fsd / 2, a stream without a modem) come into force at
+ *    sample at_sample with Psi_t += at_sample (Phi_old - Phi_new) mod 2^32, so every rotator's phase is continuous and a small step costs no symbol.
+ *    Baud, frame, slots, rings, counters and the open group stay.  Retunes wait per stream on the host and take effect in the order of the calls; a
+ *    push is cut at at_sample and the state is updated on the queue between the two launches.  An at_sample behind the stream's index takes effect
+ *    at once, at that index, and counts as late (hd_fsk4_retune_stats).  A reset drops the waiting retunes and keeps the tones in force.
  *  - Per sample i (uint64 since the stream's last reset): the tones object's rules for four tones -- q = 0 for NaN, else (int32)(clamp(v, -8, 8) * 256);
- *    a = (uint32)(i Phi_t) >> 22; r_re = (q_re C[a] + q_im C[(a + 768) & 1023]) >> 15, r_im = (q_im C[a] - q_re C[(a + 768) & 1023]) >> 15 with the
+ *    a = (uint32)(i Phi_t + Psi_t) >> 22; r_re = (q_re C[a] + q_im C[(a + 768) & 1023]) >> 15, r_im = (q_im C[a] - q_re C[(a + 768) & 1023]) >> 15 with the
  *    probe's table C; running sums mod 2^32; A_t(i) = floor(sqrt(re^2 + im^2)) of the sums over the W samples up to i (fewer in front of sample 0).
  *  - Slots: a timing grid of eight phases per symbol, slot g = 8 k + p.  Slot g's record is (A_0, A_1, A_2, A_3) at its last sample
  *    end(g) = ((g + 8) F >> 19) - 1, four uint32; it exists once that sample is pushed.  Records go to a per-stream ring on the GPU.
@@ -978,7 +983,7 @@ int  hd_ssdv_stats(hd_ssdv* v, uint32_t stream, hd_ssdv_counters* out);
  *  - Counters per stream: samples, slots, candidates (decided), gate_passes, crc_failures, refused (by max_corrected), overlaps, frames.
  *  - Queue, errors: as the tones object's; a push returns when its kernels are done.  A push longer than max_push: HD_ERR_CAPACITY.  A row longer than
  *    HD_FSK4_CHUNK samples is cut into launches; a scan's candidates into launches of at most HD_FSK4_LAUNCH over all streams.
- *  - Not built: finding or tracking the tones, timing finer than a slot, the payload's fields and upload bodies, 2FSK Horus, feeding the combiner. */
+ *  - Not built: timing finer than a slot, the payload's fields and upload bodies, 2FSK Horus, feeding the combiner. */
 #define HD_FSK4_MAX_SPB 2048
 #define HD_FSK4_CHUNK 4096         /* samples of a row per launch of the slot kernel */
 #define HD_FSK4_LAUNCH 16384       /* candidates per launch of the frame kernel over all streams */
@@ -1034,6 +1039,93 @@ int  hd_fsk4_scan(hd_fsk4* f);
 /* Hands out up to cap of the stream's waiting frames, oldest first, and returns how many were written; out null: how many wait.  Negative: HD_ERR_*. */
 int  hd_fsk4_take_frames(hd_fsk4* f, uint32_t stream, hd_fsk4_rx* out, size_t cap);
 int  hd_fsk4_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_counters* out);
+typedef struct hd_fsk4_retune_info {
+    uint64_t retunes, late, waiting;   /* retunes that took effect since the stream's last reset; those of them that were late; those that wait */
+    uint32_t psi[4];                   /* the phase words in force */
+} hd_fsk4_retune_info;
+/* Moves the stream's four tones at at_sample without a reset (see "Retune" above). */
+int  hd_fsk4_retune(hd_fsk4* f, uint32_t stream, double f0_hz, double spacing_hz, uint64_t at_sample);
+int  hd_fsk4_retune_stats(hd_fsk4* f, uint32_t stream, hd_fsk4_retune_info* out);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------------------------
+ * 4FSK tone tracker.  A payload's oscillator is a few hundred Hz off when it starts and moves by more than the modem's tolerance (0.1 baud for nothing
+ * lost, NOTES.md) during a flight.  A tracker keeps, per stream, a Welch-averaged spectrum of the decimated IQ -- the tone search's kernel and segments,
+ * accumulators of its own -- and at the end of every epoch looks for four equally spaced tones in it (kernels/fsk4_track.hip: k_fsk4_comb, one
+ * workgroup per stream, one launch for every stream whose epoch ended); attached to an fsk4 object it retunes that object's streams.  Attached to an
+ * engine like a tones object; destroy it before the engine.  Kernel, host restatement (hd_host_fsk4_comb_detect, hd_host_fsk4_track_*) and a numpy
+ * model (tests/fsk4_track_model.py) agree byte for byte on the detector, which is integer arithmetic behind the quantisation.  bin = fsd / 4096; bin
+ * index k belongs to f = (k - 2048) bin.  In this order:
+ *   1. Non-finite input: any non-finite sum, or a maximum that is not > 0, gives valid = 0 and every other field 0.
+ *   2. Quantisation: q[k] = (uint32)floor(acc[k] / max(acc) * 2^19), one double division per bin (0 for a negative sum); prefix sums fit 32 bits.
+ *   3. Floor: the lower median of q (element 2047 of the sorted bins).
+ *   4. Window: w = max(3, (int)nearbyint(0.5 baud / bin) | 1) bins, the two-tone detector's; h = w / 2.
+ *   5. Coarse search: spacing d in quarter bins, d_lo = ceil(4 spacing_lo / bin) .. d_hi = floor(4 spacing_hi / bin); the lowest centre c0 in whole
+ *      bins; centre t is c0 + ((t d + 2) >> 2), and all four windows lie inside the band b_lo = 2048 + ceil(f_lo / bin) .. b_hi = 2048 + floor(f_hi /
+ *      bin) (clipped to 0 .. 4095): c0 - h >= b_lo, centre 3 + h <= b_hi.  A candidate's score is the weakest of its four window sums of q -- a lone
+ *      carrier, an RTTY pair or three tones of four score like noise.  The largest score wins, then the lowest d, then the lowest c0.
+ *   6. Refinement, per tone, four rounds from c = the coarse centre: over the bins m within +-w of c (inside 0 .. 4095) with weights
+ *      max(q[m] - floor, 0), sw = sum of the weights, sm = sum of (m - c) weight; centroid = 256 c + floor((512 sm + sw) / (2 sw)) in 1/256 bin (256 c
+ *      where sw = 0); the next round's c = (centroid + 128) >> 8.
+ *   7. Fit: the least-squares line through the four centroids c_t: S10 = -3 c_0 - c_1 + c_2 + 3 c_3, spacing_q8 = floor((S10 + 5) / 10),
+ *      f0_q8 = floor((5 (c_0 + c_1 + c_2 + c_3) - 3 S10 + 10) / 20).
+ *   8. Known spacing (spacing_lo == spacing_hi): d = nearbyint(4 spacing / bin) alone is searched, spacing_q8 = 64 d and only f0 is fitted,
+ *      f0_q8 = floor((c_0 + c_1 + c_2 + c_3 - 6 spacing_q8 + 2) / 4).
+ *   9. Quality: quality_q8 = floor(256 (score - w floor) / max(w floor, 1)), 0 where the score is below w floor.  valid = quality_q8 >= min_quality_q8
+ *      and the stream has at least min_segments effective segments.
+ *  In Hz: f0_hz = (f0_q8 / 256 - 2048) bin, spacing_hz = spacing_q8 / 256 bin, tone t = f0_hz + t spacing_hz.
+ *  A spacing below 2 baud is HD_ERR_UNSUPPORTED (the tones' lobes overlap and the spectrum is nearly flat over four baud); a band or a spacing range
+ *  that leaves no candidate is HD_ERR_INVALID.
+ *  Epochs: an epoch of a stream is epoch_segments consecutive segments by the stream's absolute segment index (segment j is samples 2048 j ..
+ *  2048 j + 4095), so epoch e ends with sample 2048 ((e + 1) epoch_segments + 1), its end sample.  A push is cut into rounds so that no spectrum launch
+ *  crosses a stream's epoch end; after a round k_fsk4_comb runs for the streams whose epoch ended in it and then multiplies their accumulators by
+ *  decay_q8 / 256 (one rounding per bin).  The effective segment count goes the same way on the host: + epoch_segments, the test, * decay_q8 / 256.
+ *  Records, estimates and accumulators do not depend on how the samples were cut into pushes.  A stream without hd_fsk4_track_set_stream takes no samples.
+ *  Closing the loop (hd_fsk4_track_attach): after every epoch with a valid record one of whose tones differs from the attached modem's by more than
+ *  deadband / 256 baud, the tracker calls hd_fsk4_retune with at_sample = the epoch's end sample.  Both objects count samples from the same reset; per
+ *  call, push the tracker first, then the fsk4 object: in that order no retune is late and the decode does not depend on the cut.  A stream without a
+ *  modem is left alone; acquisition from nominal tones is a retune like any other.
+ *  Not built: narrowing the search around a lock, spacings below 2 baud, 2FSK. */
+typedef struct hd_fsk4_track hd_fsk4_track;
+typedef struct hd_fsk4_track_params {
+    uint32_t max_push;         /* as the tone search's */
+    uint32_t epoch_segments;   /* default 4 */
+    uint32_t decay_q8;         /* 0 .. 256: what an epoch leaves of the sums for the next; default 128 */
+    uint32_t min_quality_q8;   /* default 192 (NOTES.md has the measurements on either side) */
+    uint32_t min_segments;     /* default 4 */
+    uint32_t deadband;         /* 1/256 baud; default 8 */
+} hd_fsk4_track_params;
+typedef struct hd_fsk4_comb_params {   /* what hd_host_fsk4_comb_detect takes: one stream's search, and the two validity tests */
+    double baud, spacing_lo_hz, spacing_hi_hz, f_lo_hz, f_hi_hz;
+    uint32_t min_quality_q8, segments_ok;
+} hd_fsk4_comb_params;
+typedef struct hd_fsk4_comb_record {
+    int32_t  f0_q8, spacing_q8;        /* 1/256 bin; f0 on the bin index */
+    uint32_t c0, d, w, floor, score, quality_q8, valid;
+    int32_t  centroid_q8[4];
+    uint32_t _pad[3];
+} hd_fsk4_comb_record;
+typedef struct hd_fsk4_track_est {
+    hd_fsk4_comb_record rec;
+    double   f0_hz, spacing_hz;
+    uint64_t end_sample, epoch;        /* the record's epoch: its end sample and its number from 0 */
+} hd_fsk4_track_est;
+typedef struct hd_fsk4_track_info {
+    uint64_t samples, segments, epochs, valid_epochs, retunes;
+} hd_fsk4_track_info;
+void hd_fsk4_track_params_default(hd_fsk4_track_params* p);
+int  hd_fsk4_track_create(hd_engine* e, const hd_fsk4_track_params* p /* null: the defaults */, hd_fsk4_track** out);
+void hd_fsk4_track_destroy(hd_fsk4_track* tr);
+int  hd_fsk4_track_reset(hd_fsk4_track* tr, uint32_t stream /* UINT32_MAX: all */);   /* sums, counts, carry and records; the stream's search stays */
+/* Gives the stream its search (and resets it).  HD_ERR_UNSUPPORTED: spacing_lo_hz < 2 baud; HD_ERR_INVALID: nothing to search. */
+int  hd_fsk4_track_set_stream(hd_fsk4_track* tr, uint32_t stream, double baud, double spacing_lo_hz, double spacing_hi_hz, double f_lo_hz, double f_hi_hz);
+int  hd_fsk4_track_attach(hd_fsk4_track* tr, hd_fsk4* f /* null: detach */);   /* an fsk4 object of the same engine; destroy the tracker first */
+/* The three doors of the tone search, with its rules. */
+int  hd_fsk4_track_push_engine(hd_fsk4_track* tr);
+int  hd_fsk4_track_push_device(hd_fsk4_track* tr, const float* d_iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_fsk4_track_push_host(hd_fsk4_track* tr, const float* iq, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* The newest record; HD_ERR_UNSUPPORTED while the stream has none. */
+int  hd_fsk4_track_estimate(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_est* out);
+int  hd_fsk4_track_stats(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_info* out);
 
 #ifdef __cplusplus
 }

@@ -319,6 +319,28 @@ size_t hd_host_fsk4_slots(const hd_host_fsk4*, uint64_t first, uint32_t* out, si
 int    hd_host_fsk4_candidates(hd_host_fsk4*, hd_fsk4_candidate* out, size_t cap);
 size_t hd_host_fsk4_encode(const hd_fsk4_frame* frame, const uint8_t* payload, uint8_t* out);
 uint32_t hd_host_fsk4_crc16(const uint8_t* bytes, size_t n);
+/* hd_fsk4_retune and hd_fsk4_retune_stats of the one stream, with their rules and errors. */
+int    hd_host_fsk4_retune(hd_host_fsk4*, double f0_hz, double spacing_hz, uint64_t at_sample);
+int    hd_host_fsk4_retune_stats(const hd_host_fsk4*, hd_fsk4_retune_info* out);
+
+/* ---- 4FSK tone tracker (hd_fsk4_track_*, include/habdec_amd.h has the definition) ----
+ * hd_host_fsk4_comb_detect: steps 1 .. 9 on 4096 fftshifted sums; the same integers as k_fsk4_comb, byte for byte.  HD_ERR_UNSUPPORTED: a spacing below
+ * 2 baud; HD_ERR_INVALID: nothing to search; the record is all zero then.  hd_host_fsk4_track_*: one stream of the tracker with the tone search's
+ * double-precision spectrum (hd_host_tone_search_*), so its sums agree with the device's to the float transform's error, not to the bit; epochs, decay,
+ * records and the retunes of an attached hd_host_fsk4 as the engine's object.  hd_host_fsk4_track_new: NULL unless decimated_rate > 0 and the parameters
+ * are ones hd_fsk4_track_create takes.  hd_host_fsk4_track_records: all records since the last reset, oldest first; out null: how many.
+ * hd_host_fsk4_track_acc: the 4096 sums. */
+int    hd_host_fsk4_comb_detect(const double* acc, double decimated_rate, const hd_fsk4_comb_params* p, hd_fsk4_comb_record* out);
+typedef struct hd_host_fsk4_track hd_host_fsk4_track;
+hd_host_fsk4_track* hd_host_fsk4_track_new(double decimated_rate, const hd_fsk4_track_params* params);
+void   hd_host_fsk4_track_free(hd_host_fsk4_track*);
+void   hd_host_fsk4_track_reset(hd_host_fsk4_track*);
+int    hd_host_fsk4_track_set_stream(hd_host_fsk4_track*, double baud, double spacing_lo_hz, double spacing_hi_hz, double f_lo_hz, double f_hi_hz);
+void   hd_host_fsk4_track_attach(hd_host_fsk4_track*, hd_host_fsk4* modem);
+void   hd_host_fsk4_track_push(hd_host_fsk4_track*, const float* iq, size_t n);
+int    hd_host_fsk4_track_records(hd_host_fsk4_track*, hd_fsk4_track_est* out, size_t cap);
+int    hd_host_fsk4_track_stats(const hd_host_fsk4_track*, hd_fsk4_track_info* out);
+int    hd_host_fsk4_track_acc(const hd_host_fsk4_track*, double* out);
 
 #ifdef __cplusplus
 }
