@@ -299,6 +299,7 @@ int hd_engine_create(const hd_engine_config* cfg, hd_engine** out)
         HD_HIP(e->lpf_x.alloc((size_t)S * N));
         HD_HIP(e->lpf_k.alloc((size_t)S * N));
         HD_HIP(e->lpf_ntaps.alloc(S));
+        HD_HIP(e->lpf_flags.alloc((size_t)S * 2));
     }
     // Pay first-use costs now: run every kernel once on an all-idle call.
     {
@@ -1166,7 +1167,7 @@ int enqueue_front(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, cons
 // Fast mode, a long low-pass (configs[4]: 4097 taps): filter through transforms -- [history | inputs | zeros] of N per stream, X conj(K), back -- so that
 // k_fir_demod is handed the filtered samples (it still does the discriminator, the ring append, the carries, the slide).  Returns the transform length in
 // *lpN, 0 where the direct sums run.
-int lowpass_transforms(hd_engine* e, const CallPlan& p, const CallRoute& r, const CallBufs& b, uint32_t* lpN)
+int lowpass_transforms(hd_engine* e, const CallPlan& p, const CallRoute& r, const CallBufs& b, const uint32_t tag, uint32_t* lpN)
 {
     *lpN = 0;
     // (Not the run that starts a stream's filter from zeros: a transform's rounding is ~1e-6 of the input's PEAK everywhere, and the start-up transient -- outputs
@@ -1185,7 +1186,7 @@ int lowpass_transforms(hd_engine* e, const CallPlan& p, const CallRoute& r, cons
         if (rocfft_execute(e->lpf_fwd[w], kb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass taps) failed");
         e->lpf_k_N = N; e->lpf_k_stale = false;
     }
-    HDK(launch_lp_gather, qb, S, b.fcur, e->fbuf_stride, e->lpf_x.p, N, r.dcall, e->fir_hist_cap, e->fir_head.p, e->head_cap, b.fprev);
+    HDK(launch_lp_gather, qb, S, b.fcur, e->fbuf_stride, e->lpf_x.p, N, r.dcall, e->fir_hist_cap, e->fir_head.p, e->head_cap, b.fprev, e->lpf_flags.p, tag);
     void* xb[1] = {e->lpf_x.p};
     if (rocfft_execute(e->lpf_fwd[w], xb, nullptr, e->lpf_info) != rocfft_status_success) return fail(HD_ERR_DEVICE, "rocfft_execute (low-pass forward) failed");
     HDK(launch_lp_mul, qb, S, e->lpf_x.p, e->lpf_k.p, N, r.dcall);
@@ -1211,11 +1212,11 @@ int enqueue_back(hd_engine* e, hd_engine::CallSlot& sl, const CallPlan& p, CallR
         if (!HDK(launch_tail, qb, r.tail_lanes, (int)p.R2, (int)p.T2, S, r.ta, ev_ride ? sl.ev_done : nullptr)) return fail(HD_ERR_INVALID, "stream tail refused a shape it was selected for");
     } else {
         uint32_t lpN = 0;
-        if (const int rc = lowpass_transforms(e, p, r, b, &lpN)) return rc;
+        if (const int rc = lowpass_transforms(e, p, r, b, sl.seq, &lpN)) return rc;
         if (!HDK(launch_fir_demod, qb, S, p.max_m, lpN ? 0u : p.max_taps, e->lds_per_wg, b.fcur, e->fbuf_stride, e->lp_taps.p, e->taps_cap, e->demod.p, e->demod.n / S,
                              e->cfg.keep_filtered ? e->filtered.p : nullptr, e->carry[b.cin].p, e->carry[b.cout].p, r.dcall, e->fir_hist_cap,
                              e->tail.p, e->tail_cap, e->d_symstate.p, b.fnext, e->fir_head.p, e->head_cap, b.fprev, e->demod_ck_acc.p,
-                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f))
+                             lpN ? e->lpf_x.p : nullptr, lpN, lpN ? 1.0f / (float)lpN : 1.0f, lpN ? e->lpf_flags.p : nullptr, sl.seq))
             return fail(HD_ERR_DEVICE, "low-pass kernel could not be launched with " + std::to_string(p.max_taps) + " taps");    // (plan_call admits no such call)
         HDK(launch_symbols, qb, S, p.max_m, p.max_new, e->max_R, e->tail.p, e->tail_cap, e->d_symstate.p, e->flipmask.p, e->weight.p, e->d_sym.p,
                            r.dcall, sl.h_slots.dev, e->slot_words, e->flips_cap ? e->flips_dbg.p : nullptr, e->flips_cap, e->min_R, sl.seq, ev_ride ? sl.ev_done : nullptr,

@@ -262,6 +262,7 @@ struct hd_engine {
     rocfft_execution_info lpf_info = nullptr;
     DevBuf<char> lpf_workbuf;
     DevBuf<float2> lpf_x, lpf_k;           // [S][lpf_N[1]]: the input images / filtered samples of the call in the back half; the taps' spectra
+    DevBuf<uint32_t> lpf_flags;            // [S][2]: the tag (CallSlot::seq, never 0) of the last call whose block held a sample exactly zero / any other sample (fir_demod.hip k_lp_gather)
     PinBuf<uint32_t> lpf_ntaps;            // [S]: tap counts the spectra in lpf_k were made from
     uint32_t lpf_k_N = 0;                  // ... and the transform length (0: none yet)
     bool lpf_k_stale = true;

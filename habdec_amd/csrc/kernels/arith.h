@@ -34,8 +34,8 @@ constexpr bool kFastArith = true;
 #else
 constexpr bool kFastArith = false;
 #endif
-// Fast mode also takes the symbol extractor's window sums (SymbolExtractor.h:162-224: std::accumulate over R samples per candidate position) by sliding from an
-// exactly summed anchor (sym_common.h: window_sums_slide); -DHD_FAST_EXACT_WINDOWS keeps them in the exact mode's order (A/B builds).
+// Fast mode also takes the symbol extractor's window sums (SymbolExtractor.h:162-224: std::accumulate over R samples per candidate position) from one sum
+// of the samples a lane's windows share (sym_common.h: window_sums_shared; nothing is subtracted: a window of zeros sums to +0); -DHD_FAST_EXACT_WINDOWS keeps them in the exact mode's order (A/B builds).
 #ifdef HD_FAST_EXACT_WINDOWS
 constexpr bool kFastWindows = false;
 #else

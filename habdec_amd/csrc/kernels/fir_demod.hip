@@ -61,6 +61,35 @@ __device__ __forceinline__ void fir_block16(fd_f32x2 (&acc)[kFirOut], const fd_f
     }
 }
 
+// Sample j of a stream's block [history (T-1) | inputs (m)], the history exactly as k_fir_demod's tile loader builds it (the transform route, below).
+struct LpBlock {
+    const float2* buf;
+    const float2* head_in;
+    uint32_t fir_hist_cap, H, L, Tp, head_n;
+    bool zero_hist, refold;
+    __device__ __forceinline__ LpBlock(const StreamCall& c, const uint32_t s, const float2* fbuf, const size_t stride, const uint32_t fir_hist_cap_,
+                                       const float2* head_side, const uint32_t head_cap, const float2* fbuf_prev)
+    {
+        const uint32_t T = c.fir_taps;
+        Tp = sc_taps_prev(c) ? sc_taps_prev(c) : T; H = T - 1; L = H + c.fir_m;
+        fir_hist_cap = fir_hist_cap_;
+        buf = fbuf + (size_t)s * stride;
+        zero_hist = c.fir_zero_hist != 0;
+        refold = Tp != T && !zero_hist;
+        head_n = refold ? sc_head_n(c) : 0u;
+        head_in = sc_head_prev(c) ? fbuf_prev + (size_t)s * stride + fir_hist_cap : head_side + (size_t)s * head_cap;
+    }
+    __device__ __forceinline__ float2 at(const uint32_t j) const       // j < L
+    {
+        if (j >= H) return buf[fir_hist_cap + (j - H)];                   // the run's inputs: pending + new decimated samples
+        if (zero_hist) return make_float2(0.f, 0.f);                      // history restarts from zeros
+        if (!refold) return buf[fir_hist_cap - H + j];
+        if (j < Tp - 1) return buf[fir_hist_cap - (Tp - 1) + j];          // first run after a tap-count change (FirHistory, dev_types.h)
+        if (j - (Tp - 1) < head_n) return head_in[j - (Tp - 1)];
+        return make_float2(0.f, 0.f);
+    }
+};
+
 __global__ __launch_bounds__(kFirLanes) void k_fir_demod(const float2* __restrict__ fbuf, size_t stride,
                                                           const float* __restrict__ taps, uint32_t taps_stride,
                                                           float* __restrict__ demod, size_t demod_stride,
@@ -74,7 +103,8 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_demod(const float2* __restric
                                                           const float2* __restrict__ fbuf_prev /* the previous call's low-pass buffers */,
                                                           uint32_t* __restrict__ ck_acc /* [S][2]: the call's discriminator checksum, accumulated by the stream's tiles (or null) */,
                                                           const float2* __restrict__ pre /* fast mode, long filters: the low-pass output already computed by FFT (k_lp_gather ... below), [S][pre_stride], to be scaled by pre_scale; null = filter here */,
-                                                          const uint32_t pre_stride, const float pre_scale)
+                                                          const uint32_t pre_stride, const float pre_scale,
+                                                          const uint32_t* __restrict__ pre_flags /* with `pre`: k_lp_gather's flags, [S][2] */, const uint32_t pre_tag)
 {
     extern __shared__ __attribute__((aligned(16))) float2 lds[];   // [kFirTile + T + kFirSlack] inputs, then reused for outputs
     __shared__ uint32_t s_ck[2];
@@ -122,13 +152,37 @@ __global__ __launch_bounds__(kFirLanes) void k_fir_demod(const float2* __restric
     for (int q = 0; q < kFirOut; ++q) acc[q] = fd_f32x2{0.f, 0.f};
     if (pre) {
         // the filtered samples exist already (the transform route): this kernel is the discriminator, the symbol ring's append, the carries and the slide
-        if (active) {
+        // ... unless the stream's block held a run of samples that are exactly zero (k_lp_gather's flags carry this call's tag): its signal stops or starts in
+        // this block, and where the direct sum is exactly 0 the transforms return their rounding floor.  Such a stream gets direct fused sums here, from global
+        // memory (zeros where the whole block is zeros): a lane's kFirOut outputs on a rolling window of kFirOut samples, one load and kFirOut fused
+        // multiply-adds per tap.  Rare -- a call or two per silence -- and not worth an LDS image.
+        const bool direct = pre_flags && pre_flags[2 * s] == pre_tag, mixed = pre_flags && pre_flags[2 * s + 1] == pre_tag;     // (wave-uniform)
+        if (active && !direct) {
             const float2* ps = pre + (size_t)s * pre_stride;
 #pragma unroll
             for (int q = 0; q < kFirOut; ++q) {
                 const long i = i0 + (long)kFirOut * (long)threadIdx.x + q;
                 if (i >= 0 && i < (long)m) { const float2 v = ps[i]; acc[q] = fd_f32x2{v.x * pre_scale, v.y * pre_scale}; }
             }
+        } else if (active && mixed) {
+            const LpBlock blk(c, s, fbuf, stride, fir_hist_cap, head_side, head_cap, fbuf_prev);
+            const float* tp = taps + (size_t)s * taps_stride;
+            const long ib = i0 + (long)kFirOut * (long)threadIdx.x;  // the lane's first output (lane 0 of the first tile: -kFirOut, no output exists)
+            auto smp = [&](const long j) { return j >= 0 && j < (long)blk.L ? blk.at((uint32_t)j) : make_float2(0.f, 0.f); };
+            float2 win[kFirOut];                                     // block samples ib + t .. ib + t + kFirOut - 1: output q takes win[q] with tap t
+#pragma unroll
+            for (int q = 0; q < kFirOut; ++q) win[q] = smp(ib + q);
+            for (uint32_t t = 0; t < T; ++t) {
+                const float k = tp[t];
+                const float2 nx = smp(ib + (long)t + kFirOut);
+#pragma unroll
+                for (int q = 0; q < kFirOut; ++q) acc[q] = fd_f32x2{__builtin_fmaf(win[q].x, k, acc[q].x), __builtin_fmaf(win[q].y, k, acc[q].y)};
+#pragma unroll
+                for (int q = 0; q + 1 < kFirOut; ++q) win[q] = win[q + 1];
+                win[kFirOut - 1] = nx;
+            }
+#pragma unroll
+            for (int q = 0; q < kFirOut; ++q) if (ib + q < 0 || ib + q >= (long)m) acc[q] = fd_f32x2{0.f, 0.f};      // (as on the other routes)
         }
     } else {
     const uint32_t need = ((live + (uint32_t)kFirOut - 1u) / (uint32_t)kFirOut) * (uint32_t)kFirOut + T + kFirSlack;   // + what whole blocks read past the last tap (zero-filled)
@@ -296,7 +350,7 @@ bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32
                       const DemodCarry* carry_in, DemodCarry* carry_out, const StreamCall* call, uint32_t fir_hist_cap,
                       float* sym_ring, uint32_t ring_cap, const SymState* sym, float2* fbuf_next,
                       float2* head_side, uint32_t head_cap, const float2* fbuf_prev, uint32_t* ck_acc,
-                      const float2* pre, uint32_t pre_stride, float pre_scale)
+                      const float2* pre, uint32_t pre_stride, float pre_scale, const uint32_t* pre_flags, uint32_t pre_tag)
 {
     const uint32_t tiles = max_m ? (max_m + kFirAdvance - 1) / kFirAdvance : 1;
     const size_t lds = fir_demod_lds_bytes(max_taps);
@@ -313,7 +367,7 @@ bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32
     }
     dim3 grid(tiles, n_streams);
     hipLaunchKernelGGL(k_fir_demod, grid, dim3(kFirLanes), lds, st, fbuf, stride, taps, taps_stride, demod, demod_stride, filtered,
-                       carry_in, carry_out, call, fir_hist_cap, sym_ring, ring_cap, sym, fbuf_next, head_side, head_cap, fbuf_prev, ck_acc, pre, pre_stride, pre_scale);
+                       carry_in, carry_out, call, fir_hist_cap, sym_ring, ring_cap, sym, fbuf_next, head_side, head_cap, fbuf_prev, ck_acc, pre, pre_stride, pre_scale, pre_flags, pre_tag);
     return true;
 }
 
@@ -323,29 +377,43 @@ bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32
 // with the history exactly as k_fir_demod's tile loader builds it: zeros on a restart (Q5), the FirHistory reconstruction after a tap-count change -- and
 // multiply the spectra; k_fir_demod then runs with `pre` set.  The result differs from the direct sum by the transforms' rounding (~1e-6 of the input's peak,
 // tests/test_gpu_fast.py); the exact mode never takes this route.
+//
+// Where the signal STOPS or STARTS inside a block -- samples that are exactly zero, a muted receiver or a zero-padded file -- that floor will not do: the direct sum
+// of a window of zeros is exactly 0, the reference's discriminator gives 0 there, and the same discriminator turns a floor of 1e-6 into arbitrary phases (it
+// is why the run that starts a filter from zeros never takes this route, engine.cpp lowpass_transforms).  k_lp_gather therefore notes per stream whether
+// the block it builds holds a RUN of zeros -- 64 consecutive samples with both parts exactly zero, one wave's share of the block -- and whether it holds any
+// other sample: flags[2 s] and flags[2 s + 1] take the call's tag.  (A run, not a sample: an output is exactly 0 only under T >= 1024 zeros, and any run
+// of 127 covers some wave's 64; a lone (0, 0) inside live signal -- every few thousand samples of 8-bit IQ -- changes no output by more than any other
+// sample does and stays on the transforms.)
+// k_fir_demod, which takes the transforms' rows as its filtered samples, does not take them for a stream that has the first flag: zeros where the whole block
+// is zeros, the direct fused sums where it is mixed.  Streams without a zero sample keep the transforms' rows; a stream pays the direct sums in the call or
+// two in which its signal stops or starts.  (No launch of its own: a fix-up kernel behind the inverse transform cost 5 us of a 0.93 ms step at
+// configs[4], NOTES.md.)  (tests/test_gpu_fast_silence.py)
+
 __global__ __launch_bounds__(256) void k_lp_gather(const float2* __restrict__ fbuf, size_t stride, float2* __restrict__ work, uint32_t N, const StreamCall* __restrict__ call,
-                                                    uint32_t fir_hist_cap, const float2* __restrict__ head_side, uint32_t head_cap, const float2* __restrict__ fbuf_prev)
+                                                    uint32_t fir_hist_cap, const float2* __restrict__ head_side, uint32_t head_cap, const float2* __restrict__ fbuf_prev,
+                                                    uint32_t* __restrict__ flags /* [S][2]: the tag of the last call whose block held a zero sample / a non-zero one */, const uint32_t tag)
 {
     const uint32_t s = blockIdx.y;
     const StreamCall c = call[s];
-    const uint32_t m = c.fir_m, T = c.fir_taps;
-    if (!m || !T) return;
-    const uint32_t Tp = sc_taps_prev(c) ? sc_taps_prev(c) : T, H = T - 1, L = H + m;
-    const float2* buf = fbuf + (size_t)s * stride;
-    const bool refold = Tp != T && !c.fir_zero_hist;
-    const uint32_t head_n = refold ? sc_head_n(c) : 0u;
-    const float2* head_in = sc_head_prev(c) ? fbuf_prev + (size_t)s * stride + fir_hist_cap : head_side + (size_t)s * head_cap;
+    if (!c.fir_m || !c.fir_taps) return;
+    const LpBlock blk(c, s, fbuf, stride, fir_hist_cap, head_side, head_cap, fbuf_prev);
     float2* w = work + (size_t)s * N;
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < N; j += gridDim.x * 256u) {
+    bool run = false, other = false;
+    for (uint32_t j0 = blockIdx.x * 256u; j0 < N; j0 += gridDim.x * 256u) {      // (block-uniform trip count: the ballots below see whole waves)
+        const uint32_t j = j0 + threadIdx.x;
         float2 v = make_float2(0.f, 0.f);
-        if (j < L) {
-            if (j >= H) v = buf[fir_hist_cap + (j - H)];                     // the run's inputs: pending + new decimated samples
-            else if (c.fir_zero_hist) v = make_float2(0.f, 0.f);              // history restarts from zeros
-            else if (!refold) v = buf[fir_hist_cap - H + j];
-            else if (j < Tp - 1) v = buf[fir_hist_cap - (Tp - 1) + j];        // first run after a tap-count change (FirHistory, dev_types.h)
-            else if (j - (Tp - 1) < head_n) v = head_in[j - (Tp - 1)];
-        }
-        w[j] = v;
+        const bool in = j < blk.L;
+        if (in) v = blk.at(j);
+        if (j < N) w[j] = v;
+        const bool z = in && v.x == 0.f && v.y == 0.f;
+        if (__builtin_amdgcn_ballot_w64(z) == ~0ull) run = true;         // this wave's 64 consecutive samples are all inside the block and all zero
+        if (in && !z) other = true;
+    }
+    const bool wo = __builtin_amdgcn_ballot_w64(other) != 0ull;
+    if ((threadIdx.x & 63u) == 0u) {                                      // (every writer of a call stores the same word)
+        if (run) flags[2 * s] = tag;
+        if (wo) flags[2 * s + 1] = tag;
     }
 }
 // the taps as a complex sequence of N (zero-padded): transformed once per design into `kf`
@@ -366,9 +434,9 @@ __global__ __launch_bounds__(256) void k_lp_mul(float2* __restrict__ work, const
     }
 }
 void launch_lp_gather(hipStream_t st, uint32_t n_streams, const float2* fbuf, size_t stride, float2* work, uint32_t N, const StreamCall* call, uint32_t fir_hist_cap,
-                      const float2* head_side, uint32_t head_cap, const float2* fbuf_prev)
+                      const float2* head_side, uint32_t head_cap, const float2* fbuf_prev, uint32_t* flags, uint32_t tag)
 {
-    hipLaunchKernelGGL(k_lp_gather, dim3((N + 1023) / 1024, n_streams), dim3(256), 0, st, fbuf, stride, work, N, call, fir_hist_cap, head_side, head_cap, fbuf_prev);
+    hipLaunchKernelGGL(k_lp_gather, dim3((N + 1023) / 1024, n_streams), dim3(256), 0, st, fbuf, stride, work, N, call, fir_hist_cap, head_side, head_cap, fbuf_prev, flags, tag);
 }
 void launch_lp_taps_gather(hipStream_t st, uint32_t n_streams, const float* taps, uint32_t taps_stride, const uint32_t* ntaps, float2* kf, uint32_t N)
 {

@@ -38,11 +38,13 @@ bool launch_fir_demod(hipStream_t st, uint32_t n_streams, uint32_t max_m, uint32
                       float2* head_side /* [S][head_cap] */, uint32_t head_cap, const float2* fbuf_prev /* the previous call's low-pass buffers: FirHistory, dev_types.h */,
                       uint32_t* ck_acc = nullptr /* [S][2], zero before the launch: the call's discriminator checksum accumulates here (BitsHeader::demod_ck; launch_symbols collects it) */,
                       const float2* pre = nullptr /* the low-pass output computed through transforms (below), [S][pre_stride] x pre_scale: the kernel then does everything but the filter */,
-                      uint32_t pre_stride = 0, float pre_scale = 1.0f);
+                      uint32_t pre_stride = 0, float pre_scale = 1.0f,
+                      const uint32_t* pre_flags = nullptr /* with `pre`: the flags launch_lp_gather left -- a stream whose block held a zero sample in the call `pre_tag` is summed directly */,
+                      uint32_t pre_tag = 0);
 // The transform route of a long low-pass (fast mode): input image [history | inputs | zeros] of N per stream, the taps' image, the product of the spectra
 // X conj(K); rocFFT runs between them (engine.cpp)
 void launch_lp_gather(hipStream_t st, uint32_t n_streams, const float2* fbuf, size_t stride, float2* work, uint32_t N, const StreamCall* call, uint32_t fir_hist_cap,
-                      const float2* head_side, uint32_t head_cap, const float2* fbuf_prev);
+                      const float2* head_side, uint32_t head_cap, const float2* fbuf_prev, uint32_t* flags /* [S][2] */, uint32_t tag);
 void launch_lp_taps_gather(hipStream_t st, uint32_t n_streams, const float* taps, uint32_t taps_stride, const uint32_t* ntaps, float2* kf, uint32_t N);
 void launch_lp_mul(hipStream_t st, uint32_t n_streams, float2* work, const float2* kf, uint32_t N, const StreamCall* call);
 // Fills the LDS carve for `lanes` (64 or 256) lanes per stream; returns false when (ratio2, ntaps2) has no tail instantiation or the

@@ -187,49 +187,71 @@ __device__ __forceinline__ unsigned int sign_flags(const float (&wl)[KP], const 
     return nvalid >= (uint32_t)KP ? bits : bits & ((1u << nvalid) - 1u);
 }
 
-// FAST arithmetic mode (arith.h) only.  The same KP window sums, cheaper: acc[0] = w[0] + ... + w[R-1] as four interleaved partial sums (two packed chains
-// over the 16-byte reads, joined at the end), then each neighbour from its predecessor: acc[j] = acc[j-1] + (w[j-1+R] - w[j-1]) -- R / 2 + 2 (KP - 1) adds
-// per lane where the exact-order form needs (R + KP - 1) KP / 2 packed ones (R = 427 at /4 and 300 baud: a seventh).  Not std::accumulate's order, so not its
-// rounding: a sum of R terms carries R roundings either way, the slide adds two per step over at most KP - 1 steps from an exactly summed anchor, and the
-// difference stays at the level of the sums' own rounding noise (<= 1e-6 of the largest window sum; tests/test_gpu_fast.py compares every decision the
-// sums feed -- flags, flip points, bits, characters -- with the reference's on every stream).  `w` is 16-byte aligned and readable up to w[R + KP + 7].
+// FAST arithmetic mode (arith.h) only.  The same KP window sums, cheaper: the samples every one of the lane's windows contains, core = w[KP] + ... + w[R-1],
+// are summed ONCE, as four interleaved partial sums (two packed chains over the 16-byte reads, joined at the end); window j then adds what it has of the
+// head and of the tail: acc[j] = (core + (w[j] + ... + w[KP-1])) + (w[R] + ... + w[R+j-1]), the two brackets as running sums -- (R - KP) / 2 + 4 (KP - 1)
+// adds per lane where the exact-order form needs (R + KP - 1) KP / 2 packed ones (R = 427 at /4 and 300 baud: a seventh).  Not std::accumulate's order, so
+// not its rounding: a sum of R terms carries R roundings either way and the difference stays at the level of the sums' own rounding noise (<= 1e-6 of the
+// largest window sum; tests/test_gpu_fast.py compares every decision the sums feed -- flags, flip points, bits, characters -- with the reference's on every
+// stream).  NOTHING IS EVER SUBTRACTED: a window whose samples are all zero sums to +0 exactly, as std::accumulate's does -- sgnf has three values, and a
+// form that slides (acc[j] = acc[j-1] + (w[j-1+R] - w[j-1])) leaves the rounding residue of what it took away where a signal stops, another sign than
+// the reference's 0 (tests/test_gpu_fast_silence.py).  `w` is 16-byte aligned and readable up to w[R + KP + 7].
 template <int KP>
-__device__ __forceinline__ void window_sums_slide(const float* __restrict__ w, uint32_t R, float (&acc)[KP])
+__device__ __forceinline__ void window_sums_shared(const float* __restrict__ w, uint32_t R, float (&acc)[KP])
 {
     static_assert(KP % 4 == 0 && KP >= 4, "whole 16-byte chunks per lane");
+    if (R < (uint32_t)KP) {                                 // tiny windows share no core: every sum on its own, in index order
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            float s = 0.0f;
+            for (uint32_t e = 0; e < R; ++e) s = s + w[j + e];
+            acc[j] = s;
+        }
+        return;
+    }
     const float4* w4 = reinterpret_cast<const float4*>(w);
-    float head[KP];                                         // w[0 .. KP): what the slide subtracts
+    float head[KP];                                         // w[0 .. KP): window j takes head[j ..]
 #pragma unroll
     for (int c = 0; c < KP / 4; ++c) { const float4 x = w4[c]; head[4 * c] = x.x; head[4 * c + 1] = x.y; head[4 * c + 2] = x.z; head[4 * c + 3] = x.w; }
+    const float4* c4 = w4 + KP / 4;                         // the core: n = R - KP samples from w[KP] on
+    const uint32_t n = R - (uint32_t)KP;
     f32x2 a = {0.0f, 0.0f}, b = {0.0f, 0.0f};
     uint32_t e = 0;
-    if (R >= 16u) {
-        float4 xa = w4[0], xb = w4[1], ya, yb;              // two images of eight elements taking turns, one ahead
-        for (; e + 24 <= R; e += 16) {
-            ya = w4[(e >> 2) + 2]; yb = w4[(e >> 2) + 3];
+    if (n >= 16u) {
+        float4 xa = c4[0], xb = c4[1], ya, yb;              // two images of eight elements taking turns, one ahead
+        for (; e + 24 <= n; e += 16) {
+            ya = c4[(e >> 2) + 2]; yb = c4[(e >> 2) + 3];
             __builtin_amdgcn_sched_barrier(0);
             a = a + (f32x2){xa.x, xa.y}; b = b + (f32x2){xa.z, xa.w}; a = a + (f32x2){xb.x, xb.y}; b = b + (f32x2){xb.z, xb.w};
-            xa = w4[(e >> 2) + 4]; xb = w4[(e >> 2) + 5];
+            xa = c4[(e >> 2) + 4]; xb = c4[(e >> 2) + 5];
             __builtin_amdgcn_sched_barrier(0);
             a = a + (f32x2){ya.x, ya.y}; b = b + (f32x2){ya.z, ya.w}; a = a + (f32x2){yb.x, yb.y}; b = b + (f32x2){yb.z, yb.w};
         }
-        // xa, xb hold elements [e, e + 8), all inside the window (e + 8 <= R here: the loop leaves 8 <= R - e < 24)
+        // xa, xb hold elements [e, e + 8), all inside the core (e + 8 <= n here: the loop leaves 8 <= n - e < 24)
         a = a + (f32x2){xa.x, xa.y}; b = b + (f32x2){xa.z, xa.w}; a = a + (f32x2){xb.x, xb.y}; b = b + (f32x2){xb.z, xb.w};
         e += 8;
-        if (e + 8 <= R) {
-            const float4 za = w4[e >> 2], zb = w4[(e >> 2) + 1];
+        if (e + 8 <= n) {
+            const float4 za = c4[e >> 2], zb = c4[(e >> 2) + 1];
             a = a + (f32x2){za.x, za.y}; b = b + (f32x2){za.z, za.w}; a = a + (f32x2){zb.x, zb.y}; b = b + (f32x2){zb.z, zb.w};
             e += 8;
         }
     }
-    float sum = (a.x + a.y) + (b.x + b.y);
-    for (; e < R; ++e) sum = sum + w[e];                    // the R % 8 elements left (the whole window when R < 16)
-    acc[0] = sum;
+    float core = (a.x + a.y) + (b.x + b.y);
+    for (; e < n; ++e) core = core + w[KP + e];             // the n % 8 elements left (the whole core when n < 16)
     float tail[KP - 1];
 #pragma unroll
     for (int d = 0; d < KP - 1; ++d) tail[d] = w[R + d];
+    float hs[KP];                                           // hs[j] = w[j] + ... + w[KP-1]
+    hs[KP - 1] = head[KP - 1];
 #pragma unroll
-    for (int j = 1; j < KP; ++j) { sum = sum + (tail[j - 1] - head[j - 1]); acc[j] = sum; }
+    for (int j = KP - 2; j >= 0; --j) hs[j] = head[j] + hs[j + 1];
+    acc[0] = core + hs[0];
+    float ts = tail[0];                                     // w[R] + ... + w[R+j-1]
+#pragma unroll
+    for (int j = 1; j < KP; ++j) {
+        acc[j] = (core + hs[j]) + ts;
+        if (j < KP - 1) ts = ts + tail[j];
+    }
 }
 
 constexpr int kWidePos = 8;

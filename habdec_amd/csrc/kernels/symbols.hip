@@ -181,8 +181,8 @@ __global__ __launch_bounds__(kSymLanes) void k_symbols(const float* __restrict__
         const bool any = (int32_t)(pend - p0) > 0;
         float wp[kAvgPos];
         if (any) {
-            // (fast mode: an exactly summed anchor per lane and its neighbours by sliding -- a seventh of the adds at R = 427; sym_common.h)
-            if constexpr (kFastArith && kFastWindows) window_sums_slide<kAvgPos>(win + tid * kAvgPos, R, wp);
+            // (fast mode: the samples a lane's windows share summed once, head and tail added per window -- a seventh of the adds at R = 427; sym_common.h)
+            if constexpr (kFastArith && kFastWindows) window_sums_shared<kAvgPos>(win + tid * kAvgPos, R, wp);
             else if constexpr (kAvgPos >= 8) window_sums_wide<kAvgPos>(win + tid * kAvgPos, R, wp); else window_sums(win + tid * kAvgPos, R, wp);
 #pragma unroll
             for (int j = 0; j < kAvgPos; ++j) {

@@ -336,7 +336,7 @@ __device__ __forceinline__ void tail_body(const TailArgs& a, const uint32_t s, u
             const bool any = KP * tid < cnt;
             float wp[KP];
             if (any) {
-                if constexpr (kFastArith && kFastWindows) window_sums_slide<(int)KP>(V + off + KP * tid, R, wp); else window_sums8(V + off + KP * tid, R, wp);
+                if constexpr (kFastArith && kFastWindows) window_sums_shared<(int)KP>(V + off + KP * tid, R, wp); else window_sums8(V + off + KP * tid, R, wp);
                 TSTAMP(19);
 #pragma unroll
                 for (int j = 0; j < (int)KP; ++j) WS[off + R + KP * tid + j] = wp[j];

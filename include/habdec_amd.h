@@ -76,8 +76,14 @@ typedef struct hd_engine_config {
      * 0 = HD_ARITH_EXACT (default): separately rounded multiply and add in ascending tap order, one accumulator per output -- every decimated, filtered
      *     and demodulated float is bit-identical to the reference's CPU arithmetic.
      * 1 = HD_ARITH_FAST: fused multiply-add (half the vector instructions of every FIR in the chain).  Intermediate floats agree with the exact mode to
-     *     <= 1e-5 of the signal's peak (measured <= 3e-7); the discriminator and the symbol extractor are the exact mode's code, and on every stream of
-     *     the parity suite the decoded characters and sentences are identical to the reference's.  Not bit-identical floats: choose it for throughput. */
+     *     <= 1e-5 of the signal's peak, norm-wise per call.  Measured, per route: the decimator stages <= 3e-7; a low-pass as direct sums <= 7.6e-7
+     *     (4097 taps); a low-pass of 1024 taps and more through transforms (the default from there on; HD_NO_LP_FFT=1 keeps the direct sums)
+     *     6.6e-6 at 4097 taps, 8.4e-6 at 18899.  The discriminator and the symbol extractor are the exact mode's code, and on every stream of
+     *     the parity suite the decoded characters and sentences are identical to the reference's -- streams that go to EXACT zeros and come back
+     *     included, on every route (tests/test_gpu_fast_silence.py): a window of zeros sums to +0 as the reference's does, and a stream whose
+     *     low-pass block holds a run of 64 samples that are exactly zero is filtered by direct sums in that call, not through the transforms, so where the
+     *     reference filters exact zeros this mode does too and its discriminator output has the reference's bits there.
+     *     Not bit-identical floats elsewhere: choose it for throughput. */
     int32_t  arith;
 } hd_engine_config;
 #define HD_ARITH_EXACT 0
