@@ -17,7 +17,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 OUT = HERE / "libhabdec_amd.so"
 FAULT_OUT = HERE / "libhabdec_amd_fault.so"
-SOURCES = ["engine.cpp", "wideband.cpp", "demod_rows.cpp", "host_api.cpp", "kernels/decimate.hip", "kernels/fir_demod.hip", "kernels/baud_probe.hip", "kernels/clocked.hip", "kernels/combine.hip", "kernels/fsk4.hip", "kernels/fsk4_track.hip", "kernels/iq_unpack.hip", "kernels/spectrum_wave.hip", "kernels/ssdv.hip", "kernels/survey.hip", "kernels/symbols.hip", "kernels/tail.hip", "kernels/tone_search.hip", "kernels/tones.hip", "kernels/waterfall.hip"]
+SOURCES = ["engine.cpp", "wideband.cpp", "demod_rows.cpp", "host_api.cpp", "kernels/afsk.hip", "kernels/decimate.hip", "kernels/fir_demod.hip", "kernels/baud_probe.hip", "kernels/clocked.hip", "kernels/combine.hip", "kernels/fsk4.hip", "kernels/fsk4_track.hip", "kernels/iq_unpack.hip", "kernels/spectrum_wave.hip", "kernels/ssdv.hip", "kernels/survey.hip", "kernels/symbols.hip", "kernels/tail.hip", "kernels/tone_search.hip", "kernels/tones.hip", "kernels/waterfall.hip"]
 # the translation units that carry a FIR of the chain are compiled once per arithmetic mode (kernels/arith.h): as they are -> namespace hd::exact
 # (separately rounded multiply and add), with -DHD_FAST_ARITH -> namespace hd::fast (fused multiply-add); hd_engine_config.arith picks at run time
 MODE_SOURCES = ["kernels/decimate.hip", "kernels/fir_demod.hip", "kernels/tail.hip", "kernels/symbols.hip"]

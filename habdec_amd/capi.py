@@ -226,6 +226,25 @@ FSK4_TRACK_EST_DTYPE = np.dtype([("rec", FSK4_COMB_RECORD_DTYPE), ("f0_hz", "<f8
 assert FSK4_COMB_RECORD_DTYPE.itemsize == 64 and FSK4_TRACK_EST_DTYPE.itemsize == 96
 
 
+class hd_afsk_params(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("max_push", "max_frame_bytes", "repair_bits", "repair_flips", "require_addr", "_pad")]
+
+
+class hd_afsk_counters(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("samples", "slots", "flags", "unshaped", "fcs_failures", "frames_plain", "frames_repaired", "refused", "overlaps")] + \
+        [("F", C.c_uint32), ("W", C.c_uint32), ("step", C.c_uint32 * 2)]
+
+
+# one hd_afsk_rx, one hd_afsk_candidate
+AFSK_MAX_SPB, AFSK_CHUNK, AFSK_LAUNCH, AFSK_RING, AFSK_MAX_FRAME, AFSK_MIN_FRAME = 2048, 4096, 4096, 65536, 332, 17
+AFSK_OPEN, AFSK_ABORT, AFSK_UNSHAPED, AFSK_FCS_FAILED, AFSK_REFUSED, AFSK_PLAIN, AFSK_REPAIRED = range(7)
+AFSK_RX_DTYPE = np.dtype([("slot", "<u8"), ("start_sample", "<u8"), ("close_slot", "<u8"), ("metric", "<u8"), ("len", "<u4"), ("flips", "<u4"), ("phase", "<u4"),
+                          ("addr_ok", "<u4"), ("fcs", "<u4"), ("_pad", "<u4"), ("data", "u1", (AFSK_MAX_FRAME,)), ("_pad2", "<u4")])
+AFSK_CANDIDATE_DTYPE = np.dtype([("slot", "<u8"), ("close_slot", "<u8"), ("metric", "<u8"), ("result", "<u4"), ("bits", "<u4"), ("len", "<u4"), ("flips", "<u4"),
+                                 ("addr_ok", "<u4"), ("fcs", "<u4"), ("data", "u1", (AFSK_MAX_FRAME,)), ("_pad", "<u4")])
+assert AFSK_RX_DTYPE.itemsize == 392 and AFSK_CANDIDATE_DTYPE.itemsize == 384
+
+
 # IQ sample formats (HD_IQ_*): what the *_fmt calls take; numpy dtype of one component, bytes per complex sample
 IQ_CF32, IQ_CS16, IQ_CS8, IQ_CU8 = 0, 1, 2, 3
 IQ_DTYPES = {IQ_CF32: np.dtype(np.float32), IQ_CS16: np.dtype("<i2"), IQ_CS8: np.dtype(np.int8), IQ_CU8: np.dtype(np.uint8)}
@@ -422,6 +441,17 @@ ENGINE_API = {
     "hd_fsk4_track_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
     "hd_fsk4_track_estimate": (_int, [_vp, _u32, _vp]),
     "hd_fsk4_track_stats": (_int, [_vp, _u32, C.POINTER(hd_fsk4_track_info)]),
+    "hd_afsk_params_default": (None, [C.POINTER(hd_afsk_params)]),
+    "hd_afsk_create": (_int, [_vp, C.POINTER(hd_afsk_params), C.POINTER(_vp)]),
+    "hd_afsk_destroy": (None, [_vp]),
+    "hd_afsk_reset": (_int, [_vp, _u32]),
+    "hd_afsk_set_modem": (_int, [_vp, _u32, _dbl, _dbl, _dbl]),
+    "hd_afsk_set_bell202": (_int, [_vp, _u32]),
+    "hd_afsk_push_engine": (_int, [_vp]),
+    "hd_afsk_push_device": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_afsk_push_host": (_int, [_vp, _vp, _sz, _vp, _u32]),
+    "hd_afsk_take_frames": (_int, [_vp, _u32, _vp, _sz]),
+    "hd_afsk_stats": (_int, [_vp, _u32, C.POINTER(hd_afsk_counters)]),
     "hd_stream_set_format_trial": (_int, [_vp, _u32, _int]),
     "hd_stream_format_trial": (_int, [_vp, _u32, C.POINTER(hd_format_trial_result)]),
 }
@@ -551,6 +581,20 @@ HOST_API = {
     "hd_host_fsk4_track_records": (_int, [_vp, _vp, _sz]),
     "hd_host_fsk4_track_stats": (_int, [_vp, C.POINTER(hd_fsk4_track_info)]),
     "hd_host_fsk4_track_acc": (_int, [_vp, _vp]),
+    "hd_host_afsk_new": (_vp, [_dbl, C.POINTER(hd_afsk_params)]),
+    "hd_host_afsk_free": (None, [_vp]),
+    "hd_host_afsk_reset": (None, [_vp]),
+    "hd_host_afsk_set_modem": (_int, [_vp, _dbl, _dbl, _dbl]),
+    "hd_host_afsk_push": (_sz, [_vp, _vp, _sz]),
+    "hd_host_afsk_take_frames": (_int, [_vp, _vp, _sz]),
+    "hd_host_afsk_stats": (_int, [_vp, C.POINTER(hd_afsk_counters)]),
+    "hd_host_afsk_slots": (_sz, [_vp, C.c_uint64, _vp, _sz]),
+    "hd_host_afsk_candidates": (_int, [_vp, _vp, _sz]),
+    "hd_host_afsk_crc16": (_u32, [_vp, _sz]),
+    "hd_host_ax25_frame": (_sz, [C.c_char_p, _vp, _sz, _vp, _sz]),
+    "hd_host_ax25_levels": (_sz, [_vp, _sz, _u32, _u32, _vp, _sz]),
+    "hd_host_ax25_encode": (_sz, [C.c_char_p, _vp, _sz, _u32, _u32, _vp, _sz]),
+    "hd_host_ax25_format": (_int, [_vp, _sz, _vp, _sz]),
     "hd_host_format_trial_new": (_vp, []),
     "hd_host_format_trial_free": (None, [_vp]),
     "hd_host_format_trial_push_bits": (None, [_vp, _u8p, _sz]),

@@ -15,11 +15,14 @@
 // host/fsk4.hpp) is the seventh: the tones' doors, descriptor and chunked slot launches in front, the SSDV object's chunked candidate launches and host
 // delivery behind.  The 4FSK tone tracker (kernels/fsk4_track.hip, host/fsk4_track.hpp) is the eighth: the tone search's doors, descriptor and kernel over
 // accumulators of its own, cut into rounds at every stream's epoch end (launch_rounds, which the modem's retunes use too), the comb detector behind them.
+// The AFSK / AX.25 modem (kernels/afsk.hip, host/afsk.hpp) is the ninth: the clocked decoder's doors and descriptor, the 4FSK modem's chunked slot
+// launches, a gate launch that lists the flags, and chunked candidate launches whose records come back at places the host gave them.
 #include <atomic>
 #include <chrono>
 #include <cstddef>
 
 #include "engine_state.h"
+#include "host/afsk.hpp"
 #include "host/baud_probe.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
@@ -28,6 +31,7 @@
 #include "host/ssdv.hpp"
 #include "host/tones.hpp"
 #include "host/tone_search.hpp"
+#include "kernels/afsk.h"
 #include "kernels/combine.h"
 #include "kernels/fsk4.h"
 #include "kernels/fsk4_track.h"
@@ -2139,6 +2143,312 @@ int hd_debug_fsk4_track_guards(hd_fsk4_track* tr, uint32_t stream)
     std::lock_guard<std::recursive_mutex> lock(tr->e->mtx);
     if (const int rc = enter(tr->e)) return rc;
     return damaged_guards({{tr->acc, stream}, {tr->carry, (size_t)stream * 2}, {tr->carry, (size_t)stream * 2 + 1}, {tr->rec, stream}});
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------- AFSK / AX.25 (kernels/afsk.hip) -------------------------------------- */
+
+struct hd_afsk {
+    static constexpr const char* kNull = "null afsk object";
+    hd_engine* e = nullptr;
+    hd_afsk_params prm{};
+    uint32_t S = 0;
+    DevBuf<hd::AfskState> st;                    // [S]
+    Guarded<uint32_t> ring32;                    // [S * 4]: guard | kAfskRing32 running sums | guard
+    Guarded<int32_t> slots;                      // [S]: guard | HD_AFSK_RING records | guard
+    Guarded<uint32_t> count;                     // one row: guard | a scan's flags per stream [S] | guard
+    Guarded<uint32_t> list;                      // [S]: guard | kListCap offsets of the scan's flags | guard
+    Guarded<uint32_t> out;                       // one row: guard | HD_AFSK_LAUNCH results (hd_afsk_candidate) | guard
+    DevBuf<hd::AfskPatterns> pat;                // [1]
+    DevBuf<int32_t> ctab;                        // [1024]
+    DevBuf<float> slab;                          // hd_afsk_push_host: the rows packed end to end, grown on demand
+    PinBuf<hd::ClockedSrc> src;                  // [S]: a slot launch's descriptors, read by the kernel in place (a launch is waited for before the next is written)
+    PinBuf<hd::AfskGate> gate;                   // [S]: the gate launch's
+    PinBuf<hd::AfskCand> cand;                   // [S]: a frame launch's
+    std::vector<hd::AfskStream> stream;          // [S]: the modem (s: the state a reset gives, with n and g as the device has them), selection, delivery, counters
+    std::vector<uint32_t> h_count;               // [S]
+    std::vector<hd_afsk_candidate> h_out;        // a launch's results
+    uint64_t pushed_calls = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;       // set by the measurement hook only: recorded around the slot launches of a push ...
+    hipEvent_t f0 = nullptr, f1 = nullptr;       // ... and around the gate and the frame launches of its scan
+    bool frames_launched = false;
+    // A stream's list holds every flag a scan can find: flags of one phase lie at least seven bits apart, and a scan has at most HD_AFSK_RING slots.
+    static constexpr uint32_t kListCap = HD_AFSK_RING / 4;
+};
+// (the strides the kernels were written against, afsk.h)
+static_assert(Guarded<uint32_t>::stride_of(hd::kAfskRing32, hd::kAfskGuard) == hd::kAfskRing32 + 2 * hd::kAfskGuard, "afsk ring stride");
+static_assert(sizeof(hd_afsk_candidate) == 384 && sizeof(hd_afsk_rx) == 392 && sizeof(hd::AfskCand) == 24, "afsk record layouts");
+static_assert(hd_afsk::kListCap >= HD_AFSK_RING / 7 + 8, "the flag list holds a scan's flags");
+
+namespace {
+
+constexpr size_t kAfskOutWords = sizeof(hd_afsk_candidate) / sizeof(uint32_t);
+
+// launch_chunks over the frame launch's descriptors: the object's engine and streams, `cand` under the name the helper knows, the scan's closing event.
+struct AfskFrameLaunches {
+    hd_engine* e;
+    uint32_t S;
+    PinBuf<hd::AfskCand>& src;
+    hipEvent_t t0, t1;
+};
+
+// Every slot whose longest walk's last slot exists and is not decided.  The gate lists each stream's flags in slot order; the frame kernel takes them
+// in launches of at most HD_AFSK_LAUNCH over all streams, a stream's part of a launch at a place the host gave it -- what a scan delivers cannot
+// depend on the order in which waves finished.  Every slot a candidate reads is in the ring: afsk_params_check.
+int afsk_scan(hd_afsk* a)
+{
+    hipStream_t q = a->e->qa;
+    a->frames_launched = false;
+    bool any = false;
+    for (uint32_t s = 0; s < a->S; ++s) {
+        const hd::AfskStream& st = a->stream[s];
+        hd::AfskGate& d = a->gate.p[s];
+        d.base = st.decided;
+        d.n = (uint32_t)std::min<uint64_t>(st.decidable(st.s.g), HD_AFSK_RING);
+        any |= d.n != 0;
+    }
+    if (!any) return HD_OK;
+    std::atomic_thread_fence(std::memory_order_release);
+    if (a->f0) HD_HIP(hipEventRecord(a->f0, q));
+    hd::launch_afsk_gate(q, a->S, a->gate.dev, a->slots.base(), a->slots.stride, a->count.base(), a->list.base(), a->list.stride, hd_afsk::kListCap);
+    HD_HIP(hipGetLastError());
+    if (a->f1) HD_HIP(hipEventRecord(a->f1, q));
+    HD_HIP(hipMemcpyAsync(a->h_count.data(), a->count.row(0), (size_t)a->S * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+    HD_HIP(hipStreamSynchronize(q));
+    a->frames_launched = true;
+    uint32_t max_cand = 0, active = 0;
+    for (uint32_t s = 0; s < a->S; ++s) {
+        hd::AfskCand& d = a->cand.p[s];
+        d.base = a->gate.p[s].base;
+        d.n_total = a->gate.p[s].n ? std::min<uint32_t>(a->h_count[s], hd_afsk::kListCap) : 0u;
+        d.off = 0; d.n = 0; d.out_off = 0;
+        max_cand = std::max(max_cand, d.n_total);
+        active += d.n_total != 0;
+    }
+    if (max_cand) {
+        uint32_t cap = 0, total = 0;
+        hipError_t fetch = hipSuccess;
+        AfskFrameLaunches view{a->e, a->S, a->cand, nullptr, a->f1};
+        const int rc = launch_chunks(
+            &view, max_cand, std::max(1u, (uint32_t)HD_AFSK_LAUNCH / active), "",
+            [&](uint32_t, hd::AfskCand& d) { d.out_off = total; total += d.n; cap = std::max(cap, d.n); },
+            [&] {
+                hd::launch_afsk_frames(q, a->S, cap, a->cand.dev, a->pat.p, a->prm.require_addr, a->slots.base(), a->slots.stride, a->list.base(), a->list.stride,
+                                       reinterpret_cast<hd_afsk_candidate*>(a->out.row(0)), HD_AFSK_LAUNCH);
+                cap = 0;
+                return true;
+            },
+            [&] {                                // the launch is done: its records, stream by stream in slot order
+                const uint32_t k = std::min<uint32_t>(total, HD_AFSK_LAUNCH);
+                total = 0;
+                if (fetch != hipSuccess || !k) return;
+                fetch = hipMemcpy(a->h_out.data(), a->out.row(0), (size_t)k * sizeof(hd_afsk_candidate), hipMemcpyDeviceToHost);
+                if (fetch != hipSuccess) return;
+                for (uint32_t s = 0; s < a->S; ++s) {
+                    const hd::AfskCand& d = a->cand.p[s];
+                    for (uint32_t i = 0; i < d.n && d.out_off + i < k; ++i) a->stream[s].accept(a->h_out[d.out_off + i]);
+                }
+            });
+        if (rc) return rc;
+        HD_HIP(fetch);
+    }
+    for (uint32_t s = 0; s < a->S; ++s) a->stream[s].decided_more(a->gate.p[s].n);
+    return HD_OK;
+}
+
+// Its own: a stream without a modem is passed by, in front of the max_push test.  `cap`, the longest part of a row in the launch, sizes its LDS; behind
+// the wait the host's copy of n and g follows the device's.  Then the scan.
+int afsk_launch(hd_afsk* a, uint32_t max_n)
+{
+    if (const int rc = check_max_push(a, "hd_afsk", &max_n, [a](uint32_t s) { if (!a->stream[s].s.F) a->src.p[s].n_total = 0; })) return rc;
+    uint32_t cap = 0;
+    const int rc = launch_chunks(
+        a, max_n, HD_AFSK_CHUNK, "afsk: the launch's chunk does not fit the LDS",
+        [&](uint32_t, const hd::ClockedSrc& d) { cap = std::max(cap, d.n); },
+        [&] {
+            const uint32_t longest = cap;
+            cap = 0;
+            return hd::launch_afsk_slots(a->e->qa, a->S, longest, a->src.dev, a->st.p, a->ring32.base(), a->ring32.stride, a->ctab.p, a->slots.base(), a->slots.stride);
+        },
+        [&] {
+            for (uint32_t s = 0; s < a->S; ++s) {
+                hd::AfskState& m = a->stream[s].s;
+                if (!m.F || !a->src.p[s].n) continue;
+                m.n += a->src.p[s].n;
+                m.g = hd::afsk_slots_before(m.F, m.n);
+            }
+        });
+    if (rc) return rc;
+    return afsk_scan(a);
+}
+
+// (The rings need no clearing: nothing in front of a stream's index 0 is read, and no candidate reads a slot that was not written since.)
+int afsk_clear(hd_afsk* a, uint32_t s0, uint32_t ns)
+{
+    hipStream_t q = a->e->qa;
+    for (uint32_t s = s0; s < s0 + ns; ++s) {
+        a->stream[s].reset();
+        HD_HIP(hipMemcpyAsync(a->st.p + s, &a->stream[s].s, sizeof(hd::AfskState), hipMemcpyHostToDevice, q));
+    }
+    HD_HIP(hipStreamSynchronize(q));
+    return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hd_afsk_params_default(hd_afsk_params* p) { if (p) hd::afsk_params_default(p); }
+
+int hd_afsk_create(hd_engine* e, const hd_afsk_params* params, hd_afsk** out)
+{
+    if (!e || !out) return fail(HD_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(e->mtx);
+    std::unique_ptr<hd_afsk> a(new hd_afsk);
+    a->e = e; a->S = e->S;
+    hd::afsk_params_default(&a->prm);
+    if (params) a->prm = *params;
+    // (a launch takes at least one candidate of every active stream and its results must fit HD_AFSK_LAUNCH records)
+    if (e->S > HD_AFSK_LAUNCH) return fail(HD_ERR_UNSUPPORTED, "hd_afsk_create: at most " + std::to_string(HD_AFSK_LAUNCH) + " streams");
+    hd::AfskPatterns pat;
+    const int ok = hd::afsk_params_check(a->prm, std::max<uint32_t>(e->n2_cap, 4096u), pat);
+    if (ok == HD_ERR_INVALID)
+        return fail(ok, "afsk parameters: 17 <= max_frame_bytes <= 332, repair_flips <= 4, at most 64 flip patterns with the untouched one");
+    if (ok) return fail(ok, "afsk parameters: the slot ring holds 8 L + 72 + max_push <= " + std::to_string(HD_AFSK_RING) + " slots");
+    if (const int rc = enter(e)) return rc;
+    const uint32_t S = a->S;
+    a->stream.resize(S);
+    for (auto& st : a->stream) { st.pat = pat; st.require_addr = a->prm.require_addr; }
+    a->h_count.resize(S);
+    a->h_out.resize(HD_AFSK_LAUNCH);
+    int32_t C[1024];
+    hd::tones_table(C);
+    HD_HIP(a->st.alloc_unfilled(S));
+    HD_HIP(a->ring32.alloc((size_t)S * 4, hd::kAfskRing32, hd::kAfskGuard, hd::kAfskGuardWord, e->qa));
+    HD_HIP(a->slots.alloc(S, HD_AFSK_RING, hd::kAfskGuard, hd::kAfskGuardWord, e->qa));
+    HD_HIP(a->count.alloc(1, S, hd::kAfskGuard, hd::kAfskGuardWord, e->qa));
+    HD_HIP(a->list.alloc(S, hd_afsk::kListCap, hd::kAfskGuard, hd::kAfskGuardWord, e->qa));
+    HD_HIP(a->out.alloc(1, (size_t)HD_AFSK_LAUNCH * kAfskOutWords, hd::kAfskGuard, hd::kAfskGuardWord, e->qa));
+    HD_HIP(a->pat.alloc_unfilled(1));
+    HD_HIP(a->ctab.alloc_unfilled(1024));
+    HD_HIP(a->src.alloc(S));
+    HD_HIP(a->gate.alloc(S));
+    HD_HIP(a->cand.alloc(S));
+    HD_HIP(hipMemcpyAsync(a->ctab.p, C, sizeof C, hipMemcpyHostToDevice, e->qa));
+    HD_HIP(hipMemcpyAsync(a->pat.p, &pat, sizeof pat, hipMemcpyHostToDevice, e->qa));
+    if (const int rc = afsk_clear(a.get(), 0, S)) return rc;           // (waits for the queue: `C` and `pat` are locals)
+    *out = a.release();
+    return HD_OK;
+}
+
+void hd_afsk_destroy(hd_afsk* a) { destroy(a); }
+
+int hd_afsk_reset(hd_afsk* a, uint32_t stream) { return reset(a, stream, afsk_clear); }
+
+int hd_afsk_set_modem(hd_afsk* a, uint32_t stream, double baud, double mark_hz, double space_hz)
+{
+    if (const int rc = check_object(a, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    hd::AfskState m;
+    const int rc = hd::afsk_modem(m, a->e->fsd, baud, mark_hz, space_hz);
+    if (rc == HD_ERR_UNSUPPORTED) return fail(rc, "afsk: 8 <= decimated rate / baud <= " + std::to_string(HD_AFSK_MAX_SPB));
+    if (rc) return fail(rc, "afsk: 0 < mark, space < decimated rate / 2, and two different tones");
+    if (const int rc2 = enter(a->e)) return rc2;
+    a->stream[stream].s = m;
+    return afsk_clear(a, stream, 1);
+}
+
+int hd_afsk_set_bell202(hd_afsk* a, uint32_t stream) { return hd_afsk_set_modem(a, stream, 1200.0, 1200.0, 2200.0); }
+
+int hd_afsk_push_engine(hd_afsk* a) { return push_engine(a, "hd_afsk_push_engine", afsk_launch); }
+
+int hd_afsk_push_device(hd_afsk* a, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(a, d_rows, stride, n_per_stream, n, true, afsk_launch);
+}
+
+int hd_afsk_push_host(hd_afsk* a, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n)
+{
+    return push_rows(a, rows, stride, n_per_stream, n, false, afsk_launch);
+}
+
+int hd_afsk_take_frames(hd_afsk* a, uint32_t stream, hd_afsk_rx* out, size_t cap)
+{
+    if (const int rc = check_object(a, stream)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    return (int)a->stream[stream].take(out, cap);
+}
+
+// (samples and slots are the device's own: a host copy that had drifted would show here)
+int hd_afsk_stats(hd_afsk* a, uint32_t stream, hd_afsk_counters* out)
+{
+    if (const int rc = check_object(a, stream)) return rc;
+    if (!out) return fail(HD_ERR_INVALID, "null output");
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    hd::AfskState h;
+    HD_HIP(hipMemcpy(&h, a->st.p + stream, sizeof h, hipMemcpyDeviceToHost));
+    a->stream[stream].stats(out, h.n, h.g);
+    return HD_OK;
+}
+
+// The measurement hook (tools/micro/afsk_rate.py; not part of the ABI): hd_afsk_push_engine with the slot launches and the gate and frame launches of its
+// scan each between two HIP events (0 where none was launched), and the host time of the whole call in microseconds.
+int hd_debug_afsk_push_timed(hd_afsk* a, float* slots_ms, float* scan_ms, double* host_us)
+{
+    if (!a || !slots_ms || !scan_ms || !host_us) return fail(HD_ERR_INVALID, "null argument");
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    HD_HIP(hipEventCreate(&a->f0));
+    HD_HIP(hipEventCreate(&a->f1));
+    a->frames_launched = false;
+    const int rc = push_timed(a, slots_ms, host_us, hd_afsk_push_engine);
+    *scan_ms = 0;
+    if (rc == HD_OK && a->frames_launched && hipEventQuery(a->f1) == hipSuccess) (void)hipEventElapsedTime(scan_ms, a->f0, a->f1);
+    (void)hipGetLastError();
+    (void)hipEventDestroy(a->f0); (void)hipEventDestroy(a->f1);
+    a->f0 = a->f1 = nullptr;
+    return rc;
+}
+
+// Test hooks (tests/test_gpu_afsk.py; not part of the ABI).  The records of the slots first .. first + n - 1 as the stream's ring holds them, n words.
+int hd_debug_afsk_slots(hd_afsk* a, uint32_t stream, uint64_t first, int32_t* out, size_t n)
+{
+    if (!a || stream >= a->S || !out || n > HD_AFSK_RING) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    for (size_t k = 0; k < n;) {
+        const size_t at = (size_t)((first + k) & (HD_AFSK_RING - 1u)), run = std::min<size_t>(n - k, HD_AFSK_RING - at);
+        HD_HIP(hipMemcpy(out + k, a->slots.row(stream) + at, run * sizeof(int32_t), hipMemcpyDeviceToHost));
+        k += run;
+    }
+    return (int)n;
+}
+
+// The log of the stream's candidates, as hd_host_afsk_candidates.
+int hd_debug_afsk_candidates(hd_afsk* a, uint32_t stream, hd_afsk_candidate* out, size_t cap)
+{
+    if (!a || stream >= a->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    return (int)a->stream[stream].take_log(out, cap);
+}
+
+// The dynamic LDS a slot launch whose longest row has `cap` samples asks for, in bytes; 0: no such launch (tests/test_afsk_kernels.py holds the chunk's
+// figure to two workgroups a CU).  No GPU is touched.
+uint32_t hd_debug_afsk_slot_lds(uint32_t cap) { return hd::afsk_slots_lds_bytes(cap); }
+
+// How many of the guard words around the stream's four rings, its slots and its list, the counts and the results no longer hold their pattern.
+int hd_debug_afsk_guards(hd_afsk* a, uint32_t stream)
+{
+    if (!a || stream >= a->S) return fail(HD_ERR_INVALID, "bad argument");
+    std::lock_guard<std::recursive_mutex> lock(a->e->mtx);
+    if (const int rc = enter(a->e)) return rc;
+    const size_t r = (size_t)stream * 4;
+    return damaged_guards({{a->ring32, r}, {a->ring32, r + 1}, {a->ring32, r + 2}, {a->ring32, r + 3}, {a->slots, stream}, {a->list, stream}, {a->count, 0}, {a->out, 0}});
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include "../../include/habdec_amd_host.h"
 #include "host/afc_tracker.hpp"
 #include "host/baud_probe.hpp"
+#include "host/afsk.hpp"
 #include "host/clocked.hpp"
 #include "host/combine.hpp"
 #include "host/fsk4.hpp"
@@ -664,6 +665,95 @@ int hd_host_fsk4_track_acc(const hd_host_fsk4_track* h, double* out)
     if (!h || !out) return HD_ERR_INVALID;
     std::memcpy(out, h->t.ts.acc.data(), hd::kFsk4CombBins * sizeof(double));
     return (int)hd::kFsk4CombBins;
+}
+
+/* ---- AFSK / AX.25 (kernels/afsk.hip; see host/afsk.hpp) ---- */
+struct hd_host_afsk {
+    double fsd;
+    hd_afsk_params prm;
+    hd::AfskStream st;
+};
+hd_host_afsk* hd_host_afsk_new(double decimated_rate, const hd_afsk_params* params)
+{
+    hd_afsk_params prm;
+    hd::afsk_params_default(&prm);
+    if (params) prm = *params;
+    hd::AfskPatterns pat;
+    if (!(decimated_rate > 0) || hd::afsk_params_check(prm, 4096u, pat)) return nullptr;
+    auto* h = new hd_host_afsk;
+    h->fsd = decimated_rate; h->prm = prm;
+    h->st.pat = pat; h->st.require_addr = prm.require_addr;
+    h->st.host_rings();
+    return h;
+}
+void hd_host_afsk_free(hd_host_afsk* h) { delete h; }
+void hd_host_afsk_reset(hd_host_afsk* h) { if (h) h->st.reset(); }
+int hd_host_afsk_set_modem(hd_host_afsk* h, double baud, double mark_hz, double space_hz)
+{
+    if (!h) return HD_ERR_INVALID;
+    hd::AfskState m;
+    if (const int rc = hd::afsk_modem(m, h->fsd, baud, mark_hz, space_hz)) return rc;
+    h->st.s = m;
+    h->st.reset();
+    return HD_OK;
+}
+// (in pieces of max_push, a scan behind each: the slot ring holds what one piece adds to the slots that wait)
+size_t hd_host_afsk_push(hd_host_afsk* h, const float* row, size_t n)
+{
+    if (!h || !row || !h->st.s.F) return 0;
+    for (size_t at = 0; at < n;) {
+        const size_t k = std::min<size_t>(n - at, h->prm.max_push);
+        h->st.push_samples(row + at, k);
+        h->st.scan();
+        at += k;
+    }
+    return n;
+}
+int hd_host_afsk_take_frames(hd_host_afsk* h, hd_afsk_rx* out, size_t cap) { return h ? (int)h->st.take(out, cap) : HD_ERR_INVALID; }
+int hd_host_afsk_stats(const hd_host_afsk* h, hd_afsk_counters* out)
+{
+    if (!h || !out) return HD_ERR_INVALID;
+    h->st.stats(out, h->st.s.n, h->st.s.g);
+    return HD_OK;
+}
+size_t hd_host_afsk_slots(const hd_host_afsk* h, uint64_t first, int32_t* out, size_t n)
+{
+    if (!h || !out || first + n > h->st.s.g || h->st.s.g - first > HD_AFSK_RING) return 0;
+    for (size_t k = 0; k < n; ++k) out[k] = h->st.slot_d(first + k);
+    return n;
+}
+int hd_host_afsk_candidates(hd_host_afsk* h, hd_afsk_candidate* out, size_t cap) { return h ? (int)h->st.take_log(out, cap) : HD_ERR_INVALID; }
+uint32_t hd_host_afsk_crc16(const uint8_t* bytes, size_t n) { return bytes || !n ? hd::afsk_crc16(bytes, n) : 0u; }
+size_t hd_host_ax25_frame(const char* path, const uint8_t* info, size_t n_info, uint8_t* out, size_t cap)
+{
+    if (!path || (!info && n_info) || !out) return 0;
+    const std::vector<uint8_t> f = hd::ax25_frame(path, info, n_info);
+    if (f.empty() || f.size() > cap) return 0;
+    std::memcpy(out, f.data(), f.size());
+    return f.size();
+}
+size_t hd_host_ax25_levels(const uint8_t* frame, size_t n, uint32_t flags_before, uint32_t flags_after, uint8_t* out, size_t cap)
+{
+    if (!frame && n) return 0;
+    const std::vector<uint8_t> lv = hd::ax25_levels(frame, n, flags_before, flags_after);
+    if (out && lv.size() <= cap) std::memcpy(out, lv.data(), lv.size());
+    return lv.size();
+}
+size_t hd_host_ax25_encode(const char* path, const uint8_t* info, size_t n_info, uint32_t flags_before, uint32_t flags_after, uint8_t* out, size_t cap)
+{
+    if (!path || (!info && n_info)) return 0;
+    const std::vector<uint8_t> f = hd::ax25_frame(path, info, n_info);
+    if (f.empty()) return 0;
+    return hd_host_ax25_levels(f.data(), f.size(), flags_before, flags_after, out, cap);
+}
+int hd_host_ax25_format(const uint8_t* data, size_t n, char* out, size_t cap)
+{
+    if (!data || !out || !cap) return HD_ERR_INVALID;
+    std::string s;
+    if (const int rc = hd::ax25_format(data, n, s)) return rc;
+    if (s.size() + 1 > cap) return HD_ERR_CAPACITY;
+    std::memcpy(out, s.c_str(), s.size() + 1);
+    return (int)s.size();
 }
 
 /* ---- baud-rate probe (kernels/baud_probe.hip; see host/baud_probe.hpp) ---- */

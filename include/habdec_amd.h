@@ -1133,6 +1133,124 @@ int  hd_fsk4_track_push_host(hd_fsk4_track* tr, const float* iq, size_t stride, 
 int  hd_fsk4_track_estimate(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_est* out);
 int  hd_fsk4_track_stats(hd_fsk4_track* tr, uint32_t stream, hd_fsk4_track_info* out);
 
+/* ---- APRS: Bell 202 AFSK carrying AX.25 UI frames -- tone pair, HDLC flag search on a timing grid, CRC-guided repair (not in the reference) ----
+ * survey -> front tune -> hd_stream_set_lowpass_bw wide enough for the FM signal -> afsk.  The third modulation: the stream's polar discriminator is
+ * an FM demodulator, and with the low-pass opened its row (hd_stream_demodulated) is the audio a packet modem takes.  An afsk object is attached to an
+ * engine like a clocked decoder (its device, mutex and first queue; destroy it before the engine) and reads the same float rows through the same three
+ * doors with the same rules.  Frames leave through hd_afsk_take_frames alone, never through the sentence callbacks.  No other TNC is at hand:
+ * agreement with them rests on the published AX.25 / Bell 202 format as restated here.  Kernels (kernels/afsk.hip), host restatement (hd_host_afsk_*)
+ * and a numpy model (tests/afsk_model.py) agree byte for byte on all of the following.  fsd = hd_engine_decimated_rate(e); every index is absolute per
+ * stream since its last reset (uint64); how the samples are cut into pushes matters to no record, frame or counter.
+ *  - On air: a frame is flag(s) 0x7E, the bytes least significant bit first with a 0 stuffed behind every five 1s, flag(s); NRZI: a 0 is a change of
+ *    tone, a 1 none.  A UI frame is destination, source and up to eight digipeater addresses of seven bytes (six characters << 1, then the SSID byte
+ *    0b?11ssss? whose bit 0 is set in the last address and whose bit 7 is the digipeater's H bit), control 0x03, PID 0xF0, the information, the FCS.
+ *  - Modem (hd_afsk_set_modem; it resets the stream): F = floor(fsd / baud * 65536 + 0.5); W = (F + 32768) >> 16, one bit;
+ *    Phi_t = (uint32)(int64)nearbyint(f_t / fsd * 2^32) for mark and space.  HD_ERR_UNSUPPORTED unless 8 <= fsd / baud <= HD_AFSK_MAX_SPB;
+ *    HD_ERR_INVALID unless 0 < mark, space < fsd / 2 and mark != space.  hd_afsk_set_bell202: 1200 baud, 1200 / 2200 Hz; the 300 baud HF pair is
+ *    hd_afsk_set_modem(a, s, 300, 1600, 1800).  After create no stream has a modem, and a stream without one is passed by.
+ *  - Sample: q = 0 for NaN, else (int32)(clamp(v, -4, 4) * 1024) truncated toward zero, the clocked decoder's rule.
+ *  - Tone pair, per tone t: a = (uint32)(i Phi_t) >> 22; r_re = (q C[a]) >> 15, r_im = (-q C[(a + 768) & 1023]) >> 15 with the probe's table C and
+ *    arithmetic shifts; running sums mod 2^32 over the W samples up to i (samples in front of index 0 are zero); A_t(i) = floor(sqrt(re^2 + im^2));
+ *    d(i) = A_mark(i) - A_space(i), an int32.
+ *  - Slots: eight phases per bit, slot g = 8 k + p, which ends at sample end(g) = ((g + 8) F >> 19) - 1.  Its record is d(end(g)); it exists once
+ *    that sample is pushed.  Records go to a per-stream ring of HD_AFSK_RING slots on the GPU.
+ *  - Bits, per phase: level l_k = (d > 0); NRZI data bit n_k = (l_k == l_{k-1}); the confidence of a level is |d|.
+ *  - Candidate: every slot g = 8 k + p >= 64 at which n_{k-7} .. n_k = 0,1,1,1,1,1,1,0 on hard levels -- a flag whose last bit is k.  It is decided
+ *    exactly once, by the first scan after slot g + 8 L exists, L = ceil(8 max_frame_bytes 6 / 5) + 8 bits; every push ends with a scan.  The rule is
+ *    fixed, so that the state after n samples is a function of those samples; a smaller max_frame_bytes buys latency.
+ *  - Walk from bit k + 1 with a count of consecutive 1s: a 1 is kept, the seventh consecutive 1 ends the walk (HD_AFSK_ABORT); a 0 after exactly
+ *    five 1s is dropped (stuffed); a 0 after six 1s closes the frame, and the last seven kept bits (a 0 and six 1s) belong to the flag; any other 0 is
+ *    kept.  No closing flag within L bits: HD_AFSK_OPEN.  The kept bits in front of the closing flag, least significant bit first, are the frame; it
+ *    is shaped iff their count is a multiple of 8 and HD_AFSK_MIN_FRAME <= bytes <= max_frame_bytes, FCS included (else HD_AFSK_UNSHAPED; two flags
+ *    in a row give a zero-length frame, which is not shaped).
+ *  - FCS: the last two frame bytes are CRC-16/X-25 over the rest (reflected 0x8408, initial 0xFFFF, final xor 0xFFFF, low byte first; its check
+ *    value over "123456789" is 0x906E).
+ *  - Address check: the address field ends at the first byte with bit 0 set; its index must be 7 m - 1 with 2 <= m <= 10 and lie in front of the
+ *    FCS.  Every callsign byte (the first six of each address) has bit 0 clear and byte >> 1 in 'A'-'Z', '0'-'9' or ' '.
+ *  - Repair, for a shaped frame whose FCS fails: the list is the repair_bits levels with the smallest |d| among the levels of bit k + 1 up to the bit
+ *    in front of the closing flag's eight, ties to the earlier bit.  All subsets of size 1, then 2, up to repair_flips are tried in the list's
+ *    lexicographic order; with the untouched pattern they number at most 64 (1 + 8 + 28 = 37 by default), or create refuses.  A pattern flips
+ *    levels, so each flip changes two NRZI bits and may move stuffing: its walk is run afresh.  A pattern counts iff its walk is shaped, closes at
+ *    the same bit as the hard walk, its FCS agrees and its address field passes the check.  The first pattern that counts wins
+ *    (HD_AFSK_REPAIRED, flips = the subset's size).  Either limit 0: no repair.  No pattern counts: HD_AFSK_REFUSED if one of them failed at
+ *    the address check alone, else HD_AFSK_FCS_FAILED.
+ *  - Plain frames (HD_AFSK_PLAIN: shaped, FCS right on hard levels) must pass the address check when require_addr is set (else HD_AFSK_REFUSED);
+ *    without it they are delivered with addr_ok = 0.  In noise about 2^-8 of the bit positions of a phase are flags, roughly a percent of those walk to
+ *    a shaped frame, an FCS trial passes with 2^-16 and the address check passes a random field with about (37/256)^12.
+ *  - Selection: only plain and repaired candidates count.  The first opens a group; those less than 8 slots (one bit: the neighbouring phases of one
+ *    frame) behind it contest the delivery -- fewest flips, then the largest metric (the sum of |d| over the walked bits, uint64), then the lowest
+ *    slot -- and the winner is delivered once every slot of the contest is decided.  A later passing candidate whose slot lies more than 8 slots
+ *    in front of the delivered frame's closing-flag slot is an overlap: dropped, overlaps += 1.  A closing flag shared with the next frame is a
+ *    candidate like any other.  Frames wait on the host, per stream in increasing position, until hd_afsk_take_frames.
+ *  - Counters per stream: samples, slots, flags (candidates decided), unshaped (abort, open or not shaped), fcs_failures, frames_plain,
+ *    frames_repaired, refused (address check), overlaps; the modem's integers F, W, step[2].
+ *  - Queue, errors: as the clocked decoder's; a push returns when its kernels are done.  A push longer than max_push: HD_ERR_CAPACITY.  A row longer
+ *    than HD_AFSK_CHUNK samples is cut into launches; a scan's candidates into launches of at most HD_AFSK_LAUNCH over all streams.  The slot ring must
+ *    hold the longest walk on all phases, the gate's look back and a push: 8 L + 72 + max_push <= HD_AFSK_RING, or create refuses (HD_ERR_UNSUPPORTED).
+ *  - Not built: a band-pass or de-emphasis stage in front of the tone pair (a DC offset on the row leaks into the space filter with a weight of about
+ *    0.09, NOTES.md); several slicers with different space gains; 9600 baud G3RUH; connected-mode AX.25; parsing of APRS position formats. */
+#define HD_AFSK_MAX_SPB 2048
+#define HD_AFSK_CHUNK 4096         /* samples of a row per launch of the slot kernel */
+#define HD_AFSK_LAUNCH 4096        /* candidates per launch of the frame kernel over all streams */
+#define HD_AFSK_RING 65536         /* slots of a stream's ring */
+#define HD_AFSK_MAX_FRAME 332      /* bytes, FCS included */
+#define HD_AFSK_MIN_FRAME 17
+#define HD_AFSK_OPEN 0             /* hd_afsk_candidate.result */
+#define HD_AFSK_ABORT 1
+#define HD_AFSK_UNSHAPED 2
+#define HD_AFSK_FCS_FAILED 3
+#define HD_AFSK_REFUSED 4
+#define HD_AFSK_PLAIN 5
+#define HD_AFSK_REPAIRED 6
+typedef struct hd_afsk hd_afsk;
+typedef struct hd_afsk_params {
+    uint32_t max_push;         /* longest push per stream in samples; 0: what the engine's longest call leaves, or 4096 */
+    uint32_t max_frame_bytes;  /* HD_AFSK_MIN_FRAME .. HD_AFSK_MAX_FRAME, FCS included; default 332 */
+    uint32_t repair_bits;      /* default 8 */
+    uint32_t repair_flips;     /* 0 .. 4; default 2 */
+    uint32_t require_addr;     /* default 1 */
+    uint32_t _pad;
+} hd_afsk_params;
+typedef struct hd_afsk_rx {    /* one delivered frame */
+    uint64_t slot;             /* the slot of the opening flag's last bit, 8 k + phase */
+    uint64_t start_sample;     /* the first sample behind that bit: (slot + 8) F >> 19 */
+    uint64_t close_slot;       /* the slot of the closing flag's last bit */
+    uint64_t metric;
+    uint32_t len;              /* bytes of data */
+    uint32_t flips, phase, addr_ok, fcs, _pad;
+    uint8_t  data[HD_AFSK_MAX_FRAME];   /* the frame without its FCS */
+    uint32_t _pad2;
+} hd_afsk_rx;
+typedef struct hd_afsk_candidate {   /* one candidate, whatever became of it (the frame kernel's, the restatement's and the test hooks' record) */
+    uint64_t slot, close_slot /* 0 unless closed */, metric;
+    uint32_t result;           /* HD_AFSK_OPEN .. HD_AFSK_REPAIRED */
+    uint32_t bits;             /* the bits the hard walk took */
+    uint32_t len;              /* the frame's bytes, FCS included; 0 unless shaped */
+    uint32_t flips, addr_ok, fcs;
+    uint8_t  data[HD_AFSK_MAX_FRAME];   /* the frame with its FCS: the winning pattern's, the hard walk's where none won */
+    uint32_t _pad;
+} hd_afsk_candidate;
+typedef struct hd_afsk_counters {
+    uint64_t samples, slots, flags, unshaped, fcs_failures, frames_plain, frames_repaired, refused, overlaps;
+    uint32_t F, W, step[2];    /* the modem's integers: F = 0, no modem */
+} hd_afsk_counters;
+void hd_afsk_params_default(hd_afsk_params* p);
+/* HD_ERR_INVALID: max_frame_bytes, repair_flips, more than 64 flip patterns; HD_ERR_UNSUPPORTED: the ring does not hold 8 L + 72 + max_push slots,
+ * more than HD_AFSK_LAUNCH streams. */
+int  hd_afsk_create(hd_engine* e, const hd_afsk_params* p /* null: the defaults */, hd_afsk** out);
+void hd_afsk_destroy(hd_afsk* a);
+/* Samples, slots, candidates, counters and the open group of the stream start again; the modem stays, and so do frames not yet taken. */
+int  hd_afsk_reset(hd_afsk* a, uint32_t stream /* UINT32_MAX: all */);
+int  hd_afsk_set_modem(hd_afsk* a, uint32_t stream, double baud, double mark_hz, double space_hz);   /* resets the stream */
+int  hd_afsk_set_bell202(hd_afsk* a, uint32_t stream);                                               /* 1200 baud, 1200 / 2200 Hz */
+/* The three doors of the clocked decoder, with its rules; each ends with a scan. */
+int  hd_afsk_push_engine(hd_afsk* a);
+int  hd_afsk_push_device(hd_afsk* a, const float* d_rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+int  hd_afsk_push_host(hd_afsk* a, const float* rows, size_t stride, const uint32_t* n_per_stream, uint32_t n);
+/* Hands out up to cap of the stream's waiting frames, oldest first, and returns how many were written; out null: how many wait.  Negative: HD_ERR_*. */
+int  hd_afsk_take_frames(hd_afsk* a, uint32_t stream, hd_afsk_rx* out, size_t cap);
+int  hd_afsk_stats(hd_afsk* a, uint32_t stream, hd_afsk_counters* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -342,6 +342,36 @@ int    hd_host_fsk4_track_records(hd_host_fsk4_track*, hd_fsk4_track_est* out, s
 int    hd_host_fsk4_track_stats(const hd_host_fsk4_track*, hd_fsk4_track_info* out);
 int    hd_host_fsk4_track_acc(const hd_host_fsk4_track*, double* out);
 
+/* ---- AFSK / AX.25 (hd_afsk_*, include/habdec_amd.h has the definition): one stream of it in plain C++, sample by sample, candidate by candidate ----
+ * The same integers as the kernels: slot records, candidate records, frames and counters of the same samples equal the device's byte for byte, however
+ * the samples are cut into pushes.  Selection, delivery and counters are the code the engine's object runs.  hd_host_afsk_new: NULL unless
+ * decimated_rate > 0 and the parameters are ones hd_afsk_create takes (max_push 0: 4096).  hd_host_afsk_set_modem: the errors of hd_afsk_set_modem.
+ * hd_host_afsk_push: n floats, then a scan; 0 without a modem.  hd_host_afsk_slots: the records of the slots first .. first + n - 1 (n int32) while
+ * the ring still holds them; returns how many it wrote.  hd_host_afsk_candidates: takes the log of the candidates, oldest first (the log keeps the newest
+ * 16384); out null: how many wait.  hd_host_afsk_crc16: the FCS of n bytes.
+ * AX.25 UI frames.  path is the TNC2 header, "SRC-SSID>DST,DIGI1,DIGI2*" (callsigns of 'A'-'Z', '0'-'9', SSID 0 .. 15, at most eight digipeaters, '*'
+ * sets a digipeater's H bit).  hd_host_ax25_frame: addresses, control 0x03, PID 0xF0, info, FCS -> the frame's bytes; returns their number, 0 for a
+ * path that is none or a capacity too small.  hd_host_ax25_levels: frame bytes (FCS included) -> flags_before flags, the stuffed bits, flags_after
+ * flags as NRZI levels, one byte (0 / 1) a bit, the level in front of the first bit 0; returns their number and writes them where they fit cap (out
+ * null: the count alone).  hd_host_ax25_encode: both in one.  hd_host_ax25_format: a UI frame without its FCS -> the TNC2 monitor line
+ * "SRC-SSID>DST,DIGI*:info" with its terminating 0, the '*' behind the last digipeater whose H bit is set, bytes outside 32 .. 126 as <0xNN>; returns
+ * the line's length, HD_ERR_INVALID for an address field that fails the address check, HD_ERR_UNSUPPORTED for a frame that is not UI, HD_ERR_CAPACITY. */
+typedef struct hd_host_afsk hd_host_afsk;
+hd_host_afsk* hd_host_afsk_new(double decimated_rate, const hd_afsk_params* params);
+void   hd_host_afsk_free(hd_host_afsk*);
+void   hd_host_afsk_reset(hd_host_afsk*);
+int    hd_host_afsk_set_modem(hd_host_afsk*, double baud, double mark_hz, double space_hz);
+size_t hd_host_afsk_push(hd_host_afsk*, const float* row, size_t n);
+int    hd_host_afsk_take_frames(hd_host_afsk*, hd_afsk_rx* out, size_t cap);
+int    hd_host_afsk_stats(const hd_host_afsk*, hd_afsk_counters* out);
+size_t hd_host_afsk_slots(const hd_host_afsk*, uint64_t first, int32_t* out, size_t n);
+int    hd_host_afsk_candidates(hd_host_afsk*, hd_afsk_candidate* out, size_t cap);
+uint32_t hd_host_afsk_crc16(const uint8_t* bytes, size_t n);
+size_t hd_host_ax25_frame(const char* path, const uint8_t* info, size_t n_info, uint8_t* out, size_t cap);
+size_t hd_host_ax25_levels(const uint8_t* frame, size_t n, uint32_t flags_before, uint32_t flags_after, uint8_t* out, size_t cap);
+size_t hd_host_ax25_encode(const char* path, const uint8_t* info, size_t n_info, uint32_t flags_before, uint32_t flags_after, uint8_t* out, size_t cap);
+int    hd_host_ax25_format(const uint8_t* data, size_t n, char* out, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
